@@ -66,6 +66,10 @@ def parse():
     ap.add_argument("--block", type=int, default=1,
                     help="> 1: a step is one BLOCK Arnoldi step with this many vectors (<= 4) advanced together "
                          "(nlg_block_arnoldi_step); value counts every vector's matvec")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): H (the Hessenberg "
+                         "matrix) and every field of the new basis vector(s) (v<column>_<field>), rank 0's elements; a field "
+                         "larger than its share of the 64 MB budget is written as a fixed, seeded sample of its points")
     return ap.parse_args()
 
 
@@ -105,6 +109,29 @@ def algorithmic_bytes(cls, E, n, dim, k, ncomp, lvs, lps, nshared, main_len, lor
         first = lps if fused else main_len
         return 8.0 * (k + 2) * (first + main_len * lorder) / 2.0
     return None
+
+
+DUMP_BYTES = 60 << 20     # sampled fields; H and the .npy headers fit in the rest of 64 MB
+
+
+def dump_outputs(outdir, H, vecs, nscal, dim):
+    """Write H and the fields of `vecs` ({basis column: nek_dvector}) as float64 .npy files.  A field of more points than its even
+    share of DUMP_BYTES keeps a sorted random subset of them, drawn from a generator seeded by the array's position in the dump, so
+    that two runs of the same configuration write the same points."""
+    from neklab_amd import host
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "H.npy"), np.asarray(H, dtype=np.float64))
+    fields = [("vx", host.VX), ("vy", host.VY)] + ([("vz", host.VZ)] if dim == 3 else []) + [("pr", host.PR)]
+    fields += [("t%d" % k, host.THETA + k) for k in range(nscal)]
+    cap = DUMP_BYTES // (8 * len(vecs) * len(fields))
+    seed = 0
+    for col, v in sorted(vecs.items()):
+        for nm, f in fields:
+            a = v.get_field(f)
+            if a.size > cap:
+                a = a[np.sort(np.random.default_rng(seed).choice(a.size, cap, replace=False))]
+            np.save(os.path.join(outdir, "v%d_%s.npy" % (col, nm)), a)
+            seed += 1
 
 
 def spawn_ranks(args):
@@ -295,6 +322,8 @@ def main():
         tim[kcls] = (cnt.value, ms.value / max(cnt.value, 1))
     host.check(lib.nlg_prof_enable(ctx.h, 0))
     host.check(lib.nlg_prof_sample(ctx.h, 1))
+    if args.dump_outputs and rank == 0:      # before the unit timings below, which overwrite basis column m
+        dump_outputs(args.dump_outputs, H, {c: B[c] for c in range(m + 1 - sblk, m + 1)}, nscal, dim)
     # shared local dofs: copies of labels that occur more than once
     _, inv, counts = np.unique(hm.glo_num.ravel(), return_inverse=True, return_counts=True)
     nshared = int(np.sum(counts[inv] > 1))

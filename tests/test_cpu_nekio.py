@@ -124,20 +124,51 @@ def test_glo_num_from_vertices_3d():
     assert len(set(zip(g3.ravel().tolist(), hm.glo_num.ravel().tolist()))) == len(np.unique(hm.glo_num)) == len(np.unique(g3))
 
 
-def test_re2_reader_on_the_reference_files_if_present():
+def _write_re2_2d(path, xc, yc, curves, bcs):
+    """A "#v002" .re2 file in Nek5000's layout (header, fp64 element, curve and velocity-BC records); the BC parameters
+    (neighbour element / face of periodic faces), which read_re2 does not return, are written as zeros."""
+    nel = xc.shape[0]
+    rec = np.zeros((nel, 9))
+    rec[:, 1:5], rec[:, 5:9] = xc, yc
+    out = [("#v002%9d%3d%9d this is the hdr" % (nel, 2, nel)).ljust(80).encode(), np.float32(6.54321).tobytes(), rec.tobytes(),
+           np.float64(len(curves)).tobytes()]
+    out += [np.array([e, s, *par], dtype=np.float64).tobytes() + typ.encode().ljust(8) for e, s, par, typ in curves]
+    out.append(np.float64(len(bcs)).tobytes())
+    out += [np.array([e, f, 0, 0, 0, 0, 0], dtype=np.float64).tobytes() + tag.encode().ljust(8) for e, f, tag in bcs]
+    with open(path, "wb") as fh:
+        fh.write(b"".join(out))
+
+
+def _write_ma2(path, pmap, vert, depth, nrank):
+    """A "#v001" .ma2 file in Nek5000's layout: header, then per element the bisection leaf and the global vertex ids (int32)."""
+    nel, nv = vert.shape
+    nvg = int(vert.max())
+    hdr = "#v001" + "".join("%12d" % v for v in (nel, nvg, depth, nrank, nel * nv, nvg, 0))
+    a = np.concatenate([pmap[:, None], vert], axis=1).astype(np.int32)
+    with open(path, "wb") as fh:
+        fh.write(hdr.ljust(132).encode() + np.float32(6.54321).tobytes() + a.tobytes())
+
+
+def test_re2_ma2_readers_on_the_reference_mesh(tmp_path):
+    """read_re2 / read_ma2 on 1cyl.re2 / 1cyl.ma2 of the reference's cylinder case, written back in the binary layouts from the
+    stored fixtures (vertices, curves, partition map and vertex ids: reference_cyl_mesh.npz; velocity BCs:
+    reference_cyl_baseflow.npz; the .ma2 header's bisection depth 10 and 1024 partition slots are those of the shipped file)."""
     import os
-    D = "/root/reference/examples/cylinder/stability/direct/"
-    if not os.path.exists(D + "1cyl.re2"):
-        pytest.skip("reference tree not present (GPU box)")
-    r, m = nekio.read_re2(D + "1cyl.re2"), nekio.read_ma2(D + "1cyl.ma2")
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from refdata import HERE, load_cylinder_mesh
+    xc, yc, curves, vert, pmap = load_cylinder_mesh()
+    d = np.load(os.path.join(HERE, "golden", "reference_cyl_baseflow.npz"))
+    bcs = [(int(e), int(f), str(t)) for e, f, t in zip(d["bc_elem"], d["bc_face"], d["bc_tag"])]
+    _write_re2_2d(str(tmp_path / "1cyl.re2"), xc, yc, curves, bcs)
+    _write_ma2(str(tmp_path / "1cyl.ma2"), pmap, vert, 10, 1024)
+    r, m = nekio.read_re2(str(tmp_path / "1cyl.re2")), nekio.read_ma2(str(tmp_path / "1cyl.ma2"))
     assert (r["nel"], r["dim"], len(r["curves"]), len(r["bcs"])) == (1996, 2, 80, 208)
     assert {c[3] for c in r["curves"]} == {"C"} and {b[2] for b in r["bcs"]} == {"v", "W", "O", "P"}
     assert (m["nel"], m["depth"], m["nrank"]) == (1996, 10, 1024) and m["vert"].shape == (1996, 4)
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from refdata import load_cylinder_mesh
-    xc, yc, curves, vert, pmap = load_cylinder_mesh()
-    assert np.array_equal(xc, r["xc"]) and np.array_equal(vert, m["vert"]) and np.array_equal(pmap, m["pmap"])
+    assert np.array_equal(xc, r["xc"]) and np.array_equal(yc, r["yc"]) and r["bcs"] == bcs
+    assert all(c[:2] == o[:2] and np.array_equal(c[2], o[2]) for c, o in zip(r["curves"], curves))
+    assert np.array_equal(vert, m["vert"]) and np.array_equal(pmap, m["pmap"]) and m["nvert_global"] == 2033
 
 
 def test_pressure_from_mesh1_is_exact_for_polynomials():
