@@ -890,7 +890,7 @@ struct nlg_linop {
     double *pr_b = nullptr;    // the right-hand side the pressure PCG started from (after the projection): A x = b - r afterwards
     double *pcv[4][3] = {};    // mask_i / diag(H) per BDF order
     // velocity PCG in the x-planes-first layout (3-D, lx1 <= 8: internal.h xp_slot): the preconditioners and the residual
-    // weight permuted once; 0 = natural layout (2-D, lx1 > 8, NLG_XP=0)
+    // weight permuted once; 0 = natural layout (2-D)
     int use_xp = -1;
     double *pcv_xp[4][3] = {}, *nwv_xp = nullptr;
     // the same preconditioners as ONE array 1 / diag(H) per BDF order plus one mask byte per point (bit c = mask of component c), in the
@@ -1588,8 +1588,7 @@ int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
         {
             // deferred solution update (as in the velocity solve, k_cg_update): the gradient kernel's fused direction update stores direction
             // i into slot i mod php of a ring, the update kernel of the preconditioner streams neither x nor p, pres_solve assembles x
-            static const bool fuse = !(getenv("NLG_FUSE_PPUPDATE") && atoi(getenv("NLG_FUSE_PPUPDATE")) == 0);
-            if (op->php > 0 && fuse && sem_opgradt_fuses_pupdate(m)) {
+            if (op->php > 0 && sem_opgradt_fuses_pupdate(m)) {
                 upd.x = nullptr;
                 upd.p = nullptr;
                 P.hist.p0[0] = op->prh;
@@ -1624,10 +1623,7 @@ int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
     Q.pw_part = op->d_part;
     P.pw_part = Q.pw_part;
     P.pw_n = sem_opdiv_blocks(m);
-    {
-        static const bool fuse = !(getenv("NLG_FUSE_PPUPDATE") && atoi(getenv("NLG_FUSE_PPUPDATE")) == 0);
-        P.fused_pupdate = fuse && sem_opgradt_fuses_pupdate(m);
-    }
+    P.fused_pupdate = sem_opgradt_fuses_pupdate(m);
     if (P.precond && (m->dim == 3 || (c.pprecond == 0 && m->pprec.overlap))) {
         P.rz_part = op->d_part + 2 * m->E;
         P.rz_n = m->dim == 3 ? (int)((m->E + 3) / 4) : (int)((m->E * m->np2 + NT - 1) / NT);
@@ -2327,10 +2323,7 @@ int nlg_linop_init(nlg_linop *op) {
             NLG_LAUNCH(k_recipmask, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, op->pcv[k][c], (const double *)dg,
                                (const double *)m->d_mask[c]);
     }
-    if (op->use_xp < 0) {
-        const char *ev = getenv("NLG_XP");
-        op->use_xp = (dim == 3 && !(m->n > 8 && getenv("NLG_AXHELM_CUBE") && atoi(getenv("NLG_AXHELM_CUBE")) != 0) && m->d_slot_xp && (m->gs.d_indices_xp || m->gs.ngroups == 0) && !(ev && atoi(ev) == 0)) ? 1 : 0;
-    }
+    if (op->use_xp < 0) op->use_xp = (dim == 3 && m->d_slot_xp && (m->gs.d_indices_xp || m->gs.ngroups == 0)) ? 1 : 0;
     if (op->use_xp > 0) {
         for (int k = 1; k <= op->cfg.torder; ++k) {
             for (int c = 0; c < dim; ++c)

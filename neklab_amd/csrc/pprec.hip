@@ -531,9 +531,6 @@ __global__ __launch_bounds__(64, 4) void k_fdm_ext_mfma8(const double *__restric
 }
 
 // z += (own + neighbours' ghost values at this point, from W after QQ^T) + prolonged coarse correction; r.z and z sums
-// relative weight of the coarse-level correction in the additive sum (1 = plain additive; NLG_COARSE_SCALE for experiments: PCG does not
-// care about the overall scale of a preconditioner, but it does about the balance of its two terms)
-__device__ __constant__ double c_coarse_scale = 1.0;
 
 template <int N>
 __global__ __launch_bounds__(NT) void k_sch_finish(const double *__restrict__ flag, int64_t E, const double *__restrict__ W,
@@ -586,7 +583,7 @@ __global__ __launch_bounds__(NT) void k_sch_finish(const double *__restrict__ fl
 #pragma unroll
                 for (int c = 0; c < 8; ++c) av[c] = agg[vv[c]];
 #pragma unroll
-                for (int c = 0; c < 8; ++c) cv[c] = c_coarse_scale * (xc[vv[c]] + xa[av[c]]);
+                for (int c = 0; c < 8; ++c) cv[c] = xc[vv[c]] + xa[av[c]];
             }
 #pragma unroll
             for (int it = 0; it < NIT; ++it)
@@ -1357,10 +1354,6 @@ int up(const std::vector<T> &v, T **d) {
 namespace nlg {
 
 int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
-    if (getenv("NLG_COARSE_SCALE")) {
-        const double cs = atof(getenv("NLG_COARSE_SCALE"));
-        NLG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_coarse_scale), &cs, sizeof(double)));
-    }
     nlg_pprec &P = m->pprec;
     nlg_ctx *ctx = m->ctx;
     hipStream_t st = ctx->stream;
@@ -1744,15 +1737,13 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
         std::vector<int> nb;
         // several ranks: the hats of the vertices on a rank boundary are cut there, and the two halves of one hat are
         // coupled as strongly as the operator penalises a jump, which inflates the diagonal the vertex-level Jacobi term
-        // divides by.  Such vertices therefore become aggregates of their own (mode 1): the aggregate level is global,
+        // divides by.  Such vertices therefore become aggregates of their own: the aggregate level is global,
         // knows the coupling between the halves and solves them exactly; their Jacobi term is dropped.
         // 3 x 16^3 elements, pressure iterations per time step: plain 2x2x2 aggregates 41.75, planar 2x2 patches of
-        // boundary vertices 21 (mode 2), the same without their Jacobi term 16.5 (mode 3), singletons 12.75 (mode 1);
-        // one rank 12.5.
-        int iface_mode = 1;
-        if (const char *ev = getenv("NLG_IFACE_AGG")) iface_mode = atoi(ev);
-        if (!(ctx->distributed() && ctx->nranks > 1)) iface_mode = 0;
-        if (iface_mode) {
+        // boundary vertices 21, the same without their Jacobi term 16.5, singletons 12.75 (the two patch variants were
+        // removed); one rank 12.5.
+        const bool iface = ctx->distributed() && ctx->nranks > 1;
+        if (iface) {
             for (int idx : m->halo.h_cidx) {
                 const int64_t e = idx / np1;
                 const int pt = idx % np1;
@@ -1767,12 +1758,11 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
                     const int v = vg[(size_t)e * NC + c];
                     if (viface[v] && agg[v] < 0) ++cnt;
                 }
-                if (iface_mode == 1 ? cnt < 1 : cnt < NC / 2) continue;
+                if (cnt < 1) continue;
                 for (int c = 0; c < NC; ++c) {
                     const int v = vg[(size_t)e * NC + c];
-                    if (viface[v] && agg[v] < 0) agg[v] = iface_mode == 1 ? na++ : na;
+                    if (viface[v] && agg[v] < 0) agg[v] = na++;
                 }
-                if (iface_mode != 1) ++na;
             }
         }
         // an element whose corners are all free becomes an aggregate (2 x 2 x 2 vertices on structured meshes): the
@@ -1787,7 +1777,7 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
             for (int c = 0; c < NC; ++c) agg[vg[(size_t)e * NC + c]] = na;
             ++na;
         }
-        if (iface_mode)   // the far-side corners of the boundary elements
+        if (iface)   // the far-side corners of the boundary elements
             for (int64_t e = 0; e < E; ++e) {
                 int cnt = 0;
                 for (int c = 0; c < NC; ++c)
@@ -1814,7 +1804,7 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
                 }
             agg[v] = best >= 0 ? best : na++;
         }
-        if (iface_mode == 1 || iface_mode == 3)
+        if (iface)
             for (int v = 0; v < nvert; ++v)
                 if (viface[v]) dinv[v] = 0.0;
     }
@@ -2000,24 +1990,6 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
         NLG_HIP(hipGetLastError());
         NLG_HIP(hipMalloc(&d_full, sizeof(double) * (size_t)ntot * ntot));
         NLG_TRY(allgather_f64(ctx, d_rows, d_full, (int64_t)na_max * ntot));
-        if (getenv("NLG_PPREC_DEBUG")) {
-            std::vector<double> F((size_t)ntot * ntot);
-            NLG_HIP(hipMemcpyAsync(F.data(), d_full, sizeof(double) * F.size(), hipMemcpyDeviceToHost, st));
-            NLG_HIP(hipStreamSynchronize(st));
-            double amax = 0.0, asym = 0.0, rowsum = 0.0, offb = 0.0;
-            for (int64_t i = 0; i < ntot; ++i) {
-                double rs = 0.0;
-                for (int64_t j = 0; j < ntot; ++j) {
-                    amax = std::max(amax, std::fabs(F[i * ntot + j]));
-                    asym = std::max(asym, std::fabs(F[i * ntot + j] - F[j * ntot + i]));
-                    rs += F[i * ntot + j];
-                    if (i / na_max != j / na_max) offb = std::max(offb, std::fabs(F[i * ntot + j]));
-                }
-                rowsum = std::max(rowsum, std::fabs(rs));
-            }
-            fprintf(stderr, "[pprec rank %d] ntot %lld na %d ni %d  max|A| %.3e  asym %.3e  max|row sum| %.3e  max off-block %.3e\n", me,
-                    (long long)ntot, na, (int)ifa.size(), amax, asym, rowsum, offb);
-        }
         int *d_na_of = nullptr;
         NLG_TRY(up(na_all, &d_na_of));
         const double alpha = m->has_outflow ? 0.0 : tr_all / nreal / nreal;
@@ -2116,8 +2088,7 @@ int pprec_coarse(nlg_mesh *m, hipStream_t st, const double *flag, const double *
         NLG_LAUNCH(k_q1_restrict_local<2>, gq, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, uu, ld, P.lt, P.lW);
     }
     // 3-D overlapping variant: the rest of the coarse chain rides in the launches of the fine level (pprec_fine, merged launches)
-    static const bool hfuse = !(getenv("NLG_HFUSE") && atoi(getenv("NLG_HFUSE")) == 0);
-    P.coarse_pending = hfuse && overlap && m->gs.npairs > 0 && (m->dim == 2 ? nl == 1 : m->gs.d_indices_fg != nullptr);
+    P.coarse_pending = overlap && m->gs.npairs > 0 && (m->dim == 2 ? nl == 1 : m->gs.d_indices_fg != nullptr);
     if (P.coarse_pending) {
         NLG_HIP(hipGetLastError());
         *xc = P.d_x;
@@ -2268,15 +2239,14 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
         nb_agg = fused ? (P.na + WPE_ - 1) / WPE_ : 0;   /* (b) + aggregate restriction: one wave per aggregate */     \
         NLG_LAUNCH((k_fdm_ext<N_, 1, WPE_>), dim3((unsigned)(E + nb_agg), (unsigned)nl), dim3(64 * WPE_), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, r, P.d_wq, P.d_W, z, (const int *)P.d_exttab, ld, P.lW, (int)E, ag); \
     } break;
-        // lx1 = 8: the six transforms on the matrix pipe (k_fdm_ext_mfma8); NLG_FDM_MFMA=0 selects the vector-pipe kernel (A/B runs)
-        static const bool fdm_mfma = !(getenv("NLG_FDM_MFMA") && atoi(getenv("NLG_FDM_MFMA")) == 0);
-        if (m->n == 8 && fdm_mfma) {
-            nb_agg = fused ? P.na : 0;
-            NLG_LAUNCH(k_fdm_ext_mfma8, dim3((unsigned)(E + nb_agg), (unsigned)nl), dim3(64), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, r, P.d_wq, P.d_W, z,
-                       (const int *)P.d_exttab, ld, P.lW, (int)E, ag);
-        } else
         switch (m->n) {
-            FX_CASE(4) FX_CASE(5) FX_CASE(6) FX_CASE(7) FX_CASE(8) FX_CASE(9) FX_CASE(10) FX_CASE(12)
+            FX_CASE(4) FX_CASE(5) FX_CASE(6) FX_CASE(7)
+            case 8:   // the six transforms on the matrix pipe
+                nb_agg = fused ? P.na : 0;
+                NLG_LAUNCH(k_fdm_ext_mfma8, dim3((unsigned)(E + nb_agg), (unsigned)nl), dim3(64), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, r, P.d_wq, P.d_W, z,
+                           (const int *)P.d_exttab, ld, P.lW, (int)E, ag);
+                break;
+            FX_CASE(9) FX_CASE(10) FX_CASE(12)
             default: set_error("pprec: overlapping variant built for lx1 = 4..10 and 12, got %d", m->n); return 1;
         }
 #undef FX_CASE

@@ -9,7 +9,7 @@
 // The Nek5000 routines behind those calls are restated from the published algorithm.
 //
 // Kernel / roofline summary (fp64, all HBM-bound; algorithmic bytes per element, n = lx1):
-//   k_axhelm3   : (16*NF + 56) n^3 B   (u in, w out, 6 metric factors + mass)          12n^4+20n^3 flop/field
+//   k_axhelm3r/c: (16*NF + 56) n^3 B   (u in, w out, 6 metric factors + mass)          12n^4+20n^3 flop/field
 //   k_gs        : 20 B per shared local dof and field (value in/out + 4-byte index)
 //   k_opgradt3  : 8 n2^3 (1 + 9) + 24 n^3 B ; k_opdiv3 : 24 n^3 + 8 n2^3 (9 + 1) B
 #include <algorithm>
@@ -518,105 +518,6 @@ __global__ __launch_bounds__(NT) void k_colmul(F3 w, CF3 wt, int64_t n, int64_t 
 // 3-D: (N x N) threads per element sweep the k-slabs; u column and w column live in registers,
 // the r/s contractions go through an LDS slab, geometric factors are read once for NF fields.
 // =================================================================================================
-// One thread per (i, j, field), runtime sweep over the k-slabs.  The element's u and the three metric-weighted
-// derivative fields live in LDS cubes, so no register array is indexed by k (a fully unrolled register-column
-// version made hipcc allocate 256 VGPRs and spill ~200 more: 1.9 ms per launch at E = 10k instead of ~0.15 ms).
-// The fields of one element sit in different waves of the same block: the metric factors come from HBM once and
-// are served to the other fields by L1.
-template <int N>
-__global__ __launch_bounds__(512) void k_axhelm3(int64_t E, int nf, int epb, const double *__restrict__ Dg,
-                                                const double *__restrict__ G0, const double *__restrict__ G1,
-                                                const double *__restrict__ G2, const double *__restrict__ G3,
-                                                const double *__restrict__ G4, const double *__restrict__ G5,
-                                                const double *__restrict__ bm1, CF3 u, F3 w, double h1, double h2,
-                                                double *__restrict__ pw_part, CF3 zf, const double *__restrict__ beta_p,
-                                                const double *__restrict__ done_p, int64_t uoff) {
-    constexpr int NP = N * N * N, NS = N * N;
-    extern __shared__ double smem[];
-    __shared__ double sred[8];
-    double *sD = smem;                   // N*N
-    const int tid = threadIdx.x;
-    const int slot = tid / NS;           // (element, field) slot inside the block
-    const int ij = tid % NS;
-    const int i = ij % N, j = ij / N;
-    double *sU = smem + NS + (size_t)slot * 4 * NP;
-    double *sR = sU + NP, *sS = sR + NP, *sT = sS + NP;
-    for (int p = tid; p < NS; p += blockDim.x) sD[p] = Dg[p];
-    const int64_t gslot = (int64_t)blockIdx.x * epb + slot;   // epb = (element, field) slots per block
-    const int64_t e = gslot / nf;
-    const int c = (int)(gslot % nf);
-    const bool act = e < E;
-    const int64_t base = (act ? e : 0) * NP;
-    const double *uc = c == 0 ? u.p[0] : (c == 1 ? u.p[1] : u.p[2]);
-    double *wc = c == 0 ? w.p[0] : (c == 1 ? w.p[1] : w.p[2]);
-    // fused direction update of the surrounding PCG (beta_p != null): u <- z + beta u before the operator is applied,
-    // unless the solver has converged (the separate update kernel is gated the same way)
-    if (done_p && done_p[0] != 0.0) return;   // converged: nothing consumes w any more
-    const bool upd = beta_p != nullptr && done_p[0] == 0.0;
-    const double beta = upd ? beta_p[0] : 0.0;
-    const double *zc = c == 0 ? zf.p[0] : (c == 1 ? zf.p[1] : zf.p[2]);
-#pragma unroll 1
-    for (int k = 0; k < N; ++k) {
-        double v = act ? uc[base + ij + k * NS] : 0.0;
-        if (upd && act) {
-            v = zc[base + ij + k * NS] + beta * v;
-            const_cast<double *>(uc)[uoff + base + ij + k * NS] = v;   // uoff: the updated direction goes to the next slot of the direction history (0 = in place)
-        }
-        sU[ij + k * NS] = v;
-    }
-    __syncthreads();
-    double di[N], dj[N], dti[N], dtj[N];
-#pragma unroll
-    for (int l = 0; l < N; ++l) {
-        di[l] = sD[i * N + l];
-        dj[l] = sD[j * N + l];
-        dti[l] = sD[l * N + i];
-        dtj[l] = sD[l * N + j];
-    }
-#pragma unroll 1
-    for (int k = 0; k < N; ++k) {
-        const int64_t q = base + ij + k * NS;
-        const double g0 = G0[q], g1 = G1[q], g2 = G2[q], g3 = G3[q], g4 = G4[q], g5 = G5[q];
-        double ur = 0.0, us = 0.0, ut = 0.0;
-#pragma unroll
-        for (int l = 0; l < N; ++l) {
-            ur += di[l] * sU[l + N * j + k * NS];
-            us += dj[l] * sU[i + N * l + k * NS];
-            ut += sD[k * N + l] * sU[ij + l * NS];
-        }
-        sR[ij + k * NS] = h1 * (g0 * ur + g1 * us + g2 * ut);
-        sS[ij + k * NS] = h1 * (g1 * ur + g3 * us + g4 * ut);
-        sT[ij + k * NS] = h1 * (g2 * ur + g4 * us + g5 * ut);
-    }
-    __syncthreads();
-    double pw = 0.0;
-#pragma unroll 1
-    for (int k = 0; k < N; ++k) {
-        const int64_t q = base + ij + k * NS;
-        double a = h2 * bm1[q] * sU[ij + k * NS];
-#pragma unroll
-        for (int l = 0; l < N; ++l)
-            a += dti[l] * sR[l + N * j + k * NS] + dtj[l] * sS[i + N * l + k * NS] + sD[l * N + k] * sT[ij + l * NS];
-        if (act) {
-            wc[q] = a;
-            pw += a * sU[ij + k * NS];
-        }
-    }
-    if (pw_part) {
-        // first-stage sum of u . w_local of the surrounding PCG: for a continuous u this is (u, QQ^T w_local) with
-        // the inverse-multiplicity weight, so the solver needs no separate pass over p and w
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pw += __shfl_down(pw, o, 64);
-        if ((tid & 63) == 0) sred[tid >> 6] = pw;
-        __syncthreads();
-        if (tid == 0) {
-            double a = 0.0;
-            for (int q = 0; q < (int)((blockDim.x + 63) >> 6); ++q) a += sred[q];
-            pw_part[blockIdx.x] = a;
-        }
-    }
-}
-
 // LDS hand-over between the lanes of ONE wave: LDS operations of a wave execute in order, so no s_barrier is needed;
 // the fence keeps the compiler from moving LDS accesses across the point.
 __device__ __forceinline__ void wave_lds_sync() {
@@ -638,8 +539,13 @@ __device__ __forceinline__ double readlane_f64(double v, int srclane) {
 // t contraction stays in registers.  A wave only ever touches its own slabs and LDS operations of one wave execute in
 // order, so the kernel needs no barrier at all; ~2.5 KB of LDS per wave, occupancy set by registers alone.
 // XP: u, zf and w live in the x-planes-first layout (xp_slot); the metric factors stay natural.
-template <int N, int WPB, bool XP>
-__global__ __launch_bounds__(64 * WPB) void k_axhelm3r(int64_t E, int nf, const double *__restrict__ Dg,
+// Three waves = (element, field) slots per block: the three components of ONE element share a block, hence an XCD and its L2 --
+// the seven metric arrays are 37 % of the kernel's bytes, and with four slots per block two thirds of the elements had their
+// components in two blocks, i.e. on two XCDs (measured traffic 1.18 x algorithmic).  Same box: 5.62 (four) -> 5.46 (three) ms
+// per step, 6.46 with six.
+constexpr int kAxhelm3rWaves = 3;
+template <int N, bool XP>
+__global__ __launch_bounds__(64 * kAxhelm3rWaves) void k_axhelm3r(int64_t E, int nf, const double *__restrict__ Dg,
                                                        const double *__restrict__ G0, const double *__restrict__ G1,
                                                        const double *__restrict__ G2, const double *__restrict__ G3,
                                                        const double *__restrict__ G4, const double *__restrict__ G5,
@@ -647,7 +553,7 @@ __global__ __launch_bounds__(64 * WPB) void k_axhelm3r(int64_t E, int nf, const 
                                                        double *__restrict__ pw_part, CF3 zf, const double *__restrict__ beta_p,
                                                        const double *__restrict__ done_p, const int *__restrict__ xptab, int64_t ld, int64_t uoff) {
     static_assert(N * N <= 64, "one lane per (i, j)");
-    constexpr int NP = N * N * N, NS = N * N, NQ = N + 1;
+    constexpr int NP = N * N * N, NS = N * N, NQ = N + 1, WPB = kAxhelm3rWaves;
     __shared__ double sD[N * N];
     __shared__ double sU[WPB][N * NQ], sR[WPB][N * NQ], sS[WPB][N * NQ];
     __shared__ double sred[WPB];
@@ -932,18 +838,21 @@ __device__ __forceinline__ void lds_barrier() {
 // Register-column variant for N > 8: one block of ceil(N N / 64) waves per (element, field); thread (i, j) keeps its
 // k-column of u and of w in registers as in k_axhelm3r, the three N x N slabs are shared by the block's waves, so the two
 // hand-overs per slab are block barriers (two or three waves: cheap) instead of the wave-level LDS ordering.  Row k of D
-// comes from LDS at a block-uniform address (broadcast).  Replaces the LDS-cube kernel k_axhelm3, which ran at 25 % of
+// comes from LDS at a block-uniform address (broadcast).  Replaced the LDS-cube kernel k_axhelm3, which ran at 25 % of
 // the HBM roofline at lx1 = 10 (452 us for 912 MB at 6000 elements) against 58 % for k_axhelm3r at lx1 = 8.
 // PPB (element, field) pairs per block (round 3): N N threads fill only 75 - 78 % of the lanes of their waves at N = 10, 12; three pairs
 // side by side (thread -> pair tid / (N N)) fill 94 - 96 %.  Each pair has its own three slabs in LDS; the barriers are the block's.
-template <int N, bool XP = false, int PPB = 1>
+// Measured at 10^4 elements: lx1 = 12 838 -> 778 us (144 of 192 lanes -> 432 of 448), lx1 = 10 397 -> 519 us, hence one pair
+// per block below lx1 = 12.
+constexpr int axhelm3c_ppb(int n) { return n == 12 ? 3 : 1; }
+template <int N, bool XP, int PPB>
 __global__ __launch_bounds__(((PPB * N * N + 63) / 64) * 64) void k_axhelm3c(int64_t E, int nf, const double *__restrict__ Dg,
                                                                         const double *__restrict__ G0, const double *__restrict__ G1,
                                                                         const double *__restrict__ G2, const double *__restrict__ G3,
                                                                         const double *__restrict__ G4, const double *__restrict__ G5,
                                                                         const double *__restrict__ bm1, CF3 u, F3 w, double h1, double h2,
                                                                         double *__restrict__ pw_part, CF3 zf, const double *__restrict__ beta_p,
-                                                                        const double *__restrict__ done_p, const int *__restrict__ xptab, int64_t ld, int64_t uoff, int xcd_map) {
+                                                                        const double *__restrict__ done_p, const int *__restrict__ xptab, int64_t ld, int64_t uoff) {
     constexpr int NP = N * N * N, NS = N * N, NQ = N + 1, NTB = ((PPB * NS + 63) / 64) * 64, NWB = NTB / 64;
     __shared__ double sD[NS];
     __shared__ double mUa[PPB][N * NQ], mRa[PPB][N * NQ], mSa[PPB][N * NQ];
@@ -970,7 +879,7 @@ __global__ __launch_bounds__(((PPB * N * N + 63) / 64) * 64) void k_axhelm3c(int
     const int64_t pr_ = act ? pair : 0;
     int64_t e = pr_ / nf;
     int c = (int)(pr_ % nf);
-    if (PPB == 1 && nf == 3 && xcd_map) {
+    if (PPB == 1 && nf == 3) {
         // one pair per block (lx1 = 10): blocks go to the XCDs round-robin, so the three components of an element -- which read the same seven
         // metric arrays -- are given block numbers that are equal modulo 8: they run on ONE XCD, close in time, and share its L2
         // (groups of 8 elements x 3 components = 24 consecutive blocks; the elements behind the last full group keep the plain order)
@@ -1210,8 +1119,9 @@ __device__ __forceinline__ void contract(const double *__restrict__ in, double *
 // Each thread owns whole 1-D columns: it loads the N2 (or N) entries of a column once into registers and produces
 // all outputs of the contraction from them; the small interpolation / derivative matrices arrive as BY-VALUE kernel
 // arguments, i.e. in the scalar kernarg segment, so the matrix operand of every FMA is an SGPR pair and costs no
-// LDS or vector-memory traffic.  NC = velocity components processed per pass (3 when the LDS image of all three
-// fits, else 1).
+// LDS or vector-memory traffic.  All NC = 3 velocity components are in flight in one pass (lx1 <= 7; larger lx1 use the
+// in-place kernels below).  The pass is still written as a loop over components: without it the compiler schedules
+// these kernels differently.
 // elem_slot: natural ix-fastest index (FG = false) or the corner/edge/face-grouped slot fg_slot of internal.h.
 template <int N, bool FG>
 __device__ __forceinline__ int elem_slot(int a, int j, int k) {
@@ -1227,19 +1137,11 @@ struct PMats {
     double Dm[(N - 2) * N];   // D12
 };
 
-// Block size of the two pressure-mesh kernels: with all three velocity components in flight (NC = 3, lx1 <= 8) the stages
-// keep 144 - 216 of 256 threads busy; with one component at a time (NC = 1, lx1 > 8: the LDS budget) only 64 - 128 of them
-// have work, so those instantiations run with 128 threads per block (and twice the blocks per CU).
-template <int N, int NC>
-struct PBlock {
-    static constexpr int NTB = (NC == 1 && N > 8) ? 128 : 256;
-};
-
 // opgradt: w_i = sum_j T_j^T (g_ji o p),  T_j = (D12 along r_j, I12 otherwise)
-template <int N, int NC, bool FG, bool ML = true>
-__global__ __launch_bounds__(((NC == 1 && N > 8) ? 128 : 256)) void k_opgradt3(int64_t E, PMats<N> M, CF9 g, CP4 pl, F3L wl, CP4 gatel, int nl) {
+template <int N, bool FG, bool ML = true>
+__global__ __launch_bounds__(NT) void k_opgradt3(int64_t E, PMats<N> M, CF9 g, CP4 pl, F3L wl, CP4 gatel, int nl) {
     constexpr int N2 = N - 2, NS2 = N2 * N2;
-    constexpr int NT = PBlock<N, NC>::NTB;   // (shadows the file-level block size: 128 threads when one component is in flight)
+    constexpr int NC = 3;
     constexpr int NP2 = N2 * N2 * N2, NP1 = N * N * N;
     constexpr int SA = N2 * N2 * N, SB = N2 * N * N;
     __shared__ double sA[NC * 3][SA];
@@ -1336,11 +1238,11 @@ __global__ __launch_bounds__(((NC == 1 && N > 8) ? 128 : 256)) void k_opgradt3(i
 // opdiv: out = scale * sum_i sum_j g_ji o (T_j (wt_i o u_i)); wt (may hold nulls) fuses mask * binvm1 into the load
 // `pdot`/`part` (may be null): first-stage sums of the surrounding PCG, part[e] = sum_q pdot_q out_q and
 // part[E + e] = sum_q out_q over the element -- saves a separate pass over two pressure-mesh vectors.
-template <int N, int NC, bool FG, bool ML = true>
-__global__ __launch_bounds__(((NC == 1 && N > 8) ? 128 : 256)) void k_opdiv3(int64_t E, PMats<N> M, CF9 g, CF3L ul, CF3 wt, P4 outl,
+template <int N, bool FG, bool ML = true>
+__global__ __launch_bounds__(NT) void k_opdiv3(int64_t E, PMats<N> M, CF9 g, CF3L ul, CF3 wt, P4 outl,
                                                double scale, CP4 pdotl, P4 partl, CP4 gatel, int nl) {
     constexpr int N2 = N - 2, NS2 = N2 * N2;
-    constexpr int NT = PBlock<N, NC>::NTB;
+    constexpr int NC = 3;
     constexpr int NP2 = N2 * N2 * N2, NP1 = N * N * N;
     constexpr int SB = N2 * N * N, SC = N2 * N2 * N;
     constexpr int SBTOT = NC * 2 * SB, SPTOT = NC * 3 * NP2;
@@ -1498,9 +1400,10 @@ __global__ __launch_bounds__(((NC == 1 && N > 8) ? 128 : 256)) void k_opdiv3(int
     }
 }
 
-// ---- lx1 > 8 variants: one velocity component at a time through ONE LDS array ------------------------------------
-// With NC = 1 the kernels above need sA (3 N2^2 N) + sB (2 N2 N^2) doubles = 52 KB at lx1 = 12: three 128-thread blocks per CU,
-// 1.5 waves per SIMD, nothing to hide the global-load -> LDS -> barrier chain behind (14 - 31 % of the HBM roofline measured).
+// ---- lx1 >= 8 variants: one velocity component at a time through ONE LDS array -----------------------------------
+// One component at a time, the kernels above needed sA (3 N2^2 N) + sB (2 N2 N^2) doubles = 52 KB at lx1 = 12: three 128-thread blocks per CU,
+// 1.5 waves per SIMD, nothing to hide the global-load -> LDS -> barrier chain behind (14 - 31 % of the HBM roofline measured;
+// that form is gone).
 // Here the y stage runs IN PLACE: the LDS array is organised in regions, one per (i2, k) column of the y stage, of 3 N2 slots
 // (+1 pad).  The z stage of opgradt fills slots [j N2 + j2] (arrays A0 | A1 | A2); the thread that owns the region reads its
 // 3 N2 values into registers and overwrites them with the 2 N <= 3 N2 values B0 | B1 (slots [j], [N + j]); the x stage gathers
@@ -1508,7 +1411,7 @@ __global__ __launch_bounds__(((NC == 1 && N > 8) ? 128 : 256)) void k_opdiv3(int
 // pressure point in the registers of the thread that owns its z column, so the per-array products never go through LDS.
 // 30 KB (lx1 = 12) / 16 KB (lx1 = 10) per block: 5 / 10 blocks per CU.  Also used at lx1 = 8 with ONE wave per element
 // (64 x-stage columns = 64 lanes, 7.3 KB, 77 VGPRs: 21 waves per CU, no cross-wave barrier): 81 / 87 us instead of 86 / 93 us
-// for k_opgradt3 / k_opdiv3<8, 3> with their 256-thread blocks.  The 1-D matrices come from global memory through
+// for k_opgradt3 / k_opdiv3 with their 256-thread blocks at lx1 = 8 (no longer instantiated).  The 1-D matrices come from global memory through
 // wave-uniform scalar loads (compile-time indices on `const __restrict__` kernel arguments): as by-value arguments the 4 x 120
 // doubles of lx1 = 12 need 960 SGPRs, i.e. 500 of them spilled to VGPR lanes and one v_readlane per FMA.
 template <int N>
@@ -2215,15 +2118,13 @@ __global__ void k_conv_combine_adj(int dim, int64_t n, CF3 Ur, CF3 du, double *a
 // entry a wave needs has a wave-uniform address -> scalar loads straight into FMA operands (two 96-entry matrices
 // do not fit the scalar register file as kernel arguments: 366 spilled SGPRs and 2 ms per launch at E = 10k).
 // LDS leading dimensions are padded to odd values where a thread walks a row.
-// lx1 > 8: the LDS arrays exceed the 64 KB a kernel may declare statically, so they are carved out of dynamic LDS (up to
-// 160 KB per workgroup on gfx950: one block per CU): lx1 = 9, 10 keep u in LDS as before (104 KB at lx1 = 10); at lx1 = 12
-// (ULDS = false) the stage arrays alone take 134 KB and the x stages read u from global memory (41 KB per element, L2).
-// NTC threads: one per fine-mesh column along z (ND^2 = 324 at lx1 = 12 -> 384 threads).
-// Two blocks per CU wherever the LDS image allows it (lx1 <= 10: 78 KB at lx1 = 10 with u read from global memory): the launch
-// bound caps the registers at 256 -- 289 were allocated at lx1 = 10 without it, i.e. ONE block per CU -- at the price of 140 bytes
-// of scratch per lane; 17.2 -> 11.0 ms per step at lx1 = 10.
-template <int N, int ND, int NTC, bool ULDS, bool DYN, bool ML = true>
-__global__ __launch_bounds__(NTC, (DYN && N > 10) ? 1 : 2) void k_conv3(int64_t E, const double *__restrict__ Jg, const double *__restrict__ DJg,
+// Used for lx1 = 4 ... 7 and 9 (lx1 = 8, 10 and 12 run the matrix-core or plane-sweep kernels below).
+// lx1 = 9: the LDS arrays exceed the 64 KB a kernel may declare statically, so they are carved out of dynamic LDS (DYN).
+// NTC threads: one per fine-mesh column along z.
+// Two blocks per CU: the launch bound caps the registers at 256 -- 289 were allocated at lx1 = 10 without it, i.e. ONE block per
+// CU -- at the price of 140 bytes of scratch per lane; 17.2 -> 11.0 ms per step at lx1 = 10 (when this kernel still ran there).
+template <int N, int ND, int NTC, bool DYN, bool ML = true>
+__global__ __launch_bounds__(NTC, 2) void k_conv3(int64_t E, const double *__restrict__ Jg, const double *__restrict__ DJg,
                                                  CF3 Ur, CF9 GU, CF3L ul, F3L outl, int nl, int adjoint) {
     constexpr int NP = N * N * N, NPD = ND * ND * ND;
     constexpr int NQ = N | 1, NDQ = ND | 1;          // padded (odd) leading dimensions
@@ -2247,11 +2148,10 @@ __global__ __launch_bounds__(NTC, (DYN && N > 10) ? 1 : 2) void k_conv3(int64_t 
     // lanes (the vectors of a block step) one after the other: the twelve base-flow fields of the element are then served by
     // L2 / the Infinity Cache for every lane after the first
     for (int lv = 0; lv < (ML ? nl : 1); ++lv) {   // ML = false: the single-vector kernel (a runtime lane loop costs it 25 - 30 %)
-    if (ULDS)
-        for (int t = tid; t < 3 * NP; t += NT) {
-            const int c = t / NP, q = t % NP;
-            sU[c][(q % N) + NQ * (q / N)] = ul.p[lv][c][e * NP + q];
-        }
+    for (int t = tid; t < 3 * NP; t += NT) {
+        const int c = t / NP, q = t % NP;
+        sU[c][(q % N) + NQ * (q / N)] = ul.p[lv][c][e * NP + q];
+    }
     double ufr[3][ND];
     constexpr int OD = (ND + NW - 1) / NW;   // fine-index outputs per wave
     constexpr int ON = (N + NW - 1) / NW;    // coarse-index outputs per wave
@@ -2262,7 +2162,7 @@ __global__ __launch_bounds__(NTC, (DYN && N > 10) ? 1 : 2) void k_conv3(int64_t 
         for (int col = lane; col < N * N; col += 64) {
             double v[N];
 #pragma unroll
-            for (int i = 0; i < N; ++i) v[i] = ULDS ? sU[mcomp][i + NQ * col] : ul.p[lv][mcomp][e * NP + i + N * col];
+            for (int i = 0; i < N; ++i) v[i] = sU[mcomp][i + NQ * col];
 #pragma unroll
             for (int o = 0; o < OD; ++o) {
                 const int a = wave + NW * o;
@@ -2325,7 +2225,7 @@ __global__ __launch_bounds__(NTC, (DYN && N > 10) ? 1 : 2) void k_conv3(int64_t 
         for (int col = lane; col < N * N; col += 64) {
             double v[N];
 #pragma unroll
-            for (int i = 0; i < N; ++i) v[i] = ULDS ? sU[ic][i + NQ * col] : ul.p[lv][ic][e * NP + i + N * col];
+            for (int i = 0; i < N; ++i) v[i] = sU[ic][i + NQ * col];
 #pragma unroll
             for (int o = 0; o < OD; ++o) {
                 const int a = wave + NW * o;
@@ -2462,8 +2362,8 @@ __global__ __launch_bounds__(NTC, (DYN && N > 10) ? 1 : 2) void k_conv3(int64_t 
     }
 }
 
-// Plane-sweep form of the fused convective term for lx1 >= 9 (round 3).  k_conv3 above keeps the whole fine-mesh image of one
-// component in LDS (134 KB at lx1 = 12: ONE six-wave block per CU, every stage waiting on the one before it, eighteen
+// Plane-sweep form of the fused convective term (round 3; runs at lx1 = 12).  k_conv3 above, run there, kept the whole fine-mesh
+// image of one component in LDS (134 KB at lx1 = 12: ONE six-wave block per CU, every stage waiting on the one before it, eighteen
 // serialised round trips to HBM per element).  Here the z direction goes FIRST and LAST: for every fine level c
 //   S1  Z0_m = (J_z u_m)(c), Z1_m = (DJ_z u_m)(c) on the coarse (i, j) plane         thread (i, j, m) holds its column u_m(i, j, :)
 //   S2  x stage: J_x Z0, DJ_x Z0, J_x Z1 -> (a, j)                                    lanes (j, m), waves over a
@@ -3711,25 +3611,6 @@ static int xp_perm(nlg_mesh *m, double *const *src, double *const *dst, int nf, 
 int sem_to_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl, int64_t ld, double *const *wts) { return xp_perm(m, src, dst, nf, true, nl, ld, wts); }
 int sem_from_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl, int64_t ld) { return xp_perm(m, src, dst, nf, false, nl, ld); }
 
-// (element, field) slots per block of k_axhelm3: bounded by 512 threads and by 64 KB of dynamic LDS
-// waves = (element, field) slots per block of k_axhelm3r.  Three: the three components of ONE element share a block, hence an XCD and its
-// L2 -- the seven metric arrays are 37 % of the kernel's bytes, and with four slots per block two thirds of the elements had their
-// components in two blocks, i.e. on two XCDs (measured traffic 1.18 x algorithmic).  Same box: 5.62 (four) -> 5.46 (three) ms per step,
-// 6.46 with six.  NLG_AXHELM_WPB = 4 / 6 for A/B runs.
-static int axhelm3_wpb() {
-    static const int w = getenv("NLG_AXHELM_WPB") ? atoi(getenv("NLG_AXHELM_WPB")) : 3;
-    return (w == 4 || w == 6) ? w : 3;
-}
-static int axhelm3_nslot(int N) {
-    if (N <= 8) return axhelm3_wpb();   // k_axhelm3r: one wave per (element, field) slot
-    int nslot = 512 / (N * N);
-    const int lds_cap = (int)((64 * 1024 / 8 - N * N) / (4 * N * N * N));
-    if (nslot > lds_cap) nslot = lds_cap;
-    if (nslot > 6) nslot = 6;
-    if (nslot < 1) nslot = 1;
-    return nslot;
-}
-
 int sem_gs_pairs(nlg_mesh *m, double *w, const double *gate, int nl, int64_t ld, int64_t ldg) {
     if (m->gs.npairs == 0) return 0;
     F3 f = {{w, nullptr, nullptr}};
@@ -3751,31 +3632,21 @@ int sem_gs_pairs_fg(nlg_mesh *m, double *w, const double *gate, int nl, int64_t 
     return 0;
 }
 
-// pairs per block of k_axhelm3c (NLG_AXHELM_PPB=1: one pair per block, the round-2 form)
-static int axhelm3c_ppb(int n) {
-    static const int env = getenv("NLG_AXHELM_PPB") ? atoi(getenv("NLG_AXHELM_PPB")) : 0;
-    if (env == 1) return 1;
-    return n == 12 ? 3 : 1;   // measured at 10^4 elements: lx1 = 12 838 -> 778 us (144 of 192 lanes -> 432 of 448), lx1 = 10 397 -> 519 us
-}
-
 int sem_axhelm_blocks(nlg_mesh *m, int nf) {
     if (m->dim == 2) {
         const int epb = NT / (m->n * m->n) > 0 ? NT / (m->n * m->n) : 1;
         return (int)((m->E + epb - 1) / epb);
     }
-    static const bool use_cube = getenv("NLG_AXHELM_CUBE") && atoi(getenv("NLG_AXHELM_CUBE")) != 0;
-    if (m->n > 8 && !use_cube) return (int)((m->E * nf + axhelm3c_ppb(m->n) - 1) / axhelm3c_ppb(m->n));   // k_axhelm3c: PPB (element, field) pairs per block
-    const int nslot = axhelm3_nslot(m->n);
-    return (int)((m->E * nf + nslot - 1) / nslot);
+    const int slots = m->n > 8 ? axhelm3c_ppb(m->n) : kAxhelm3rWaves;   // (element, field) pairs per block of k_axhelm3c / k_axhelm3r
+    return (int)((m->E * nf + slots - 1) / slots);
 }
 
 int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h1, double h2, double *pw_part,
                double *const *zf, const double *beta_p, const double *done_p, bool xp, int nl, int64_t ld, int64_t uoff) {
     NLG_CHECK(nf >= 1 && nf <= 3, "sem_axhelm: nf=%d unsupported", nf);
     NLG_CHECK(uoff == 0 || beta_p, "sem_axhelm: an output offset for the direction without the fused direction update");
-    static const bool use_cube0 = getenv("NLG_AXHELM_CUBE") && atoi(getenv("NLG_AXHELM_CUBE")) != 0;
-    if (nl > 1 && (m->dim == 2 || (m->n > 8 && use_cube0))) {
-        // kernels without the lane dimension (2-D, the LDS-cube variant): one launch per lane at the lane's offsets
+    if (nl > 1 && m->dim == 2) {
+        // the 2-D kernel has no lane dimension: one launch per lane at the lane's offsets
         for (int v = 0; v < nl; ++v) {
             double *uu[3], *ww[3], *zz[3];
             for (int c = 0; c < nf; ++c) uu[c] = u[c] + v * ld, ww[c] = w[c] + v * ld, zz[c] = zf ? zf[c] + v * ld : nullptr;
@@ -3791,53 +3662,24 @@ int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h
     hipStream_t s = m->ctx->stream;
     NLG_CHECK(!beta_p || (zf && done_p), "sem_axhelm: the fused direction update needs zf and the done flag");
     CF3 cz = {{zf ? zf[0] : nullptr, (zf && nf > 1) ? zf[1] : nullptr, (zf && nf > 2) ? zf[2] : nullptr}};
-    static const bool use_cube = getenv("NLG_AXHELM_CUBE") && atoi(getenv("NLG_AXHELM_CUBE")) != 0;   // the LDS-cube kernel (lx1 > 8), for A/B runs
     if (m->dim == 3) {
 #define AX3(N_)                                                                                                       \
     {                                                                                                                 \
-        const int nslot = axhelm3_nslot(N_);                                                                          \
         const int64_t tot = m->E * nf;                                                                                \
-        const int grid = (int)((tot + nslot - 1) / nslot);                                                            \
-        const size_t lds = sizeof(double) * (size_t)(N_ * N_ + nslot * 4 * N_ * N_ * N_);                             \
+        const int *tab = xp ? (const int *)m->d_slot_xp : nullptr;                                                    \
         if constexpr (N_ <= 8) {                                                                                      \
-            if (xp && nslot == 3)                                                                                     \
-            NLG_LAUNCH((k_axhelm3r<N_, 3, true>), dim3(grid, nl), dim3(192), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], \
-                               m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)m->d_slot_xp, ld, uoff); \
-            else if (xp && nslot == 6)                                                                                \
-            NLG_LAUNCH((k_axhelm3r<N_, 6, true>), dim3(grid, nl), dim3(384), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], \
-                               m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)m->d_slot_xp, ld, uoff); \
-            else if (xp)                                                                                              \
-            NLG_LAUNCH((k_axhelm3r<N_, 4, true>), dim3(grid, nl), dim3(256), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], \
-                               m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)m->d_slot_xp, ld, uoff); \
-            else if (nslot == 3)                                                                                      \
-            NLG_LAUNCH((k_axhelm3r<N_, 3, false>), dim3(grid, nl), dim3(192), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], \
-                               m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)nullptr, ld, uoff); \
-            else if (nslot == 6)                                                                                      \
-            NLG_LAUNCH((k_axhelm3r<N_, 6, false>), dim3(grid, nl), dim3(384), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], \
-                               m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)nullptr, ld, uoff); \
+            const dim3 grid((unsigned)((tot + kAxhelm3rWaves - 1) / kAxhelm3rWaves), nl), block(64 * kAxhelm3rWaves); \
+            if (xp)                                                                                                   \
+                NLG_LAUNCH((k_axhelm3r<N_, true>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
             else                                                                                                      \
-            NLG_LAUNCH((k_axhelm3r<N_, 4, false>), dim3(grid, nl), dim3(256), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], \
-                               m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)nullptr, ld, uoff); \
-        } else if (use_cube)                                                                                          \
-        NLG_LAUNCH((k_axhelm3<N_>), dim3(grid), dim3(nslot * N_ * N_), lds, s, m->E, nf, nslot, m->d_D,      \
-                           m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, uoff); \
-        else                                                                                                          \
-        {                                                                                                             \
-            constexpr int PPB_ = 3;                                                                    \
-            static const int xcd3c = !(getenv("NLG_AXHELM_XCD") && atoi(getenv("NLG_AXHELM_XCD")) == 0);              \
-            const bool one = axhelm3c_ppb(N_) == 1;                                                                   \
-            const unsigned gb = (unsigned)((tot + (one ? 1 : PPB_) - 1) / (one ? 1 : PPB_));                          \
-            if (one) {                                                                                                \
-                if (xp)                                                                                               \
-                    NLG_LAUNCH((k_axhelm3c<N_, true, 1>), dim3(gb, nl), dim3(((N_ * N_ + 63) / 64) * 64), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)m->d_slot_xp, ld, uoff, xcd3c); \
-                else                                                                                                  \
-                    NLG_LAUNCH((k_axhelm3c<N_, false, 1>), dim3(gb, nl), dim3(((N_ * N_ + 63) / 64) * 64), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)nullptr, ld, uoff, xcd3c); \
-            } else {                                                                                                  \
-                if (xp)                                                                                               \
-                    NLG_LAUNCH((k_axhelm3c<N_, true, PPB_>), dim3(gb, nl), dim3(((PPB_ * N_ * N_ + 63) / 64) * 64), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)m->d_slot_xp, ld, uoff, xcd3c); \
-                else                                                                                                  \
-                    NLG_LAUNCH((k_axhelm3c<N_, false, PPB_>), dim3(gb, nl), dim3(((PPB_ * N_ * N_ + 63) / 64) * 64), 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, (const int *)nullptr, ld, uoff, xcd3c); \
-            }                                                                                                         \
+                NLG_LAUNCH((k_axhelm3r<N_, false>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
+        } else {                                                                                                      \
+            constexpr int PPB_ = axhelm3c_ppb(N_);                                                                    \
+            const dim3 grid((unsigned)((tot + PPB_ - 1) / PPB_), nl), block(((PPB_ * N_ * N_ + 63) / 64) * 64);       \
+            if (xp)                                                                                                   \
+                NLG_LAUNCH((k_axhelm3c<N_, true, PPB_>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
+            else                                                                                                      \
+                NLG_LAUNCH((k_axhelm3c<N_, false, PPB_>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
         }                                                                                                             \
     }
         NLG_FOR_N(AX3)
@@ -3920,11 +3762,6 @@ int sem_helm_diag(nlg_mesh *m, double *out, double h1, double h2) {
     return 0;
 }
 
-static bool pkern_old() {   // NLG_PKERN_OLD=1: the two-array kernels k_opgradt3 / k_opdiv3<N, 1> for lx1 > 8 (A/B runs)
-    static const bool v = getenv("NLG_PKERN_OLD") && atoi(getenv("NLG_PKERN_OLD")) != 0;
-    return v;
-}
-
 template <int N>
 static void fill_pmats(const nlg_mesh *m, PMats<N> &M) {
     const int n2 = N - 2;
@@ -3960,7 +3797,7 @@ int sem_opgradt(nlg_mesh *m, const double *p, double *const *w, bool face_groupe
 // does sem_opgradt perform the PCG direction update itself when asked to (nlg_pupd)?  3-D, lx1 >= 8: the in-place kernels
 // (lx1 = 12: the extra 2 x 10 memory operations per z column push k_opgradt3n<12> from 354 to 550 us -- more than the separate
 //  update kernel costs -- so the fusion stops at lx1 = 10)
-bool sem_opgradt_fuses_pupdate(const nlg_mesh *m) { return m->dim == 3 && m->n >= 8 && m->n <= 10 && !pkern_old(); }
+bool sem_opgradt_fuses_pupdate(const nlg_mesh *m) { return m->dim == 3 && m->n >= 8 && m->n <= 10; }
 
 // nl <= 4 pressure fields -> nl velocity-mesh field triples in one launch (block stepper); gates: per-lane done flags (may be null)
 int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const *const *w, bool face_grouped, const double *const *gate,
@@ -3980,8 +3817,6 @@ int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const
     CF9 g = rst2w_ptrs(m);
     hipStream_t s = m->ctx->stream;
     if (m->dim == 3) {
-        const bool old_big = pkern_old();
-        static const bool n8new = !(getenv("NLG_PKERN_N8") && atoi(getenv("NLG_PKERN_N8")) == 0);   // lx1 = 8: one wave per element through the in-place kernels (5 - 6 % faster than <8, 3>; NLG_PKERN_N8=0 for A/B)
         CP4 pl, gl;
         F3L wl;
         for (int v = 0; v < 4; ++v) {
@@ -3989,7 +3824,7 @@ int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const
             gl.p[v] = (v < nl && gate) ? gate[v] : nullptr;
             for (int c = 0; c < 3; ++c) wl.p[v][c] = v < nl ? w[v][c] : nullptr;
         }
-        if (m->n == 8 && nl == 1 && n8new && !old_big && sem_small_mesh(m)) {   // strong-scaling regime: three waves per element
+        if (m->n == 8 && nl == 1 && sem_small_mesh(m)) {   // strong-scaling regime: three waves per element
             const F3 w3 = {{w[0][0], w[0][1], w[0][2]}};
             const double *g0 = gate ? gate[0] : nullptr;
             if (upd) {
@@ -4007,37 +3842,30 @@ int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const
             return 0;
         }
 #define GT3_(N_, ML_)                                                                                                        \
-    {                                                                                                                  \
+    if constexpr (N_ < 8) {                                                                                            \
         PMats<N_> M;                                                                                                   \
         fill_pmats<N_>(m, M);                                                                                          \
-        if (N_ <= 8 && face_grouped && !(N_ == 8 && n8new))                                                            \
-            NLG_LAUNCH((k_opgradt3<N_, 3, true, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, pl, wl, gl, nl);    \
-        else if (N_ <= 8 && !(N_ == 8 && n8new))                                                                       \
-            NLG_LAUNCH((k_opgradt3<N_, 3, false, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, pl, wl, gl, nl);   \
-        else if (!old_big && face_grouped)                                                                             \
-            {                                                                                                          \
-                if (upd)                                                                                               \
-                    NLG_LAUNCH((k_opgradt3n<(N_ >= 8 && N_ <= 10 ? N_ : 9), true, ML_, true>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, pu);    \
-                else                                                                                                   \
-                    NLG_LAUNCH((k_opgradt3n<(N_ >= 8 ? N_ : 9), true, ML_, false>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, NoPUpd{});    \
-            }                                                                                                          \
-        else if (!old_big)                                                                                             \
-            {                                                                                                          \
-                if (upd)                                                                                               \
-                    NLG_LAUNCH((k_opgradt3n<(N_ >= 8 && N_ <= 10 ? N_ : 9), false, ML_, true>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, pu);   \
-                else                                                                                                   \
-                    NLG_LAUNCH((k_opgradt3n<(N_ >= 8 ? N_ : 9), false, ML_, false>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, NoPUpd{});   \
-            }                                                                                                          \
-        else if (face_grouped)                                                                                         \
-            NLG_LAUNCH((k_opgradt3<N_, 1, true, ML_>), dim3((unsigned)m->E), dim3(PBlock<N_, 1>::NTB), 0, s, m->E, M, g, pl, wl, gl, nl);    \
+        if (face_grouped)                                                                                              \
+            NLG_LAUNCH((k_opgradt3<N_, true, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, pl, wl, gl, nl);       \
         else                                                                                                           \
-            NLG_LAUNCH((k_opgradt3<N_, 1, false, ML_>), dim3((unsigned)m->E), dim3(PBlock<N_, 1>::NTB), 0, s, m->E, M, g, pl, wl, gl, nl);   \
+            NLG_LAUNCH((k_opgradt3<N_, false, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, pl, wl, gl, nl);      \
+    } else if (face_grouped) {                                                                                         \
+        if (upd)                                                                                                       \
+            NLG_LAUNCH((k_opgradt3n<(N_ <= 10 ? N_ : 9), true, ML_, true>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, pu);    \
+        else                                                                                                           \
+            NLG_LAUNCH((k_opgradt3n<N_, true, ML_, false>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, NoPUpd{});    \
+    } else {                                                                                                           \
+        if (upd)                                                                                                       \
+            NLG_LAUNCH((k_opgradt3n<(N_ <= 10 ? N_ : 9), false, ML_, true>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, pu);   \
+        else                                                                                                           \
+            NLG_LAUNCH((k_opgradt3n<N_, false, ML_, false>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, pl, wl, gl, nl, NoPUpd{});   \
     }
 #define GT3(N_)           \
-    if (nl == 1)          \
+    if (nl == 1) {        \
         GT3_(N_, false)   \
-    else                  \
-        GT3_(N_, true)
+    } else {              \
+        GT3_(N_, true)    \
+    }
         NLG_FOR_N(GT3)
 #undef GT3
 #undef GT3_
@@ -4092,8 +3920,6 @@ int sem_opdiv_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const 
     CF9 g = rst2w_ptrs(m);
     hipStream_t s = m->ctx->stream;
     if (m->dim == 3) {
-        const bool old_big = pkern_old();
-        static const bool n8new = !(getenv("NLG_PKERN_N8") && atoi(getenv("NLG_PKERN_N8")) == 0);   // lx1 = 8: one wave per element through the in-place kernels (5 - 6 % faster than <8, 3>; NLG_PKERN_N8=0 for A/B)
         CF3L ul;
         P4 ol, pl;
         CP4 dl, gl;
@@ -4104,7 +3930,7 @@ int sem_opdiv_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const 
             dl.p[v] = (v < nl && pdot) ? pdot[v] : nullptr;
             gl.p[v] = (v < nl && gate) ? gate[v] : nullptr;
         }
-        if (m->n == 8 && nl == 1 && n8new && !old_big && sem_small_mesh(m)) {   // strong-scaling regime: three waves per element
+        if (m->n == 8 && nl == 1 && sem_small_mesh(m)) {   // strong-scaling regime: three waves per element
             const CF3 u3 = {{u[0][0], u[0][1], u[0][2]}};
             const double *g0 = gate ? gate[0] : nullptr, *d0 = pdot ? pdot[0] : nullptr;
             double *p0 = pw_part ? pw_part[0] : nullptr;
@@ -4116,27 +3942,23 @@ int sem_opdiv_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const 
             return 0;
         }
 #define DV3_(N_, ML_)                                                                                                        \
-    {                                                                                                                  \
+    if constexpr (N_ < 8) {                                                                                            \
         PMats<N_> M;                                                                                                   \
         fill_pmats<N_>(m, M);                                                                                          \
-        if (N_ <= 8 && face_grouped && !(N_ == 8 && n8new))                                                            \
-            NLG_LAUNCH((k_opdiv3<N_, 3, true, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, ul, wt, ol, scale, dl, pl, gl, nl);  \
-        else if (N_ <= 8 && !(N_ == 8 && n8new))                                                                       \
-            NLG_LAUNCH((k_opdiv3<N_, 3, false, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, ul, wt, ol, scale, dl, pl, gl, nl); \
-        else if (!old_big && face_grouped)                                                                             \
-            NLG_LAUNCH((k_opdiv3n<(N_ >= 8 ? N_ : 9), true, ML_>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, ul, wtn, ol, scale, dl, pl, gl, nl, mb);  \
-        else if (!old_big)                                                                                             \
-            NLG_LAUNCH((k_opdiv3n<(N_ >= 8 ? N_ : 9), false, ML_>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, ul, wtn, ol, scale, dl, pl, gl, nl, mb); \
-        else if (face_grouped)                                                                                         \
-            NLG_LAUNCH((k_opdiv3<N_, 1, true, ML_>), dim3((unsigned)m->E), dim3(PBlock<N_, 1>::NTB), 0, s, m->E, M, g, ul, wt, ol, scale, dl, pl, gl, nl);  \
+        if (face_grouped)                                                                                              \
+            NLG_LAUNCH((k_opdiv3<N_, true, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, ul, wt, ol, scale, dl, pl, gl, nl);  \
         else                                                                                                           \
-            NLG_LAUNCH((k_opdiv3<N_, 1, false, ML_>), dim3((unsigned)m->E), dim3(PBlock<N_, 1>::NTB), 0, s, m->E, M, g, ul, wt, ol, scale, dl, pl, gl, nl); \
-    }
+            NLG_LAUNCH((k_opdiv3<N_, false, ML_>), dim3((unsigned)m->E), dim3(NT), 0, s, m->E, M, g, ul, wt, ol, scale, dl, pl, gl, nl); \
+    } else if (face_grouped)                                                                                           \
+        NLG_LAUNCH((k_opdiv3n<N_, true, ML_>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, ul, wtn, ol, scale, dl, pl, gl, nl, mb);  \
+    else                                                                                                               \
+        NLG_LAUNCH((k_opdiv3n<N_, false, ML_>), dim3((unsigned)m->E), dim3(PBlockN<N_>::NTB), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, ul, wtn, ol, scale, dl, pl, gl, nl, mb);
 #define DV3(N_)           \
-    if (nl == 1)          \
+    if (nl == 1) {        \
         DV3_(N_, false)   \
-    else                  \
-        DV3_(N_, true)
+    } else {              \
+        DV3_(N_, true)    \
+    }
         NLG_FOR_N(DV3)
 #undef DV3
 #undef DV3_
@@ -4283,8 +4105,7 @@ int sem_conv_setup(nlg_mesh *m, double *const *U, double **Ur, double **GU) {
     const int dim = m->dim;
     CF9 rd;
     for (int q = 0; q < 9; ++q) rd.p[q] = m->d_rstdw[q];
-    static const int use_mfma = getenv("NLG_MFMA") ? atoi(getenv("NLG_MFMA")) : 1;
-    if (dim == 3 && m->n == 8 && m->nd == 12 && use_mfma) {
+    if (dim == 3 && m->n == 8 && m->nd == 12) {
         // matrix-core path: per component one launch produces the fine-mesh value and the three derivatives
         double *ufb[3] = {sem_scratchd(m, 0), sem_scratchd(m, 1), sem_scratchd(m, 2)};
         double *du[3] = {sem_scratchd(m, 3), sem_scratchd(m, 4), sem_scratchd(m, 5)};
@@ -4368,17 +4189,12 @@ int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, d
 int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, double *const *u, const double *theta, double *out, int adjoint) {
     ProfScope ps(m->ctx, P_CONV);
     const int dim = m->dim;
-    static const bool sweep = !(getenv("NLG_CONVS_SWEEP") && atoi(getenv("NLG_CONVS_SWEEP")) == 0);   // A/B: the generic tensor kernels
-    if (sweep && dim == 3 && m->n >= 8 && m->n <= 10 && m->nd == (3 * m->n) / 2) {
+    if (dim == 3 && m->n >= 8 && m->n <= 10 && m->nd == (3 * m->n) / 2) {
         CF3 cur = {{Ur[0], Ur[1], Ur[2]}}, cgt = {{GT[0], GT[1], GT[2]}}, cu = {{u[0], u[1], u[2]}};
-        static const bool mfma = !(getenv("NLG_CONV_MFMA") && atoi(getenv("NLG_CONV_MFMA")) == 0);   // A/B: 0 = the plane-sweep kernel
-        if (mfma && m->n == 8) {
+        if (m->n == 8) {
             NLG_LAUNCH((k_conv3m_scalar<8, 12, false>), dim3((unsigned)m->E), dim3(256), 0, m->ctx->stream, m->E, (const double *)m->d_Jd, (const double *)m->d_DJd,
                        cur, cgt, cu, theta, out, adjoint);
-            NLG_HIP(hipGetLastError());
-            return 0;
-        }
-        if (mfma && m->n == 10) {
+        } else if (m->n == 10) {
             constexpr size_t lds = sizeof(double) * (2 * 16 * 100 + 3 * 225 * 10);
             static bool attr_set = false;
             if (!attr_set) {
@@ -4387,14 +4203,10 @@ int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, dou
             }
             NLG_LAUNCH((k_conv3m_scalar<10, 15, true>), dim3((unsigned)m->E), dim3(256), lds, m->ctx->stream, m->E, (const double *)m->d_Jd, (const double *)m->d_DJd,
                        cur, cgt, cu, theta, out, adjoint);
-            NLG_HIP(hipGetLastError());
-            return 0;
+        } else {
+            NLG_LAUNCH((k_conv3s_scalar<9, 13, 6>), dim3((unsigned)m->E), dim3(6 * 64), 0, m->ctx->stream, m->E, (const double *)m->d_Jd,
+                       (const double *)m->d_DJd, (const double *)m->d_Jdt, cur, cgt, cu, theta, out, adjoint);
         }
-#define CVS(N_, NW_)                                                                                                                         \
-    NLG_LAUNCH((k_conv3s_scalar<N_, (3 * N_) / 2, NW_>), dim3((unsigned)m->E), dim3(NW_ * 64), 0, m->ctx->stream, m->E, (const double *)m->d_Jd, \
-               (const double *)m->d_DJd, (const double *)m->d_Jdt, cur, cgt, cu, theta, out, adjoint);
-        if (m->n == 8) CVS(8, 4) else if (m->n == 9) CVS(9, 6) else CVS(10, 7)
-#undef CVS
         NLG_HIP(hipGetLastError());
         return 0;
     }
@@ -4447,70 +4259,49 @@ int sem_conv_apply_lanes(nlg_mesh *m, double *const *Ur, double *const *GU, int 
         for (int q = 0; q < 9; ++q) cg.p[q] = GU[q];
 #define CV3(N_)                                                                                                       \
     if (nl == 1)                                                                                                      \
-        NLG_LAUNCH((k_conv3<N_, (3 * N_) / 2, NT, true, false, false>), dim3((unsigned)m->E), dim3(NT), 0, m->ctx->stream, m->E, \
+        NLG_LAUNCH((k_conv3<N_, (3 * N_) / 2, NT, false, false>), dim3((unsigned)m->E), dim3(NT), 0, m->ctx->stream, m->E, \
                            (const double *)m->d_Jd, (const double *)m->d_DJd, cur, cg, cu, co, nl, adjoint);          \
     else                                                                                                              \
-        NLG_LAUNCH((k_conv3<N_, (3 * N_) / 2, NT, true, false, true>), dim3((unsigned)m->E), dim3(NT), 0, m->ctx->stream, m->E, \
+        NLG_LAUNCH((k_conv3<N_, (3 * N_) / 2, NT, false, true>), dim3((unsigned)m->E), dim3(NT), 0, m->ctx->stream, m->E, \
                            (const double *)m->d_Jd, (const double *)m->d_DJd, cur, cg, cu, co, nl, adjoint);
-#define CV3D(N_, NTC_, ULDS_)                                                                                          \
-    {                                                                                                                  \
-        constexpr int ND_ = (3 * N_) / 2, NQ_ = N_ | 1, NDQ_ = ND_ | 1;                                                \
-        constexpr size_t lds = sizeof(double) * (2 * NDQ_ * N_ * N_ + 3 * ND_ * ND_ * N_ + (ULDS_ ? 3 * NQ_ * N_ * N_ : 0)); \
-        static bool attr_set = false;                                                                                  \
-        if (!attr_set) {                                                                                               \
-            NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3<N_, ND_, NTC_, ULDS_, true>),          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-            attr_set = true;                                                                                           \
-        }                                                                                                              \
-        NLG_LAUNCH((k_conv3<N_, ND_, NTC_, ULDS_, true>), dim3((unsigned)m->E), dim3(NTC_), lds, m->ctx->stream, m->E, \
-                           (const double *)m->d_Jd, (const double *)m->d_DJd, cur, cg, cu, co, nl, adjoint);          \
-    }
-#define CV3S(N_, NW_, MINB_)                                                                                                    \
-    NLG_LAUNCH((k_conv3s<N_, (3 * N_) / 2, NW_, MINB_>), dim3((unsigned)(m->E * nl)), dim3(NW_ * 64), 0, m->ctx->stream, m->E, (const double *)m->d_Jd, \
-               (const double *)m->d_DJd, (const double *)m->d_Jdt, cur, cg, cu, co, nl, adjoint);
-        static const int sweep = getenv("NLG_CONV_SWEEP") ? atoi(getenv("NLG_CONV_SWEEP")) : 1;   // A/B: 0 = the LDS-image kernel k_conv3
         switch (m->n) {
             case 4: CV3(4); break;
             case 5: CV3(5); break;
             case 6: CV3(6); break;
             case 7: CV3(7); break;
-            case 8: {
-                static const bool mfma = !(getenv("NLG_CONV_MFMA") && atoi(getenv("NLG_CONV_MFMA")) == 0);   // A/B: 0 = the vector-pipe kernel k_conv3
-                if (sweep == 3)
-                    CV3S(8, 3, 3)
-                else if (mfma)
-                    NLG_LAUNCH((k_conv3m<8, 12, false>), dim3((unsigned)m->E, (unsigned)nl), dim3(256), 0, m->ctx->stream, m->E, (const double *)m->d_Jd,
-                               (const double *)m->d_DJd, cur, cg, cu, co, adjoint);
-                else
-                    CV3(8);   // (measured: see DESIGN.md section 5)
+            case 8:
+                NLG_LAUNCH((k_conv3m<8, 12, false>), dim3((unsigned)m->E, (unsigned)nl), dim3(256), 0, m->ctx->stream, m->E, (const double *)m->d_Jd,
+                           (const double *)m->d_DJd, cur, cg, cu, co, adjoint);
+                break;
+            case 9: {
+                constexpr size_t lds = sizeof(double) * (2 * 13 * 81 + 3 * 169 * 9 + 3 * 9 * 81);   // x-stage, y-stage and u arrays: 69 KB
+                static bool attr_set = false;
+                if (!attr_set) {
+                    NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3<9, 13, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    attr_set = true;
+                }
+                NLG_LAUNCH((k_conv3<9, 13, 256, true>), dim3((unsigned)m->E), dim3(256), lds, m->ctx->stream, m->E, (const double *)m->d_Jd,
+                           (const double *)m->d_DJd, cur, cg, cu, co, nl, adjoint);
             } break;
-            case 9: CV3D(9, 256, true); break;
             case 10: {
-                static const bool mfma = !(getenv("NLG_CONV_MFMA") && atoi(getenv("NLG_CONV_MFMA")) == 0);   // A/B: 0 = the plane-sweep kernel k_conv3s
-                if (mfma) {
-                    constexpr size_t lds = sizeof(double) * (2 * 16 * 100 + 3 * 225 * 10);   // 79.6 KB: two blocks per CU
-                    static bool attr_set = false;
-                    if (!attr_set) {
-                        NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3m<10, 15, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                        attr_set = true;
-                    }
-                    NLG_LAUNCH((k_conv3m<10, 15, true>), dim3((unsigned)m->E, (unsigned)nl), dim3(256), lds, m->ctx->stream, m->E, (const double *)m->d_Jd,
-                               (const double *)m->d_DJd, cur, cg, cu, co, adjoint);
-                } else if (sweep)
-                    CV3S(10, 5, 2)
-                else
-                    CV3D(10, 256, false);   // (u from global memory: 78 KB of LDS instead of 104 KB, two blocks per CU)
+                constexpr size_t lds = sizeof(double) * (2 * 16 * 100 + 3 * 225 * 10);   // 79.6 KB: two blocks per CU
+                static bool attr_set = false;
+                if (!attr_set) {
+                    NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3m<10, 15, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    attr_set = true;
+                }
+                NLG_LAUNCH((k_conv3m<10, 15, true>), dim3((unsigned)m->E, (unsigned)nl), dim3(256), lds, m->ctx->stream, m->E, (const double *)m->d_Jd,
+                           (const double *)m->d_DJd, cur, cg, cu, co, adjoint);
             } break;
             default:
                 // lx1 = 12 stays on the plane-sweep kernel: lxd = 18 needs a SECOND 16-row tile for fine rows 16, 17 in every forward
                 // pass (3252 MFMA per element against 1320 at lx1 = 10) and 137 KB of LDS, i.e. one block per CU; built and measured
                 // (k_conv3m<12, 18>, parity green): 3.10 ms per launch against 3.10 ms -- a tie, so the instantiation was dropped
-                if (sweep) CV3S(12, 7, 1) else CV3D(12, 384, false);
+                NLG_LAUNCH((k_conv3s<12, 18, 7, 1>), dim3((unsigned)(m->E * nl)), dim3(7 * 64), 0, m->ctx->stream, m->E, (const double *)m->d_Jd,
+                           (const double *)m->d_DJd, (const double *)m->d_Jdt, cur, cg, cu, co, nl, adjoint);
                 break;
         }
 #undef CV3
-#undef CV3D
-#undef CV3S
         NLG_HIP(hipGetLastError());
         return 0;
     }

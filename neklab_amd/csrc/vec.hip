@@ -955,13 +955,12 @@ int basis_cgs2_dev(nlg_basis *b, int k, nlg_vec *w) {
             // rounding, at two thirds of the traffic
             // (measured, CGS2 + norm + scale at 10^4 elements: k = 64: 6.29 -> 4.94 ms, 32: 3.28 -> 2.79, 16: 1.78 -> 1.88,
             // 8: 1.04 -> 1.46 — the fully unrolled KMAX = 64 kernel does all 128 FMAs whatever k — hence the lower bound)
-            static const int fuse_max = getenv("NLG_CGS2_FUSE_MAX") ? atoi(getenv("NLG_CGS2_FUSE_MAX")) : 128;
-            if (k >= 24 && fuse_max >= 24) {
-                // first subtraction and second projection in one sweep over the LAST kf <= 64 basis vectors
+            if (k >= 24) {
+                // first subtraction and second projection in one sweep over the LAST kf <= 128 basis vectors
                 // (k_block_axpy_dot); the k0 = k - kf vectors before them are subtracted first and projected after
                 const nlg_vec *v0 = b->views[0];
                 // k <= 64: one register tile (k_block_axpy_dot<64>); up to 128: two tiles, the second parked in LDS (k_block_axpy_dot2<64>)
-                const int kf = std::min(std::min(k, fuse_max), 128) > 64 ? std::min(std::min(k, fuse_max), 128) : std::min(std::min(k, fuse_max), 64);
+                const int kf = std::min(k, 128);
                 const int k0 = k - kf;
                 const int64_t nv = (int64_t)v0->ncomp * b->mesh->lvs;   // velocity (+ scalar) part; the pressure follows
                 const int G = 256;                                     // one block per CU (one wave per SIMD)

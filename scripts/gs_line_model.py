@@ -1,5 +1,6 @@
 """Block-level traffic model of the gather-scatter k_gs<3> on an 8x8x8-element box, lx1 = 8: which thread block fetches which 128-byte line, for the
-natural, slab-permuted (xp), pair-interleaved (xp2 = NLG_XP_LAYOUT=1) and face-grouped layouts (DESIGN.md section 5, round-4 lessons).  CPU only."""
+natural, slab-permuted (xp), pair-interleaved (xp2) and face-grouped layouts (DESIGN.md section 5, round-4 lessons).  CPU only.
+The pair-interleaved layout xp2 was built, measured and removed from the product; it lives on here only as a model."""
 import numpy as np, sys
 import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neklab_amd.mesh import box_mesh

@@ -1,8 +1,7 @@
 """Workload for the MFMA counters: the base-flow side of the convective term (sem_conv_setup -> k_interp4_mfma<8,12>) at
 the benchmark size, E = 10 000, lx1 = 8: what the nonlinear map of the Newton-Krylov solver runs once per time step.
     rocprofv3 --kernel-trace --stats -d out -o mfma -- python3 scripts/mfma_profile.py
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d out2 -- python3 scripts/mfma_profile.py
-NLG_MFMA=0 selects the generic tensor kernel for the comparison."""
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --output-format csv -d out2 -- python3 scripts/mfma_profile.py"""
 import os
 import sys
 

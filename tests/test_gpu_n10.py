@@ -1,6 +1,6 @@
 """The lx1 > 8 kernel instantiations (BASELINE.json configs 4 and 5: lx1 = 10, 12) inside the time stepper, against the
-oracle: k_axhelm3c<10|12> (register columns, block barriers), the 128-thread k_opgradt3 / k_opdiv3<N, 1>, the multi-wave
-k_fdm_ext<N, 1, 2|3>, the dynamic-LDS k_conv3<10, 15> / <12, 18>, natural-layout velocity PCG.  Tolerance mode with the
+oracle: k_axhelm3c<10|12> (register columns, block barriers), the in-place k_opgradt3n / k_opdiv3n<N>, the multi-wave
+k_fdm_ext<N, 1, 2|3>, the matrix-pipe k_conv3m<10, 15> and the plane-sweep k_conv3s<12, 18>, slab-permuted velocity PCG.  Tolerance mode with the
 two-level Schwarz preconditioner (1e-9) and fixed iteration counts with Jacobi (1e-11), direct and adjoint."""
 import numpy as np
 import pytest

@@ -1,6 +1,7 @@
 """GPU parity of the propagator and the Arnoldi step against the oracle at lx1 = 8 in 3-D: the kernel instantiations the
-headline benchmark is made of (k_axhelm3r<8,4> with the fused direction update and (p, w) sums, k_cg_update<3>, face-grouped
-k_opdiv3 / k_opgradt3<8,3>, k_fdm_ext<8,1>, k_sch_finish<8>, k_conv3<8,12>, the done-flag gating, the pressure projection),
+headline benchmark is made of (k_axhelm3r<8> with the fused direction update and (p, w) sums, k_cg_update<3>, face-grouped
+k_opdiv3w / k_opgradt3w<8> (k_opdiv3n / k_opgradt3n<8> above 4096 elements), k_fdm_ext_mfma8, k_sch_finish<8>, k_conv3m<8,12>,
+the done-flag gating, the pressure projection),
 inside the time stepper rather than operator by operator.
 
 Two modes.  Fixed iteration counts with the Jacobi preconditioner (pprecond = 1): the iteration is the oracle's own, so
