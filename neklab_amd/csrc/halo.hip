@@ -45,7 +45,7 @@ template <int NF>
 __global__ __launch_bounds__(NT) void k_halo_unpack(int64_t nlab, const int *__restrict__ roff,
                                                     const int *__restrict__ rpos, const int *__restrict__ coff,
                                                     const int *__restrict__ cidx, int64_t ntot,
-                                                    const double *__restrict__ buf, F3 f, int64_t ld) {
+                                                    const double *__restrict__ buf, F3 f, int64_t ld, bool assign) {
     const int64_t l = blockIdx.x * (int64_t)NT + threadIdx.x;
     if (l >= nlab) return;
     buf += (int64_t)blockIdx.y * NF * ntot;
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(NT) void k_halo_unpack(int64_t nlab, const int *__r
     for (int q = coff[l]; q < coff[l + 1]; ++q) {
         const int i = cidx[q];
 #pragma unroll
-        for (int c = 0; c < NF; ++c) f.p[c][i] += s[c];
+        for (int c = 0; c < NF; ++c) f.p[c][i] = assign ? s[c] : f.p[c][i] + s[c];
     }
 }
 
@@ -399,7 +399,7 @@ int halo_begin(nlg_mesh *m, double *const *fields, int nf, int layout, int nl, i
     return 0;
 }
 
-int halo_finish(nlg_mesh *m, double *const *fields, int nf, int layout, int nl, int64_t ld) {
+int halo_finish(nlg_mesh *m, double *const *fields, int nf, int layout, int nl, int64_t ld, bool assign) {
     nlg_halo &h = m->halo;
     if (!h.active) return 0;
     const int *cidx = layout == LAYOUT_FG ? h.d_cidx_fg : (layout == LAYOUT_XP ? h.d_cidx_xp : h.d_cidx);
@@ -408,18 +408,18 @@ int halo_finish(nlg_mesh *m, double *const *fields, int nf, int layout, int nl, 
     F3 f = {{fields[0], nf > 1 ? fields[1] : nullptr, nf > 2 ? fields[2] : nullptr}};
     const dim3 g2((unsigned)((h.nlab + NT - 1) / NT), (unsigned)nl);
     if (nf == 1)
-        NLG_LAUNCH(k_halo_unpack<1>, g2, dim3(NT), 0, st, h.nlab, h.d_roff, h.d_rpos, h.d_coff, cidx, h.ntot, h.d_recv, f, ld);
+        NLG_LAUNCH(k_halo_unpack<1>, g2, dim3(NT), 0, st, h.nlab, h.d_roff, h.d_rpos, h.d_coff, cidx, h.ntot, h.d_recv, f, ld, assign);
     else if (nf == 2)
-        NLG_LAUNCH(k_halo_unpack<2>, g2, dim3(NT), 0, st, h.nlab, h.d_roff, h.d_rpos, h.d_coff, cidx, h.ntot, h.d_recv, f, ld);
+        NLG_LAUNCH(k_halo_unpack<2>, g2, dim3(NT), 0, st, h.nlab, h.d_roff, h.d_rpos, h.d_coff, cidx, h.ntot, h.d_recv, f, ld, assign);
     else
-        NLG_LAUNCH(k_halo_unpack<3>, g2, dim3(NT), 0, st, h.nlab, h.d_roff, h.d_rpos, h.d_coff, cidx, h.ntot, h.d_recv, f, ld);
+        NLG_LAUNCH(k_halo_unpack<3>, g2, dim3(NT), 0, st, h.nlab, h.d_roff, h.d_rpos, h.d_coff, cidx, h.ntot, h.d_recv, f, ld, assign);
     NLG_HIP(hipGetLastError());
     return 0;
 }
 
-int halo_exchange(nlg_mesh *m, double *const *fields, int nf, int layout, int nl, int64_t ld) {
+int halo_exchange(nlg_mesh *m, double *const *fields, int nf, int layout, int nl, int64_t ld, bool assign) {
     NLG_TRY(halo_begin(m, fields, nf, layout, nl, ld));
-    return halo_finish(m, fields, nf, layout, nl, ld);
+    return halo_finish(m, fields, nf, layout, nl, ld, assign);
 }
 
 void halo_free(nlg_mesh *m) {

@@ -235,12 +235,14 @@ struct nlg_pprec {
     double hat1[16] = {};                        // (1 + z2)/2 at the GL points: the 1-D hat function of the upper corner
     double *d_S = nullptr, *d_invden = nullptr;  // FDM: [E][3][n2*n2] eigenvector matrices, [E][n2^dim] 1/(sum of eigenvalues)
     double *d_dinv = nullptr;                    // 1 / diag(A_c)
-    // overlapping variant (3-D, lx1 <= 8): extended 1-D eigen-decompositions [E][3][n*n], eigenvalues [E][3][n], the
-    // velocity-shaped exchange array (face-grouped layout) and the zero-denominator threshold
+    // overlapping variant: extended 1-D eigen-decompositions [E][3][n*n], eigenvalues [E][3][n], the velocity-shaped
+    // exchange arrays and the zero-denominator threshold.  2-D: W in the natural layout, summed by pairs-only gather-scatters.
+    // 3-D: W = the extended grids (natural layout) the restriction writes and k_fdm_ext reads, Wr = the return values at the
+    // face slots (face-grouped layout) k_fdm_ext writes and k_sch_finish reads; each ghost value goes straight to its consumer
     bool overlap = false;
-    int *d_exttab = nullptr;                     // [n^3] packed per-point constants of the extended grid (k_fdm_ext)
-    int *d_wslot = nullptr;                      // [n2^3][3] face slot of W next to a pressure point per direction, -1 = none
-    double *d_Sx = nullptr, *d_lamx = nullptr, *d_W = nullptr, *d_wq = nullptr;   // d_wq: count^-1/2 weights [E][n2^3]
+    int *d_pin = nullptr;                        // 3-D: [E][6 n2^2] index in W the layer value next to an element face point goes to, -1 = none
+    int *d_pret = nullptr;                       // 3-D: [E][6 n2^2] index in Wr the solve at a ghost point goes to, -1 = none
+    double *d_Sx = nullptr, *d_lamx = nullptr, *d_W = nullptr, *d_Wr = nullptr, *d_wq = nullptr;   // d_wq: count^-1/2 weights [E][n2^3]
     double thrx = 0.0;
     int *d_agg = nullptr, *d_ap = nullptr, *d_am = nullptr;
     double *d_Ainv = nullptr;                    // dense inverse on the aggregates: this rank's rows, [na][ncols]
@@ -248,7 +250,7 @@ struct nlg_pprec {
     int na_max = 0, ncols = 0;                   // several ranks: ncols = nranks * na_max columns (global aggregate level)
     double *d_rag = nullptr;                     // [ncols] aggregate residuals of all ranks (all-gather of d_ra)
     double *d_rc = nullptr, *d_x = nullptr, *d_ra = nullptr, *d_xa = nullptr;
-    // lanes of a block step: `lanes_cap` copies of W, tq, rc / x, ra, xa at these strides (pprec_reserve_lanes)
+    // lanes of a block step: `lanes_cap` copies of W, Wr, tq, rc / x, ra, xa at these strides (pprec_reserve_lanes)
     int lanes_cap = 1;
     int64_t lW = 0, lt = 0, lv = 0, la = 0, la_x = 0;
     bool coarse_pending = false;                 // pprec_coarse has left its chain (gather, restriction, dense solve) to the merged launches of pprec_fine
@@ -392,10 +394,12 @@ bool linop_can_block(const nlg_linop *op);   // the multi-vector stepper covers 
 
 // ---- halo.hip ----
 int halo_setup(nlg_mesh *m, const int64_t *glo_num);
-int halo_exchange(nlg_mesh *m, double *const *fields, int nf, int layout = 0, int nl = 1, int64_t ld = 0);   // LAYOUT_*; = halo_begin + halo_finish
+// LAYOUT_*; = halo_begin + halo_finish.  assign: every local copy of a shared point becomes the sum of the OTHER ranks' copies
+// (copy mode: a value that exactly one element on another rank produced for this rank's element), instead of adding that sum
+int halo_exchange(nlg_mesh *m, double *const *fields, int nf, int layout = 0, int nl = 1, int64_t ld = 0, bool assign = false);
 int gs_split(nlg_mesh *m);   // builds gs.tab_halo / tab_rest from gs.h_groups and the halo lists
 int halo_begin(nlg_mesh *m, double *const *fields, int nf, int layout, int nl = 1, int64_t ld = 0);    // pack + start of the exchange
-int halo_finish(nlg_mesh *m, double *const *fields, int nf, int layout, int nl = 1, int64_t ld = 0);   // end of the exchange + unpack
+int halo_finish(nlg_mesh *m, double *const *fields, int nf, int layout, int nl = 1, int64_t ld = 0, bool assign = false);   // end of the exchange + unpack
 void halo_free(nlg_mesh *m);
 
 // ---- sem.hip (device-pointer level operators; all on ctx->stream) ----
@@ -404,7 +408,6 @@ void halo_free(nlg_mesh *m);
 int sem_gs(nlg_mesh *m, double *const *fields, int nf, const double *gate = nullptr, int layout = 0, int nl = 1, int64_t ld = 0, int64_t ldg = 0);   // in place QQ^T; gate: device flag, non-zero = skip; layout: LAYOUT_NAT or LAYOUT_XP
 int sem_to_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl = 1, int64_t ld = 0, double *const *wts = nullptr);     // natural -> x-planes-first (out of place); wts: dst = wts * src
 int sem_from_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl = 1, int64_t ld = 0);
-int sem_gs_pairs_fg(nlg_mesh *m, double *w, const double *gate = nullptr, int nl = 1, int64_t ld = 0, int64_t ldg = 0);
 int sem_gs_pairs(nlg_mesh *m, double *w, const double *gate = nullptr, int nl = 1, int64_t ld = 0, int64_t ldg = 0);   // the same in the natural layout (2-D Schwarz exchange)   // rank-local QQ^T over the two-copy groups (face interiors) of one field in the face-grouped layout
 int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h1, double h2, double *pw_part = nullptr,
                double *const *zf = nullptr, const double *beta_p = nullptr, const double *done_p = nullptr, bool xp = false, int nl = 1, int64_t ld = 0, int64_t uoff = 0);   // uoff: the updated direction is stored uoff doubles behind u (direction history of the PCG); zf: fused u <- zf + beta u; xp: u, zf, w in the x-planes-first layout (3-D, lx1 <= 8)

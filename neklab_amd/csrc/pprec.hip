@@ -239,21 +239,76 @@ __device__ __forceinline__ void agg_restrict_body(int bx, const double *flag, in
     if (lane == 0) ra[a] = s;
 }
 
+// the vertex gather and the aggregate restriction of the coarse chain, both straight from the element-corner values t: they ride
+// in the launch of k_fdm_ext*, so that the coarse chain adds one launch (k_dense_gemv) to the fine level.  The restriction
+// recomputes the vertex sums of its members in the order of the gather, so ra is bit-identical to restricting rc.
+struct ChainArgs {
+    int nb_gather;                 // blocks of the vertex gather; the blocks of the aggregate restriction follow
+    int nvert;
+    const int *vp, *vi;            // vertex -> incident (element, corner) entries, CSR
+    const double *t;
+    double *rc;
+    const double *dinv;
+    double om;
+    double *x;
+    int na;
+    const int *ap, *am;            // aggregate -> member vertices, CSR
+    double *ra;
+    int64_t lt, lv, la;
+};
+// (as a part of a merged launch: `bx` = block index inside this part, any multiple of 64 threads per block)
+__device__ __forceinline__ void chain_body(int bx, const double *flag, int64_t ld, const ChainArgs &g) {
+    if (flag) flag += (int64_t)blockIdx.y * ld;
+    if (flag && flag[0] != 0.0) return;
+    const double *__restrict__ t = g.t + (int64_t)blockIdx.y * g.lt;
+    if (bx < g.nb_gather) {   // rc[v] = sum of t over the entries incident to v (fixed order); first damped-Jacobi sweep from zero
+        double *rc = g.rc + (int64_t)blockIdx.y * g.lv, *x = g.x + (int64_t)blockIdx.y * g.lv;
+        const int v = bx * (int)blockDim.x + (int)threadIdx.x;
+        if (v >= g.nvert) return;
+        double a = 0.0;
+        for (int q = g.vp[v]; q < g.vp[v + 1]; ++q) a += t[g.vi[q]];
+        rc[v] = a;
+        x[v] = g.om * g.dinv[v] * a;
+        return;
+    }
+    // ra[a] = sum of rc over the members of aggregate a, one wave per aggregate
+    double *ra = g.ra + (int64_t)blockIdx.y * g.la;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    const int a = (bx - g.nb_gather) * wpb + wid;
+    if (a >= g.na) return;
+    double s = 0.0;
+    for (int q = g.ap[a] + lane; q < g.ap[a + 1]; q += 64) {
+        const int v = g.am[q];
+        double c = 0.0;
+        for (int j = g.vp[v]; j < g.vp[v + 1]; ++j) c += t[g.vi[j]];
+        s += c;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if (lane == 0) ra[a] = s;
+}
+
 // ---- overlapping variant (3-D) ---------------------------------------------------------------------------
 // Extended local problems: element e plus the layer of GL points of each face neighbour that is adjacent to the
 // shared face -> an N^3 grid (N = N2 + 2, the size of the velocity mesh), solved by fast diagonalisation with 1-D
-// operators built from the line of up to three elements (pprec_setup).  The ghost layers travel through the
-// velocity-mesh gather-scatter, as Nek5000's Schwarz smoother does: a velocity-shaped work array W (face-grouped
-// layout) carries, at the interior points of an element face, the values of the adjacent pressure layer; after
-// QQ^T each face holds own + neighbour's, whatever the relative orientation of the two elements.
-//   k_q1_restrict_local (pack)  W_face = r(adjacent layer)
-//   gs (pairs only)             W_face = own + neighbour
-//   k_fdm_ext                   ext = [r | W_face - own];  solve;  z = z_int - (own ghost values, folded back);
-//                               W_face = own ghost values
-//   gs (pairs only)             W_face = own ghosts + neighbour's ghosts (= neighbour's solve at MY adjacent layer)
-//   k_sch_finish                z += W_face (+ coarse correction), r.z sums
-// i.e. z = sum_e R_e^T Atilde_e^-1 R_e r with overlapping index sets R_e: symmetric, additive.
-__device__ __forceinline__ int ext_slot(int N, int a, int b, int c) { return fg_slot(N, a, b, c); }
+// operators built from the line of up to three elements (pprec_setup).  Every ghost value is written once, by its
+// producer, into the slot its consumer reads (the destinations per element face point come from pprec_setup: pin, pret):
+//   k_q1_restrict_local (pack)  Win[e]         = extended grid of e: r wq in the interior, and each element writes r wq of
+//                                                its adjacent layers into the ghost slots of its neighbours' grids
+//   k_fdm_ext                   z_e = interior of the solve on Win[e];  the solve at the ghost points -> the neighbour's
+//                                                face slot of Wret (face-grouped layout)
+//   k_sch_finish                z += Wret at the element's faces (+ coarse correction), r.z sums
+// i.e. z = sum_e R_e^T Atilde_e^-1 R_e r with overlapping index sets R_e: symmetric, additive.  Win (natural layout) and
+// Wret are two arrays: a solve reads its grid while the neighbours' solves write their ghost values.  Edge and corner
+// slots, and the ghost slots of faces without a neighbour, are never written and stay zero.  A face on a rank boundary
+// has the element itself as destination: the copy-mode halo exchange replaces the own value by the neighbour's.
+__device__ __forceinline__ int face_pt(int N, int a, int b, int c) {
+    // compact index (0 .. 6 (N-2)^2 - 1) of an interior point of an element face of the N^3 grid, the order of fg_slot
+    const int M = N - 2;
+    if (a == 0 || a == N - 1) return (a == N - 1) * M * M + (b - 1) + M * (c - 1);
+    if (b == 0 || b == N - 1) return (2 + (b == N - 1)) * M * M + (a - 1) + M * (c - 1);
+    return (4 + (c == N - 1)) * M * M + (a - 1) + M * (b - 1);
+}
 
 // WPB waves (= elements) per block.  WPB = 1 makes every __syncthreads a single-wave barrier: the stages of one element
 // never wait for another element's.
@@ -261,20 +316,20 @@ __device__ __forceinline__ int ext_slot(int N, int a, int b, int c) { return fg_
 // with 64 lanes in two (three) rounds, 56 % (75 %) of them busy; two (three) waves take one column per lane.
 template <int N, int WPB, int WPE = 1>
 __global__ __launch_bounds__(64 * WPB * WPE) void k_fdm_ext(const double *__restrict__ flag, int64_t E, const double *__restrict__ S,
-                                                const double *__restrict__ lam, double thr, const double *__restrict__ r,
-                                                const double *__restrict__ wq, double *__restrict__ W,
-                                                double *__restrict__ z, const int *__restrict__ tab, int64_t ld, int64_t lW, int nb_fdm, AggArgs ag) {
-    constexpr int N2 = N - 2, NP = N * N * N, NP2 = N2 * N2 * N2;
+                                                const double *__restrict__ lam, double thr, const double *__restrict__ Win,
+                                                double *__restrict__ Wr, double *__restrict__ z, const int *__restrict__ pret,
+                                                int64_t ld, int64_t lW, int nb_fdm, ChainArgs cg) {
+    constexpr int N2 = N - 2, NP = N * N * N, NP2 = N2 * N2 * N2, NF = 6 * N2 * N2;
     __shared__ double sL[WPB][3][N];
     __shared__ double sA[WPB][NP];   // the six transforms run in place (fdm_stage_inplace3)
-    if ((int)blockIdx.x >= nb_fdm) {   // merged launch: the blocks behind the elements restrict the coarse residual to the aggregates
-        agg_restrict_body((int)blockIdx.x - nb_fdm, flag, ld, ag);
+    if ((int)blockIdx.x >= nb_fdm) {   // merged launch: the blocks behind the elements run the coarse chain up to the dense solve
+        chain_body((int)blockIdx.x - nb_fdm, flag, ld, cg);
         return;
     }
     {   // blockIdx.y = lane of a block step
         const int64_t lo = (int64_t)blockIdx.y * ld;
         if (flag) flag += lo;
-        r += lo, z += lo, W += (int64_t)blockIdx.y * lW;
+        z += lo, Win += (int64_t)blockIdx.y * lW, Wr += (int64_t)blockIdx.y * lW;
     }
     if (flag && flag[0] != 0.0) return;
     static_assert(WPB == 1 || WPE == 1, "either several elements per block or several waves per element");
@@ -296,37 +351,28 @@ __global__ __launch_bounds__(64 * WPB * WPE) void k_fdm_ext(const double *__rest
         for (int q = lane; q < 3 * N * N; q += ST) sS[wv][q] = Sgg[q];
     const double *Sg = SLDS ? sS[wv] : Sgg;
     for (int q = lane; q < 3 * N; q += ST) sL[wv][q / N][q % N] = lam[ee * (3 * N) + q];
-    const double *re = r + ee * NP2;
-    double *We = W + ee * NP;
-    // packed per-point constants (pprec_setup): bits 0-1 boundary directions, 2-12 exchange slot, 13-22 pressure point,
-    // 23-28 ghost-neighbour flags; kept in registers for the store phase
+    // one coalesced round trip: the extended grid, and the destinations of the ghost values (kept in registers for the store
+    // phase; clamped loads at the points that are not face points)
     constexpr int NQL = (NP + ST - 1) / ST;
-    int te[NQL];
-#pragma unroll
-    for (int u = 0; u < NQL; ++u) {
-        const int q = lane + ST * u;
-        te[u] = q < NP ? tab[q] : 3;
-    }
-    // branch-free: every lane issues all its loads (clamped to valid addresses) before the first use, so a wave pays ONE
-    // global-memory latency here; with the loads inside `if (nb <= 1)` / `nb == 0 ? :` the compiler emitted, per point, branch ->
-    // two loads -> wait -> branch -> load -> wait: sixteen serialised round trips per wave
+    int pr[NQL];
     {
-        double own[NQL], gw[NQL];
+        const double *We = Win + ee * NP;
+        const int *pe = pret + ee * NF;
+        double w[NQL];
 #pragma unroll
         for (int u = 0; u < NQL; ++u) {
-            const int nb = te[u] & 3;
-            const int q2 = nb <= 1 ? ((te[u] >> 13) & 1023) : 0;
-            const int sl = nb == 1 ? ((te[u] >> 2) & 2047) : 0;
-            own[u] = re[q2] * wq[ee * NP2 + q2];
-            gw[u] = We[sl];
+            const int q = lane + ST * u;
+            const int qc = q < NP ? q : 0;
+            const int a = qc % N, b = (qc / N) % N, c = qc / (N * N);
+            const int nb = (a == 0 || a == N - 1) + (b == 0 || b == N - 1) + (c == 0 || c == N - 1);
+            w[u] = We[qc];
+            pr[u] = pe[nb == 1 ? face_pt(N, a, b, c) : 0];
         }
 #pragma unroll
         for (int u = 0; u < NQL; ++u) {
             const int q = lane + ST * u;
             if (q >= NP) break;
-            const int nb = te[u] & 3;
-            const double v = nb == 0 ? own[u] : (nb == 1 ? gw[u] - own[u] : 0.0);
-            sA[wv][q] = v;
+            sA[wv][q] = w[u];
         }
     }
     __syncthreads();
@@ -352,40 +398,13 @@ __global__ __launch_bounds__(64 * WPB * WPE) void k_fdm_ext(const double *__rest
         for (int u = 0; u < NQL; ++u) {
             const int q = lane + ST * u;
             if (q >= NP) break;
-            const int nb = te[u] & 3;
-            if constexpr (N <= 10) {
-                // (LDS reads unconditional with clamped indices, selected afterwards: no divergent branches around them)
-                const int fl = nb == 0 ? (te[u] >> 23) : 0;
-                const double c0 = sA[wv][q];
-                const double m1 = sA[wv][q >= 1 ? q - 1 : q], p1 = sA[wv][q + 1 < NP ? q + 1 : q];
-                const double mN = sA[wv][q >= N ? q - N : q], pN = sA[wv][q + N < NP ? q + N : q];
-                const double mM = sA[wv][q >= N * N ? q - N * N : q], pM = sA[wv][q + N * N < NP ? q + N * N : q];
-                double v = c0;
-                v -= (fl & 1) ? m1 : 0.0;
-                v -= (fl & 2) ? p1 : 0.0;
-                v -= (fl & 4) ? mN : 0.0;
-                v -= (fl & 8) ? pN : 0.0;
-                v -= (fl & 16) ? mM : 0.0;
-                v -= (fl & 32) ? pM : 0.0;
-                if (nb == 1)
-                    We[(te[u] >> 2) & 2047] = c0;   // ghost value: belongs to the neighbour's adjacent layer
-                else if (nb == 0)
-                    z[e * NP2 + ((te[u] >> 13) & 1023)] = v;
-            } else {   // lx1 = 12 (three waves per element): the branchy form is faster there (213 vs 240 us)
-                if (nb == 1) {
-                    We[(te[u] >> 2) & 2047] = sA[wv][q];
-                } else if (nb == 0) {
-                    const int fl = te[u] >> 23;
-                    double v = sA[wv][q];
-                    if (fl & 1) v -= sA[wv][q - 1];
-                    if (fl & 2) v -= sA[wv][q + 1];
-                    if (fl & 4) v -= sA[wv][q - N];
-                    if (fl & 8) v -= sA[wv][q + N];
-                    if (fl & 16) v -= sA[wv][q - N * N];
-                    if (fl & 32) v -= sA[wv][q + N * N];
-                    z[e * NP2 + ((te[u] >> 13) & 1023)] = v;
-                }
-            }
+            const int a = q % N, b = (q / N) % N, c = q / (N * N);
+            const int nb = (a == 0 || a == N - 1) + (b == 0 || b == N - 1) + (c == 0 || c == N - 1);
+            const double v = sA[wv][q];
+            if (nb == 0)
+                z[e * NP2 + (a - 1) + N2 * ((b - 1) + N2 * (c - 1))] = v;
+            else if (nb == 1 && pr[u] >= 0)
+                Wr[pr[u]] = v;   // ghost value: belongs to the neighbour's adjacent layer
         }
     }
 }
@@ -438,21 +457,20 @@ __device__ __forceinline__ void fdm_stage_mfma8(double *__restrict__ buf, const 
 }
 
 __global__ __launch_bounds__(64, 4) void k_fdm_ext_mfma8(const double *__restrict__ flag, int64_t E, const double *__restrict__ S,
-                                                      const double *__restrict__ lam, double thr, const double *__restrict__ r,
-                                                      const double *__restrict__ wq, double *__restrict__ W,
-                                                      double *__restrict__ z, const int *__restrict__ tab, int64_t ld, int64_t lW, int nb_fdm,
-                                                      AggArgs ag) {
-    constexpr int N = 8, N2 = 6, NP = 512, NP2 = 216, NPAD = 9 * 64;
+                                                      const double *__restrict__ lam, double thr, const double *__restrict__ Win,
+                                                      double *__restrict__ Wr, double *__restrict__ z, const int *__restrict__ pret,
+                                                      int64_t ld, int64_t lW, int nb_fdm, ChainArgs cg) {
+    constexpr int N = 8, N2 = 6, NP = 512, NP2 = 216, NF = 216;
     __shared__ double sL[3][N];
-    __shared__ double sA[NPAD];
-    if ((int)blockIdx.x >= nb_fdm) {   // merged launch: the blocks behind the elements restrict the coarse residual to the aggregates
-        agg_restrict_body((int)blockIdx.x - nb_fdm, flag, ld, ag);
+    __shared__ double sA[9 * 64];
+    if ((int)blockIdx.x >= nb_fdm) {   // merged launch: the blocks behind the elements run the coarse chain up to the dense solve
+        chain_body((int)blockIdx.x - nb_fdm, flag, ld, cg);
         return;
     }
     {   // blockIdx.y = lane of a block step
         const int64_t lo = (int64_t)blockIdx.y * ld;
         if (flag) flag += lo;
-        r += lo, z += lo, W += (int64_t)blockIdx.y * lW;
+        z += lo, Win += (int64_t)blockIdx.y * lW, Wr += (int64_t)blockIdx.y * lW;
     }
     if (flag && flag[0] != 0.0) return;
     const int lane = threadIdx.x, l15 = lane & 15, lg = lane >> 4;
@@ -462,26 +480,24 @@ __global__ __launch_bounds__(64, 4) void k_fdm_ext_mfma8(const double *__restric
 #pragma unroll
     for (int m = 0; m < 3; ++m) sS[m * N * N + lane] = Sg[m * N * N + lane];
     if (lane < 3 * N) sL[lane / N][lane % N] = lam[e * (3 * N) + lane];
-    const double *re = r + e * NP2;
-    double *We = W + e * NP;
-    int te[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) te[u] = tab[lane + 64 * u];
+    // one coalesced round trip: the extended grid (point q = lane + 64 u: a = lane & 7, b = lane >> 3, c = u), and the
+    // destinations of the ghost values (kept in registers for the store phase; clamped loads at the points that are not face points)
+    int pr[8];
     {
-        double own[8], gw[8];
+        const double *We = Win + e * NP;
+        const int *pe = pret + e * NF;
+        double w[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            const int nb = te[u] & 3;
-            const int q2 = nb <= 1 ? ((te[u] >> 13) & 1023) : 0;
-            const int sl = nb == 1 ? ((te[u] >> 2) & 2047) : 0;
-            own[u] = re[q2] * wq[e * NP2 + q2];
-            gw[u] = We[sl];
+            const int q = lane + 64 * u, a = q & 7, b = (q >> 3) & 7, c = q >> 6;
+            const int nb = (a == 0 || a == N - 1) + (b == 0 || b == N - 1) + (c == 0 || c == N - 1);
+            w[u] = We[q];
+            pr[u] = pe[nb == 1 ? face_pt(N, a, b, c) : 0];
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int q = lane + 64 * u;
-            const int nb = te[u] & 3;
-            sA[q + (q >> 3)] = nb == 0 ? own[u] : (nb == 1 ? gw[u] - own[u] : 0.0);
+            sA[q + (q >> 3)] = w[u];
         }
     }
     __syncthreads();
@@ -507,37 +523,25 @@ __global__ __launch_bounds__(64, 4) void k_fdm_ext_mfma8(const double *__restric
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-        const int q = lane + 64 * u;
-        const int nb = te[u] & 3;
-        const int fl = nb == 0 ? (te[u] >> 23) : 0;
-        const int pq = q + (q >> 3);
-        // (LDS reads unconditional with clamped indices, selected afterwards: no divergent branches around them)
-        const double c0 = sA[pq];
-        const double m1 = sA[pq >= 1 ? pq - 1 : pq], p1 = sA[pq + 1 < NPAD ? pq + 1 : pq];
-        const double mN = sA[pq >= 9 ? pq - 9 : pq], pN = sA[pq + 9 < NPAD ? pq + 9 : pq];
-        const double mM = sA[pq >= 72 ? pq - 72 : pq], pM = sA[pq + 72 < NPAD ? pq + 72 : pq];
-        double v = c0;
-        v -= (fl & 1) ? m1 : 0.0;
-        v -= (fl & 2) ? p1 : 0.0;
-        v -= (fl & 4) ? mN : 0.0;
-        v -= (fl & 8) ? pN : 0.0;
-        v -= (fl & 16) ? mM : 0.0;
-        v -= (fl & 32) ? pM : 0.0;
-        if (nb == 1)
-            We[(te[u] >> 2) & 2047] = c0;   // ghost value: belongs to the neighbour's adjacent layer
-        else if (nb == 0)
-            z[e * NP2 + ((te[u] >> 13) & 1023)] = v;
+        const int q = lane + 64 * u, a = q & 7, b = (q >> 3) & 7, c = q >> 6;
+        const int nb = (a == 0 || a == N - 1) + (b == 0 || b == N - 1) + (c == 0 || c == N - 1);
+        const double v = sA[q + (q >> 3)];
+        if (nb == 0)
+            z[e * NP2 + (a - 1) + N2 * ((b - 1) + N2 * (c - 1))] = v;
+        else if (nb == 1 && pr[u] >= 0)
+            Wr[pr[u]] = v;   // ghost value: belongs to the neighbour's adjacent layer
     }
 }
 
-// z += (own + neighbours' ghost values at this point, from W after QQ^T) + prolonged coarse correction; r.z and z sums
+// z += (neighbours' ghost values at this point: at most three return slots of the element's own faces) x wq + prolonged
+// coarse correction; r.z and z sums
 
 template <int N>
 __global__ __launch_bounds__(NT) void k_sch_finish(const double *__restrict__ flag, int64_t E, const double *__restrict__ W,
                                                    const double *__restrict__ r, const double *__restrict__ wq,
                                                    const double *__restrict__ xc, const double *__restrict__ xa,
                                                    const int *__restrict__ agg, const int *__restrict__ vg, Hat hat,
-                                                   double *__restrict__ z, double *__restrict__ part, const int *__restrict__ wslot,
+                                                   double *__restrict__ z, double *__restrict__ part,
                                                    int64_t ld, int64_t lW, int64_t lv, int64_t la) {
     constexpr int N2 = N - 2, NP = N * N * N, NP2 = N2 * N2 * N2;
     __shared__ double sred[8];
@@ -554,10 +558,10 @@ __global__ __launch_bounds__(NT) void k_sch_finish(const double *__restrict__ fl
     const bool act = e < E;
     double srz = 0.0, sz = 0.0;
     if (act) {
-        // all loads of a group of points first, unconditional and with clamped indices (the face slots of W come from the
-        // table of k_q1_restrict_local3s; a conditional load inside the point loop costs a branch and a full wait per point),
-        // then the arithmetic with selects
+        // all loads of a group of points first, unconditional and with clamped indices (a conditional load inside the point
+        // loop costs a branch and a full wait per point), then the arithmetic with selects
         constexpr int NIT = 4;   // points per lane in flight (lx1 = 8: the whole element)
+        constexpr int M = N2, MM = N2 * N2, FB = 8 + 12 * N2;   // FB: first face slot of the face-grouped layout (fg_slot)
         const double *We = W + e * NP;
         double cv[8];
 #pragma unroll
@@ -573,8 +577,10 @@ __global__ __launch_bounds__(NT) void k_sch_finish(const double *__restrict__ fl
                 zv[it] = z[i];
                 qv[it] = wq[i];
                 rv[it] = r[i];
-#pragma unroll
-                for (int d = 0; d < 3; ++d) sl[it][d] = wslot[3 * qc + d];
+                const int a = qc % N2, b = (qc / N2) % N2, c = qc / (N2 * N2);   // return slots of the faces next to qc
+                sl[it][0] = a == 0 ? FB + b + M * c : (a == M - 1 ? FB + MM + b + M * c : -1);
+                sl[it][1] = b == 0 ? FB + 2 * MM + a + M * c : (b == M - 1 ? FB + 3 * MM + a + M * c : -1);
+                sl[it][2] = c == 0 ? FB + 4 * MM + a + M * b : (c == M - 1 ? FB + 5 * MM + a + M * b : -1);
             }
             if (q0 == 0 && xc) {
                 int vv[8], av[8];
@@ -772,7 +778,8 @@ template <int DIM>
 __global__ __launch_bounds__(NT) void k_q1_restrict_local(const double *__restrict__ flag, int64_t E, int n2, Hat hat,
                                                           double *__restrict__ r, double *__restrict__ t,
                                                           double *__restrict__ W, const double *__restrict__ wq,
-                                                          nlg_pcg_upd u, int64_t ld = 0, int64_t lt = 0, int64_t lW = 0) {
+                                                          const int *__restrict__ pin, nlg_pcg_upd u, int64_t ld = 0, int64_t lt = 0,
+                                                          int64_t lW = 0) {
     __shared__ double srr[4];
     {   // blockIdx.y = lane of a block step: solver fields ld doubles apart (the integrator's slab), the preconditioner's own scratch at its strides
         const int64_t lo = (int64_t)blockIdx.y * ld;
@@ -816,16 +823,19 @@ __global__ __launch_bounds__(NT) void k_q1_restrict_local(const double *__restri
             if (b == n2 - 1) We[(a + 1) + N * (N - 1)] = vw;
         }
         if (DIM == 3 && W) {
-            // overlapping Schwarz, pack: the layers adjacent to the element faces go to the face points of W
-            const int N = n2 + 2, a = q % n2, b = (q / n2) % n2, c = q / (n2 * n2);
-            double *We = W + e * (int64_t)(N * N * N);
+            // overlapping Schwarz: the own value into the interior of the element's extended grid, and the layers adjacent to
+            // the element faces straight into the ghost slots of the neighbours' extended grids (pin, pprec_setup)
+            const int N = n2 + 2, M = n2, MM = n2 * n2, a = q % n2, b = (q / n2) % n2, c = q / (n2 * n2);
             const double vw = v * wq[e * np2 + q];
-            if (a == 0) We[fg_slot(N, 0, b + 1, c + 1)] = vw;
-            if (a == n2 - 1) We[fg_slot(N, N - 1, b + 1, c + 1)] = vw;
-            if (b == 0) We[fg_slot(N, a + 1, 0, c + 1)] = vw;
-            if (b == n2 - 1) We[fg_slot(N, a + 1, N - 1, c + 1)] = vw;
-            if (c == 0) We[fg_slot(N, a + 1, b + 1, 0)] = vw;
-            if (c == n2 - 1) We[fg_slot(N, a + 1, b + 1, N - 1)] = vw;
+            W[e * (int64_t)(N * N * N) + (a + 1) + N * ((b + 1) + N * (c + 1))] = vw;
+            const int *pe = pin + e * (int64_t)(6 * MM);
+            int pk;
+            if (a == 0 && (pk = pe[0 * MM + b + M * c]) >= 0) W[pk] = vw;
+            if (a == M - 1 && (pk = pe[1 * MM + b + M * c]) >= 0) W[pk] = vw;
+            if (b == 0 && (pk = pe[2 * MM + a + M * c]) >= 0) W[pk] = vw;
+            if (b == M - 1 && (pk = pe[3 * MM + a + M * c]) >= 0) W[pk] = vw;
+            if (c == 0 && (pk = pe[4 * MM + a + M * b]) >= 0) W[pk] = vw;
+            if (c == M - 1 && (pk = pe[5 * MM + a + M * b]) >= 0) W[pk] = vw;
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -853,13 +863,13 @@ __global__ __launch_bounds__(NT) void k_q1_restrict_local(const double *__restri
 }
 
 // The same for 3-D with the pressure-mesh size known at compile time (lx1 = 8, 10, 12): the point loop is unrolled, so all loads
-// of a wave are in flight at once, the index arithmetic is constant-folded, and the face slots of W come from a table
-// (wslot[q][d]: slot of the face point next to pressure point q in direction d, -1 if q is not in that boundary layer)
-// instead of fg_slot's branches.  Same summation order as the generic kernel: bit-identical results.
+// of a wave are in flight at once and the index arithmetic is constant-folded; the destinations of the layer values in the
+// neighbours' extended grids (pin) are loaded with the residual, not after it.  Same summation order as the generic kernel:
+// bit-identical results.
 template <int N2>
 __global__ __launch_bounds__(NT) void k_q1_restrict_local3s(const double *__restrict__ flag, int64_t E, Hat hat, double *__restrict__ r,
                                                             double *__restrict__ t, double *__restrict__ W, const double *__restrict__ wq,
-                                                            const int *__restrict__ wslot, nlg_pcg_upd u, int64_t ld, int64_t lt, int64_t lW) {
+                                                            const int *__restrict__ pin, nlg_pcg_upd u, int64_t ld, int64_t lt, int64_t lW) {
     __shared__ double srr[4];
     {   // blockIdx.y = lane of a block step: solver fields ld doubles apart (the integrator's slab), the preconditioner's own scratch at its strides
         const int64_t lo = (int64_t)blockIdx.y * ld;
@@ -872,18 +882,20 @@ __global__ __launch_bounds__(NT) void k_q1_restrict_local3s(const double *__rest
     }
     if (flag && flag[0] != 0.0) return;
     constexpr int NP2 = N2 * N2 * N2, N = N2 + 2, NIT = 4;   // four points per lane in flight (lx1 = 8: the whole element)
+    constexpr int M = N2, MM = N2 * N2;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int64_t e = (int64_t)blockIdx.x * 4 + wid;
     const bool act = e < E;
     const bool upd = u.alpha != nullptr;
     const double alpha = upd ? u.alpha[0] : 0.0, wmean = upd ? u.wmean[0] : 0.0;
+    const int *__restrict__ pe = pin + (act ? e : 0) * (6 * MM);
     double rr = 0.0;
     double a[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) a[c] = 0.0;
     for (int q0 = 0; q0 < NP2; q0 += 64 * NIT) {
         double v[NIT], pv[NIT], wv[NIT], xv[NIT], nv[NIT], qv[NIT], hh[NIT][3];
-        int sl[NIT][3];
+        int pk[NIT][3], kk[NIT][3];
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int q = q0 + lane + 64 * it;
@@ -897,8 +909,15 @@ __global__ __launch_bounds__(NT) void k_q1_restrict_local3s(const double *__rest
             }
             if (W) {
                 qv[it] = wq[i];
-#pragma unroll
-                for (int d = 0; d < 3; ++d) sl[it][d] = wslot[3 * qc + d];
+                // face point next to qc in each direction (-1: qc is not in that boundary layer) -> its destination
+                const int ia = qc % N2, ib = (qc / N2) % N2, ic = qc / (N2 * N2);
+                const int k0 = ia == 0 ? ib + M * ic : (ia == M - 1 ? MM + ib + M * ic : -1);
+                const int k1 = ib == 0 ? 2 * MM + ia + M * ic : (ib == M - 1 ? 3 * MM + ia + M * ic : -1);
+                const int k2 = ic == 0 ? 4 * MM + ia + M * ib : (ic == M - 1 ? 5 * MM + ia + M * ib : -1);
+                pk[it][0] = pe[k0 >= 0 ? k0 : 0];   // (clamped, selected below)
+                pk[it][1] = pe[k1 >= 0 ? k1 : 0];
+                pk[it][2] = pe[k2 >= 0 ? k2 : 0];
+                kk[it][0] = k0, kk[it][1] = k1, kk[it][2] = k2;
             }
             hh[it][0] = hat.h1[qc % N2], hh[it][1] = hat.h1[(qc / N2) % N2], hh[it][2] = hat.h1[qc / (N2 * N2)];   // (a load too)
         }
@@ -916,11 +935,12 @@ __global__ __launch_bounds__(NT) void k_q1_restrict_local3s(const double *__rest
             }
             const double ha = hh[it][0], hb = hh[it][1], hc = hh[it][2];
             if (W) {
-                double *We = W + e * (int64_t)(N * N * N);
+                const int ia = q % N2, ib = (q / N2) % N2, ic = q / (N2 * N2);
                 const double vw = vv * qv[it];
+                W[e * (int64_t)(N * N * N) + (ia + 1) + N * ((ib + 1) + N * (ic + 1))] = vw;   // own value: interior of the extended grid
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
-                    if (sl[it][d] >= 0) We[sl[it][d]] = vw;
+                    if (kk[it][d] >= 0 && pk[it][d] >= 0) W[pk[it][d]] = vw;   // layer value: a neighbour's ghost slot
             }
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
@@ -1137,11 +1157,12 @@ __global__ __launch_bounds__(NT) void k_dense_gemv(const double *flag, int na, i
     dense_gemv_body<T>((int)blockIdx.x, flag, ld, g);
 }
 
-// ---- merged launches: the coarse-grid chain rides in the launches of the fine level --------------------------------------
+// ---- merged launches (2-D): the coarse-grid chain rides in the launches of the fine level ----------------------------------
 // The vertex gather, the aggregate restriction and the dense solve are tiny (5 - 8 us each, one after the other); the three
 // fine-level launches they interleave with are independent of them.  One launch = the blocks of the fine kernel followed by the
 // blocks of a coarse kernel (block-uniform branch on blockIdx.x): the coarse work runs beside the fine work on otherwise idle
-// CUs and its three launches -- and their start-up latency on the stream -- disappear.
+// CUs and its three launches -- and their start-up latency on the stream -- disappear.  (3-D has no pairs passes left: the
+// gather and the restriction ride in k_fdm_ext*, chain_body, and the dense solve is a launch of its own.)
 // (a) pairs-only gather-scatter of the exchange array W + vertex gather
 __device__ __forceinline__ void pairs_body(int64_t bx, const int *__restrict__ idx, int64_t npairs, double *__restrict__ w,
                                            const double *__restrict__ gate, int64_t ldw, int64_t ldg) {
@@ -1471,6 +1492,7 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
         // lx1 = 6): unweighted 21 / 29 iterations with the exact / approximate coarse solve, weighted 14 / 18;
         // without overlap 29.
         std::vector<double> hwq((size_t)E * np2, 1.0);
+        std::vector<char> hasnb((size_t)E * 6, 0);   // [e][2 dd + side]: the face has a neighbour (on this rank or another)
         double dmax = 0.0;
         for (int64_t e = 0; e < E; ++e) {
             for (int dd = 0; dd < dim; ++dd) {
@@ -1479,6 +1501,7 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
                 for (int side = 0; side < 2; ++side) {
                     const double sum = hw[(size_t)e * np1 + face_node(dd, side, mid, dim == 3 ? mid : 0)];
                     ln[side] = sum - lm > 1e-10 * lm ? sum - lm : 0.0;
+                    hasnb[(size_t)e * 6 + dd * 2 + side] = ln[side] > 0.0;
                 }
                 const double len[3] = {ln[0], lm, ln[1]};
                 for (int side = 0; side < 2; ++side)
@@ -1544,36 +1567,74 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
         P.thrx = 1e-12 * dmax;
         NLG_TRY(up(hSx, &P.d_Sx));
         if (dim == 3) {
-            // per-point constants of the extended n^3 grid, the same for every element: number of boundary directions,
-            // slot in the face-grouped exchange array, index of the (clamped) pressure point, and which neighbours of
-            // an interior point are ghost layers.  Computed per point in the kernel they were ~2/3 of its instructions.
-            std::vector<int> tab((size_t)n * n * n);
-            for (int c = 0; c < n; ++c)
-                for (int b = 0; b < n; ++b)
-                    for (int a = 0; a < n; ++a) {
-                        const int nb = (a == 0 || a == n - 1) + (b == 0 || b == n - 1) + (c == 0 || c == n - 1);
-                        const int a2 = std::min(std::max(a, 1), n - 2) - 1, b2 = std::min(std::max(b, 1), n - 2) - 1,
-                                  c2 = std::min(std::max(c, 1), n - 2) - 1;
-                        const int q2 = a2 + n2 * (b2 + n2 * c2);
-                        const int fl = (a == 1) | ((a == n - 2) << 1) | ((b == 1) << 2) | ((b == n - 2) << 3) | ((c == 1) << 4) | ((c == n - 2) << 5);
-                        tab[(size_t)a + n * (b + n * c)] = nb | (fg_slot(n, a, b, c) << 2) | (q2 << 13) | (fl << 23);
+            // destinations of the overlap values per element face point k (compact, the order of fg_slot's face blocks):
+            //   pin[e][k]  = index in Win (natural layout) of the ghost point that the pressure layer of e next to k is for;
+            //   pret[e][k] = index in Wret (face-grouped layout) of the face slot that the solve of e at ghost point k is for;
+            // the neighbour's face point for a face inside this rank, the own one for a face on a rank boundary (copy-mode halo
+            // exchange), -1 without a neighbour.  The local partners are the two-copy groups of the face-grouped gather-scatter.
+            const int M = n2, MM = n2 * n2, NF = 6 * MM, NP = n * n * n, FB = 8 + 12 * M;
+            std::vector<int> fnat(NF);
+            for (int f6 = 0; f6 < 6; ++f6)
+                for (int v = 0; v < M; ++v)
+                    for (int u = 0; u < M; ++u) {
+                        const int dd = f6 >> 1, x = (f6 & 1) ? n - 1 : 0;
+                        const int a = dd == 0 ? x : u + 1, b = dd == 0 ? u + 1 : (dd == 1 ? x : v + 1), c = dd == 2 ? x : v + 1;
+                        const int k = f6 * MM + u + M * v;
+                        NLG_CHECK(fg_slot(n, a, b, c) == FB + k, "pprec_setup: internal (face point order)");
+                        fnat[k] = a + n * (b + n * c);
                     }
-            NLG_TRY(up(tab, &P.d_exttab));
-            // face slots of the exchange array W next to every pressure point (k_q1_restrict_local3s)
-            {
-                const int n2 = m->n2, N = n2 + 2;
-                std::vector<int> ws((size_t)n2 * n2 * n2 * 3, -1);
-                for (int q = 0; q < n2 * n2 * n2; ++q) {
-                    const int a = q % n2, b = (q / n2) % n2, c = q / (n2 * n2);
-                    if (a == 0) ws[3 * q + 0] = fg_slot(N, 0, b + 1, c + 1);
-                    if (a == n2 - 1) ws[3 * q + 0] = fg_slot(N, N - 1, b + 1, c + 1);
-                    if (b == 0) ws[3 * q + 1] = fg_slot(N, a + 1, 0, c + 1);
-                    if (b == n2 - 1) ws[3 * q + 1] = fg_slot(N, a + 1, N - 1, c + 1);
-                    if (c == 0) ws[3 * q + 2] = fg_slot(N, a + 1, b + 1, 0);
-                    if (c == n2 - 1) ws[3 * q + 2] = fg_slot(N, a + 1, b + 1, N - 1);
-                }
-                NLG_TRY(up(ws, &P.d_wslot));
+            NLG_CHECK((int64_t)E * NP < INT32_MAX, "pprec_setup: %lld elements are too many for 32-bit overlap indices", (long long)E);
+            std::vector<int> pidx((size_t)2 * m->gs.npairs), mate((size_t)E * NP, -1);
+            NLG_HIP(hipMemcpy(pidx.data(), m->gs.d_indices_fg, sizeof(int) * pidx.size(), hipMemcpyDeviceToHost));
+            auto is_face = [&](int i) { const int sl = i % NP; return sl >= FB && sl < FB + NF; };
+            for (int64_t g = 0; g < m->gs.npairs; ++g) {
+                const int i0 = pidx[2 * g], i1 = pidx[2 * g + 1];
+                NLG_CHECK(i0 >= 0 && i1 >= 0 && i0 < E * NP && i1 < E * NP, "pprec_setup: face-grouped pair index out of range");
+                if (is_face(i0) && is_face(i1)) mate[i0] = i1, mate[i1] = i0;
             }
+            std::vector<int> pin((size_t)E * NF, -1), pret((size_t)E * NF, -1);
+            for (int64_t e = 0; e < E; ++e)
+                for (int k = 0; k < NF; ++k) {
+                    const int own = (int)(e * NP + FB + k), mt = mate[own];
+                    const bool nb = hasnb[(size_t)e * 6 + k / MM];
+                    int di = -1, dr = -1;
+                    if (mt >= 0) {
+                        NLG_CHECK(nb, "pprec_setup: element %lld face %d has a partner but no neighbour length", (long long)e, k / MM);
+                        di = (mt / NP) * NP + fnat[mt % NP - FB];
+                        dr = mt;
+                    } else if (nb) {
+                        NLG_CHECK(m->halo.active, "pprec_setup: element %lld face %d: neighbour without a partner point", (long long)e, k / MM);
+                        di = (int)(e * NP + fnat[k]);
+                        dr = own;
+                    }
+                    pin[(size_t)e * NF + k] = di;
+                    pret[(size_t)e * NF + k] = dr;
+                }
+            // every ghost slot of a face with a neighbour has exactly one producer, every other slot none (a wrong index in the
+            // scatter stores of the kernels would be a fault on the device, not a wrong number)
+            {
+                std::vector<unsigned char> cin((size_t)E * NP, 0), cret((size_t)E * NP, 0);
+                int64_t nw = 0;
+                for (size_t i = 0; i < pin.size(); ++i) {
+                    if (pin[i] < 0) continue;
+                    NLG_CHECK(pin[i] < E * NP && pret[i] >= 0 && pret[i] < E * NP, "pprec_setup: overlap destination out of range");
+                    NLG_CHECK(++cin[pin[i]] == 1 && ++cret[pret[i]] == 1, "pprec_setup: overlap slot with two producers");
+                    ++nw;
+                }
+                int64_t nexp = 0;
+                for (int64_t e = 0; e < E; ++e)
+                    for (int k = 0; k < NF; ++k) {
+                        const int want = pin[(size_t)e * NF + k] >= 0;
+                        NLG_CHECK(cin[(size_t)e * NP + fnat[k]] == want && cret[(size_t)e * NP + FB + k] == want,
+                                  "pprec_setup: ghost slot of element %lld face %d without its producer", (long long)e, k / MM);
+                        nexp += want;
+                    }
+                NLG_CHECK(nexp == nw, "pprec_setup: overlap values written outside the ghost slots");
+            }
+            NLG_TRY(up(pin, &P.d_pin));
+            NLG_TRY(up(pret, &P.d_pret));
+            NLG_HIP(hipMalloc(&P.d_Wr, sizeof(double) * (size_t)m->lvs));
+            NLG_HIP(hipMemsetAsync(P.d_Wr, 0, sizeof(double) * (size_t)m->lvs, st));
         }
         NLG_TRY(up(hlx, &P.d_lamx));
         NLG_HIP(hipMalloc(&P.d_W, sizeof(double) * (size_t)m->lvs));
@@ -1667,9 +1728,9 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
                 rc = sem_cdabdtp(m, pp, ep);
                 if (rc) break;
                 if (dim == 3) {
-                    NLG_LAUNCH(k_q1_restrict_local<3>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, d_t8, (double *)nullptr, (const double *)nullptr, nlg_pcg_upd{});
+                    NLG_LAUNCH(k_q1_restrict_local<3>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, d_t8, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
                 } else {
-                    NLG_LAUNCH(k_q1_restrict_local<2>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, d_t8, (double *)nullptr, (const double *)nullptr, nlg_pcg_upd{});
+                    NLG_LAUNCH(k_q1_restrict_local<2>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, d_t8, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
                 }
                 if (hipMemcpyAsync(t8.data(), d_t8, sizeof(double) * t8.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
                     hipStreamSynchronize(st) != hipSuccess) {
@@ -1979,9 +2040,9 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
                 NLG_TRY(sem_cdabdtp(m, pp, ep));
                 if (me == r) continue;   // own block: already there
                 if (dim == 3) {
-                    NLG_LAUNCH(k_q1_restrict_local<3>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, P.d_tq, (double *)nullptr, (const double *)nullptr, nlg_pcg_upd{});
+                    NLG_LAUNCH(k_q1_restrict_local<3>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, P.d_tq, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
                 } else {
-                    NLG_LAUNCH(k_q1_restrict_local<2>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, P.d_tq, (double *)nullptr, (const double *)nullptr, nlg_pcg_upd{});
+                    NLG_LAUNCH(k_q1_restrict_local<2>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, P.d_tq, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
                 }
                 NLG_LAUNCH(k_q1_gather, dim3((nvert + NT - 1) / NT), dim3(NT), 0, st, (const double *)nullptr, nvert, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, 0.0, P.d_x);
                 NLG_LAUNCH(k_agg_restrict, dim3((na + 3) / 4), dim3(NT), 0, st, (const double *)nullptr, na, P.d_ap, P.d_am, P.d_rc, P.d_ra);
@@ -2039,6 +2100,9 @@ int pprec_reserve_lanes(nlg_mesh *m, int nl) {
         return 0;
     };
     NLG_TRY(regrow(&P.d_W, m->lvs, &P.lW));
+    int64_t lW2 = 0;
+    NLG_TRY(regrow(&P.d_Wr, m->lvs, &lW2));   // (3-D overlapping variant: the return array beside the extended grids)
+    NLG_CHECK(!P.d_Wr || lW2 == P.lW, "pprec: inconsistent lane strides");
     NLG_TRY(regrow(&P.d_tq, m->E * NC, &P.lt));
     int64_t lv2 = 0, la2 = 0;
     NLG_TRY(regrow(&P.d_rc, P.nvert, &P.lv));
@@ -2075,17 +2139,18 @@ int pprec_coarse(nlg_mesh *m, hipStream_t st, const double *flag, const double *
     NLG_CHECK(!overlap || P.overlap, "pprec: the overlapping variant is not set up for this mesh");
     double *Wp = overlap ? P.d_W : (double *)nullptr;
     const dim3 gq((unsigned)((E + 3) / 4), (unsigned)nl);
+    const int *pin = P.d_pin;
     if (m->dim == 3) {
-        if (P.d_wslot && m->n2 == 6)
-            NLG_LAUNCH(k_q1_restrict_local3s<6>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, (const int *)P.d_wslot, uu, ld, P.lt, P.lW);
-        else if (P.d_wslot && m->n2 == 8)
-            NLG_LAUNCH(k_q1_restrict_local3s<8>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, (const int *)P.d_wslot, uu, ld, P.lt, P.lW);
-        else if (P.d_wslot && m->n2 == 10)
-            NLG_LAUNCH(k_q1_restrict_local3s<10>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, (const int *)P.d_wslot, uu, ld, P.lt, P.lW);
+        if (pin && m->n2 == 6)
+            NLG_LAUNCH(k_q1_restrict_local3s<6>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
+        else if (pin && m->n2 == 8)
+            NLG_LAUNCH(k_q1_restrict_local3s<8>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
+        else if (pin && m->n2 == 10)
+            NLG_LAUNCH(k_q1_restrict_local3s<10>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
         else
-            NLG_LAUNCH(k_q1_restrict_local<3>, gq, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, uu, ld, P.lt, P.lW);
+            NLG_LAUNCH(k_q1_restrict_local<3>, gq, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
     } else {
-        NLG_LAUNCH(k_q1_restrict_local<2>, gq, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, uu, ld, P.lt, P.lW);
+        NLG_LAUNCH(k_q1_restrict_local<2>, gq, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, (const int *)nullptr, uu, ld, P.lt, P.lW);
     }
     // 3-D overlapping variant: the rest of the coarse chain rides in the launches of the fine level (pprec_fine, merged launches)
     P.coarse_pending = overlap && m->gs.npairs > 0 && (m->dim == 2 ? nl == 1 : m->gs.d_indices_fg != nullptr);
@@ -2114,15 +2179,16 @@ int pprec_coarse(nlg_mesh *m, hipStream_t st, const double *flag, const double *
     return 0;
 }
 
-// ghost layers of face neighbours on other ranks: the copies of a face on a rank boundary are summed by the halo
-// exchange exactly as the pairs kernel sums the two local copies of an interior face (edge and corner slots of W
-// are never written and travel as zeros)
-static int overlap_halo(nlg_mesh *m, hipStream_t st, bool face_grouped, int nl) {
+// ghost layers of face neighbours on other ranks.  2-D: the copies of a face on a rank boundary are summed by the halo exchange
+// exactly as the pairs kernel sums the two local copies of an interior face.  3-D (copy mode): the element has put its own value
+// into its own slot of a rank-boundary face, the exchange replaces it by the neighbour's.  Edge and corner slots are never
+// written and travel as zeros.
+static int overlap_halo(nlg_mesh *m, hipStream_t st, double *w, int layout, int nl, bool assign) {
     ++g_collectives;
     if (!m->halo.active) return 0;
     NLG_CHECK(st == m->ctx->stream, "pprec: the overlap exchange across ranks runs on the context's stream");
-    double *f1[1] = {m->pprec.d_W};
-    return halo_exchange(m, f1, 1, face_grouped, nl, m->pprec.lW);
+    double *f1[1] = {w};
+    return halo_exchange(m, f1, 1, layout, nl, m->pprec.lW, assign);
 }
 
 // Fine part: z = sum_e R_e^T Etilde_e^-1 R_e r (+ R_1 xc when xc is given), launched on `st`.
@@ -2153,8 +2219,8 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
     if (overlap && m->dim == 2) {
         NLG_CHECK(P.overlap, "pprec: the overlapping variant is not set up for this mesh");
         const unsigned gb = (unsigned)((E + 3) / 4);
-        // merged launches as in 3-D (below): the vertex gather rides with the first pairs-only gather-scatter (natural layout here),
-        // the aggregate restriction with the local solves, the dense solve with the second gather-scatter
+        // merged launches: the vertex gather rides with the first pairs-only gather-scatter (natural layout here), the aggregate
+        // restriction with the local solves, the dense solve with the second gather-scatter
         const bool fused = P.coarse_pending;
         P.coarse_pending = false;
         const int nbp = (int)((m->gs.npairs + NT - 1) / NT);
@@ -2169,7 +2235,7 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
         } else {
             NLG_TRY(sem_gs_pairs(m, P.d_W, flag));
         }
-        NLG_TRY(overlap_halo(m, st, false, 1));
+        NLG_TRY(overlap_halo(m, st, P.d_W, LAYOUT_NAT, 1, false));
         const unsigned nb_agg = fused ? (unsigned)((P.na + 3) / 4) : 0u;
 #define FX2_CASE(N_)                                                                                                  \
     case N_:                                                                                                          \
@@ -2198,7 +2264,7 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
         } else {
             NLG_TRY(sem_gs_pairs(m, P.d_W, flag));
         }
-        NLG_TRY(overlap_halo(m, st, false, 1));
+        NLG_TRY(overlap_halo(m, st, P.d_W, LAYOUT_NAT, 1, false));
         const unsigned gf = (unsigned)((E * m->np2 + NT - 1) / NT);
 #define FF2_CASE(N_)                                                                                                  \
     case N_:                                                                                                          \
@@ -2213,44 +2279,41 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
         return 0;
     }
     if (overlap) {
-        // pprec_coarse has packed the adjacent layers into P.d_W (same stream)
-        NLG_CHECK(P.overlap && m->dim == 3, "pprec: the overlapping variant is not set up for this mesh");
+        // pprec_coarse has written the extended grids into P.d_W (same stream)
+        NLG_CHECK(P.overlap && m->dim == 3 && P.d_pret, "pprec: the overlapping variant is not set up for this mesh");
         const dim3 gb((unsigned)((E + 3) / 4), (unsigned)nl);
         const bool fused = P.coarse_pending;   // set by pprec_coarse: the coarse chain is still to run
         P.coarse_pending = false;
-        const int nbp = (int)((m->gs.npairs + NT - 1) / NT);
         const int nv = P.nvert;
         const bool glob = P.ncols != P.na;
-        AggArgs ag = {0, nullptr, nullptr, nullptr, nullptr, 0, 0};
-        int nb_agg = 0;
-        if (fused) {
-            // (a) pairs-only gather-scatter of W + vertex gather of the element-corner residuals
-            const GatherArgs gg = {nv, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, P.na == nv ? 0.0 : 0.7, P.d_x, P.lt, P.lv};
-            NLG_LAUNCH(k_pairs_gather, dim3((unsigned)(nbp + (nv + NT - 1) / NT), (unsigned)nl), dim3(NT), 0, st, nbp, (const int *)m->gs.d_indices_fg,
-                       m->gs.npairs, P.d_W, P.lW, flag, ld, gg);
-            ag = AggArgs{P.na, P.d_ap, P.d_am, P.d_rc, P.d_ra, P.lv, P.la};
-        } else {
-            NLG_TRY(sem_gs_pairs_fg(m, P.d_W, flag, nl, P.lW, ld));
-        }
-        NLG_TRY(overlap_halo(m, st, true, nl));
+        NLG_TRY(overlap_halo(m, st, P.d_W, LAYOUT_NAT, nl, true));
+        // (a) local solves; the vertex gather and the aggregate restriction ride behind the elements
+        ChainArgs cg = {};
+        auto chain_blocks = [&](int threads) -> int {
+            if (!fused) return 0;
+            cg = ChainArgs{(nv + threads - 1) / threads, nv, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, P.na == nv ? 0.0 : 0.7, P.d_x,
+                           P.na, P.d_ap, P.d_am, P.d_ra, P.lt, P.lv, P.la};
+            return cg.nb_gather + (P.na + threads / 64 - 1) / (threads / 64);   // one wave per aggregate
+        };
 #define FX_CASE(N_)                                                                                                   \
     case N_: {                                                                                                        \
         constexpr int WPE_ = (N_ * N_ + 63) / 64;   /* one column per lane: 1 wave up to lx1 = 8, 2 at 9 / 10, 3 at 12 */ \
-        nb_agg = fused ? (P.na + WPE_ - 1) / WPE_ : 0;   /* (b) + aggregate restriction: one wave per aggregate */     \
-        NLG_LAUNCH((k_fdm_ext<N_, 1, WPE_>), dim3((unsigned)(E + nb_agg), (unsigned)nl), dim3(64 * WPE_), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, r, P.d_wq, P.d_W, z, (const int *)P.d_exttab, ld, P.lW, (int)E, ag); \
+        const int nb_c = chain_blocks(64 * WPE_);                                                                     \
+        NLG_LAUNCH((k_fdm_ext<N_, 1, WPE_>), dim3((unsigned)(E + nb_c), (unsigned)nl), dim3(64 * WPE_), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, \
+                   (const double *)P.d_W, P.d_Wr, z, (const int *)P.d_pret, ld, P.lW, (int)E, cg);                 \
     } break;
         switch (m->n) {
             FX_CASE(4) FX_CASE(5) FX_CASE(6) FX_CASE(7)
-            case 8:   // the six transforms on the matrix pipe
-                nb_agg = fused ? P.na : 0;
-                NLG_LAUNCH(k_fdm_ext_mfma8, dim3((unsigned)(E + nb_agg), (unsigned)nl), dim3(64), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, r, P.d_wq, P.d_W, z,
-                           (const int *)P.d_exttab, ld, P.lW, (int)E, ag);
-                break;
+            case 8: {   // the six transforms on the matrix pipe
+                const int nb_c = chain_blocks(64);
+                NLG_LAUNCH(k_fdm_ext_mfma8, dim3((unsigned)(E + nb_c), (unsigned)nl), dim3(64), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx,
+                           (const double *)P.d_W, P.d_Wr, z, (const int *)P.d_pret, ld, P.lW, (int)E, cg);
+            } break;
             FX_CASE(9) FX_CASE(10) FX_CASE(12)
             default: set_error("pprec: overlapping variant built for lx1 = 4..10 and 12, got %d", m->n); return 1;
         }
 #undef FX_CASE
-        if (fused) {
+        if (fused) {   // (b) dense aggregate solve
             const double *ra = P.d_ra;
             int na_max = 0;
             if (glob) {   // several ranks: the aggregate level is global; ONE all-gather carries the lanes of every rank
@@ -2259,22 +2322,17 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
                 ra = P.d_rag;
                 na_max = nl > 1 ? P.na_max : 0;
             }
-            // (c) second pairs-only gather-scatter of W + dense aggregate solve
-            const dim3 gc((unsigned)(nbp + (P.na + 3) / 4), (unsigned)nl);
-            if (P.d_Ainv32) {
-                const GemvArgs<float> gv = {P.na, P.ncols, (const float *)P.d_Ainv32, ra, P.d_xa, glob ? P.la_x : P.la, na_max, nl};
-                NLG_LAUNCH(k_pairs_gemv<float>, gc, dim3(NT), 0, st, nbp, (const int *)m->gs.d_indices_fg, m->gs.npairs, P.d_W, P.lW, flag, ld, gv);
-            } else {
-                const GemvArgs<double> gv = {P.na, P.ncols, (const double *)P.d_Ainv, ra, P.d_xa, glob ? P.la_x : P.la, na_max, nl};
-                NLG_LAUNCH(k_pairs_gemv<double>, gc, dim3(NT), 0, st, nbp, (const int *)m->gs.d_indices_fg, m->gs.npairs, P.d_W, P.lW, flag, ld, gv);
-            }
-        } else {
-            NLG_TRY(sem_gs_pairs_fg(m, P.d_W, flag, nl, P.lW, ld));
+            const dim3 gg((unsigned)((P.na + 3) / 4), (unsigned)nl);
+            if (P.d_Ainv32)
+                NLG_LAUNCH(k_dense_gemv<float>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const float *)P.d_Ainv32, ra, P.d_xa, ld, la_x, na_max, nl);
+            else
+                NLG_LAUNCH(k_dense_gemv<double>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const double *)P.d_Ainv, ra, P.d_xa, ld, la_x, na_max, nl);
         }
-        NLG_TRY(overlap_halo(m, st, true, nl));
+        NLG_TRY(overlap_halo(m, st, P.d_Wr, LAYOUT_FG, nl, true));
+        // (c) neighbours' ghost values + prolonged coarse correction, r.z sums
 #define FF_CASE(N_)                                                                                                   \
     case N_:                                                                                                          \
-        NLG_LAUNCH((k_sch_finish<N_>), gb, dim3(NT), 0, st, flag, E, P.d_W, r, P.d_wq, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part, (const int *)P.d_wslot, ld, P.lW, P.lv, la_x); \
+        NLG_LAUNCH((k_sch_finish<N_>), gb, dim3(NT), 0, st, flag, E, (const double *)P.d_Wr, r, P.d_wq, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part, ld, P.lW, P.lv, la_x); \
         break;
         switch (m->n) {
             FF_CASE(4) FF_CASE(5) FF_CASE(6) FF_CASE(7) FF_CASE(8) FF_CASE(9) FF_CASE(10) FF_CASE(12)
@@ -2307,10 +2365,10 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
 
 void pprec_free(nlg_mesh *m) {
     nlg_pprec &P = m->pprec;
-    double *dp[] = {P.d_S, P.d_invden, P.d_dinv, P.d_Ainv, P.d_rc, P.d_x, P.d_ra, P.d_xa, P.d_rag, P.d_tq, P.d_Sx, P.d_lamx, P.d_W, P.d_wq};
+    double *dp[] = {P.d_S, P.d_invden, P.d_dinv, P.d_Ainv, P.d_rc, P.d_x, P.d_ra, P.d_xa, P.d_rag, P.d_tq, P.d_Sx, P.d_lamx, P.d_W, P.d_Wr, P.d_wq};
     for (double *p : dp)
         if (p) hipFree(p);
-    int *ip[] = {P.d_agg, P.d_ap, P.d_am, P.d_vg, P.d_v2e_p, P.d_v2e_i, P.d_exttab, P.d_wslot};
+    int *ip[] = {P.d_agg, P.d_ap, P.d_am, P.d_vg, P.d_v2e_p, P.d_v2e_i, P.d_pin, P.d_pret};
     for (int *p : ip)
         if (p) hipFree(p);
     if (P.d_Ainv32) hipFree(P.d_Ainv32);

@@ -3621,17 +3621,6 @@ int sem_gs_pairs(nlg_mesh *m, double *w, const double *gate, int nl, int64_t ld,
     return 0;
 }
 
-int sem_gs_pairs_fg(nlg_mesh *m, double *w, const double *gate, int nl, int64_t ld, int64_t ldg) {
-    NLG_CHECK(m->gs.d_indices_fg, "sem_gs_pairs_fg: no face-grouped tables (3-D only)");
-    if (m->gs.npairs == 0) return 0;
-    F3 f = {{w, nullptr, nullptr}};
-    const dim3 grid((unsigned)((m->gs.npairs + NT - 1) / NT), (unsigned)nl);
-    NLG_LAUNCH(k_gs<1>, grid, dim3(NT), 0, m->ctx->stream, m->gs.d_offsets_fg, m->gs.d_indices_fg, m->gs.npairs,
-                       m->gs.npairs, (int64_t)0, f, gate, ld, ldg);
-    NLG_HIP(hipGetLastError());
-    return 0;
-}
-
 int sem_axhelm_blocks(nlg_mesh *m, int nf) {
     if (m->dim == 2) {
         const int epb = NT / (m->n * m->n) > 0 ? NT / (m->n * m->n) : 1;
