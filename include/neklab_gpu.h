@@ -250,7 +250,8 @@ typedef struct nlg_exptA_config {
     int fixed_iters_v; /* > 0: run exactly this many PCG iterations (parity / benchmarking mode)      */
     int fixed_iters_p;
     int pprecond;      /* pressure preconditioner: 0 = two-level Schwarz (element FDM with one layer of face overlap
-                          in 3-D for lx1 <= 8 + vertex coarse space), 1 = Jacobi, 2 = two-level without overlap    */
+                          where it is set up -- 3-D lx1 <= 12 except 11, 2-D lx1 <= 8 -- + vertex coarse space),
+                          1 = Jacobi, 2 = two-level without overlap                                                 */
     int pproj;         /* pressure residual projection onto the previous increments of the matvec (Nek5000
                           `residualProj = yes`, examples/cylinder/stability/direct/1cyl.par:23): 0 = off, 1 = on    */
     int ifheat;        /* Boussinesq coupling with one scalar (temperature): the vectors carry theta (nscal = 1), the base
@@ -348,7 +349,8 @@ int nlg_op_dssum(nlg_mesh *mesh, nlg_vec *v);
 int nlg_op_cdabdtp(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 /* out%pr = M^-1 in%pr, the two-level Schwarz preconditioner the pressure solve uses for E (Nek5000's role:
    `preconditioner = semg_xxt`, examples/cylinder/stability/direct/1cyl.par:21).  overlap != 0: local solves with one
-   layer of face overlap (3-D, lx1 <= 8); with_coarse == 0: local solves only.  M is symmetric positive semi-definite. */
+   layer of face overlap (3-D lx1 <= 12 except 11, 2-D lx1 <= 8; an error elsewhere); with_coarse == 0: local solves
+   only.  M is symmetric positive semi-definite. */
 int nlg_op_pprec(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out, int overlap, int with_coarse);
 int nlg_op_opdiv(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_opgradt(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);

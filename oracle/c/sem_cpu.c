@@ -12,6 +12,34 @@
 int nl_threads(void) { return omp_get_max_threads(); }
 void nl_set_threads(int n) { omp_set_num_threads(n > 0 ? n : 1); }
 
+/* Sums over the points in one fixed order, whatever the number of threads: blocks of NL_RB points, each summed in point order by
+ * one thread (the loop body adds to `acc`), and the block partials added pairwise.  An OpenMP reduction clause instead sums in an
+ * order set by the thread count, and the tolerance-terminated solves of the time step then stop after a number of iterations
+ * that depends on OMP_NUM_THREADS (a 700-iteration pressure solve: 3 - 4 more with one or two threads than the numpy twin). */
+#define NL_RB 128L
+static double nl_pairwise(const double *a, long n) {
+    if (n <= 8) {
+        double s = 0.0;
+        for (long i = 0; i < n; ++i) s += a[i];
+        return s;
+    }
+    const long h = n / 2;
+    return nl_pairwise(a, h) + nl_pairwise(a + h, n - h);
+}
+#define NL_SUM(N, RES, I, ...)                                                                   \
+    do {                                                                                         \
+        const long n_ = (N), nb_ = (n_ + NL_RB - 1) / NL_RB;                                     \
+        double *pt_ = malloc(sizeof(double) * (size_t)(nb_ > 0 ? nb_ : 1));                       \
+        _Pragma("omp parallel for schedule(static)") for (long b_ = 0; b_ < nb_; ++b_) {          \
+            double acc = 0.0;                                                                    \
+            const long e_ = (b_ + 1) * NL_RB < n_ ? (b_ + 1) * NL_RB : n_;                        \
+            for (long I = b_ * NL_RB; I < e_; ++I) { __VA_ARGS__ }                                \
+            pt_[b_] = acc;                                                                       \
+        }                                                                                        \
+        (RES) = nl_pairwise(pt_, nb_);                                                           \
+        free(pt_);                                                                               \
+    } while (0)
+
 /* out[c][b][a'] = sum_a M[a'][a] in[c][b][a]  (x fastest), M is mo x mi row-major */
 static void apx(const double *M, int mo, int mi, const double *in, double *out, int ny, int nz) {
     for (int q = 0; q < ny * nz; ++q)
@@ -189,9 +217,8 @@ void nl_conv(long E, int n, int nd, const double *Jd, const double *DJd, const d
 
 /* reference vector primitives: mass-weighted dot of one component (glsc3), two-sweep axpby */
 double nl_glsc3(long n, const double *a, const double *b, const double *w) {
-    double s = 0.0;
-#pragma omp parallel for reduction(+ : s) schedule(static)
-    for (long i = 0; i < n; ++i) s += a[i] * b[i] * w[i];
+    double s;
+    NL_SUM(n, s, i, acc += a[i] * b[i] * w[i];);
     return s;
 }
 void nl_axpby(long n, double alpha, const double *x, double beta, double *y) {
@@ -241,9 +268,8 @@ void nl_add_scaled(long n, const double *a, double s, const double *m, const dou
     for (long i = 0; i < n; ++i) y[i] = a[i] + s * (m ? m[i] * b[i] : b[i]);
 }
 double nl_sum(long n, const double *a) {
-    double s = 0.0;
-#pragma omp parallel for reduction(+ : s) schedule(static)
-    for (long i = 0; i < n; ++i) s += a[i];
+    double s;
+    NL_SUM(n, s, i, acc += a[i];);
     return s;
 }
 void nl_shift(long n, double *a, double s) {
@@ -261,14 +287,8 @@ int nl_pcg_helm(long E, int n, const double *D, const double *const *G, const do
     for (int c = 0; c < 3; ++c) {
         double *xc = x[c], *rc = r[c], *zc = z[c], *pc = p[c];
         const double *mc = mask[c];
-        double s = 0.0;
-#pragma omp parallel for reduction(+ : s) schedule(static)
-        for (long i = 0; i < N; ++i) {
-            xc[i] = 0.0;
-            zc[i] = mc[i] * minv[i] * rc[i];
-            pc[i] = zc[i];
-            s += rc[i] * zc[i] * vmult[i];
-        }
+        double s;
+        NL_SUM(N, s, i, xc[i] = 0.0; zc[i] = mc[i] * minv[i] * rc[i]; pc[i] = zc[i]; acc += rc[i] * zc[i] * vmult[i];);
         rz += s;
     }
     int it = 0;
@@ -286,12 +306,8 @@ int nl_pcg_helm(long E, int n, const double *D, const double *const *G, const do
             nl_gs(ngroups, off, idx, w[c]);
             double *wc = w[c];
             const double *mc = mask[c], *pc = p[c];
-            double s = 0.0;
-#pragma omp parallel for reduction(+ : s) schedule(static)
-            for (long i = 0; i < N; ++i) {
-                wc[i] *= mc[i];
-                s += pc[i] * wc[i] * vmult[i];
-            }
+            double s;
+            NL_SUM(N, s, i, wc[i] *= mc[i]; acc += pc[i] * wc[i] * vmult[i];);
             pw += s;
         }
         const double alpha = rz / pw;
@@ -299,14 +315,9 @@ int nl_pcg_helm(long E, int n, const double *D, const double *const *G, const do
         for (int c = 0; c < 3; ++c) {
             double *xc = x[c], *rc = r[c], *zc = z[c];
             const double *pc = p[c], *wc = w[c], *mc = mask[c];
-            double s = 0.0;
-#pragma omp parallel for reduction(+ : s) schedule(static)
-            for (long i = 0; i < N; ++i) {
-                xc[i] += alpha * pc[i];
-                rc[i] -= alpha * wc[i];
-                zc[i] = mc[i] * minv[i] * rc[i];
-                s += rc[i] * zc[i] * vmult[i];
-            }
+            double s;
+            NL_SUM(N, s, i, xc[i] += alpha * pc[i]; rc[i] -= alpha * wc[i]; zc[i] = mc[i] * minv[i] * rc[i];
+                   acc += rc[i] * zc[i] * vmult[i];);
             rzn += s;
         }
         const double beta = rzn / rz;
@@ -329,26 +340,15 @@ int nl_pcg_E(long E, int n, int n2, const double *I12, const double *D12, const 
              double *w, double *const *u, double tol2, int maxit, int fixed) {
     const long N2 = E * n2 * n2 * n2, N1 = E * n * n * n;
     if (proj) nl_shift(N2, r, nl_sum(N2, r) / (double)N2);
-    double rz = 0.0;
-    {
-        double s = 0.0;
-#pragma omp parallel for reduction(+ : s) schedule(static)
-        for (long i = 0; i < N2; ++i) {
-            x[i] = 0.0;
-            z[i] = minv[i] * r[i];
-            p[i] = z[i];
-            s += r[i] * z[i];
-        }
-        rz = s;
-    }
+    double rz;
+    NL_SUM(N2, rz, i, x[i] = 0.0; z[i] = minv[i] * r[i]; p[i] = z[i]; acc += r[i] * z[i];);
     if (proj) nl_shift(N2, p, nl_sum(N2, p) / (double)N2);
     int it = 0;
     const int lim = fixed > 0 ? fixed : maxit;
     double rn20 = -1.0;
     while (it < lim) {
-        double rn2 = 0.0;
-#pragma omp parallel for reduction(+ : rn2) schedule(static)
-        for (long i = 0; i < N2; ++i) rn2 += r[i] * r[i] / bm2[i];
+        double rn2;
+        NL_SUM(N2, rn2, i, acc += r[i] * r[i] / bm2[i];);
         rn2 /= volvm2;
         if (rn20 < 0.0) rn20 = rn2;
         if (rn2 <= NL_FLOOR2 * rn20) break;
@@ -362,19 +362,12 @@ int nl_pcg_E(long E, int n, int n2, const double *I12, const double *D12, const 
             for (long i = 0; i < N1; ++i) uc[i] *= mb[i];
         }
         nl_opdiv(E, n, n2, I12, D12, rst2w, (const double *const *)u, w);
-        double pw = 0.0;
-#pragma omp parallel for reduction(+ : pw) schedule(static)
-        for (long i = 0; i < N2; ++i) pw += p[i] * w[i];
+        double pw;
+        NL_SUM(N2, pw, i, acc += p[i] * w[i];);
         const double alpha = rz / pw;
         const double wm = proj ? nl_sum(N2, w) / (double)N2 : 0.0;
-        double rzn = 0.0;
-#pragma omp parallel for reduction(+ : rzn) schedule(static)
-        for (long i = 0; i < N2; ++i) {
-            x[i] += alpha * p[i];
-            r[i] -= alpha * (w[i] - wm);
-            z[i] = minv[i] * r[i];
-            rzn += r[i] * z[i];
-        }
+        double rzn;
+        NL_SUM(N2, rzn, i, x[i] += alpha * p[i]; r[i] -= alpha * (w[i] - wm); z[i] = minv[i] * r[i]; acc += r[i] * z[i];);
         const double beta = rzn / rz;
         rz = rzn;
         const double zm = proj ? nl_sum(N2, z) / (double)N2 : 0.0;

@@ -52,6 +52,8 @@ class LNSConfig:
     rhocp: float = 1.0
     buoy: tuple = (0.0, 0.0, 0.0)
     no_history: bool = False    # no restart history: impulsive start of every matvec, no history steps (nlg_exptA_config.no_history)
+    pprecond: int = 1           # pressure preconditioner (nlg_exptA_config.pprecond): 1 = Jacobi on diag(E); 0 = two-level
+                                # Schwarz with face overlap where it exists, 2 = without overlap (oracle/pprec.py)
 
 
 def dt_rule(tau, cfl_at_unit_dt, cfl_limit):
@@ -77,6 +79,13 @@ class ExptA:
             self.dt, self.nsteps = dt_rule(cfg.tau, c1, cfg.cfl_limit)
         self.nu = 1.0 / cfg.re
         self.ediag_inv = 1.0 / sem.e_diag()
+        self.pprec = None
+        if cfg.pprecond in (0, 2):
+            from .pprec import SchwarzPrec, overlap_available
+            ov = cfg.pprecond == 0 and overlap_available(sem.dim, sem.n) and bool(np.any(np.bincount(sem.glo) == 2))
+            self.pprec = SchwarzPrec(sem, overlap=ov)
+        elif cfg.pprecond != 1:
+            raise ValueError("pprecond must be 0, 1 or 2")
         self._hdiag = {}
         self.stats = {"v_iters": 0, "p_iters": 0, "steps": 0}
 
@@ -213,7 +222,14 @@ class ExptA:
         on P E P with P = I - 1 1^T / n restricted to the mean-free subspace (Nek5000 `ortho` applied
         consistently to operator, preconditioner and right-hand side)."""
         s, cfg = self.sem, self.cfg
-        minv = self.ediag_inv
+        if self.pprec is None:
+            minv = self.ediag_inv
+
+            def M(a):
+                return minv * a
+        else:
+            def M(a):
+                return self.pprec.apply(a).reshape(s.shape2)
         proj = not s.has_outflow
         npts = b.size
 
@@ -222,7 +238,7 @@ class ExptA:
 
         x = np.zeros(s.shape2)
         r = P(b.copy())
-        z = minv * r
+        z = M(r)
         p = P(z)
         rz = float(np.sum(r * z))
         it = 0
@@ -242,7 +258,7 @@ class ExptA:
             alpha = rz / pw
             x += alpha * p
             r -= alpha * P(w)
-            z = minv * r
+            z = M(r)
             rz_new = float(np.sum(r * z))
             beta = rz_new / rz
             rz = rz_new

@@ -1,0 +1,371 @@
+"""ORACLE (test infrastructure only) -- the two-level Schwarz preconditioner of the consistent Poisson operator
+E = D (mask B^-1 QQ^T) D^T, restated in float64 numpy from its definition (header of neklab_amd/csrc/pprec.hip and the
+set-up in pprec_setup):
+
+    M^-1 r = sum_e R_e^T W A~_e^-1 W R_e r  +  R_1 V(A_c) R_1^T r
+
+* A~_e: E restricted to element e with the element replaced by a box of its mean edge lengths (distance between the
+  centres of opposite faces): separable, A~ = sum_d A_d (x) B_(others), inverted through the generalised eigenproblems
+  A_d s = lam B_d s of each direction; 1 / (lam_a + lam_b [+ lam_c]) is set to zero below 1e-12 of its maximum.
+  Without overlap R_e picks the element's own pressure points and W = I.  With one layer of face overlap the 1-D operators
+  come from the line left neighbour | element | right neighbour (the ghost point decoupled where there is no neighbour),
+  R_e also picks each face neighbour's layer of GL points next to the shared face, and W = diag(count^-1/2) with count the
+  number of extended grids that hold the point.  Neighbours and the point-to-point correspondence of shared faces come
+  from the mesh's glo_num labels only: face-interior GLL point (u+1, v+1) of e <-> the neighbour's point with the same
+  label <-> the neighbour's adjacent GL layer.
+* R_1: the trilinear (bilinear) hats of the element vertices at the GL points; A_c = R_1^T E R_1 from SEM.cdabdtp
+  applied to the hat columns.  Exact mode (nvert <= exact_max): A_c^-1, shifted by alpha 1 1^T, alpha = tr / na^2,
+  without outflow.  Aggregated mode: omega diag(A_c)^-1 + P (P^T A_c P)^-1 P^T with the greedy vertex aggregates of
+  pprec_setup step 4 (one rank).
+
+Imports nothing from neklab_amd: the oracle shares no table with the device.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def overlap_available(dim, n):
+    """The layer of face overlap exists in 3-D for lx1 <= 12 except 11 and in 2-D for lx1 <= 8 (pprec_setup)."""
+    return (dim == 3 and n <= 12 and n != 11) or (dim == 2 and n <= 8)
+
+
+def gen_eig(A, B):
+    """A s = lam B s, B SPD: (lam, S) with S^T B S = I, S^T A S = diag(lam)."""
+    L = np.linalg.cholesky(B)
+    Li = np.linalg.inv(L)
+    C = Li @ A @ Li.T
+    lam, V = np.linalg.eigh(0.5 * (C + C.T))
+    return lam, Li.T @ V
+
+
+def _tens(t, mats):
+    """Apply the 1-D matrix mats[d] along local direction d (x = last numpy axis) of one element's tensor t."""
+    for d, M in enumerate(mats):
+        ax = t.ndim - 1 - d
+        t = np.moveaxis(np.tensordot(M, t, axes=([1], [ax])), 0, ax)
+    return t
+
+
+def _den(lams, dim):
+    """lam_a + lam_b (+ lam_c) on the tensor grid (x = last axis)."""
+    out = 0.0
+    for d in range(dim):
+        shape = [1] * dim
+        shape[dim - 1 - d] = len(lams[d])
+        out = out + np.asarray(lams[d]).reshape(shape)
+    return out
+
+
+class SchwarzPrec:
+    """z = M^-1 r on global pressure vectors (E * lx2^dim, element-major, x fastest)."""
+
+    def __init__(self, sem, overlap=False, with_coarse=True, exact_max=2048, omega=0.7):
+        self.sem = s = sem
+        self.dim, self.n, self.n2, self.E = s.dim, s.n, s.n2, s.E
+        self.np2 = self.n2 ** self.dim
+        self.overlap = bool(overlap)
+        self.with_coarse = bool(with_coarse)
+        if self.overlap and not overlap_available(self.dim, self.n):
+            raise ValueError("the overlapping variant is not defined for dim = %d, lx1 = %d" % (self.dim, self.n))
+        self.Dh = s.w2[:, None] * s.D12
+        self.Ih = s.w2[:, None] * s.I12
+        self.glo = s.glo.reshape(self.E, -1)
+        self._lengths()
+        if self.overlap:
+            self._neighbours()
+            if not self.has_nb.any():   # no shared face: the device has no overlapping variant either
+                raise ValueError("the overlapping variant needs at least one shared face")
+            self._setup_overlap()
+        else:
+            self._setup_local()
+        if self.with_coarse:
+            self._setup_coarse(exact_max, omega)
+
+    # ---- geometry of the local problems
+    def _pt(self, ijk):
+        """numpy index tail of local GLL point (i, j[, k])."""
+        return tuple(reversed(ijk[: self.dim]))
+
+    def _lengths(self):
+        s, dim, n, E = self.sem, self.dim, self.n, self.E
+        self.L = np.zeros((E, dim))
+        self.endfac = np.zeros((E, dim, 2))
+        mid = n // 2
+        for dd in range(dim):
+            ax = dim - dd
+            c0 = np.stack([np.take(s.X[c], 0, axis=ax).reshape(E, -1).mean(axis=1) for c in range(dim)])
+            c1 = np.stack([np.take(s.X[c], n - 1, axis=ax).reshape(E, -1).mean(axis=1) for c in range(dim)])
+            self.L[:, dd] = np.sqrt(np.sum((c1 - c0) ** 2, axis=0))
+            for side in range(2):
+                ijk = [mid] * dim
+                ijk[dd] = 0 if side == 0 else n - 1
+                idx = (slice(None),) + self._pt(ijk)
+                m, vm = s.mask[dd][idx], s.vmult[idx]
+                self.endfac[:, dd, side] = np.where(m == 0.0, 0.0, vm)
+
+    def _neighbours(self):
+        """Per element face: neighbour element, its face direction, and the map of the face-interior points to the
+        neighbour's adjacent pressure layer (global pressure index), all from the glo_num labels."""
+        dim, n, n2, E = self.dim, self.n, self.n2, self.E
+        flat = self.glo.ravel()
+        order = np.argsort(flat, kind="stable")
+        srt = flat[order]
+        starts = np.searchsorted(srt, flat, side="left")
+        ends = np.searchsorted(srt, flat, side="right")
+        npt = n ** dim
+
+        def partner(e, p):
+            g = e * npt + p
+            cand = [int(c) for c in order[starts[g]: ends[g]] if c != g]
+            if not cand:
+                return None
+            assert len(cand) == 1, "face-interior point shared by more than two elements"
+            return cand[0] // npt, cand[0] % npt
+
+        def coords(p):
+            return [p % n, (p // n) % n, p // (n * n)][:dim]
+
+        self.has_nb = np.zeros((E, dim, 2), dtype=bool)
+        self.nb_len = np.zeros((E, dim, 2))
+        # ghost[e]: extended-grid index -> global pressure index (-1: not part of R_e)
+        N = n
+        NE = N ** dim
+        self.ghost = np.full((E, NE), -1, dtype=np.int64)
+        mid = n // 2
+        for e in range(E):
+            for dd in range(dim):
+                for side in range(2):
+                    ijk = [mid] * dim
+                    ijk[dd] = 0 if side == 0 else n - 1
+                    pm = ijk[0] + n * (ijk[1] + (n * ijk[2] if dim == 3 else 0))
+                    pr = partner(e, pm)
+                    if pr is None:
+                        continue
+                    e1, p1 = pr
+                    c1 = coords(p1)
+                    d1 = [q for q in range(dim) if c1[q] in (0, n - 1)]
+                    assert len(d1) == 1, "face-interior point of the neighbour is not on exactly one face"
+                    self.has_nb[e, dd, side] = True
+                    self.nb_len[e, dd, side] = self.L[e1, d1[0]]
+                    # every face-interior point of this face -> the neighbour's adjacent layer
+                    others = [q for q in range(dim) if q != dd]
+                    rng2 = range(1, n - 1)
+                    pts = [(u,) for u in rng2] if dim == 2 else [(u, v) for v in rng2 for u in rng2]
+                    for uv in pts:
+                        g = [0] * dim
+                        g[dd] = ijk[dd]
+                        for q, w in zip(others, uv):
+                            g[q] = w
+                        p = g[0] + n * (g[1] + (n * g[2] if dim == 3 else 0))
+                        pr2 = partner(e, p)
+                        assert pr2 is not None and pr2[0] == e1, "face with more than one neighbour"
+                        c2 = coords(pr2[1])
+                        q2 = [0] * dim
+                        for q in range(dim):
+                            if c2[q] == 0:
+                                q2[q] = 0
+                            elif c2[q] == n - 1:
+                                q2[q] = n2 - 1
+                            else:
+                                q2[q] = c2[q] - 1
+                        gq = e1 * self.np2 + q2[0] + n2 * (q2[1] + (n2 * q2[2] if dim == 3 else 0))
+                        self.ghost[e, p] = gq   # extended grid = the element's GLL grid: same index as the face point
+            # interior of the extended grid: the element's own pressure points
+            for q in range(self.np2):
+                a = [q % n2, (q // n2) % n2, q // (n2 * n2)][:dim]
+                p = (a[0] + 1) + N * ((a[1] + 1) + (N * (a[2] + 1) if dim == 3 else 0))
+                self.ghost[e, p] = e * self.np2 + q
+
+    # ---- no overlap
+    def _setup_local(self):
+        dim, n, E, s = self.dim, self.n, self.E, self.sem
+        self.S = np.zeros((E, dim, self.n2, self.n2))
+        lam = np.zeros((E, dim, self.n2))
+        for e in range(E):
+            for dd in range(dim):
+                l = self.L[e, dd]
+                bi = 1.0 / (0.5 * l * s.w1)
+                bi[0] *= self.endfac[e, dd, 0]
+                bi[-1] *= self.endfac[e, dd, 1]
+                A = self.Dh @ (bi[:, None] * self.Dh.T)
+                B = 0.25 * l * l * (self.Ih @ (bi[:, None] * self.Ih.T))
+                lm, S = gen_eig(A, B)
+                self.S[e, dd], lam[e, dd] = S, np.maximum(lm, 0.0)
+        den = np.stack([_den(lam[e], dim) for e in range(E)])
+        dmax = den.max()
+        self.invden = np.where(den > 1e-12 * dmax, 1.0 / np.where(den > 0, den, 1.0), 0.0)
+
+    # ---- one layer of face overlap
+    def ext_line(self, e, dd):
+        """The extended 1-D stiffness and mass matrices (n x n: left ghost, the element's n2 points, right ghost)."""
+        s, n, n2 = self.sem, self.n, self.n2
+        lm = self.L[e, dd]
+        ln = [self.nb_len[e, dd, 0] if self.has_nb[e, dd, 0] else 0.0, self.nb_len[e, dd, 1] if self.has_nb[e, dd, 1] else 0.0]
+        lens = [ln[0], lm, ln[1]]
+        nvl = 3 * n - 2
+        Bl = np.zeros(nvl)
+        Dl = np.zeros((n, nvl))
+        Il = np.zeros((n, nvl))
+        for q in range(3):
+            if lens[q] == 0.0:
+                continue
+            ov = q * (n - 1)
+            Bl[ov: ov + n] += 0.5 * lens[q] * s.w1
+            rows = [(0, n2 - 1)] if q == 0 else ([(1 + k, k) for k in range(n2)] if q == 1 else [(n - 1, 0)])
+            for row, k in rows:
+                Dl[row, ov: ov + n] = self.Dh[k]
+                Il[row, ov: ov + n] = 0.5 * lens[q] * self.Ih[k]
+        bq = np.where(Bl > 0.0, 1.0 / np.where(Bl > 0.0, Bl, 1.0), 0.0)
+        if lens[0] > 0.0:
+            bq[0] *= 0.5
+        else:
+            bq[n - 1] *= self.endfac[e, dd, 0]
+        if lens[2] > 0.0:
+            bq[-1] *= 0.5
+        else:
+            bq[2 * (n - 1)] *= self.endfac[e, dd, 1]
+        A = Dl @ (bq[:, None] * Dl.T)
+        B = Il @ (bq[:, None] * Il.T)
+        for side, g in ((0, 0), (1, n - 1)):
+            if lens[2 * side] == 0.0:
+                A[g, :] = A[:, g] = B[g, :] = B[:, g] = 0.0
+                A[g, g] = B[g, g] = 1.0
+        return A, B
+
+    def _setup_overlap(self):
+        dim, n, E = self.dim, self.n, self.E
+        self.Sx = np.zeros((E, dim, n, n))
+        lam = np.zeros((E, dim, n))
+        for e in range(E):
+            for dd in range(dim):
+                A, B = self.ext_line(e, dd)
+                lm, S = gen_eig(A, B)
+                self.Sx[e, dd], lam[e, dd] = S, np.maximum(lm, 0.0)
+        thr = 1e-12 * np.max(lam.max(axis=2).sum(axis=1))
+        den = np.stack([_den(lam[e], dim) for e in range(E)])
+        self.invden = np.where(den > thr, 1.0 / np.where(den > 0, den, 1.0), 0.0)
+        cnt = np.bincount(self.ghost[self.ghost >= 0], minlength=E * self.np2).astype(np.float64)
+        self.wq = cnt ** -0.5
+
+    # ---- coarse level
+    def _setup_coarse(self, exact_max, omega):
+        s, dim, n, n2, E = self.sem, self.dim, self.n, self.n2, self.E
+        NC = 1 << dim
+        h1 = 0.5 * (1.0 + s.z2)
+        lab = np.zeros((E, NC), dtype=np.int64)
+        for c in range(NC):
+            ijk = [(n - 1) if (c >> d) & 1 else 0 for d in range(3)]
+            lab[:, c] = self.glo[:, ijk[0] + n * (ijk[1] + n * ijk[2])]
+        u, vg = np.unique(lab, return_inverse=True)
+        self.vg = vg = vg.reshape(E, NC)
+        self.nvert = nv = len(u)
+        R1 = np.zeros((E * self.np2, nv))
+        for c in range(NC):
+            hats = [h1 if (c >> d) & 1 else 1.0 - h1 for d in range(dim)]
+            phi = _tens(np.ones((1,) * dim), [h[:, None] for h in hats]).ravel()
+            for e in range(E):
+                R1[e * self.np2: (e + 1) * self.np2, vg[e, c]] += phi
+        self.R1 = R1
+        ER1 = np.stack([s.cdabdtp(R1[:, v]).ravel() for v in range(nv)], axis=1)
+        Ac = R1.T @ ER1
+        Ac = 0.5 * (Ac + Ac.T)
+        self.Ac = Ac
+        if nv <= exact_max:
+            agg = np.arange(nv)
+            self.om = 0.0
+            self.ambiguous = False
+        else:
+            agg, self.ambiguous = self._aggregate(Ac)
+            self.om = omega
+        na = int(agg.max()) + 1
+        P = np.zeros((nv, na))
+        P[np.arange(nv), agg] = 1.0
+        Acc = P.T @ Ac @ P
+        if not s.has_outflow:
+            Acc = Acc + np.trace(Acc) / na / na
+        self.agg, self.na, self.P = agg, na, P
+        self.Acc_inv = np.linalg.inv(Acc)
+        d = np.diag(Ac)
+        self.dinv = np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 0.0)
+
+    def _aggregate(self, Ac):
+        """pprec_setup step 4, one rank: elements whose corners are all free become aggregates (element order); every
+        other vertex (vertex order) joins the aggregate of its most strongly coupled, already aggregated vertex among the
+        vertices of its elements (the first one on ties), else starts one.  Also reports whether a choice was a near-tie
+        (the device could then resolve it differently by rounding)."""
+        E, NC, nv, vg = self.E, self.vg.shape[1], self.nvert, self.vg
+        agg = np.full(nv, -1)
+        na = 0
+        for e in range(E):
+            if np.all(agg[vg[e]] < 0):
+                agg[vg[e]] = na
+                na += 1
+        inc = [[] for _ in range(nv)]
+        for e in range(E):
+            for c in range(NC):
+                inc[vg[e, c]].append(e)
+        ambiguous = False
+        for v in range(nv):
+            if agg[v] >= 0:
+                continue
+            near = np.unique(np.concatenate([vg[e] for e in inc[v]]))
+            best, bv = -1, -1.0
+            vals = []
+            for w in near:
+                if w == v or agg[w] < 0:
+                    continue
+                cv = abs(Ac[v, w])
+                vals.append((cv, agg[w]))
+                if cv > bv:
+                    bv, best = cv, agg[w]
+            for cv, a in vals:
+                if a != best and abs(cv - bv) <= 1e-9 * max(bv, 1e-300):
+                    ambiguous = True
+            if best >= 0:
+                agg[v] = best
+            else:
+                agg[v] = na
+                na += 1
+        return agg, ambiguous
+
+    # ---- application
+    def local(self, r):
+        """sum_e R_e^T W A~_e^-1 W R_e r"""
+        dim, E = self.dim, self.E
+        r = np.asarray(r, dtype=np.float64).ravel()
+        if not self.overlap:
+            rr = r.reshape((E,) + (self.n2,) * dim)
+            z = np.empty_like(rr)
+            for e in range(E):
+                S = self.S[e]
+                t = _tens(rr[e], [S[d].T for d in range(dim)]) * self.invden[e]
+                z[e] = _tens(t, [S[d] for d in range(dim)])
+            return z.ravel()
+        rw = r * self.wq
+        z = np.zeros_like(r)
+        shp = (self.n,) * dim
+        for e in range(E):
+            idx = self.ghost[e]
+            on = idx >= 0
+            rhs = np.zeros(idx.shape)
+            rhs[on] = rw[idx[on]]
+            S = self.Sx[e]
+            t = _tens(rhs.reshape(shp), [S[d].T for d in range(dim)]) * self.invden[e]
+            sol = _tens(t, [S[d] for d in range(dim)]).ravel()
+            np.add.at(z, idx[on], sol[on])
+        return z * self.wq
+
+    def coarse(self, r):
+        """R_1 (omega diag^-1 + P A_agg^-1 P^T) R_1^T r"""
+        rc = self.R1.T @ np.asarray(r, dtype=np.float64).ravel()
+        x = self.om * self.dinv * rc + self.P @ (self.Acc_inv @ (self.P.T @ rc))
+        return self.R1 @ x
+
+    def apply(self, r):
+        z = self.local(r)
+        if self.with_coarse:
+            z = z + self.coarse(r)
+        return z
+
+    __call__ = apply

@@ -326,6 +326,43 @@ def test_c_port_time_step_matches_the_numpy_time_step():
         assert abs(A.stats["p_iters"] - B.stats["p_iters"]) <= (0 if fixed else 2), (A.stats, B.stats)
 
 
+
+def test_c_port_time_step_is_independent_of_the_thread_count():
+    """The C port's sums run over fixed blocks in a fixed order: the same time step on 1, 2 and 3 threads gives the same bits and
+    the same iteration counts.  (With OpenMP reduction clauses the tolerance-terminated pressure solve of the test above stopped
+    3 - 4 iterations later on one or two threads than on four.)"""
+    import subprocess
+    from oracle.cport import load
+    from oracle.cpu_step import CStep
+    from oracle.lns import LNSConfig
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run(["make", "-C", os.path.join(root, "oracle", "c")], check=True, capture_output=True)
+    assert load() is not None
+    hm = box_mesh((3, 2, 2), 6, periodic=(True, False, False), deform=0.05)
+    sem = SEM(hm)
+    U = [sem.mask[0] * (1.0 + 0.3 * np.cos(sem.X[1])), sem.mask[1] * 0.2 * np.sin(sem.X[0]), sem.mask[2] * 0.1 * np.sin(sem.X[1])]
+    rng = np.random.default_rng(3)
+    u0 = [sem.mask[i] * sem.dsavg(rng.standard_normal(sem.shape1)) for i in range(3)]
+    p0 = rng.standard_normal(sem.shape2)
+    cfg = LNSConfig(tau=0.04, re=40.0, torder=3, dt=0.01, vtol=1e-11, ptol=1e-10, maxit_v=200, maxit_p=3000)
+    res = []
+    keep = None
+    try:
+        for t in (1, 2, 3):
+            B = CStep(sem, U, cfg)
+            keep = B.cp.threads() if keep is None else keep
+            B.cp.set_threads(t)
+            B.reset(u0, p0)
+            for _ in range(4):
+                B.advance()
+            res.append((dict(B.stats), [a.copy() for a in B.u], B.p.copy()))
+    finally:
+        if keep is not None:
+            B.cp.set_threads(keep)
+    for st, u, p in res[1:]:
+        assert st == res[0][0]
+        assert all(np.array_equal(a, b) for a, b in zip(u, res[0][1])) and np.array_equal(p, res[0][2])
+
 def test_matvec_matches_golden_3d_n8():
     """The lx1 = 8, 3-D fixture the GPU box checks the benchmark's kernel instantiations against (first matvec only here:
     the whole fixture takes half a minute of oracle time, tests/golden/make_golden.py 3d_n8)."""
