@@ -236,13 +236,13 @@ struct nlg_pprec {
     double *d_S = nullptr, *d_invden = nullptr;  // FDM: [E][3][n2*n2] eigenvector matrices, [E][n2^dim] 1/(sum of eigenvalues)
     double *d_dinv = nullptr;                    // 1 / diag(A_c)
     // overlapping variant: extended 1-D eigen-decompositions [E][3][n*n], eigenvalues [E][3][n], the velocity-shaped
-    // exchange arrays and the zero-denominator threshold.  2-D: W in the natural layout, summed by pairs-only gather-scatters.
-    // 3-D: W = the extended grids (natural layout) the restriction writes and k_fdm_ext reads, Wr = the return values at the
-    // face slots (face-grouped layout) k_fdm_ext writes and k_sch_finish reads; each ghost value goes straight to its consumer
+    // exchange arrays and the zero-denominator threshold.  W = the extended grids (natural layout) the restriction writes and
+    // the local solves read, Wr = the return values at the face slots (3-D: face-grouped layout, 2-D: natural layout) the
+    // local solves write and the finish reads; each ghost value goes straight to its consumer
     bool overlap = false;
-    int *d_pin = nullptr;                        // 3-D: [E][6 n2^2] index in W the layer value next to an element face point goes to, -1 = none
-    int *d_pret = nullptr;                       // 3-D: [E][6 n2^2] index in Wr the solve at a ghost point goes to, -1 = none
-    double *d_Sx = nullptr, *d_lamx = nullptr, *d_W = nullptr, *d_Wr = nullptr, *d_wq = nullptr;   // d_wq: count^-1/2 weights [E][n2^3]
+    int *d_pin = nullptr;                        // [E][2 dim n2^(dim-1)] index in W the layer value next to an element face point goes to, -1 = none
+    int *d_pret = nullptr;                       // [E][2 dim n2^(dim-1)] index in Wr the solve at a ghost point goes to, -1 = none (2-D: = d_pin)
+    double *d_Sx = nullptr, *d_lamx = nullptr, *d_W = nullptr, *d_Wr = nullptr, *d_wq = nullptr;   // d_wq: count^-1/2 weights [E][n2^dim]
     double thrx = 0.0;
     int *d_agg = nullptr, *d_ap = nullptr, *d_am = nullptr;
     double *d_Ainv = nullptr;                    // dense inverse on the aggregates: this rank's rows, [na][ncols]
@@ -253,7 +253,6 @@ struct nlg_pprec {
     // lanes of a block step: `lanes_cap` copies of W, Wr, tq, rc / x, ra, xa at these strides (pprec_reserve_lanes)
     int lanes_cap = 1;
     int64_t lW = 0, lt = 0, lv = 0, la = 0, la_x = 0;
-    bool coarse_pending = false;                 // pprec_coarse has left its chain (gather, restriction, dense solve) to the merged launches of pprec_fine
 };
 
 struct nlg_mesh {
@@ -382,10 +381,9 @@ struct nlg_pcg_upd {
     const double *p = nullptr, *w = nullptr, *nw = nullptr;
     double *rr_part = nullptr;   // [(E + 3) / 4]
 };
-int pprec_coarse(nlg_mesh *m, hipStream_t st, const double *flag, const double *r, const double **xc, bool overlap = false,
-                 const nlg_pcg_upd *upd = nullptr, int nl = 1, int64_t ld = 0);
-int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r, const double *xc, double *z,
-               double *rz_part = nullptr, bool overlap = false, int nl = 1, int64_t ld = 0);
+// z = M^-1 r (rz_part: r.z and z sums, (E + 3) / 4 blocks); nl lanes of a block step v * ld doubles apart
+int pprec_apply(nlg_mesh *m, hipStream_t st, const double *flag, const double *r, double *z, double *rz_part, bool overlap,
+                bool with_coarse, const nlg_pcg_upd *upd = nullptr, int nl = 1, int64_t ld = 0);
 int pprec_reserve_lanes(nlg_mesh *m, int nl);
 void pprec_free(nlg_mesh *m);
 
@@ -408,7 +406,6 @@ void halo_free(nlg_mesh *m);
 int sem_gs(nlg_mesh *m, double *const *fields, int nf, const double *gate = nullptr, int layout = 0, int nl = 1, int64_t ld = 0, int64_t ldg = 0);   // in place QQ^T; gate: device flag, non-zero = skip; layout: LAYOUT_NAT or LAYOUT_XP
 int sem_to_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl = 1, int64_t ld = 0, double *const *wts = nullptr);     // natural -> x-planes-first (out of place); wts: dst = wts * src
 int sem_from_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl = 1, int64_t ld = 0);
-int sem_gs_pairs(nlg_mesh *m, double *w, const double *gate = nullptr, int nl = 1, int64_t ld = 0, int64_t ldg = 0);   // the same in the natural layout (2-D Schwarz exchange)   // rank-local QQ^T over the two-copy groups (face interiors) of one field in the face-grouped layout
 int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h1, double h2, double *pw_part = nullptr,
                double *const *zf = nullptr, const double *beta_p = nullptr, const double *done_p = nullptr, bool xp = false, int nl = 1, int64_t ld = 0, int64_t uoff = 0);   // uoff: the updated direction is stored uoff doubles behind u (direction history of the PCG); zf: fused u <- zf + beta u; xp: u, zf, w in the x-planes-first layout (3-D, lx1 <= 8)
 int sem_axhelm_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const *const *w, double h1, double h2, double *const *pw,

@@ -1577,8 +1577,8 @@ int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
         const bool overlap = c.pprecond == 0 && m->pprec.overlap;
         P.pc = Q.nopc;
         P.npe = m->np2;
-        // r.z / z sums from the last kernel of the preconditioner: 3-D always, 2-D with the overlapping variant
-        double *rzp = (m->dim == 3 || overlap) ? op->d_part + 2 * m->E : nullptr;
+        // r.z / z sums from the last kernel of the preconditioner
+        double *rzp = op->d_part + 2 * m->E;
         // the PCG update of an iteration rides in the preconditioner's first kernel (which reads r anyway)
         nlg_pcg_upd upd;
         upd.alpha = op->d_s + S_N + S_ALPHA;
@@ -1605,9 +1605,7 @@ int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
             // one stream: a fork/join through events costs more than it hides (measured: 98 vs 84 us per apply)
             nlg_ctx *c = m->ctx;
             ProfScope ps(c, P_PPREC);
-            const double *coarse = nullptr;
-            NLG_TRY(pprec_coarse(m, c->stream, flag, rr, &coarse, overlap, flag ? &upd : nullptr, nl, ld));   // flag == null: the initial residual
-            NLG_TRY(pprec_fine(m, c->stream, flag, rr, coarse, zz, rzp, overlap, nl, ld));   // z = local solves + prolonged coarse part
+            NLG_TRY(pprec_apply(m, c->stream, flag, rr, zz, rzp, overlap, true, flag ? &upd : nullptr, nl, ld));   // flag == null: the initial residual
             *xc = nullptr;
             return 0;
         };
@@ -1624,9 +1622,9 @@ int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
     P.pw_part = Q.pw_part;
     P.pw_n = sem_opdiv_blocks(m);
     P.fused_pupdate = sem_opgradt_fuses_pupdate(m);
-    if (P.precond && (m->dim == 3 || (c.pprecond == 0 && m->pprec.overlap))) {
+    if (P.precond) {
         P.rz_part = op->d_part + 2 * m->E;
-        P.rz_n = m->dim == 3 ? (int)((m->E + 3) / 4) : (int)((m->E * m->np2 + NT - 1) / NT);
+        P.rz_n = (int)((m->E + 3) / 4);
     }
     // ---- residual projection (c.pproj): start from the A-orthogonal projection of the solution onto the span of the
     // previous increments of this matvec; the PCG then solves for the remainder

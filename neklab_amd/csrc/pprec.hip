@@ -138,10 +138,17 @@ __global__ __launch_bounds__(NT) void k_fdm(const double *__restrict__ flag, int
                                             const double *__restrict__ invden, const double *__restrict__ r,
                                             const double *__restrict__ xc, const double *__restrict__ xa,
                                             const int *__restrict__ agg, const int *__restrict__ vg, Hat hat,
-                                            double *__restrict__ z, double *__restrict__ part) {
+                                            double *__restrict__ z, double *__restrict__ part, int64_t ld, int64_t lv, int64_t la) {
     constexpr int NP = DIM == 3 ? N2 * N2 * N2 : N2 * N2;
     __shared__ double sS[4][3][N2 * N2];
     __shared__ double sA[4][NP], sB[4][NP];
+    {   // blockIdx.y = lane of a block step
+        const int64_t lo = (int64_t)blockIdx.y * ld;
+        if (flag) flag += lo;
+        r += lo, z += lo;
+        if (part) part += lo;
+        if (xc) xc += (int64_t)blockIdx.y * lv, xa += (int64_t)blockIdx.y * la;
+    }
     if (flag && flag[0] != 0.0) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t e = (int64_t)blockIdx.x * 4 + wv;
@@ -215,32 +222,8 @@ __global__ __launch_bounds__(NT) void k_fdm(const double *__restrict__ flag, int
     }
 }
 
-// aggregate restriction of the coarse chain as a device function: it rides in the launch of k_fdm_ext (merged launches, below)
-struct AggArgs {
-    int na;
-    const int *ap, *am;
-    const double *rr;
-    double *ra;
-    int64_t lv, la;
-};
-// (as a part of a merged launch: `bx` = block index inside this part, any multiple of 64 threads per block)
-__device__ __forceinline__ void agg_restrict_body(int bx, const double *flag, int64_t ld, const AggArgs &g) {
-    if (flag) flag += (int64_t)blockIdx.y * ld;
-    if (flag && flag[0] != 0.0) return;
-    const double *rr = g.rr + (int64_t)blockIdx.y * g.lv;
-    double *ra = g.ra + (int64_t)blockIdx.y * g.la;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wpb = blockDim.x >> 6;
-    const int a = bx * wpb + wid;
-    if (a >= g.na) return;
-    double s = 0.0;
-    for (int q = g.ap[a] + lane; q < g.ap[a + 1]; q += 64) s += rr[g.am[q]];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if (lane == 0) ra[a] = s;
-}
-
 // the vertex gather and the aggregate restriction of the coarse chain, both straight from the element-corner values t: they ride
-// in the launch of k_fdm_ext*, so that the coarse chain adds one launch (k_dense_gemv) to the fine level.  The restriction
+// in the launch of k_fdm_ext* / k_fdm_ext2, so that the coarse chain adds one launch (k_dense_gemv) to the fine level.  The restriction
 // recomputes the vertex sums of its members in the order of the gather, so ra is bit-identical to restricting rc.
 struct ChainArgs {
     int nb_gather;                 // blocks of the vertex gather; the blocks of the aggregate restriction follow
@@ -288,26 +271,29 @@ __device__ __forceinline__ void chain_body(int bx, const double *flag, int64_t l
     if (lane == 0) ra[a] = s;
 }
 
-// ---- overlapping variant (3-D) ---------------------------------------------------------------------------
+// ---- overlapping variant ------------------------------------------------------------------------------------
 // Extended local problems: element e plus the layer of GL points of each face neighbour that is adjacent to the
-// shared face -> an N^3 grid (N = N2 + 2, the size of the velocity mesh), solved by fast diagonalisation with 1-D
+// shared face -> an N^dim grid (N = N2 + 2, the size of the velocity mesh), solved by fast diagonalisation with 1-D
 // operators built from the line of up to three elements (pprec_setup).  Every ghost value is written once, by its
 // producer, into the slot its consumer reads (the destinations per element face point come from pprec_setup: pin, pret):
-//   k_q1_restrict_local (pack)  Win[e]         = extended grid of e: r wq in the interior, and each element writes r wq of
+//   k_q1_restrict_local* (pack)  Win[e]        = extended grid of e: r wq in the interior, and each element writes r wq of
 //                                                its adjacent layers into the ghost slots of its neighbours' grids
-//   k_fdm_ext                   z_e = interior of the solve on Win[e];  the solve at the ghost points -> the neighbour's
-//                                                face slot of Wret (face-grouped layout)
-//   k_sch_finish                z += Wret at the element's faces (+ coarse correction), r.z sums
-// i.e. z = sum_e R_e^T Atilde_e^-1 R_e r with overlapping index sets R_e: symmetric, additive.  Win (natural layout) and
-// Wret are two arrays: a solve reads its grid while the neighbours' solves write their ghost values.  Edge and corner
-// slots, and the ghost slots of faces without a neighbour, are never written and stay zero.  A face on a rank boundary
-// has the element itself as destination: the copy-mode halo exchange replaces the own value by the neighbour's.
-__device__ __forceinline__ int face_pt(int N, int a, int b, int c) {
-    // compact index (0 .. 6 (N-2)^2 - 1) of an interior point of an element face of the N^3 grid, the order of fg_slot
-    const int M = N - 2;
-    if (a == 0 || a == N - 1) return (a == N - 1) * M * M + (b - 1) + M * (c - 1);
-    if (b == 0 || b == N - 1) return (2 + (b == N - 1)) * M * M + (a - 1) + M * (c - 1);
-    return (4 + (c == N - 1)) * M * M + (a - 1) + M * (b - 1);
+//   k_fdm_ext*, k_fdm_ext2       z_e = interior of the solve on Win[e];  the solve at the ghost points -> the neighbour's
+//                                                face slot of Wret
+//   k_sch_finish, k_sch_finish2  z += Wret at the element's faces (+ coarse correction), r.z sums
+// i.e. z = sum_e R_e^T Atilde_e^-1 R_e r with overlapping index sets R_e: symmetric, additive.  Win and Wret are two
+// velocity-shaped arrays: a solve reads its grid while the neighbours' solves write their ghost values.  Win is in the
+// natural layout; Wret is in the face-grouped layout in 3-D and in the natural one in 2-D (pin = pret there).  Edge and
+// corner slots, and the ghost slots of faces without a neighbour, are never written and stay zero.  A face on a rank
+// boundary has the element itself as destination: the copy-mode halo exchange replaces the own value by the neighbour's.
+template <int DIM = 3>
+__device__ __forceinline__ int face_pt(int N, int a, int b, int c = 1) {
+    // compact index (0 .. 2 DIM (N-2)^(DIM-1) - 1) of an interior point of an element face of the N^DIM grid, the order of
+    // fg_slot's face blocks (3-D)
+    const int M = N - 2, M2 = DIM == 3 ? M : 1;   // points per face: M M2
+    if (a == 0 || a == N - 1) return (a == N - 1) * M * M2 + (b - 1) + M * (c - 1);
+    if (b == 0 || b == N - 1) return (2 + (b == N - 1)) * M * M2 + (a - 1) + M * (c - 1);
+    return (4 + (c == N - 1)) * M * M2 + (a - 1) + M * (b - 1);
 }
 
 // WPB waves (= elements) per block.  WPB = 1 makes every __syncthreads a single-wave barrier: the stages of one element
@@ -635,8 +621,8 @@ __global__ __launch_bounds__(NT) void k_sch_finish(const double *__restrict__ fl
     }
 }
 
-// ---- 2-D twins: the exchange array W is a velocity-shaped field in the natural layout (N x N per element), the ghost
-// layers are the interior points of the element edges, one lane per extended point.
+// ---- 2-D twins: Win and Wret are velocity-shaped fields in the natural layout (N x N per element), the ghost layers are the
+// interior points of the element edges; one wave per element, four elements per block, one lane per extended point.
 template <int N, bool FWD, int AX>
 __device__ __forceinline__ void fdm_stage2(const double *__restrict__ in, double *__restrict__ out,
                                            const double *__restrict__ S, int p) {
@@ -654,16 +640,21 @@ __device__ __forceinline__ void fdm_stage2(const double *__restrict__ in, double
 
 template <int N>
 __global__ __launch_bounds__(NT) void k_fdm_ext2(const double *__restrict__ flag, int64_t E, const double *__restrict__ S,
-                                                 const double *__restrict__ lam, double thr, const double *__restrict__ r,
-                                                 const double *__restrict__ wq, double *__restrict__ W,
-                                                 double *__restrict__ z, int nb_fdm, AggArgs ag) {
+                                                 const double *__restrict__ lam, double thr, const double *__restrict__ Win,
+                                                 double *__restrict__ Wr, double *__restrict__ z, const int *__restrict__ pret,
+                                                 int64_t ld, int64_t lW, int nb_fdm, ChainArgs cg) {
     static_assert(N * N <= 64, "one lane per extended point");
-    constexpr int N2 = N - 2, NP = N * N, NP2 = N2 * N2;
+    constexpr int N2 = N - 2, NP = N * N, NP2 = N2 * N2, NF = 4 * N2;
     __shared__ double sS[4][2][N * N];
     __shared__ double sA[4][NP], sB[4][NP];
-    if ((int)blockIdx.x >= nb_fdm) {   // merged launch: the aggregate restriction of the coarse chain (see k_fdm_ext)
-        agg_restrict_body((int)blockIdx.x - nb_fdm, flag, 0, ag);
+    if ((int)blockIdx.x >= nb_fdm) {   // merged launch: the coarse chain up to the dense solve (see k_fdm_ext)
+        chain_body((int)blockIdx.x - nb_fdm, flag, ld, cg);
         return;
+    }
+    {   // blockIdx.y = lane of a block step
+        const int64_t lo = (int64_t)blockIdx.y * ld;
+        if (flag) flag += lo;
+        z += lo, Win += (int64_t)blockIdx.y * lW, Wr += (int64_t)blockIdx.y * lW;
     }
     if (flag && flag[0] != 0.0) return;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -675,16 +666,9 @@ __global__ __launch_bounds__(NT) void k_fdm_ext2(const double *__restrict__ flag
     const int p = on ? lane : 0;
     const int a = p % N, b = p / N;
     const int nb = (a == 0 || a == N - 1) + (b == 0 || b == N - 1);
-    const int a2 = min(max(a, 1), N - 2) - 1, b2 = min(max(b, 1), N - 2) - 1;
-    const int q2 = a2 + N2 * b2;
-    double v = 0.0;
-    if (nb <= 1) {
-        const double own = r[ee * NP2 + q2] * wq[ee * NP2 + q2];
-        v = nb == 0 ? own : W[ee * NP + p] - own;
-    }
-    if (on) sA[wv][p] = v;
+    const int pr = pret[ee * NF + (nb == 1 ? face_pt<2>(N, a, b) : 0)];
+    if (on) sA[wv][p] = Win[ee * NP + p];
     __syncthreads();
-    double t = 0.0;
     if (on) fdm_stage2<N, true, 0>(sA[wv], sB[wv], sS[wv][0], p);
     __syncthreads();
     if (on) fdm_stage2<N, true, 1>(sB[wv], sA[wv], sS[wv][1], p);
@@ -698,77 +682,76 @@ __global__ __launch_bounds__(NT) void k_fdm_ext2(const double *__restrict__ flag
     __syncthreads();
     if (on) fdm_stage2<N, false, 0>(sB[wv], sA[wv], sS[wv][0], p);
     __syncthreads();
-    (void)t;
     if (act && on) {
-        if (nb == 1) {
-            W[e * NP + p] = sA[wv][p];
-        } else if (nb == 0) {
-            double o = sA[wv][p];
-            if (a == 1) o -= sA[wv][p - 1];
-            if (a == N - 2) o -= sA[wv][p + 1];
-            if (b == 1) o -= sA[wv][p - N];
-            if (b == N - 2) o -= sA[wv][p + N];
-            z[e * NP2 + q2] = o;
-        }
+        if (nb == 0)
+            z[e * NP2 + (a - 1) + N2 * (b - 1)] = sA[wv][p];
+        else if (nb == 1 && pr >= 0)
+            Wr[pr] = sA[wv][p];   // ghost value: belongs to the neighbour's adjacent layer
     }
 }
 
+// z += (neighbours' ghost values at this point: at most two return slots of the element's own faces) x wq + prolonged
+// coarse correction; r.z and z sums.  One wave per element, four elements per block: the partial sums of k_sch_finish
 template <int N>
 __global__ __launch_bounds__(NT) void k_sch_finish2(const double *__restrict__ flag, int64_t E, const double *__restrict__ W,
                                                     const double *__restrict__ r, const double *__restrict__ wq,
                                                     const double *__restrict__ xc, const double *__restrict__ xa,
                                                     const int *__restrict__ agg, const int *__restrict__ vg, Hat hat,
-                                                    double *__restrict__ z, double *__restrict__ part) {
+                                                    double *__restrict__ z, double *__restrict__ part,
+                                                    int64_t ld, int64_t lW, int64_t lv, int64_t la) {
     constexpr int N2 = N - 2, NP = N * N, NP2 = N2 * N2;
-    __shared__ double srz[2][NT / 64];
+    static_assert(NP2 <= 64, "one lane per point");
+    __shared__ double sred[8];
+    {   // blockIdx.y = lane of a block step
+        const int64_t lo = (int64_t)blockIdx.y * ld;
+        if (flag) flag += lo;
+        r += lo, z += lo, W += (int64_t)blockIdx.y * lW;
+        if (part) part += lo;
+        if (xc) xc += (int64_t)blockIdx.y * lv, xa += (int64_t)blockIdx.y * la;
+    }
     if (flag && flag[0] != 0.0) return;
-    const int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x;
-    double srzv = 0.0, szv = 0.0;
-    if (i < E * NP2) {
-    const int64_t e = i / NP2;
-    const int q = (int)(i % NP2), a = q % N2, b = q / N2;
-    const double *We = W + e * NP;
-    double v = z[i];
-    if (a == 0) v += We[0 + N * (b + 1)];
-    if (a == N2 - 1) v += We[(N - 1) + N * (b + 1)];
-    if (b == 0) v += We[(a + 1) + N * 0];
-    if (b == N2 - 1) v += We[(a + 1) + N * (N - 1)];
-    v *= wq[i];
-    if (xc) {
-        double cv[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t e = (int64_t)blockIdx.x * 4 + wv;
+    double srz = 0.0, sz = 0.0;
+    if (e < E && lane < NP2) {
+        const int a = lane % N2, b = lane / N2;
+        const int64_t i = e * NP2 + lane;
+        const double *We = W + e * NP;
+        double v = z[i];
+        if (a == 0) v += We[0 + N * (b + 1)];
+        if (a == N2 - 1) v += We[(N - 1) + N * (b + 1)];
+        if (b == 0) v += We[(a + 1) + N * 0];
+        if (b == N2 - 1) v += We[(a + 1) + N * (N - 1)];
+        v *= wq[i];
+        if (xc) {
+            double cv[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int vv = vg[e * 4 + c];
-            cv[c] = xc[vv] + xa[agg[vv]];
+            for (int c = 0; c < 4; ++c) {
+                const int vv = vg[e * 4 + c];
+                cv[c] = xc[vv] + xa[agg[vv]];
+            }
+            const double ha = hat.h1[a], hb = hat.h1[b];
+            const double c0 = cv[0] + ha * (cv[1] - cv[0]), c1 = cv[2] + ha * (cv[3] - cv[2]);
+            v += c0 + hb * (c1 - c0);
         }
-        const double ha = hat.h1[a], hb = hat.h1[b];
-        const double c0 = cv[0] + ha * (cv[1] - cv[0]), c1 = cv[2] + ha * (cv[3] - cv[2]);
-        v += c0 + hb * (c1 - c0);
+        z[i] = v;
+        srz = r[i] * v;
+        sz = v;
     }
-    z[i] = v;
-    srzv = r[i] * v;
-    szv = v;
-    }
-    if (part) {   // first-stage sums of the PCG: part[b] = sum r z, part[nb + b] = sum z
+    if (part) {   // first-stage sums of the PCG: part[blk] = sum r.z, part[nblk + blk] = sum z
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            srzv += __shfl_down(srzv, o, 64);
-            szv += __shfl_down(szv, o, 64);
+            srz += __shfl_down(srz, o, 64);
+            sz += __shfl_down(sz, o, 64);
         }
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
         if (lane == 0) {
-            srz[0][wid] = srzv;
-            srz[1][wid] = szv;
+            sred[wv] = srz;
+            sred[4 + wv] = sz;
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            double a = 0.0, b = 0.0;
-            for (int w = 0; w < NT / 64; ++w) {
-                a += srz[0][w];
-                b += srz[1][w];
-            }
-            part[blockIdx.x] = a;
-            part[gridDim.x + blockIdx.x] = b;
+            part[blockIdx.x] = sred[0] + sred[1] + sred[2] + sred[3];
+            part[gridDim.x + blockIdx.x] = sred[4] + sred[5] + sred[6] + sred[7];
         }
     }
 }
@@ -813,29 +796,21 @@ __global__ __launch_bounds__(NT) void k_q1_restrict_local(const double *__restri
         }
         const double ha = hat.h1[q % n2], hb = hat.h1[(q / n2) % n2];
         const double hc = DIM == 3 ? hat.h1[q / (n2 * n2)] : 0.0;
-        if (DIM == 2 && W) {
-            const int N = n2 + 2, a = q % n2, b = q / n2;
-            double *We = W + e * (int64_t)(N * N);
-            const double vw = v * wq[e * np2 + q];
-            if (a == 0) We[0 + N * (b + 1)] = vw;
-            if (a == n2 - 1) We[(N - 1) + N * (b + 1)] = vw;
-            if (b == 0) We[(a + 1)] = vw;
-            if (b == n2 - 1) We[(a + 1) + N * (N - 1)] = vw;
-        }
-        if (DIM == 3 && W) {
+        if (W) {
             // overlapping Schwarz: the own value into the interior of the element's extended grid, and the layers adjacent to
             // the element faces straight into the ghost slots of the neighbours' extended grids (pin, pprec_setup)
-            const int N = n2 + 2, M = n2, MM = n2 * n2, a = q % n2, b = (q / n2) % n2, c = q / (n2 * n2);
+            const int N = n2 + 2, M = n2, a = q % n2, b = (q / n2) % n2, c = DIM == 3 ? q / (n2 * n2) : 0;
+            const int F = DIM == 3 ? n2 * n2 : n2;   // points per face
             const double vw = v * wq[e * np2 + q];
-            W[e * (int64_t)(N * N * N) + (a + 1) + N * ((b + 1) + N * (c + 1))] = vw;
-            const int *pe = pin + e * (int64_t)(6 * MM);
+            W[e * (int64_t)(DIM == 3 ? N * N * N : N * N) + (a + 1) + N * ((b + 1) + (DIM == 3 ? N * (c + 1) : 0))] = vw;
+            const int *pe = pin + e * (int64_t)(2 * DIM * F);
             int pk;
-            if (a == 0 && (pk = pe[0 * MM + b + M * c]) >= 0) W[pk] = vw;
-            if (a == M - 1 && (pk = pe[1 * MM + b + M * c]) >= 0) W[pk] = vw;
-            if (b == 0 && (pk = pe[2 * MM + a + M * c]) >= 0) W[pk] = vw;
-            if (b == M - 1 && (pk = pe[3 * MM + a + M * c]) >= 0) W[pk] = vw;
-            if (c == 0 && (pk = pe[4 * MM + a + M * b]) >= 0) W[pk] = vw;
-            if (c == M - 1 && (pk = pe[5 * MM + a + M * b]) >= 0) W[pk] = vw;
+            if (a == 0 && (pk = pe[0 * F + b + M * c]) >= 0) W[pk] = vw;
+            if (a == M - 1 && (pk = pe[1 * F + b + M * c]) >= 0) W[pk] = vw;
+            if (b == 0 && (pk = pe[2 * F + a + M * c]) >= 0) W[pk] = vw;
+            if (b == M - 1 && (pk = pe[3 * F + a + M * c]) >= 0) W[pk] = vw;
+            if (DIM == 3 && c == 0 && (pk = pe[4 * F + a + M * b]) >= 0) W[pk] = vw;
+            if (DIM == 3 && c == M - 1 && (pk = pe[5 * F + a + M * b]) >= 0) W[pk] = vw;
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -970,28 +945,6 @@ __global__ __launch_bounds__(NT) void k_q1_restrict_local3s(const double *__rest
 
 // rc[v] = sum of t over the (element, corner) entries incident to vertex v (fixed order), and the first damped-Jacobi
 // sweep from a zero guess
-struct GatherArgs {
-    int nvert;
-    const int *vp, *vi;
-    const double *t;
-    double *rc;
-    const double *dinv;
-    double om;
-    double *x;
-    int64_t lt, lv;
-};
-__device__ __forceinline__ void q1_gather_body(int bx, const double *flag, int64_t ld, const GatherArgs &g) {
-    if (flag) flag += (int64_t)blockIdx.y * ld;
-    if (flag && flag[0] != 0.0) return;
-    const double *t = g.t + (int64_t)blockIdx.y * g.lt;
-    double *rc = g.rc + (int64_t)blockIdx.y * g.lv, *x = g.x + (int64_t)blockIdx.y * g.lv;
-    const int v = bx * NT + threadIdx.x;
-    if (v >= g.nvert) return;
-    double a = 0.0;
-    for (int q = g.vp[v]; q < g.vp[v + 1]; ++q) a += t[g.vi[q]];
-    rc[v] = a;
-    x[v] = g.om * g.dinv[v] * a;
-}
 __global__ __launch_bounds__(NT) void k_q1_gather(const double *__restrict__ flag, int nvert, const int *__restrict__ vp,
                                                   const int *__restrict__ vi, const double *__restrict__ t,
                                                   double *__restrict__ rc, const double *__restrict__ dinv, double om,
@@ -1145,71 +1098,12 @@ __device__ __forceinline__ void dense_gemv_body(int bx, const double *flag, int6
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if (lane == 0) xa[row] = s;
 }
-// xa = Ainv ra (dense, row-major), one wave per row.  T = float for the global aggregate level of several ranks: the
-// rows of the inverse are the largest per-iteration read there (2.4k x 19.6k at 8 x 10^4 elements), a preconditioner
-// needs no more than single precision, and the symmetric matrix is rounded entry by entry, so it stays symmetric
-// across the ranks that hold its rows; sums in double.
 template <typename T>
 __global__ __launch_bounds__(NT) void k_dense_gemv(const double *flag, int na, int ncols, const T *__restrict__ Ainv,
                                                    const double *__restrict__ ra, double *__restrict__ xa, int64_t ld = 0, int64_t la = 0,
                                                    int na_max = 0, int nlanes = 1) {
     const GemvArgs<T> g = {na, ncols, Ainv, ra, xa, la, na_max, nlanes};
     dense_gemv_body<T>((int)blockIdx.x, flag, ld, g);
-}
-
-// ---- merged launches (2-D): the coarse-grid chain rides in the launches of the fine level ----------------------------------
-// The vertex gather, the aggregate restriction and the dense solve are tiny (5 - 8 us each, one after the other); the three
-// fine-level launches they interleave with are independent of them.  One launch = the blocks of the fine kernel followed by the
-// blocks of a coarse kernel (block-uniform branch on blockIdx.x): the coarse work runs beside the fine work on otherwise idle
-// CUs and its three launches -- and their start-up latency on the stream -- disappear.  (3-D has no pairs passes left: the
-// gather and the restriction ride in k_fdm_ext*, chain_body, and the dense solve is a launch of its own.)
-// (a) pairs-only gather-scatter of the exchange array W + vertex gather
-__device__ __forceinline__ void pairs_body(int64_t bx, const int *__restrict__ idx, int64_t npairs, double *__restrict__ w,
-                                           const double *__restrict__ gate, int64_t ldw, int64_t ldg) {
-    if (gate && gate[(int64_t)blockIdx.y * ldg] != 0.0) return;
-    w += (int64_t)blockIdx.y * ldw;
-    const int64_t t = bx * (int64_t)NT + threadIdx.x;
-    const int64_t np2 = npairs >> 1;
-    if (t < np2) {
-        const int4 q = reinterpret_cast<const int4 *>(idx)[t];
-        if (q.z == q.x + 1 && q.w == q.y + 1 && !((q.x | q.y) & 1)) {
-            const double2 a = *reinterpret_cast<const double2 *>(w + q.x), b = *reinterpret_cast<const double2 *>(w + q.y);
-            double2 sv;
-            sv.x = a.x + b.x;
-            sv.y = a.y + b.y;
-            *reinterpret_cast<double2 *>(w + q.x) = sv;
-            *reinterpret_cast<double2 *>(w + q.y) = sv;
-        } else {
-            const double s0 = w[q.x] + w[q.y], s1 = w[q.z] + w[q.w];
-            w[q.x] = s0;
-            w[q.y] = s0;
-            w[q.z] = s1;
-            w[q.w] = s1;
-        }
-        return;
-    }
-    const int64_t g = 2 * np2 + (t - np2);
-    if (g >= npairs) return;
-    const int2 ab = reinterpret_cast<const int2 *>(idx)[g];
-    const double sv = w[ab.x] + w[ab.y];
-    w[ab.x] = sv;
-    w[ab.y] = sv;
-}
-__global__ __launch_bounds__(NT) void k_pairs_gather(int nb_pairs, const int *__restrict__ idx, int64_t npairs, double *__restrict__ w,
-                                                     int64_t ldw, const double *__restrict__ flag, int64_t ld, GatherArgs g) {
-    if ((int)blockIdx.x < nb_pairs)
-        pairs_body(blockIdx.x, idx, npairs, w, flag, ldw, ld);
-    else
-        q1_gather_body((int)blockIdx.x - nb_pairs, flag, ld, g);
-}
-// (c) the second pairs-only gather-scatter + the dense aggregate solve
-template <typename T>
-__global__ __launch_bounds__(NT) void k_pairs_gemv(int nb_pairs, const int *__restrict__ idx, int64_t npairs, double *__restrict__ w,
-                                                   int64_t ldw, const double *__restrict__ flag, int64_t ld, GemvArgs<T> g) {
-    if ((int)blockIdx.x < nb_pairs)
-        pairs_body(blockIdx.x, idx, npairs, w, flag, ldw, ld);
-    else
-        dense_gemv_body<T>((int)blockIdx.x - nb_pairs, flag, ld, g);
 }
 
 __global__ void k_to_float(int64_t n, const double *__restrict__ a, float *__restrict__ b) {
@@ -1455,7 +1349,7 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
     NLG_TRY(up(hden, &P.d_invden));
 
     // ---- 1b. overlapping variant: extended 1-D operators from the line left neighbour | element | right neighbour
-    // (3-D: exchange array in the face-grouped layout; 2-D: natural layout)
+    // (return array Wr in the face-grouped layout in 3-D, in the natural layout in 2-D)
     if (((dim == 3 && m->gs.d_indices_fg && n <= 12 && n != 11) || (dim == 2 && n <= 8)) && m->gs.npairs > 0) {
         // normal edge length of the face neighbours, through the gather-scatter: every element puts its own
         // normal length on the interior points of its faces, the sum minus the own value is the neighbour's
@@ -1477,7 +1371,7 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
         NLG_HIP(hipMemcpyAsync(dw, hw.data(), sizeof(double) * (size_t)m->lvn, hipMemcpyHostToDevice, st));
         {
             // halo on: a face neighbour on another rank counts like a local one (its ghost layer travels with the
-            // halo exchange of the array W, pprec_fine)
+            // halo exchange of the array W, pprec_apply)
             double *f1[1] = {dw};
             NLG_TRY(sem_gs(m, f1, 1));
         }
@@ -1566,44 +1460,48 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
         NLG_TRY(up(hwq, &P.d_wq));
         P.thrx = 1e-12 * dmax;
         NLG_TRY(up(hSx, &P.d_Sx));
-        if (dim == 3) {
-            // destinations of the overlap values per element face point k (compact, the order of fg_slot's face blocks):
+        {
+            // destinations of the overlap values per element face point k (compact, the order of face_pt / fg_slot's face blocks):
             //   pin[e][k]  = index in Win (natural layout) of the ghost point that the pressure layer of e next to k is for;
-            //   pret[e][k] = index in Wret (face-grouped layout) of the face slot that the solve of e at ghost point k is for;
+            //   pret[e][k] = index in Wret of the face slot that the solve of e at ghost point k is for (3-D: face-grouped
+            //                layout, 2-D: natural layout, so pret = pin);
             // the neighbour's face point for a face inside this rank, the own one for a face on a rank boundary (copy-mode halo
-            // exchange), -1 without a neighbour.  The local partners are the two-copy groups of the face-grouped gather-scatter.
-            const int M = n2, MM = n2 * n2, NF = 6 * MM, NP = n * n * n, FB = 8 + 12 * M;
-            std::vector<int> fnat(NF);
-            for (int f6 = 0; f6 < 6; ++f6)
-                for (int v = 0; v < M; ++v)
+            // exchange), -1 without a neighbour.  The local partners are the two-copy groups of the gather-scatter in the
+            // layout of Wret.
+            const int M = n2, F = dim == 3 ? n2 * n2 : n2, NF = 2 * dim * F, NP = dim == 3 ? n * n * n : n * n, FB = 8 + 12 * M;
+            std::vector<int> fnat(NF), fret(NF), kof(NP, -1);   // face point -> slot in Win, in Wret; slot in Wret -> face point
+            for (int f = 0; f < 2 * dim; ++f)
+                for (int v = 0; v < (dim == 3 ? M : 1); ++v)
                     for (int u = 0; u < M; ++u) {
-                        const int dd = f6 >> 1, x = (f6 & 1) ? n - 1 : 0;
-                        const int a = dd == 0 ? x : u + 1, b = dd == 0 ? u + 1 : (dd == 1 ? x : v + 1), c = dd == 2 ? x : v + 1;
-                        const int k = f6 * MM + u + M * v;
-                        NLG_CHECK(fg_slot(n, a, b, c) == FB + k, "pprec_setup: internal (face point order)");
+                        const int dd = f >> 1, x = (f & 1) ? n - 1 : 0;
+                        const int a = dd == 0 ? x : u + 1, b = dd == 0 ? u + 1 : (dd == 1 ? x : v + 1);
+                        const int c = dim == 3 ? (dd == 2 ? x : v + 1) : 0;
+                        const int k = f * F + u + M * v;
                         fnat[k] = a + n * (b + n * c);
+                        NLG_CHECK(dim == 2 || fg_slot(n, a, b, c) == FB + k, "pprec_setup: internal (face point order)");
+                        fret[k] = dim == 3 ? FB + k : fnat[k];
+                        kof[fret[k]] = k;
                     }
             NLG_CHECK((int64_t)E * NP < INT32_MAX, "pprec_setup: %lld elements are too many for 32-bit overlap indices", (long long)E);
             std::vector<int> pidx((size_t)2 * m->gs.npairs), mate((size_t)E * NP, -1);
-            NLG_HIP(hipMemcpy(pidx.data(), m->gs.d_indices_fg, sizeof(int) * pidx.size(), hipMemcpyDeviceToHost));
-            auto is_face = [&](int i) { const int sl = i % NP; return sl >= FB && sl < FB + NF; };
+            NLG_HIP(hipMemcpy(pidx.data(), dim == 3 ? m->gs.d_indices_fg : m->gs.d_indices, sizeof(int) * pidx.size(), hipMemcpyDeviceToHost));
             for (int64_t g = 0; g < m->gs.npairs; ++g) {
                 const int i0 = pidx[2 * g], i1 = pidx[2 * g + 1];
-                NLG_CHECK(i0 >= 0 && i1 >= 0 && i0 < E * NP && i1 < E * NP, "pprec_setup: face-grouped pair index out of range");
-                if (is_face(i0) && is_face(i1)) mate[i0] = i1, mate[i1] = i0;
+                NLG_CHECK(i0 >= 0 && i1 >= 0 && i0 < E * NP && i1 < E * NP, "pprec_setup: pair index out of range");
+                if (kof[i0 % NP] >= 0 && kof[i1 % NP] >= 0) mate[i0] = i1, mate[i1] = i0;
             }
             std::vector<int> pin((size_t)E * NF, -1), pret((size_t)E * NF, -1);
             for (int64_t e = 0; e < E; ++e)
                 for (int k = 0; k < NF; ++k) {
-                    const int own = (int)(e * NP + FB + k), mt = mate[own];
-                    const bool nb = hasnb[(size_t)e * 6 + k / MM];
+                    const int own = (int)(e * NP + fret[k]), mt = mate[own];
+                    const bool nb = hasnb[(size_t)e * 6 + k / F];
                     int di = -1, dr = -1;
                     if (mt >= 0) {
-                        NLG_CHECK(nb, "pprec_setup: element %lld face %d has a partner but no neighbour length", (long long)e, k / MM);
-                        di = (mt / NP) * NP + fnat[mt % NP - FB];
+                        NLG_CHECK(nb, "pprec_setup: element %lld face %d has a partner but no neighbour length", (long long)e, k / F);
+                        di = (mt / NP) * NP + fnat[kof[mt % NP]];
                         dr = mt;
                     } else if (nb) {
-                        NLG_CHECK(m->halo.active, "pprec_setup: element %lld face %d: neighbour without a partner point", (long long)e, k / MM);
+                        NLG_CHECK(m->halo.active, "pprec_setup: element %lld face %d: neighbour without a partner point", (long long)e, k / F);
                         di = (int)(e * NP + fnat[k]);
                         dr = own;
                     }
@@ -1625,8 +1523,8 @@ int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
                 for (int64_t e = 0; e < E; ++e)
                     for (int k = 0; k < NF; ++k) {
                         const int want = pin[(size_t)e * NF + k] >= 0;
-                        NLG_CHECK(cin[(size_t)e * NP + fnat[k]] == want && cret[(size_t)e * NP + FB + k] == want,
-                                  "pprec_setup: ghost slot of element %lld face %d without its producer", (long long)e, k / MM);
+                        NLG_CHECK(cin[(size_t)e * NP + fnat[k]] == want && cret[(size_t)e * NP + fret[k]] == want,
+                                  "pprec_setup: ghost slot of element %lld face %d without its producer", (long long)e, k / F);
                         nexp += want;
                     }
                 NLG_CHECK(nexp == nw, "pprec_setup: overlap values written outside the ghost slots");
@@ -2101,7 +1999,7 @@ int pprec_reserve_lanes(nlg_mesh *m, int nl) {
     };
     NLG_TRY(regrow(&P.d_W, m->lvs, &P.lW));
     int64_t lW2 = 0;
-    NLG_TRY(regrow(&P.d_Wr, m->lvs, &lW2));   // (3-D overlapping variant: the return array beside the extended grids)
+    NLG_TRY(regrow(&P.d_Wr, m->lvs, &lW2));   // (overlapping variant: the return array beside the extended grids)
     NLG_CHECK(!P.d_Wr || lW2 == P.lW, "pprec: inconsistent lane strides");
     NLG_TRY(regrow(&P.d_tq, m->E * NC, &P.lt));
     int64_t lv2 = 0, la2 = 0;
@@ -2121,180 +2019,119 @@ int pprec_reserve_lanes(nlg_mesh *m, int nl) {
     return 0;
 }
 
-// Coarse part of M^-1 r on `st`: xc[v] = omega dinv[v] (R_1^T r)[v] and P.d_xa = aggregate-level solve; pprec_fine
-// adds the two while prolonging.  nl > 1: the lanes of a block step in the same launches (r, flag and the fused PCG update of
-// lane v sit v * ld doubles behind the given pointers).
-int pprec_coarse(nlg_mesh *m, hipStream_t st, const double *flag, const double *r, const double **xc, bool overlap,
-                 const nlg_pcg_upd *upd, int nl, int64_t ld) {
-    const nlg_pcg_upd uu = upd ? *upd : nlg_pcg_upd{};
-    double *rw = const_cast<double *>(r);   // written only when the PCG update rides along
-    nlg_pprec &P = m->pprec;
-    NLG_CHECK(P.ready, "pprec: preconditioner not set up");
-    NLG_TRY(pprec_reserve_lanes(m, nl));
-    const int64_t E = m->E;
-    const int nv = P.nvert;
-    const double om = P.na == nv ? 0.0 : 0.7;   // exact coarse solve when every vertex is its own aggregate
-    Hat hat;
-    for (int k = 0; k < 12; ++k) hat.h1[k] = P.hat1[k];
-    NLG_CHECK(!overlap || P.overlap, "pprec: the overlapping variant is not set up for this mesh");
-    double *Wp = overlap ? P.d_W : (double *)nullptr;
-    const dim3 gq((unsigned)((E + 3) / 4), (unsigned)nl);
-    const int *pin = P.d_pin;
-    if (m->dim == 3) {
-        if (pin && m->n2 == 6)
-            NLG_LAUNCH(k_q1_restrict_local3s<6>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
-        else if (pin && m->n2 == 8)
-            NLG_LAUNCH(k_q1_restrict_local3s<8>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
-        else if (pin && m->n2 == 10)
-            NLG_LAUNCH(k_q1_restrict_local3s<10>, gq, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
-        else
-            NLG_LAUNCH(k_q1_restrict_local<3>, gq, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
-    } else {
-        NLG_LAUNCH(k_q1_restrict_local<2>, gq, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, (const int *)nullptr, uu, ld, P.lt, P.lW);
-    }
-    // 3-D overlapping variant: the rest of the coarse chain rides in the launches of the fine level (pprec_fine, merged launches)
-    P.coarse_pending = overlap && m->gs.npairs > 0 && (m->dim == 2 ? nl == 1 : m->gs.d_indices_fg != nullptr);
-    if (P.coarse_pending) {
-        NLG_HIP(hipGetLastError());
-        *xc = P.d_x;
-        return 0;
-    }
-    NLG_LAUNCH(k_q1_gather, dim3((nv + NT - 1) / NT, nl), dim3(NT), 0, st, flag, nv, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, om, P.d_x, ld, P.lt, P.lv);
-    NLG_LAUNCH(k_agg_restrict, dim3((P.na + 3) / 4, nl), dim3(NT), 0, st, flag, P.na, P.d_ap, P.d_am, P.d_rc, P.d_ra, ld, P.lv, P.la);
-    const double *ra = P.d_ra;
-    int na_max = 0;
-    if (P.ncols != P.na) {   // several ranks: the aggregate level is global; ONE all-gather carries the lanes of every rank
-        NLG_CHECK(st == m->ctx->stream, "pprec: the global aggregate level runs on the context's stream");
-        NLG_TRY(allgather_f64(m->ctx, P.d_ra, P.d_rag, (int64_t)P.na_max * nl));
-        ra = P.d_rag;
-        na_max = nl > 1 ? P.na_max : 0;   // (one lane: the gathered array is the plain column vector)
-    }
-    const dim3 gg((unsigned)((P.na + 3) / 4), (unsigned)nl);
-    if (P.d_Ainv32)
-        NLG_LAUNCH(k_dense_gemv<float>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const float *)P.d_Ainv32, ra, P.d_xa, ld, P.ncols != P.na ? P.la_x : P.la, na_max, nl);
-    else
-        NLG_LAUNCH(k_dense_gemv<double>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const double *)P.d_Ainv, ra, P.d_xa, ld, P.ncols != P.na ? P.la_x : P.la, na_max, nl);
-    NLG_HIP(hipGetLastError());
-    *xc = P.d_x;   // the Jacobi term; pprec_fine adds xa[agg[v]] while prolonging
-    return 0;
-}
-
-// ghost layers of face neighbours on other ranks.  2-D: the copies of a face on a rank boundary are summed by the halo exchange
-// exactly as the pairs kernel sums the two local copies of an interior face.  3-D (copy mode): the element has put its own value
-// into its own slot of a rank-boundary face, the exchange replaces it by the neighbour's.  Edge and corner slots are never
-// written and travel as zeros.
-static int overlap_halo(nlg_mesh *m, hipStream_t st, double *w, int layout, int nl, bool assign) {
+// ghost layers of face neighbours on other ranks (copy mode): the element has put its own value into its own slot of a
+// rank-boundary face, the exchange replaces it by the neighbour's.  Edge and corner slots are never written and travel as zeros.
+static int overlap_halo(nlg_mesh *m, hipStream_t st, double *w, int layout, int nl) {
     ++g_collectives;
     if (!m->halo.active) return 0;
     NLG_CHECK(st == m->ctx->stream, "pprec: the overlap exchange across ranks runs on the context's stream");
     double *f1[1] = {w};
-    return halo_exchange(m, f1, 1, layout, nl, m->pprec.lW, assign);
+    return halo_exchange(m, f1, 1, layout, nl, m->pprec.lW, true);
 }
 
-// Fine part: z = sum_e R_e^T Etilde_e^-1 R_e r (+ R_1 xc when xc is given), launched on `st`.
-int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r, const double *xc, double *z,
-               double *rz_part, bool overlap, int nl, int64_t ld) {
+// z = M^-1 r on `st`: the local solves (with or without the face overlap) plus, when with_coarse, the prolonged coarse
+// correction xc[v] + xa[agg[v]] (xc = omega dinv (R_1^T r), xa = aggregate-level solve).  rz_part: r.z and z sums of the last
+// kernel ((E + 3) / 4 blocks).  upd: the PCG update of r rides in the restriction.  nl > 1: the lanes of a block step in the
+// same launches (flag, r, z, rz_part and the fused PCG update of lane v sit v * ld doubles behind the given pointers).
+// Launches per application: restriction, coarse chain (without overlap: gather, aggregate restriction; with overlap they ride
+// in the local solves), dense aggregate solve, local solves, and with overlap the finish.
+int pprec_apply(nlg_mesh *m, hipStream_t st, const double *flag, const double *r, double *z, double *rz_part, bool overlap,
+                bool with_coarse, const nlg_pcg_upd *upd, int nl, int64_t ld) {
+    const nlg_pcg_upd uu = upd ? *upd : nlg_pcg_upd{};
+    double *rw = const_cast<double *>(r);   // written only when the PCG update rides along
     nlg_pprec &P = m->pprec;
     NLG_CHECK(P.ready, "pprec: preconditioner not set up");
+    NLG_CHECK(!overlap || P.overlap, "pprec: the overlapping variant is not set up for this mesh");
     NLG_TRY(pprec_reserve_lanes(m, nl));
     const int64_t E = m->E;
+    const int nv = P.nvert;
+    const double om = P.na == nv ? 0.0 : 0.7;   // exact coarse solve when every vertex is its own aggregate
+    const bool glob = P.ncols != P.na;
+    const int64_t la_x = glob ? P.la_x : P.la;
+    const double *xc = with_coarse ? P.d_x : nullptr;   // the Jacobi term; the finish adds xa[agg[v]] while prolonging
+    const int *vg = P.d_vg;
     Hat hat;
     for (int k = 0; k < 12; ++k) hat.h1[k] = P.hat1[k];
-    const int *vg = P.d_vg;
-    if (nl > 1 && !(overlap && m->dim == 3)) {
-        // kernels without the lane dimension (2-D, the variant without overlap): lane by lane, on the lane's copies of the scratch
-        NLG_CHECK(xc == nullptr || xc == P.d_x, "pprec_fine: foreign coarse vector with several lanes");
-        nlg_pprec keep = P;
-        int rc = 0;
-        for (int v = 0; v < nl && rc == 0; ++v) {
-            P.d_W = keep.d_W ? keep.d_W + v * keep.lW : nullptr;
-            P.d_xa = keep.d_xa + v * (keep.ncols != keep.na ? keep.la_x : keep.la);
-            rc = pprec_fine(m, st, flag ? flag + v * ld : nullptr, r + v * ld, xc ? keep.d_x + v * keep.lv : nullptr, z + v * ld,
-                            rz_part ? rz_part + v * ld : nullptr, overlap, 1, 0);
-        }
-        P.d_W = keep.d_W, P.d_xa = keep.d_xa;
-        return rc;
+    const dim3 gb((unsigned)((E + 3) / 4), (unsigned)nl);
+
+    // (1) element-local restriction t = R_1^T r per element (+ the extended grids Win of the overlapping variant)
+    double *Wp = overlap ? P.d_W : (double *)nullptr;
+    const int *pin = P.d_pin;
+    if (m->dim == 3) {
+        if (pin && m->n2 == 6)
+            NLG_LAUNCH(k_q1_restrict_local3s<6>, gb, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
+        else if (pin && m->n2 == 8)
+            NLG_LAUNCH(k_q1_restrict_local3s<8>, gb, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
+        else if (pin && m->n2 == 10)
+            NLG_LAUNCH(k_q1_restrict_local3s<10>, gb, dim3(NT), 0, st, flag, E, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
+        else
+            NLG_LAUNCH(k_q1_restrict_local<3>, gb, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
+    } else {
+        NLG_LAUNCH(k_q1_restrict_local<2>, gb, dim3(NT), 0, st, flag, E, m->n2, hat, rw, P.d_tq, Wp, (const double *)P.d_wq, pin, uu, ld, P.lt, P.lW);
     }
-    const int64_t la_x = P.ncols != P.na ? P.la_x : P.la;
-    if (overlap && m->dim == 2) {
-        NLG_CHECK(P.overlap, "pprec: the overlapping variant is not set up for this mesh");
-        const unsigned gb = (unsigned)((E + 3) / 4);
-        // merged launches: the vertex gather rides with the first pairs-only gather-scatter (natural layout here), the aggregate
-        // restriction with the local solves, the dense solve with the second gather-scatter
-        const bool fused = P.coarse_pending;
-        P.coarse_pending = false;
-        const int nbp = (int)((m->gs.npairs + NT - 1) / NT);
-        const int nv = P.nvert;
-        const bool glob = P.ncols != P.na;
-        AggArgs ag = {0, nullptr, nullptr, nullptr, nullptr, 0, 0};
-        if (fused) {
-            const GatherArgs gg = {nv, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, P.na == nv ? 0.0 : 0.7, P.d_x, P.lt, P.lv};
-            NLG_LAUNCH(k_pairs_gather, dim3((unsigned)(nbp + (nv + NT - 1) / NT)), dim3(NT), 0, st, nbp, (const int *)m->gs.d_indices, m->gs.npairs, P.d_W,
-                       (int64_t)0, flag, (int64_t)0, gg);
-            ag = AggArgs{P.na, P.d_ap, P.d_am, P.d_rc, P.d_ra, P.lv, P.la};
-        } else {
-            NLG_TRY(sem_gs_pairs(m, P.d_W, flag));
+    // dense aggregate solve xa = Ainv ra
+    auto dense_solve = [&]() -> int {
+        const double *ra = P.d_ra;
+        int na_max = 0;
+        if (glob) {   // several ranks: the aggregate level is global; ONE all-gather carries the lanes of every rank
+            NLG_CHECK(st == m->ctx->stream, "pprec: the global aggregate level runs on the context's stream");
+            NLG_TRY(allgather_f64(m->ctx, P.d_ra, P.d_rag, (int64_t)P.na_max * nl));
+            ra = P.d_rag;
+            na_max = nl > 1 ? P.na_max : 0;   // (one lane: the gathered array is the plain column vector)
         }
-        NLG_TRY(overlap_halo(m, st, P.d_W, LAYOUT_NAT, 1, false));
-        const unsigned nb_agg = fused ? (unsigned)((P.na + 3) / 4) : 0u;
+        const dim3 gg((unsigned)((P.na + 3) / 4), (unsigned)nl);
+        if (P.d_Ainv32)
+            NLG_LAUNCH(k_dense_gemv<float>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const float *)P.d_Ainv32, ra, P.d_xa, ld, la_x, na_max, nl);
+        else
+            NLG_LAUNCH(k_dense_gemv<double>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const double *)P.d_Ainv, ra, P.d_xa, ld, la_x, na_max, nl);
+        return 0;
+    };
+
+    if (!overlap) {
+        // (2) coarse chain: vertex gather, aggregate restriction, dense solve; (3) local solves + prolonged coarse correction
+        if (with_coarse) {
+            NLG_LAUNCH(k_q1_gather, dim3((nv + NT - 1) / NT, nl), dim3(NT), 0, st, flag, nv, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, om, P.d_x, ld, P.lt, P.lv);
+            NLG_LAUNCH(k_agg_restrict, dim3((P.na + 3) / 4, nl), dim3(NT), 0, st, flag, P.na, P.d_ap, P.d_am, P.d_rc, P.d_ra, ld, P.lv, P.la);
+            NLG_TRY(dense_solve());
+        }
+#define FDM_CASE(N_)                                                                                                  \
+    case N_:                                                                                                          \
+        if (m->dim == 3)                                                                                              \
+            NLG_LAUNCH((k_fdm<N_ - 2, 3>), gb, dim3(NT), 0, st, flag, E, P.d_S, P.d_invden, r, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part, ld, P.lv, la_x); \
+        else                                                                                                          \
+            NLG_LAUNCH((k_fdm<N_ - 2, 2>), gb, dim3(NT), 0, st, flag, E, P.d_S, P.d_invden, r, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part, ld, P.lv, la_x); \
+        break;
+        switch (m->n) {
+            FDM_CASE(4) FDM_CASE(5) FDM_CASE(6) FDM_CASE(7) FDM_CASE(8) FDM_CASE(9) FDM_CASE(10) FDM_CASE(12)
+            default: set_error("pprec: unsupported lx1 = %d", m->n); return 1;
+        }
+#undef FDM_CASE
+        NLG_HIP(hipGetLastError());
+        return 0;
+    }
+
+    // (2) local solves on Win; the vertex gather and the aggregate restriction ride behind the elements
+    NLG_TRY(overlap_halo(m, st, P.d_W, LAYOUT_NAT, nl));
+    ChainArgs cg = {};
+    auto chain_blocks = [&](int threads) -> int {
+        if (!with_coarse) return 0;
+        cg = ChainArgs{(nv + threads - 1) / threads, nv, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, om, P.d_x,
+                       P.na, P.d_ap, P.d_am, P.d_ra, P.lt, P.lv, P.la};
+        return cg.nb_gather + (P.na + threads / 64 - 1) / (threads / 64);   // one wave per aggregate
+    };
+    if (m->dim == 2) {
+        const int nb_c = chain_blocks(NT);
 #define FX2_CASE(N_)                                                                                                  \
     case N_:                                                                                                          \
-        NLG_LAUNCH((k_fdm_ext2<N_>), dim3(gb + nb_agg), dim3(NT), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, r, P.d_wq, P.d_W, z, (int)gb, ag); \
+        NLG_LAUNCH((k_fdm_ext2<N_>), dim3(gb.x + nb_c, (unsigned)nl), dim3(NT), 0, st, flag, E, P.d_Sx, P.d_lamx, P.thrx, \
+                   (const double *)P.d_W, P.d_Wr, z, (const int *)P.d_pret, ld, P.lW, (int)gb.x, cg);               \
         break;
         switch (m->n) {
             FX2_CASE(4) FX2_CASE(5) FX2_CASE(6) FX2_CASE(7) FX2_CASE(8)
             default: set_error("pprec: overlapping variant built for lx1 = 4..8, got %d", m->n); return 1;
         }
 #undef FX2_CASE
-        if (fused) {
-            const double *ra = P.d_ra;
-            if (glob) {
-                NLG_CHECK(st == m->ctx->stream, "pprec: the global aggregate level runs on the context's stream");
-                NLG_TRY(allgather_f64(m->ctx, P.d_ra, P.d_rag, (int64_t)P.na_max));
-                ra = P.d_rag;
-            }
-            const dim3 gc((unsigned)(nbp + (P.na + 3) / 4));
-            if (P.d_Ainv32) {
-                const GemvArgs<float> gv = {P.na, P.ncols, (const float *)P.d_Ainv32, ra, P.d_xa, 0, 0, 1};
-                NLG_LAUNCH(k_pairs_gemv<float>, gc, dim3(NT), 0, st, nbp, (const int *)m->gs.d_indices, m->gs.npairs, P.d_W, (int64_t)0, flag, (int64_t)0, gv);
-            } else {
-                const GemvArgs<double> gv = {P.na, P.ncols, (const double *)P.d_Ainv, ra, P.d_xa, 0, 0, 1};
-                NLG_LAUNCH(k_pairs_gemv<double>, gc, dim3(NT), 0, st, nbp, (const int *)m->gs.d_indices, m->gs.npairs, P.d_W, (int64_t)0, flag, (int64_t)0, gv);
-            }
-        } else {
-            NLG_TRY(sem_gs_pairs(m, P.d_W, flag));
-        }
-        NLG_TRY(overlap_halo(m, st, P.d_W, LAYOUT_NAT, 1, false));
-        const unsigned gf = (unsigned)((E * m->np2 + NT - 1) / NT);
-#define FF2_CASE(N_)                                                                                                  \
-    case N_:                                                                                                          \
-        NLG_LAUNCH((k_sch_finish2<N_>), dim3(gf), dim3(NT), 0, st, flag, E, P.d_W, r, P.d_wq, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part); \
-        break;
-        switch (m->n) {
-            FF2_CASE(4) FF2_CASE(5) FF2_CASE(6) FF2_CASE(7) FF2_CASE(8)
-            default: break;
-        }
-#undef FF2_CASE
-        NLG_HIP(hipGetLastError());
-        return 0;
-    }
-    if (overlap) {
-        // pprec_coarse has written the extended grids into P.d_W (same stream)
-        NLG_CHECK(P.overlap && m->dim == 3 && P.d_pret, "pprec: the overlapping variant is not set up for this mesh");
-        const dim3 gb((unsigned)((E + 3) / 4), (unsigned)nl);
-        const bool fused = P.coarse_pending;   // set by pprec_coarse: the coarse chain is still to run
-        P.coarse_pending = false;
-        const int nv = P.nvert;
-        const bool glob = P.ncols != P.na;
-        NLG_TRY(overlap_halo(m, st, P.d_W, LAYOUT_NAT, nl, true));
-        // (a) local solves; the vertex gather and the aggregate restriction ride behind the elements
-        ChainArgs cg = {};
-        auto chain_blocks = [&](int threads) -> int {
-            if (!fused) return 0;
-            cg = ChainArgs{(nv + threads - 1) / threads, nv, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, P.na == nv ? 0.0 : 0.7, P.d_x,
-                           P.na, P.d_ap, P.d_am, P.d_ra, P.lt, P.lv, P.la};
-            return cg.nb_gather + (P.na + threads / 64 - 1) / (threads / 64);   // one wave per aggregate
-        };
+    } else {
 #define FX_CASE(N_)                                                                                                   \
     case N_: {                                                                                                        \
         constexpr int WPE_ = (N_ * N_ + 63) / 64;   /* one column per lane: 1 wave up to lx1 = 8, 2 at 9 / 10, 3 at 12 */ \
@@ -2313,52 +2150,28 @@ int pprec_fine(nlg_mesh *m, hipStream_t st, const double *flag, const double *r,
             default: set_error("pprec: overlapping variant built for lx1 = 4..10 and 12, got %d", m->n); return 1;
         }
 #undef FX_CASE
-        if (fused) {   // (b) dense aggregate solve
-            const double *ra = P.d_ra;
-            int na_max = 0;
-            if (glob) {   // several ranks: the aggregate level is global; ONE all-gather carries the lanes of every rank
-                NLG_CHECK(st == m->ctx->stream, "pprec: the global aggregate level runs on the context's stream");
-                NLG_TRY(allgather_f64(m->ctx, P.d_ra, P.d_rag, (int64_t)P.na_max * nl));
-                ra = P.d_rag;
-                na_max = nl > 1 ? P.na_max : 0;
-            }
-            const dim3 gg((unsigned)((P.na + 3) / 4), (unsigned)nl);
-            if (P.d_Ainv32)
-                NLG_LAUNCH(k_dense_gemv<float>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const float *)P.d_Ainv32, ra, P.d_xa, ld, la_x, na_max, nl);
-            else
-                NLG_LAUNCH(k_dense_gemv<double>, gg, dim3(NT), 0, st, flag, P.na, P.ncols, (const double *)P.d_Ainv, ra, P.d_xa, ld, la_x, na_max, nl);
-        }
-        NLG_TRY(overlap_halo(m, st, P.d_Wr, LAYOUT_FG, nl, true));
-        // (c) neighbours' ghost values + prolonged coarse correction, r.z sums
-#define FF_CASE(N_)                                                                                                   \
+    }
+    // (3) dense aggregate solve
+    if (with_coarse) NLG_TRY(dense_solve());
+    // (4) neighbours' ghost values + prolonged coarse correction, r.z sums
+    NLG_TRY(overlap_halo(m, st, P.d_Wr, m->dim == 3 ? LAYOUT_FG : LAYOUT_NAT, nl));
+#define FF_CASE(K_, N_)                                                                                               \
     case N_:                                                                                                          \
-        NLG_LAUNCH((k_sch_finish<N_>), gb, dim3(NT), 0, st, flag, E, (const double *)P.d_Wr, r, P.d_wq, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part, ld, P.lW, P.lv, la_x); \
+        NLG_LAUNCH((K_<N_>), gb, dim3(NT), 0, st, flag, E, (const double *)P.d_Wr, r, P.d_wq, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part, ld, P.lW, P.lv, la_x); \
         break;
+    if (m->dim == 2) {
         switch (m->n) {
-            FF_CASE(4) FF_CASE(5) FF_CASE(6) FF_CASE(7) FF_CASE(8) FF_CASE(9) FF_CASE(10) FF_CASE(12)
+            FF_CASE(k_sch_finish2, 4) FF_CASE(k_sch_finish2, 5) FF_CASE(k_sch_finish2, 6) FF_CASE(k_sch_finish2, 7) FF_CASE(k_sch_finish2, 8)
             default: break;
         }
+    } else {
+        switch (m->n) {
+            FF_CASE(k_sch_finish, 4) FF_CASE(k_sch_finish, 5) FF_CASE(k_sch_finish, 6) FF_CASE(k_sch_finish, 7) FF_CASE(k_sch_finish, 8)
+            FF_CASE(k_sch_finish, 9) FF_CASE(k_sch_finish, 10) FF_CASE(k_sch_finish, 12)
+            default: break;
+        }
+    }
 #undef FF_CASE
-        NLG_HIP(hipGetLastError());
-        return 0;
-    }
-#define FDM_CASE(N_)                                                                                                  \
-    if (m->dim == 3)                                                                                                  \
-        NLG_LAUNCH((k_fdm<N_ - 2, 3>), dim3((unsigned)((E + 3) / 4)), dim3(NT), 0, st, flag, E, P.d_S, P.d_invden, r, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part); \
-    else                                                                                                              \
-        NLG_LAUNCH((k_fdm<N_ - 2, 2>), dim3((unsigned)((E + 3) / 4)), dim3(NT), 0, st, flag, E, P.d_S, P.d_invden, r, xc, P.d_xa, P.d_agg, vg, hat, z, rz_part);
-    switch (m->n) {
-        case 4: FDM_CASE(4); break;
-        case 5: FDM_CASE(5); break;
-        case 6: FDM_CASE(6); break;
-        case 7: FDM_CASE(7); break;
-        case 8: FDM_CASE(8); break;
-        case 9: FDM_CASE(9); break;
-        case 10: FDM_CASE(10); break;
-        case 12: FDM_CASE(12); break;
-        default: set_error("pprec: unsupported lx1 = %d", m->n); return 1;
-    }
-#undef FDM_CASE
     NLG_HIP(hipGetLastError());
     return 0;
 }

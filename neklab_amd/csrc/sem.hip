@@ -3611,16 +3611,6 @@ static int xp_perm(nlg_mesh *m, double *const *src, double *const *dst, int nf, 
 int sem_to_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl, int64_t ld, double *const *wts) { return xp_perm(m, src, dst, nf, true, nl, ld, wts); }
 int sem_from_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl, int64_t ld) { return xp_perm(m, src, dst, nf, false, nl, ld); }
 
-int sem_gs_pairs(nlg_mesh *m, double *w, const double *gate, int nl, int64_t ld, int64_t ldg) {
-    if (m->gs.npairs == 0) return 0;
-    F3 f = {{w, nullptr, nullptr}};
-    const dim3 grid((unsigned)((m->gs.npairs + NT - 1) / NT), (unsigned)nl);
-    NLG_LAUNCH(k_gs<1>, grid, dim3(NT), 0, m->ctx->stream, m->gs.d_offsets, m->gs.d_indices, m->gs.npairs,
-                       m->gs.npairs, (int64_t)0, f, gate, ld, ldg);
-    NLG_HIP(hipGetLastError());
-    return 0;
-}
-
 int sem_axhelm_blocks(nlg_mesh *m, int nf) {
     if (m->dim == 2) {
         const int epb = NT / (m->n * m->n) > 0 ? NT / (m->n * m->n) : 1;
@@ -5043,11 +5033,7 @@ int nlg_op_cdabdtp(nlg_mesh *m, const nlg_vec *in, nlg_vec *out) {
 
 int nlg_op_pprec(nlg_mesh *m, const nlg_vec *in, nlg_vec *out, int overlap, int with_coarse) {
     NLG_CHECK(m && in && out && in->mesh == m && out->mesh == m && in != out, "nlg_op_pprec: bad arguments");
-    const double *xc = nullptr;
-    // the coarse call also packs the overlap layers, so it always runs; its result is dropped when not wanted
-    NLG_TRY(pprec_coarse(m, m->ctx->stream, nullptr, in->pr(), &xc, overlap != 0));
-    NLG_TRY(pprec_fine(m, m->ctx->stream, nullptr, in->pr(), with_coarse ? xc : nullptr, out->pr(), nullptr, overlap != 0));
-    return 0;
+    return pprec_apply(m, m->ctx->stream, nullptr, in->pr(), out->pr(), nullptr, overlap != 0, with_coarse != 0);
 }
 
 int nlg_op_opdiv(nlg_mesh *m, const nlg_vec *in, nlg_vec *out) {
