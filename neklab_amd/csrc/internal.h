@@ -387,9 +387,6 @@ int pprec_apply(nlg_mesh *m, hipStream_t st, const double *flag, const double *r
 int pprec_reserve_lanes(nlg_mesh *m, int nl);
 void pprec_free(nlg_mesh *m);
 
-// ---- lns.hip
-bool linop_can_block(const nlg_linop *op);   // the multi-vector stepper covers this operator (round 4: also with the Boussinesq coupling and the wavenumber projection)
-
 // ---- halo.hip ----
 int halo_setup(nlg_mesh *m, const int64_t *glo_num);
 // LAYOUT_*; = halo_begin + halo_finish.  assign: every local copy of a shared point becomes the sum of the OTHER ranks' copies

@@ -170,7 +170,7 @@ int nlg_block_arnoldi_step(nlg_linop *op, nlg_basis *basis, int k, int s, double
     NLG_CHECK(k >= 0 && k + 2 * s <= basis->nvec, "nlg_block_arnoldi_step: k=%d, s=%d need basis columns up to %d (nvec=%d)", k, s,
               k + 2 * s - 1, basis->nvec);
     NLG_CHECK(ldh >= k + 2 * s, "nlg_block_arnoldi_step: ldh=%d too small for k=%d, s=%d", ldh, k, s);
-    if (s > 1 && linop_can_block(op)) {   // the s vectors advance together (shared operator data per iteration)
+    if (s > 1) {   // the s vectors advance together (shared operator data per iteration)
         const nlg_vec *vi[4];
         nlg_vec *vo[4];
         for (int v = 0; v < s; ++v) vi[v] = basis->views[k + v], vo[v] = basis->views[k + s + v];

@@ -861,6 +861,23 @@ const double BDF_B0[4] = {0.0, 1.0, 1.5, 11.0 / 6.0};
 const double BDF_C[4][3] = {{0, 0, 0}, {1.0, 0, 0}, {2.0, -0.5, 0}, {3.0, -1.5, 1.0 / 3.0}};
 const double EXT_C[4][3] = {{0, 0, 0}, {1.0, 0, 0}, {2.0, -1.0, 0}, {3.0, -3.0, 1.0}};
 
+// the iteration counts of one solve in one lane: they predict how many iterations the next solve launches before the host first
+// looks at the convergence flags (CGProblem::chunk), so each lane keeps its own, as if it ran alone
+struct IterPred {
+    int last;
+    std::vector<int> hist;   // iteration counts of the previous matvec, by time-step index (the pattern repeats)
+    int predict(int istep) const { return (istep < (int)hist.size() && hist[istep] > 0) ? hist[istep] : last; }
+    void record(int istep, int iters) {
+        last = iters;
+        if ((int)hist.size() <= istep) hist.resize(istep + 1, 0);
+        hist[istep] = iters;
+    }
+};
+struct LanePred {
+    IterPred v{8}, p{16};   // velocity and pressure solves
+    int last_titers = 8;    // scalar solve
+};
+
 }  // namespace
 
 struct nlg_linop {
@@ -868,17 +885,19 @@ struct nlg_linop {
     nlg_exptA_config cfg;
     nlg_vec *baseflow = nullptr;
     bool inited = false;
+    bool set_up = false;   // the allocations that do not depend on the base flow or tau are made (nlg_linop_init)
     double dt = 0, cfl = 0;
     int nsteps = 0;
     // convective-term precomputation on the fine mesh
     double *Ur[3] = {}, *GU[9] = {};
+    // Every pointer of the list in lane_buffers is lane 0's copy of a per-lane work buffer; lane v's copy is at_lane(op, ptr, v).
     // state: three rotating velocity buffers and three rotating forcing buffers per component
     double *ubuf[3][3] = {};   // [slot][component]; slot 0 = current, 1 = lag1, 2 = lag2 (after rotation)
     double *fbuf[3][3] = {};
     double *p = nullptr;
     // work
     double *rhs[3] = {}, *x[3] = {}, *z[3] = {}, *pv[3] = {}, *w[3] = {}, *gp[3] = {};
-    // single-reduction PCG (Chronopoulos-Gear; several ranks, NLG_PCG_SINGLE_RED): the search direction and its image as recurrences
+    // single-reduction PCG (Chronopoulos-Gear; opt-in, NLG_PCG_SINGLE_RED=1): the search direction and its image as recurrences
     bool use_sr = false;
     int php = 0;               // the same for the pressure PCG (ring prh[php][lps]; the update rides in the preconditioner, the direction update in the gradient kernel)
     double *prh = nullptr;
@@ -905,20 +924,16 @@ struct nlg_linop {
     double *d_s = nullptr;     // solver scalars (two blocks of S_N)
     double *d_part = nullptr;  // first-stage sums written by opdiv ([2][E]) and by the FDM kernel ([2][E/4])
     double *d_cgpart = nullptr;   // [3][NB] first-stage sums of the PCG vector kernels
-    double *d_red = nullptr;      // several ranks: [lanes][3] sums of all lanes for ONE all-reduce (owner only, not in the slab)
+    double *d_red = nullptr;      // several ranks: [lanes][3] sums of all lanes for ONE all-reduce (not in the slab)
     double *h_s = nullptr;     // pinned
     // All per-lane work buffers (integrator state, PCG vectors, projection space, scalars, partial sums) are carved from ONE
-    // allocation of `slab_cap` lanes at a constant stride `slab_ld` doubles: lane v's copy of any of them is the owner's
+    // allocation of `slab_cap` lanes at a constant stride `slab_ld` doubles: lane v's copy of any of them is lane 0's
     // pointer + v * slab_ld, which is what lets one launch with gridDim.y = lanes serve the whole block (lane_lo()).
     double *slab = nullptr;
     int64_t slab_ld = 0;
     int slab_cap = 0;
-    int64_t n_launch = 0, n_coll = 0;   // kernel launches / collectives issued by the time stepper (nlg_linop_get_counters)
-    int istep = 0, adjoint = 0;
-    // block stepper: lanes 1 .. 3 (created on first use by the operator that owns them); a lane shares the base-flow data
-    // of its owner and must never free it
-    nlg_linop *lanes[3] = {nullptr, nullptr, nullptr};
-    bool is_lane = false;
+    int istep = 0, adjoint = 0;   // the lanes of a block step advance in lockstep: one time-step index for all
+    LanePred pred[kMaxLanes];
     int adv_k = 1;             // state handed from one phase of a time step to the next (adv_a / adv_b / adv_c)
     double adv_b0 = 1.0, adv_h2 = 0.0;
     // wavenumber projection (exptA_proj_linop): lines along the homogeneous direction, cos / sin of alpha x, 1 / sum bm1
@@ -936,12 +951,8 @@ struct nlg_linop {
     // BDF order, gradient of the base temperature on the fine mesh
     double *tbuf[3] = {}, *ftbuf[3] = {}, *trhs = nullptr, *tx = nullptr, *tz = nullptr, *tpv = nullptr, *tw = nullptr;
     double *pct[4] = {}, *GT[3] = {};
-    int64_t st_titers = 0;
-    int last_titers = 8;
     int nonlinear = 0;         // 1: full Navier-Stokes step, N(u) = (u.grad)u = half of the linearised term about U = u
-    int64_t st_steps = 0, st_viters = 0, st_piters = 0, st_matvecs = 0;
-    int last_piters = 16, last_viters = 8;
-    std::vector<int> pit_hist, vit_hist;   // iteration counts of the previous matvec, by time-step index (the pattern repeats)
+    int64_t st_steps = 0, st_viters = 0, st_piters = 0, st_titers = 0, st_matvecs = 0;   // summed over the lanes
 };
 
 namespace {
@@ -1000,25 +1011,43 @@ int64_t lane_stride(nlg_linop *op) {
     return off;
 }
 
-// point the members of `ln` (the owner itself for lane 0) at lane `v` of the owner's slab; the rotating buffers return to
-// their canonical places, which keeps "lane v = lane 0 + v * slab_ld" true for every member whatever was run before
-void lane_bind(nlg_linop *owner, nlg_linop *ln, int v) {
+// point the lane-0 work buffers at the slab (null without one); the rotating buffers return to their canonical places
+void lane_bind(nlg_linop *op) {
     int64_t off = 0;
-    double *base = owner->slab + (int64_t)v * owner->slab_ld;
-    const bool heat = ln->cfg.ifheat;
-    ln->cfg.ifheat = owner->cfg.ifheat;   // (same buffer list as the owner's)
-    ln->use_sr = owner->use_sr;
-    ln->ph = owner->ph;
-    ln->php = owner->php;
-    lane_buffers(ln, [&](double **p, int64_t len) {
-        *p = base + off;
+    lane_buffers(op, [&](double **p, int64_t len) {
+        *p = op->slab ? op->slab + off : nullptr;
         off += round_up(len, kAlign);
     });
-    ln->cfg.ifheat = heat;
-    ln->slab_ld = owner->slab_ld;
 }
 
-// make room for `cap` lanes (the work buffers hold no state between two matvecs, so growing = a new allocation)
+// lane v's copy of a work buffer of the list in lane_buffers, from lane 0's pointer
+inline double *at_lane(const nlg_linop *op, double *p, int v) { return p + (int64_t)v * op->slab_ld; }
+inline F3 at_lane3(const nlg_linop *op, double *const *a, int v) {
+    F3 r = {{a[0], a[1], a[2]}};
+    for (double *&q : r.p)
+        if (q) q = at_lane(op, q, v);
+    return r;
+}
+
+// the copies of a set of component fields in lanes 0 .. nl - 1, as the *_lanes functions of sem.hip take them
+struct LaneFields {
+    F3 f[kMaxLanes];
+    double *const *p[kMaxLanes];
+    LaneFields(const nlg_linop *op, double *const *a, int nl) {
+        for (int v = 0; v < nl; ++v) f[v] = at_lane3(op, a, v), p[v] = f[v].p;
+    }
+    LaneFields(const LaneFields &) = delete;
+};
+
+// rotate three levels (of every lane, by the lane-0 pointers): the oldest becomes the newest
+template <typename T>
+void rotate3(T (&levels)[3]) {
+    std::swap(levels[2], levels[1]);
+    std::swap(levels[1], levels[0]);
+}
+
+// make room for `cap` lanes (the work buffers hold no state between two matvecs, so growing = a new allocation).  A grow that
+// fails leaves no slab and null work-buffer pointers; the next call allocates again at the size it needs.
 int slab_ensure(nlg_linop *op, int cap) {
     if (op->slab && op->slab_cap >= cap) return 0;
     nlg_ctx *ctx = op->mesh->ctx;
@@ -1026,6 +1055,7 @@ int slab_ensure(nlg_linop *op, int cap) {
     if (op->slab) NLG_HIP(hipFree(op->slab));   // (first: the old and the new slab need not exist together)
     op->slab = nullptr;
     op->slab_cap = 0;
+    lane_bind(op);
     // the direction rings (deferred solution update) are bandwidth bought with memory: where the slab does not fit with them -- a block of
     // lanes next to a Krylov basis that fills the card -- they shrink and finally go (k_cg_update then updates x every iteration again)
     int64_t ld = 0;
@@ -1055,10 +1085,7 @@ int slab_ensure(nlg_linop *op, int cap) {
     op->slab = nslab;
     op->slab_ld = ld;
     op->slab_cap = cap;
-    lane_bind(op, op, 0);
-    for (int v = 1; v < kMaxLanes; ++v)
-        if (op->lanes[v - 1]) lane_bind(op, op->lanes[v - 1], v);
-    if (!op->d_red) NLG_TRY(lalloc(op, &op->d_red, 3 * kMaxLanes));
+    lane_bind(op);
     return 0;
 }
 
@@ -1272,13 +1299,12 @@ int run_pcg(nlg_linop *op, const CGProblem &P, Apply apply, int *iters_out) {
     return 0;
 }
 
-// The lanes of a time step: ops[0] is the operator itself, ops[1..] its lanes (all bound to one slab); nl = 1 is the
-// single-vector path.  Every phase launches once for all lanes and keeps the host-side bookkeeping per lane.
+// The lanes 0 .. nl - 1 of a time step in the operator's slab; nl = 1 is the single-vector path.  Every phase launches once for
+// all lanes and keeps the iteration predictions per lane.
 struct Lanes {
-    nlg_linop *const *ops;
+    nlg_linop *op;
     int nl;
-    nlg_linop *op() const { return ops[0]; }
-    int64_t ld() const { return nl > 1 ? ops[0]->slab_ld : 0; }
+    int64_t ld() const { return nl > 1 ? op->slab_ld : 0; }   // the lane stride the kernels receive
 };
 
 // The velocity solve in three pieces: problem set-up, one operator application, bookkeeping afterwards.
@@ -1291,7 +1317,7 @@ struct HelmSolve {
 };
 
 int helm_problem(const Lanes &L, int order, double h2, HelmSolve &H) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     const int dim = m->dim;
     const auto &c = op->cfg;
@@ -1328,11 +1354,7 @@ int helm_problem(const Lanes &L, int order, double h2, HelmSolve &H) {
     // the iteration count barely changes from one time step to the next: launch exactly the previous count, then look at
     // the flags every second iteration; launches issued after convergence are gated on the device but still cost a launch
     P.chunk = 2;
-    for (int v = 0; v < L.nl; ++v) {
-        const nlg_linop *ln = L.ops[v];
-        const int pred = (ln->istep < (int)ln->vit_hist.size() && ln->vit_hist[ln->istep] > 0) ? ln->vit_hist[ln->istep] : ln->last_viters;
-        P.chunk = std::max(P.chunk, std::min(pred, 64));
-    }
+    for (int v = 0; v < L.nl; ++v) P.chunk = std::max(P.chunk, std::min(op->pred[v].v.predict(op->istep), 64));
     H.nu = 1.0 / c.re;
     // w = QQ^T (nu A + h2 B) p.  The Dirichlet mask is not applied to w: p is masked (z = pc r with pc = mask/diag), so
     // (p, w) does not see the masked entries, and k_cg_update zeroes the residual where pc == 0.
@@ -1352,7 +1374,7 @@ int helm_problem(const Lanes &L, int order, double h2, HelmSolve &H) {
 }
 
 int helm_apply(const Lanes &L, const HelmSolve &H) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     const int dim = m->dim;
     if (H.P.hist.ph > 0) {
@@ -1371,24 +1393,11 @@ int helm_apply(const Lanes &L, const HelmSolve &H) {
     return 0;
 }
 
-int helm_finish(const Lanes &L, const HelmSolve &H, const int *iters) {
-    nlg_linop *op = L.op();
-    (void)op;   // (slab-permuted solve: the increment stays in that layout, adv_b reads it through the slot table)
-    for (int v = 0; v < L.nl; ++v) {
-        nlg_linop *ln = L.ops[v];
-        ln->st_viters += iters[v];
-        ln->last_viters = iters[v];
-        if ((int)ln->vit_hist.size() <= ln->istep) ln->vit_hist.resize(ln->istep + 1, 0);
-        ln->vit_hist[ln->istep] = iters[v];
-    }
-    return 0;
-}
-
 int helm_solve(const Lanes &L, int order, double h2) {
+    nlg_linop *op = L.op;
     HelmSolve H;
     NLG_TRY(helm_problem(L, order, h2, H));
-    if (L.op()->use_sr) {
-        nlg_linop *op = L.op();
+    if (op->use_sr) {
         nlg_mesh *m = op->mesh;
         H.P.sd = op->cgs;
         H.P.apply_plain = [&, op, m]() -> int {   // w = QQ^T (nu A + h2 B) z and the first-stage sums of (z, w): no direction update inside
@@ -1398,15 +1407,20 @@ int helm_solve(const Lanes &L, int order, double h2) {
     }
     auto apply = [&](double *) -> int { return helm_apply(L, H); };
     int iters[kMaxLanes] = {};
-    NLG_TRY(run_pcg(L.op(), H.P, apply, iters));
-    return helm_finish(L, H, iters);
+    NLG_TRY(run_pcg(op, H.P, apply, iters));
+    // (slab-permuted solve: the increment stays in that layout, adv_b reads it through the slot table)
+    for (int v = 0; v < L.nl; ++v) {
+        op->st_viters += iters[v];
+        op->pred[v].v.record(op->istep, iters[v]);
+    }
+    return 0;
 }
 
 // One scalar (temperature) step of the Boussinesq coupling, see oracle/lns.py advance (ifheat branch):
 //   rhocp (b0 theta^{n+1} - sum bd_j theta^{n-j}) / dt = -rhocp EXT[(U.grad) theta + (u.grad) Theta] + conductivity lap theta^{n+1}
 // in residual form, Jacobi-PCG; the new level ends in tbuf[0].
 int heat_step(const Lanes &L, int k, double b0) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     const auto &c = op->cfg;
@@ -1417,21 +1431,18 @@ int heat_step(const Lanes &L, int k, double b0) {
     // after it -- right-hand side, operator, gather-scatter, the whole PCG -- is ONE launch for all lanes (gridDim.y), as in the velocity solve
     const int adj = (op->adjoint && !op->nonlinear) ? 1 : 0;
     for (int v = 0; v < nl; ++v) {
-        nlg_linop *ln = L.ops[v];
-        NLG_TRY(sem_conv_scalar_apply(m, op->Ur, op->GT, ln->ubuf[0], ln->tbuf[0], ln->ftbuf[2], adj));
+        const F3 u = at_lane3(op, op->ubuf[0], v);
+        double *ft = at_lane(op, op->ftbuf[2], v);
+        NLG_TRY(sem_conv_scalar_apply(m, op->Ur, op->GT, u.p, at_lane(op, op->tbuf[0], v), ft, adj));
         if (adj) {
             // adjoint temperature equation: rhocp theta+_t = rhocp (U.grad) theta+ + conductivity lap theta+ + rhocp b . u+
             // (stored term N_t = -conv(U, theta+) - bm1 b . u+ ; oracle/lns.py advance, adjoint branch)
             for (int i = 0; i < m->dim; ++i)
                 if (c.buoy[i] != 0.0)
-                    NLG_LAUNCH(k_mul3_acc, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, ln->ftbuf[2], (const double *)m->d_bm1,
-                                       (const double *)ln->ubuf[0][i], -c.buoy[i]);
+                    NLG_LAUNCH(k_mul3_acc, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, ft, (const double *)m->d_bm1, (const double *)u.p[i], -c.buoy[i]);
         }
-        double *t = ln->ftbuf[2];
-        ln->ftbuf[2] = ln->ftbuf[1];
-        ln->ftbuf[1] = ln->ftbuf[0];
-        ln->ftbuf[0] = t;
     }
+    rotate3(op->ftbuf);
     Hist h;
     h.k = k;
     for (int j = 0; j < 3; ++j) {
@@ -1477,7 +1488,7 @@ int heat_step(const Lanes &L, int k, double b0) {
     P.nl = nl;
     P.ld = ld;
     P.chunk = 2;
-    for (int v = 0; v < nl; ++v) P.chunk = std::max(P.chunk, std::min(L.ops[v]->last_titers, 64));
+    for (int v = 0; v < nl; ++v) P.chunk = std::max(P.chunk, std::min(op->pred[v].last_titers, 64));
     P.pw_part = op->d_part;
     P.pw_n = sem_axhelm_blocks(m, 1);
     P.pw_sum = false;
@@ -1514,8 +1525,8 @@ int heat_step(const Lanes &L, int k, double b0) {
     int iters[kMaxLanes] = {};
     NLG_TRY(run_pcg(op, P, apply, iters));
     for (int v = 0; v < nl; ++v) {
-        L.ops[v]->st_titers += iters[v];
-        L.ops[v]->last_titers = iters[v];
+        op->st_titers += iters[v];
+        op->pred[v].last_titers = iters[v];
     }
     // theta^{n+1} = theta^n + x into the oldest level, then rotate: new -> current
     {
@@ -1525,13 +1536,7 @@ int heat_step(const Lanes &L, int k, double b0) {
             NLG_LAUNCH(k_add_hist<1>, lgrid(grid_for(m->lvn), nl), dim3(NT), 0, st, (const double *)op->d_s, m->lvn, 1, (const int *)nullptr, y, a, b, P.hist, ld);
         else
             NLG_LAUNCH(k_lin3<1>, lgrid(grid_for(m->lvn), nl), dim3(NT), 0, st, m->lvn, y, a, b, 1.0, none, 0.0, ld);
-        for (int v = 0; v < nl; ++v) {
-            nlg_linop *ln = L.ops[v];
-            double *t = ln->tbuf[2];
-            ln->tbuf[2] = ln->tbuf[1];
-            ln->tbuf[1] = ln->tbuf[0];
-            ln->tbuf[0] = t;
-        }
+        rotate3(op->tbuf);
     }
     NLG_HIP(hipGetLastError());
     return 0;
@@ -1549,7 +1554,7 @@ struct PresSolve {
 };
 
 int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     const auto &c = op->cfg;
     const int nl = L.nl;
@@ -1611,11 +1616,7 @@ int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
         };
     }
     P.chunk = 2;
-    for (int v = 0; v < nl; ++v) {
-        const nlg_linop *ln = L.ops[v];
-        const int pred = (ln->istep < (int)ln->pit_hist.size() && ln->pit_hist[ln->istep] > 0) ? ln->pit_hist[ln->istep] : ln->last_piters;
-        P.chunk = std::max(P.chunk, std::min(pred, 96));
-    }
+    for (int v = 0; v < nl; ++v) P.chunk = std::max(P.chunk, std::min(op->pred[v].p.predict(op->istep), 96));
     // fused first-stage sums (rank-local; the all-reduce follows the second stage): p.w and sum w from the divergence kernel,
     // r.z and sum z from the preconditioner's last kernel
     Q.pw_part = op->d_part;
@@ -1650,7 +1651,7 @@ int pres_problem(const Lanes &L, double scale, PresSolve &Q) {
 
 // gated: launches past convergence (the host only looks at the flags once per chunk) return at once
 int pres_apply(const Lanes &L, const PresSolve &Q) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     // direction ring (deferred solution update): read direction it - 1, the fused update stores direction it one slot further
     double *p_in = op->pr_p, *p_out = op->pr_p;
     if (Q.P.hist.ph > 0) {
@@ -1681,17 +1682,14 @@ int pres_apply(const Lanes &L, const PresSolve &Q) {
 }
 
 int pres_finish(const Lanes &L, const PresSolve &Q, const int *iters) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     const int nl = L.nl;
     const int64_t ld = L.ld();
     for (int v = 0; v < nl; ++v) {
-        nlg_linop *ln = L.ops[v];
-        ln->st_piters += iters[v];
-        ln->last_piters = iters[v];
-        if ((int)ln->pit_hist.size() <= ln->istep) ln->pit_hist.resize(ln->istep + 1, 0);
-        ln->pit_hist[ln->istep] = iters[v];
+        op->st_piters += iters[v];
+        op->pred[v].p.record(op->istep, iters[v]);
     }
     if (Q.proj) {
         double *alpha = op->d_pc, *beta = op->d_pc + PROJ_L, *nrm2 = op->d_pc + 2 * PROJ_L, *ppart = op->d_pc + 4 * PROJ_L;
@@ -1728,7 +1726,7 @@ int pres_finish(const Lanes &L, const PresSolve &Q, const int *iters) {
         const int slot = nold < PROJ_L ? nold : 0;                           // full: start over with the newest member
         NLG_LAUNCH(k_proj_store, lgrid(grid_for(m->lpn), nl), dim3(NT), 0, st, m->lpn, (const double *)op->pr_z, (const double *)op->pr_w,
                    (const double *)nrm2, op->prX + (size_t)slot * m->lps, op->prB + (size_t)slot * m->lps, ld);
-        for (int v = 0; v < nl; ++v) L.ops[v]->nproj = nold < PROJ_L ? nold + 1 : 1;
+        op->nproj = nold < PROJ_L ? nold + 1 : 1;
         NLG_HIP(hipGetLastError());
     }
     return 0;
@@ -1739,9 +1737,9 @@ int pres_solve(const Lanes &L, double scale) {
     NLG_TRY(pres_problem(L, scale, Q));
     auto apply = [&](double *) -> int { return pres_apply(L, Q); };
     int iters[kMaxLanes] = {};
-    NLG_TRY(run_pcg(L.op(), Q.P, apply, iters));
+    NLG_TRY(run_pcg(L.op, Q.P, apply, iters));
     if (Q.P.hist.ph > 0) {   // x = sum alpha_i p_i, in iteration order (k_add_hist without an addend)
-        nlg_linop *op = L.op();
+        nlg_linop *op = L.op;
         nlg_mesh *m = op->mesh;
         F3 y = {{op->pr_x, nullptr, nullptr}};
         CF3 none = {{nullptr, nullptr, nullptr}}, x = {{op->pr_x, nullptr, nullptr}};
@@ -1751,33 +1749,20 @@ int pres_solve(const Lanes &L, double scale) {
     return pres_finish(L, Q, iters);
 }
 
-// rotate a set of three level pointers in every lane: the oldest becomes the newest
-void rotate3(const Lanes &L, double *(nlg_linop::*buf)[3][3]) {
-    for (int v = 0; v < L.nl; ++v) {
-        double *(&b)[3][3] = L.ops[v]->*buf;
-        double *t[3] = {b[2][0], b[2][1], b[2][2]};
-        for (int c = 0; c < 3; ++c) {
-            b[2][c] = b[1][c];
-            b[1][c] = b[0][c];
-            b[0][c] = t[c];
-        }
-    }
-}
-
 // one restated nek_advance step (perturbation mode), see oracle/lns.py ExptA.advance; three phases around the two solves
 int adv_a(const Lanes &L) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     const int dim = m->dim, nl = L.nl;
     const int64_t ld = L.ld();
     const double dt = op->dt, nu = 1.0 / op->cfg.re;
-    for (int v = 0; v < nl; ++v) L.ops[v]->istep += 1;
+    op->istep += 1;
     // gauge: keep the pressure mean-free (see oracle/lns.py advance)
     NLG_TRY(sem_ortho(m, op->p, nl, ld));
     const int k = std::min(op->istep, op->cfg.torder);
     const double b0 = BDF_B0[k];
-    for (int v = 0; v < nl; ++v) L.ops[v]->adv_k = k, L.ops[v]->adv_b0 = b0, L.ops[v]->adv_h2 = b0 / dt;
+    op->adv_k = k, op->adv_b0 = b0, op->adv_h2 = b0 / dt;
     if (op->nonlinear) {   // the "base flow" is the current state (velocity, and temperature when coupled); one lane only
         NLG_TRY(sem_conv_setup(m, op->ubuf[0], op->Ur, op->GU));
         if (op->cfg.ifheat) NLG_TRY(sem_conv_scalar_setup(m, op->tbuf[0], op->GT));
@@ -1788,18 +1773,17 @@ int adv_a(const Lanes &L) {
     if (nl == 1) {
         NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], Fnew, op->nonlinear ? 0 : op->adjoint));
     } else {   // convective terms of all lanes against the shared base-flow fields: one launch
-        double *const *ul[kMaxLanes], *const *ol[kMaxLanes];
-        for (int v = 0; v < nl; ++v) ul[v] = L.ops[v]->ubuf[0], ol[v] = L.ops[v]->fbuf[2];
-        NLG_TRY(sem_conv_apply_lanes(m, op->Ur, op->GU, nl, ul, ol, op->adjoint));
+        const LaneFields ul(op, op->ubuf[0], nl), ol(op, Fnew, nl);
+        NLG_TRY(sem_conv_apply_lanes(m, op->Ur, op->GU, nl, ul.p, ol.p, op->adjoint));
     }
     if (op->cfg.ifheat && op->adjoint && !op->nonlinear) {
         // adjoint momentum equation: - theta+ grad Theta with the new theta+ (stored F is +N: add the weak term); lane by lane
-        for (int v = 0; v < nl; ++v) NLG_TRY(sem_scalar_grad_apply(m, op->GT, L.ops[v]->tbuf[0], L.ops[v]->fbuf[2], 1.0));
+        for (int v = 0; v < nl; ++v) NLG_TRY(sem_scalar_grad_apply(m, op->GT, at_lane(op, op->tbuf[0], v), at_lane3(op, Fnew, v).p, 1.0));
     } else if (op->cfg.ifheat) {
         const double bs = op->nonlinear ? 2.0 : 1.0;   // the nonlinear step halves the whole stored term (F holds 2 N there)
         for (int v = 0; v < nl; ++v)
-            launch_nf(dim, k_buoyancy<1>, k_buoyancy<2>, k_buoyancy<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(L.ops[v]->fbuf[2], dim),
-                      (const double *)m->d_bm1, (const double *)L.ops[v]->tbuf[0], bs * op->cfg.buoy[0], bs * op->cfg.buoy[1], bs * op->cfg.buoy[2]);
+            launch_nf(dim, k_buoyancy<1>, k_buoyancy<2>, k_buoyancy<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(at_lane3(op, Fnew, v).p, dim),
+                      (const double *)m->d_bm1, (const double *)at_lane(op, op->tbuf[0], v), bs * op->cfg.buoy[0], bs * op->cfg.buoy[1], bs * op->cfg.buoy[2]);
     }
     if (op->force_re) {
         // forcing of this step: evaluated at the time level the step starts from, (istep - 1) dt, like the explicit terms
@@ -1811,7 +1795,7 @@ int adv_a(const Lanes &L) {
         launch_nf(dim, k_add_force<1>, k_add_force<2>, k_add_force<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(Fnew, dim),
                   (const double *)m->d_bm1, fr, fi, std::cos(ph), -std::sin(ph));
     }
-    rotate3(L, &nlg_linop::fbuf);
+    rotate3(op->fbuf);
     Hist h;
     h.k = k;
     for (int j = 0; j < 3; ++j) {
@@ -1828,9 +1812,9 @@ int adv_a(const Lanes &L) {
         NLG_TRY(sem_opgradt(m, op->p, op->gp));
     } else {
         const double *pp[kMaxLanes];
-        double *const *gl[kMaxLanes];
-        for (int v = 0; v < nl; ++v) pp[v] = L.ops[v]->p, gl[v] = L.ops[v]->gp;
-        NLG_TRY(sem_opgradt_lanes(m, nl, pp, gl, false, nullptr));
+        for (int v = 0; v < nl; ++v) pp[v] = at_lane(op, op->p, v);
+        const LaneFields gl(op, op->gp, nl);
+        NLG_TRY(sem_opgradt_lanes(m, nl, pp, gl.p, false, nullptr));
     }
     NLG_TRY(sem_axhelm(m, op->ubuf[0], op->w, dim, nu, h2, nullptr, nullptr, nullptr, nullptr, false, nl, ld));
     if (op->use_xp > 0) {
@@ -1855,7 +1839,7 @@ int adv_a(const Lanes &L) {
 }
 
 int adv_b(const Lanes &L) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     const int dim = m->dim, nl = L.nl;
@@ -1881,17 +1865,17 @@ int adv_b(const Lanes &L) {
     if (nl == 1) {
         NLG_TRY(sem_opdiv(m, unew, op->pr_r, -(b0 / dt)));
     } else {
-        double *const *ul[kMaxLanes];
+        const LaneFields ul(op, unew, nl);
         double *ol[kMaxLanes], *none[kMaxLanes] = {};
-        for (int v = 0; v < nl; ++v) ul[v] = L.ops[v]->ubuf[2], ol[v] = L.ops[v]->pr_r;
-        NLG_TRY(sem_opdiv_lanes(m, nl, ul, ol, -(b0 / dt), nullptr, false, nullptr, none, nullptr));
+        for (int v = 0; v < nl; ++v) ol[v] = at_lane(op, op->pr_r, v);
+        NLG_TRY(sem_opdiv_lanes(m, nl, ul.p, ol, -(b0 / dt), nullptr, false, nullptr, none, nullptr));
     }
     NLG_TRY(sem_ortho(m, op->pr_r, nl, ld));
     return 0;
 }
 
 int adv_c(const Lanes &L) {
-    nlg_linop *op = L.op();
+    nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     const int dim = m->dim, nl = L.nl;
@@ -1907,9 +1891,9 @@ int adv_c(const Lanes &L) {
         NLG_TRY(sem_opgradt(m, op->pr_x, op->gp, fg));
     } else {
         const double *pp[kMaxLanes];
-        double *const *gl[kMaxLanes];
-        for (int v = 0; v < nl; ++v) pp[v] = L.ops[v]->pr_x, gl[v] = L.ops[v]->gp;
-        NLG_TRY(sem_opgradt_lanes(m, nl, pp, gl, fg, nullptr));
+        for (int v = 0; v < nl; ++v) pp[v] = at_lane(op, op->pr_x, v);
+        const LaneFields gl(op, op->gp, nl);
+        NLG_TRY(sem_opgradt_lanes(m, nl, pp, gl.p, fg, nullptr));
     }
     // u = uh + (dt / b0) mask binv QQ^T D^T dp: gather-scatter, then weights and update in one pass
     NLG_TRY(sem_gs(m, op->gp, dim, nullptr, fg ? LAYOUT_FG : LAYOUT_NAT, nl, ld, 0));
@@ -1924,29 +1908,25 @@ int adv_c(const Lanes &L) {
     }
     NLG_HIP(hipGetLastError());
     // rotate velocity history: new -> current, current -> lag1, lag1 -> lag2
-    rotate3(L, &nlg_linop::ubuf);
-    for (int v = 0; v < nl; ++v) L.ops[v]->st_steps += 1;
+    rotate3(op->ubuf);
+    op->st_steps += nl;
     return 0;
 }
 
 int advance(const Lanes &L) {
     NLG_TRY(adv_a(L));
-    NLG_TRY(helm_solve(L, L.op()->adv_k, L.op()->adv_h2));
+    NLG_TRY(helm_solve(L, L.op->adv_k, L.op->adv_h2));
     NLG_TRY(adv_b(L));
-    NLG_TRY(pres_solve(L, L.op()->dt / L.op()->adv_b0));
+    NLG_TRY(pres_solve(L, L.op->dt / L.op->adv_b0));
     return adv_c(L);
 }
-int advance(nlg_linop *op) {
-    nlg_linop *one[1] = {op};
-    return advance(Lanes{one, 1});
-}
 
-// integrator state of nl lanes <- 0: the rotating velocity / forcing (/ temperature) levels are the first buffers of a lane, in
-// canonical order after the re-binding, so ONE strided memset clears them in every lane
+// integrator state of nl lanes <- 0, in a slab of at least nl lanes: the rotating velocity / forcing (/ temperature) levels are the
+// first buffers of a lane, in canonical order after the re-binding, so ONE strided memset clears them in every lane
 int reset_state(nlg_linop *op, int nl) {
     nlg_mesh *m = op->mesh;
-    lane_bind(op, op, 0);
-    for (int v = 1; v < nl; ++v) lane_bind(op, op->lanes[v - 1], v);
+    NLG_TRY(slab_ensure(op, nl));
+    lane_bind(op);
     const int64_t nlev = (int64_t)(6 * m->dim + (op->cfg.ifheat ? 6 : 0)) * m->lvs;
     // one 1-D fill per lane: the 2-D fill of the runtime (hipMemset2DAsync over the slab pitch) ran at 0.2 TB/s -- 14.6 ms per block
     // step of four lanes, 8.5 % of it -- against 4.6 TB/s for the 1-D fill
@@ -1954,36 +1934,35 @@ int reset_state(nlg_linop *op, int nl) {
     return 0;
 }
 
-int load_state(nlg_linop *op, const nlg_vec *v, int irst) {
+int load_state(nlg_linop *op, int lane, const nlg_vec *v, int irst) {
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     for (int c = 0; c < m->dim; ++c)
-        NLG_HIP(hipMemcpyAsync(op->ubuf[0][c], v->vel(c, irst), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
-    NLG_HIP(hipMemcpyAsync(op->p, v->pr(irst), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
+        NLG_HIP(hipMemcpyAsync(at_lane(op, op->ubuf[0][c], lane), v->vel(c, irst), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
+    NLG_HIP(hipMemcpyAsync(at_lane(op, op->p, lane), v->pr(irst), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
     if (op->cfg.ifheat)
-        NLG_HIP(hipMemcpyAsync(op->tbuf[0], v->theta(0, irst), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
+        NLG_HIP(hipMemcpyAsync(at_lane(op, op->tbuf[0], lane), v->theta(0, irst), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
-int store_state(nlg_linop *op, nlg_vec *v, int irst) {
+int store_state(nlg_linop *op, int lane, nlg_vec *v, int irst) {
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     for (int c = 0; c < m->dim; ++c)
-        NLG_HIP(hipMemcpyAsync(v->vel(c, irst), op->ubuf[0][c], sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
-    NLG_HIP(hipMemcpyAsync(v->pr(irst), op->p, sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
+        NLG_HIP(hipMemcpyAsync(v->vel(c, irst), at_lane(op, op->ubuf[0][c], lane), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
+    NLG_HIP(hipMemcpyAsync(v->pr(irst), at_lane(op, op->p, lane), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
     if (op->cfg.ifheat)
-        NLG_HIP(hipMemcpyAsync(v->theta(0, irst), op->tbuf[0], sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
+        NLG_HIP(hipMemcpyAsync(v->theta(0, irst), at_lane(op, op->tbuf[0], lane), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
-// no-op unless nlg_linop_set_projection has been called.  `tab` holds the projection tables (the operator itself), `dat` the state that is
-// projected: the operator again, or one of its lanes in a block step
-int project_alpha(const nlg_linop *tab, nlg_linop *dat, int slot) {
-    if (tab->proj_nlines == 0) return 0;
-    nlg_mesh *m = tab->mesh;
-    const unsigned grid = (unsigned)((tab->proj_nlines + NT / 64 - 1) / (NT / 64));
-    F3 u = f3(dat->ubuf[slot], m->dim);
-    if (tab->proj_gslot) {
+// no-op unless nlg_linop_set_projection has been called: projects level `slot` of the state of lane `lane`
+int project_alpha(nlg_linop *op, int lane, int slot) {
+    if (op->proj_nlines == 0) return 0;
+    nlg_mesh *m = op->mesh;
+    const unsigned grid = (unsigned)((op->proj_nlines + NT / 64 - 1) / (NT / 64));
+    F3 u = f3(at_lane3(op, op->ubuf[slot], lane).p, m->dim);
+    if (op->proj_gslot) {
         // several ranks: partial sums -> global slots -> all-reduce -> apply (the reference's planar_avg is a global
         // operation, exponential_propagator_proj.f90:146-169)
         hipStream_t st = m->ctx->stream;
@@ -1991,108 +1970,56 @@ int project_alpha(const nlg_linop *tab, nlg_linop *dat, int slot) {
                         const double *cv, const double *sv, const double *iden, F3 f) -> int {
             const unsigned g = (unsigned)((nl + NT / 64 - 1) / (NT / 64));
             const int64_t cnt = nglob * 2 * nf;
-            NLG_HIP(hipMemsetAsync(tab->proj_glob, 0, sizeof(double) * (size_t)cnt, st));
+            NLG_HIP(hipMemsetAsync(op->proj_glob, 0, sizeof(double) * (size_t)cnt, st));
             CF3 cf = {{f.p[0], f.p[1], f.p[2]}};
             if (nl > 0) {
                 if (nf == 3)
-                    NLG_LAUNCH(k_proj_sums<3>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, tab->proj_glob);
+                    NLG_LAUNCH(k_proj_sums<3>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, op->proj_glob);
                 else if (nf == 2)
-                    NLG_LAUNCH(k_proj_sums<2>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, tab->proj_glob);
+                    NLG_LAUNCH(k_proj_sums<2>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, op->proj_glob);
                 else
-                    NLG_LAUNCH(k_proj_sums<1>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, tab->proj_glob);
+                    NLG_LAUNCH(k_proj_sums<1>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, op->proj_glob);
             }
-            NLG_TRY(allreduce_sum(m->ctx, tab->proj_glob, (int)cnt));
+            NLG_TRY(allreduce_sum(m->ctx, op->proj_glob, (int)cnt));
             if (nl > 0) {
                 if (nf == 3)
-                    NLG_LAUNCH(k_proj_apply<3>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)tab->proj_glob, f);
+                    NLG_LAUNCH(k_proj_apply<3>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)op->proj_glob, f);
                 else if (nf == 2)
-                    NLG_LAUNCH(k_proj_apply<2>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)tab->proj_glob, f);
+                    NLG_LAUNCH(k_proj_apply<2>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)op->proj_glob, f);
                 else
-                    NLG_LAUNCH(k_proj_apply<1>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)tab->proj_glob, f);
+                    NLG_LAUNCH(k_proj_apply<1>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)op->proj_glob, f);
             }
             return 0;
         };
-        NLG_TRY(pass(m->dim, tab->proj_nlines, tab->proj_off, tab->proj_idx, tab->proj_gslot, tab->proj_nglob, m->d_bm1, tab->proj_cv, tab->proj_sv,
-                     tab->proj_iden, u));
-        if (tab->proj_gslot2 && slot == 0) {
-            F3 pp = {{dat->p, nullptr, nullptr}};
-            NLG_TRY(pass(1, tab->proj_nlines2, tab->proj_off2, tab->proj_idx2, tab->proj_gslot2, tab->proj_nglob2, m->d_bm2, tab->proj_cv2,
-                         tab->proj_sv2, tab->proj_iden2, pp));
+        NLG_TRY(pass(m->dim, op->proj_nlines, op->proj_off, op->proj_idx, op->proj_gslot, op->proj_nglob, m->d_bm1, op->proj_cv, op->proj_sv,
+                     op->proj_iden, u));
+        if (op->proj_gslot2 && slot == 0) {
+            F3 pp = {{at_lane(op, op->p, lane), nullptr, nullptr}};
+            NLG_TRY(pass(1, op->proj_nlines2, op->proj_off2, op->proj_idx2, op->proj_gslot2, op->proj_nglob2, m->d_bm2, op->proj_cv2,
+                         op->proj_sv2, op->proj_iden2, pp));
         }
         NLG_HIP(hipGetLastError());
         return 0;
     }
     if (m->dim == 3)
-        NLG_LAUNCH(k_proj_alpha<3>, dim3(grid), dim3(NT), 0, m->ctx->stream, (int64_t)tab->proj_nlines, (const int *)tab->proj_off,
-                           (const int *)tab->proj_idx, (const double *)m->d_bm1, (const double *)tab->proj_cv, (const double *)tab->proj_sv,
-                           (const double *)tab->proj_iden, u);
+        NLG_LAUNCH(k_proj_alpha<3>, dim3(grid), dim3(NT), 0, m->ctx->stream, (int64_t)op->proj_nlines, (const int *)op->proj_off,
+                           (const int *)op->proj_idx, (const double *)m->d_bm1, (const double *)op->proj_cv, (const double *)op->proj_sv,
+                           (const double *)op->proj_iden, u);
     else
-        NLG_LAUNCH(k_proj_alpha<2>, dim3(grid), dim3(NT), 0, m->ctx->stream, (int64_t)tab->proj_nlines, (const int *)tab->proj_off,
-                           (const int *)tab->proj_idx, (const double *)m->d_bm1, (const double *)tab->proj_cv, (const double *)tab->proj_sv,
-                           (const double *)tab->proj_iden, u);
-    if (tab->proj_nlines2 > 0 && slot == 0) {
+        NLG_LAUNCH(k_proj_alpha<2>, dim3(grid), dim3(NT), 0, m->ctx->stream, (int64_t)op->proj_nlines, (const int *)op->proj_off,
+                           (const int *)op->proj_idx, (const double *)m->d_bm1, (const double *)op->proj_cv, (const double *)op->proj_sv,
+                           (const double *)op->proj_iden, u);
+    if (op->proj_nlines2 > 0 && slot == 0) {
         // the pressure is part of the state the integrator starts from (lagged pressure of the correction scheme) but not
         // of the inner product: left unprojected it is a subspace the Arnoldi norm cannot see (observed: a spurious
         // |mu| = 1.41 for plane Poiseuille flow at alpha = 2 instead of 0.945)
-        const unsigned grid2 = (unsigned)((tab->proj_nlines2 + NT / 64 - 1) / (NT / 64));
-        F3 pp = {{dat->p, nullptr, nullptr}};
-        NLG_LAUNCH(k_proj_alpha<1>, dim3(grid2), dim3(NT), 0, m->ctx->stream, (int64_t)tab->proj_nlines2, (const int *)tab->proj_off2,
-                           (const int *)tab->proj_idx2, (const double *)m->d_bm2, (const double *)tab->proj_cv2, (const double *)tab->proj_sv2,
-                           (const double *)tab->proj_iden2, pp);
+        const unsigned grid2 = (unsigned)((op->proj_nlines2 + NT / 64 - 1) / (NT / 64));
+        F3 pp = {{at_lane(op, op->p, lane), nullptr, nullptr}};
+        NLG_LAUNCH(k_proj_alpha<1>, dim3(grid2), dim3(NT), 0, m->ctx->stream, (int64_t)op->proj_nlines2, (const int *)op->proj_off2,
+                           (const int *)op->proj_idx2, (const double *)m->d_bm2, (const double *)op->proj_cv2, (const double *)op->proj_sv2,
+                           (const double *)op->proj_iden2, pp);
     }
     NLG_HIP(hipGetLastError());
-    return 0;
-}
-
-int project_alpha(nlg_linop *op, int slot = 0) { return project_alpha(op, op, slot); }
-
-int do_matvec(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout, int adjoint) {
-    NLG_CHECK(op && vin && vout, "exptA matvec: NULL argument");
-    NLG_CHECK(op->inited, "exptA matvec: nlg_linop_init has not been called (reference: exptA%%init(), 1cyl.usr:20)");
-    nlg_mesh *m = op->mesh;
-    NLG_CHECK(vin->mesh == m && vout->mesh == m,
-              "exptA matvec: vector on a different mesh (reference: type_error, exponential_propagator.f90:53-58)");
-    NLG_CHECK(vin->nscal == (op->cfg.ifheat ? 1 : 0) && vout->nscal == vin->nscal,
-              "exptA matvec: the vectors carry %d scalar(s), the operator expects %d (cfg.ifheat)", vin->nscal, op->cfg.ifheat ? 1 : 0);
-    const bool nohist = op->cfg.no_history != 0;
-    NLG_CHECK(nohist || (vin->lorder >= op->cfg.torder && vout->lorder >= op->cfg.torder),
-              "exptA matvec: vector lorder %d < time order %d", vin->lorder, op->cfg.torder);
-    NLG_CHECK(vin != vout, "exptA matvec: vec_in and vec_out must be distinct (intent(in) / intent(out))");
-    const int nrst = nohist ? 0 : op->cfg.torder - 1;   // no_history: impulsive start, no history steps (include/neklab_gpu.h)
-    NLG_TRY(reset_state(op, 1));
-    op->istep = 0;
-    op->adjoint = adjoint;
-    // the projection space belongs to one matvec: the result must not depend on earlier calls.  (Keeping it across matvecs, as a
-    // Nek5000 run does across time steps, was measured in round 4: 11.76 -> 11.40 pressure iterations per time step over 844 matvecs
-    // of a real Arnoldi / Krylov-Schur run -- successive Krylov vectors are orthogonal, their pressure increments share little --
-    // while bench.py, which re-applies the operator to the SAME column every step, would show 12.5 -> 6.5: an artefact, not adopted.)
-    op->nproj = 0;
-    NLG_TRY(load_state(op, vin, 0));
-    NLG_TRY(project_alpha(op));                       // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
-    for (int istep = 1; istep <= op->nsteps; ++istep) {
-        NLG_TRY(advance(op));
-        if (istep <= nrst && vin->nrst > 0) {
-            NLG_TRY(load_state(op, vin, istep));   // get_rst, :129-142
-            NLG_TRY(project_alpha(op));            // (projected operator: replayed states are projected as well, see below)
-        }
-    }
-    // ... and the final state, :66.  The reference projects the initial condition and the final state only.  Here the
-    // replayed history states and the lagged states of the multistep scheme are projected too: otherwise the extended map
-    // (state, history) that the Arnoldi process iterates has a spurious unstable mode -- observed for plane Poiseuille flow
-    // at alpha = 2, Re = 7500: a "converged" |mu| = 1.41 in front of the Orr-Sommerfeld pair |mu| = 0.9448; with the
-    // consistent projection the leading pair is 0.94454 (DESIGN.md 3.6).
-    NLG_TRY(project_alpha(op));
-    NLG_TRY(project_alpha(op, 1));
-    NLG_TRY(project_alpha(op, 2));
-    // vec_out is intent(out): default-initialised (history cleared, nrst = 0), then filled
-    NLG_TRY(nlg_vec_zero(vout));
-    NLG_TRY(store_state(op, vout, 0));
-    for (int irst = 1; irst <= nrst; ++irst) {   // compute_rst, :109-127
-        NLG_TRY(advance(op));
-        NLG_TRY(store_state(op, vout, irst));
-        vout->nrst = std::max(vout->nrst, irst);
-    }
-    op->st_matvecs += 1;
     return 0;
 }
 
@@ -2104,11 +2031,80 @@ int do_matvec(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout, int adjoint) {
 // is shared.  The time step is the single-vector one (advance(Lanes)) with every kernel launched ONCE for all lanes
 // (gridDim.y = lanes, or a lane loop inside the fused element kernels), own alpha / beta / convergence flag per lane -- each
 // lane performs exactly the iteration of the single-vector path -- and, across ranks, ONE halo exchange / all-reduce per
-// gather-scatter / reduction carrying all lanes.
+// gather-scatter / reduction carrying all lanes.  A single matvec is the block of one.
 // =====================================================================================================================
-// lane v of the block stepper: lane 0 is the operator itself, lanes 1 .. 3 are created on first use
-nlg_linop *lane_get(nlg_linop *op0, int v);
-int lane_refresh(nlg_linop *op0, nlg_linop *ln);
+int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *const *vout, int adjoint) {
+    NLG_CHECK(op && vin && vout, "exptA block matvec: NULL argument");
+    NLG_CHECK(s >= 1 && s <= kMaxLanes, "exptA block matvec: %d vectors unsupported (1..%d)", s, kMaxLanes);
+    NLG_CHECK(op->inited, "exptA block matvec: nlg_linop_init has not been called");
+    nlg_mesh *m = op->mesh;
+    const int want_scal = op->cfg.ifheat ? 1 : 0;
+    for (int v = 0; v < s; ++v) {
+        NLG_CHECK(vin[v] && vout[v] && vin[v]->mesh == m && vout[v]->mesh == m, "exptA block matvec: vector %d NULL or on a different mesh", v);
+        NLG_CHECK(vin[v]->nscal == want_scal && vout[v]->nscal == want_scal, "exptA block matvec: vector %d carries %d scalars, the operator %d", v,
+                  vin[v]->nscal, want_scal);
+        NLG_CHECK(op->cfg.no_history || (vin[v]->lorder >= op->cfg.torder && vout[v]->lorder >= op->cfg.torder), "exptA block matvec: vector lorder < time order");
+        for (int u = 0; u < s; ++u) NLG_CHECK(vin[v] != vout[u], "exptA block matvec: an input vector is also an output vector");
+        for (int u = 0; u < v; ++u) NLG_CHECK(vout[v] != vout[u], "exptA block matvec: the same output vector twice");
+    }
+    const int nrst = op->cfg.no_history ? 0 : op->cfg.torder - 1;   // no_history: impulsive start, no history steps (include/neklab_gpu.h)
+    NLG_TRY(reset_state(op, s));
+    op->istep = 0;
+    op->adjoint = adjoint;
+    // the projection space belongs to one matvec: the result must not depend on earlier calls.  (Keeping it across matvecs, as a
+    // Nek5000 run does across time steps, was measured in round 4: 11.76 -> 11.40 pressure iterations per time step over 844 matvecs
+    // of a real Arnoldi / Krylov-Schur run -- successive Krylov vectors are orthogonal, their pressure increments share little --
+    // while bench.py, which re-applies the operator to the SAME column every step, would show 12.5 -> 6.5: an artefact, not adopted.)
+    op->nproj = 0;
+    for (int v = 0; v < s; ++v) {
+        NLG_TRY(load_state(op, v, vin[v], 0));
+        NLG_TRY(project_alpha(op, v, 0));   // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
+    }
+    const Lanes L{op, s};
+    for (int istep = 1; istep <= op->nsteps; ++istep) {
+        NLG_TRY(advance(L));
+        if (istep <= nrst)
+            for (int v = 0; v < s; ++v)
+                if (vin[v]->nrst > 0) {
+                    NLG_TRY(load_state(op, v, vin[v], istep));   // get_rst, exponential_propagator.f90:129-142
+                    NLG_TRY(project_alpha(op, v, 0));            // (projected operator: replayed states are projected as well, see below)
+                }
+    }
+    // ... and the final state, :66.  The reference projects the initial condition and the final state only.  Here the
+    // replayed history states and the lagged states of the multistep scheme are projected too: otherwise the extended map
+    // (state, history) that the Arnoldi process iterates has a spurious unstable mode -- observed for plane Poiseuille flow
+    // at alpha = 2, Re = 7500: a "converged" |mu| = 1.41 in front of the Orr-Sommerfeld pair |mu| = 0.9448; with the
+    // consistent projection the leading pair is 0.94454 (DESIGN.md 3.6).
+    for (int v = 0; v < s; ++v) {
+        for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha(op, v, slot));
+        // vec_out is intent(out): default-initialised (history cleared, nrst = 0), then filled
+        NLG_TRY(nlg_vec_zero(vout[v]));
+        NLG_TRY(store_state(op, v, vout[v], 0));
+    }
+    for (int irst = 1; irst <= nrst; ++irst) {   // compute_rst, :109-127
+        NLG_TRY(advance(L));
+        for (int v = 0; v < s; ++v) {
+            NLG_TRY(store_state(op, v, vout[v], irst));
+            vout[v]->nrst = std::max(vout[v]->nrst, irst);
+        }
+    }
+    op->st_matvecs += s;
+    return 0;
+}
+
+int do_matvec(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout, int adjoint) {
+    NLG_CHECK(op && vin && vout, "exptA matvec: NULL argument");
+    NLG_CHECK(op->inited, "exptA matvec: nlg_linop_init has not been called (reference: exptA%%init(), 1cyl.usr:20)");
+    nlg_mesh *m = op->mesh;
+    NLG_CHECK(vin->mesh == m && vout->mesh == m,
+              "exptA matvec: vector on a different mesh (reference: type_error, exponential_propagator.f90:53-58)");
+    NLG_CHECK(vin->nscal == (op->cfg.ifheat ? 1 : 0) && vout->nscal == vin->nscal,
+              "exptA matvec: the vectors carry %d scalar(s), the operator expects %d (cfg.ifheat)", vin->nscal, op->cfg.ifheat ? 1 : 0);
+    NLG_CHECK(op->cfg.no_history || (vin->lorder >= op->cfg.torder && vout->lorder >= op->cfg.torder),
+              "exptA matvec: vector lorder %d < time order %d", vin->lorder, op->cfg.torder);
+    NLG_CHECK(vin != vout, "exptA matvec: vec_in and vec_out must be distinct (intent(in) / intent(out))");
+    return do_matvec_block(op, 1, &vin, &vout, adjoint);
+}
 
 // vec_out = state after the nsteps of one application started from `ic` (null: rest) under the time-harmonic body force
 // Re[(f_re + i f_im) exp(i s omega t)], s = -1 for the adjoint equations: evaluate_rhs / evaluate_imaginary_part of the
@@ -2126,17 +2122,17 @@ int do_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, c
     op->istep = 0;
     op->adjoint = adjoint;
     op->nproj = 0;
-    if (ic) NLG_TRY(load_state(op, ic, 0));
+    if (ic) NLG_TRY(load_state(op, 0, ic, 0));
     op->force_re = f_re;
     op->force_im = f_im;
     op->force_omega = omega;
     op->force_sign = adjoint ? -1.0 : 1.0;
     int rc = 0;
-    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) rc = advance(op);
+    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) rc = advance(Lanes{op, 1});
     op->force_re = op->force_im = nullptr;
     if (rc) return rc;
     NLG_TRY(nlg_vec_zero(vout));
-    NLG_TRY(store_state(op, vout, 0));
+    NLG_TRY(store_state(op, 0, vout, 0));
     return 0;
 }
 
@@ -2158,12 +2154,12 @@ int do_nonlinear_map(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout) {
     op->adjoint = 0;
     op->nproj = 0;
     op->nonlinear = 1;
-    int rc = load_state(op, vin, 0);
-    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) rc = advance(op);
+    int rc = load_state(op, 0, vin, 0);
+    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) rc = advance(Lanes{op, 1});
     op->nonlinear = 0;
     if (rc) return rc;
     NLG_TRY(nlg_vec_zero(vout));
-    NLG_TRY(store_state(op, vout, 0));
+    NLG_TRY(store_state(op, 0, vout, 0));
     NLG_TRY(nlg_vec_axpby(-1.0, vin, 1.0, vout));   // vec_out%sub(vec_in), fixed_point.f90:29
     // the base-flow dependent set-up now belongs to vec_in: a later linear matvec needs nlg_linop_set_baseflow
     return 0;
@@ -2211,14 +2207,6 @@ int nlg_linop_create(nlg_mesh *mesh, const nlg_exptA_config *cfg, const nlg_vec 
 int nlg_linop_destroy(nlg_linop *op) {
     if (!op) return 0;
     hipDeviceSynchronize();
-    for (nlg_linop *&ln : op->lanes) {
-        if (ln) nlg_linop_destroy(ln);
-        ln = nullptr;
-    }
-    if (op->is_lane) {   // a lane owns nothing: its work buffers are the owner's slab, the base-flow data is shared
-        delete op;
-        return 0;
-    }
     auto fr = [](double *p) {
         if (p) hipFree(p);
     };
@@ -2264,7 +2252,7 @@ int nlg_linop_init(nlg_linop *op) {
     hipStream_t st = ctx->stream;
     const int dim = m->dim;
     NLG_HIP(hipSetDevice(ctx->device));
-    if (!op->slab) {
+    if (!op->set_up) {
         for (int c = 0; c < dim; ++c) {
             NLG_HIP(hipMalloc(&op->Ur[c], sizeof(double) * (size_t)m->lfn));
             for (int k = 1; k <= op->cfg.torder; ++k) NLG_TRY(lalloc(op, &op->pcv[k][c], m->lvs));
@@ -2291,6 +2279,8 @@ int nlg_linop_init(nlg_linop *op) {
         // (preconditioner class 7.06 -> 6.83 ms per step), the assembly of x and the colder directions give it back (44.5 ms either way)
         op->php = (dim == 3 && sem_opgradt_fuses_pupdate(m) && getenv("NLG_PCG_DEFER_XP")) ? std::max(0, std::min(kAlphaRing, atoi(getenv("NLG_PCG_DEFER_XP")))) : 0;
         NLG_TRY(slab_ensure(op, 1));   // the work buffers of one lane; a block matvec grows the slab on first use
+        NLG_TRY(lalloc(op, &op->d_red, 3 * kMaxLanes));
+        op->set_up = true;
     }
     double *U[3] = {op->baseflow->vel(0), op->baseflow->vel(1), dim == 3 ? op->baseflow->vel(2) : nullptr};
     // dt / nsteps (reference: neklab_nek_setup.f90:195-198)
@@ -2398,6 +2388,9 @@ int nlg_linop_init(nlg_linop *op) {
 
 int nlg_linop_matvec(nlg_linop *op, const nlg_vec *vec_in, nlg_vec *vec_out) { return do_matvec(op, vec_in, vec_out, 0); }
 int nlg_linop_rmatvec(nlg_linop *op, const nlg_vec *vec_in, nlg_vec *vec_out) { return do_matvec(op, vec_in, vec_out, 1); }
+int nlg_linop_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vec_in, nlg_vec *const *vec_out, int transpose) {
+    return do_matvec_block(op, s, vec_in, vec_out, transpose ? 1 : 0);
+}
 
 int nlg_linop_nonlinear_map(nlg_linop *op, const nlg_vec *vec_in, nlg_vec *vec_out) { return do_nonlinear_map(op, vec_in, vec_out); }
 
@@ -2539,9 +2532,10 @@ int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_
 int nlg_linop_project(nlg_linop *op, nlg_vec *v) {
     NLG_CHECK(op && v && v->mesh == op->mesh, "nlg_linop_project: bad argument");
     NLG_CHECK(op->proj_nlines > 0, "nlg_linop_project: no projection set (nlg_linop_set_projection)");
-    NLG_TRY(load_state(op, v, 0));
-    NLG_TRY(project_alpha(op));
-    NLG_TRY(store_state(op, v, 0));
+    NLG_TRY(slab_ensure(op, 1));
+    NLG_TRY(load_state(op, 0, v, 0));
+    NLG_TRY(project_alpha(op, 0, 0));
+    NLG_TRY(store_state(op, 0, v, 0));
     return 0;
 }
 
@@ -2577,117 +2571,6 @@ int nlg_linop_get_stats(const nlg_linop *op, int64_t *steps, int64_t *v_iters, i
     if (p_iters) *p_iters = op->st_piters;
     if (matvecs) *matvecs = op->st_matvecs;
     return 0;
-}
-
-}  // extern "C"
-
-namespace {
-
-// lane v >= 1: an operator object whose work buffers are lane v of the owner's slab; base-flow data shared with the owner
-nlg_linop *lane_get(nlg_linop *op0, int v) {
-    if (v == 0) return op0;
-    if (op0->lanes[v - 1]) return op0->lanes[v - 1];
-    nlg_linop *ln = new nlg_linop();
-    ln->mesh = op0->mesh;
-    ln->is_lane = true;
-    ln->cfg = op0->cfg;
-    op0->lanes[v - 1] = ln;
-    return ln;
-}
-
-// base-flow data, time step and tolerances follow the owner (it may have been re-initialised since the lane was made)
-int lane_refresh(nlg_linop *op0, nlg_linop *ln) {
-    if (ln == op0) return 0;
-    ln->cfg = op0->cfg;
-    ln->baseflow = op0->baseflow;
-    ln->inited = op0->inited;
-    ln->dt = op0->dt, ln->cfl = op0->cfl, ln->nsteps = op0->nsteps;
-    for (int c = 0; c < 3; ++c) {
-        ln->Ur[c] = op0->Ur[c];
-        for (int k = 0; k < 4; ++k) ln->pcv[k][c] = op0->pcv[k][c], ln->pcv_xp[k][c] = op0->pcv_xp[k][c];
-    }
-    for (int q = 0; q < 9; ++q) ln->GU[q] = op0->GU[q];
-    for (int q = 0; q < 3; ++q) ln->GT[q] = op0->GT[q];          // Boussinesq coupling: base-temperature gradient and the scalar's
-    for (int k = 0; k < 4; ++k) ln->pct[k] = op0->pct[k];        // Jacobi preconditioners are the owner's
-    ln->pce = op0->pce, ln->nwv = op0->nwv, ln->nwv_xp = op0->nwv_xp, ln->nwp = op0->nwp;
-    ln->use_xp = op0->use_xp;
-    ln->h_s = nullptr;   // the PCG reads every lane's scalars through the owner's pinned buffer
-    return 0;
-}
-
-int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *const *vout, int adjoint) {
-    NLG_CHECK(op && vin && vout, "exptA block matvec: NULL argument");
-    NLG_CHECK(s >= 1 && s <= kMaxLanes, "exptA block matvec: %d vectors unsupported (1..%d)", s, kMaxLanes);
-    NLG_CHECK(op->inited, "exptA block matvec: nlg_linop_init has not been called");
-    NLG_CHECK(!op->is_lane, "exptA block matvec: called on a lane");
-    nlg_mesh *m = op->mesh;
-    const int want_scal = op->cfg.ifheat ? 1 : 0;
-    for (int v = 0; v < s; ++v) {
-        NLG_CHECK(vin[v] && vout[v] && vin[v]->mesh == m && vout[v]->mesh == m, "exptA block matvec: vector %d NULL or on a different mesh", v);
-        NLG_CHECK(vin[v]->nscal == want_scal && vout[v]->nscal == want_scal, "exptA block matvec: vector %d carries %d scalars, the operator %d", v,
-                  vin[v]->nscal, want_scal);
-        NLG_CHECK(op->cfg.no_history || (vin[v]->lorder >= op->cfg.torder && vout[v]->lorder >= op->cfg.torder), "exptA block matvec: vector lorder < time order");
-        for (int u = 0; u < s; ++u) NLG_CHECK(vin[v] != vout[u], "exptA block matvec: an input vector is also an output vector");
-        for (int u = 0; u < v; ++u) NLG_CHECK(vout[v] != vout[u], "exptA block matvec: the same output vector twice");
-    }
-    nlg_linop *ops[kMaxLanes];
-    for (int v = 0; v < s; ++v) {
-        ops[v] = lane_get(op, v);
-        NLG_CHECK(ops[v], "exptA block matvec: lane allocation failed");
-        NLG_TRY(lane_refresh(op, ops[v]));
-    }
-    NLG_TRY(slab_ensure(op, s));
-    NLG_TRY(reset_state(op, s));
-    const int nrst = op->cfg.no_history ? 0 : op->cfg.torder - 1;
-    for (int v = 0; v < s; ++v) {
-        nlg_linop *ln = ops[v];
-        ln->istep = 0;
-        ln->adjoint = adjoint;
-        ln->nproj = 0;
-        NLG_TRY(load_state(ln, vin[v], 0));
-        NLG_TRY(project_alpha(op, ln, 0));   // exptA_proj_linop: the projections of do_matvec, lane by lane against the owner's tables
-    }
-    const Lanes L{ops, s};
-    for (int istep = 1; istep <= op->nsteps; ++istep) {
-        NLG_TRY(advance(L));
-        if (istep <= nrst)
-            for (int v = 0; v < s; ++v)
-                if (vin[v]->nrst > 0) {
-                    NLG_TRY(load_state(ops[v], vin[v], istep));   // get_rst, exponential_propagator.f90:129-142
-                    NLG_TRY(project_alpha(op, ops[v], 0));
-                }
-    }
-    for (int v = 0; v < s; ++v) {
-        for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha(op, ops[v], slot));   // final state and the lagged levels (see do_matvec)
-        NLG_TRY(nlg_vec_zero(vout[v]));
-        NLG_TRY(store_state(ops[v], vout[v], 0));
-    }
-    for (int irst = 1; irst <= nrst; ++irst) {   // compute_rst, :109-127
-        NLG_TRY(advance(L));
-        for (int v = 0; v < s; ++v) {
-            NLG_TRY(store_state(ops[v], vout[v], irst));
-            vout[v]->nrst = std::max(vout[v]->nrst, irst);
-        }
-    }
-    // the lanes' counters are part of the operator's statistics
-    for (int v = 1; v < s; ++v) {
-        op->st_steps += ops[v]->st_steps, op->st_viters += ops[v]->st_viters, op->st_piters += ops[v]->st_piters, op->st_titers += ops[v]->st_titers;
-        ops[v]->st_steps = ops[v]->st_viters = ops[v]->st_piters = ops[v]->st_titers = 0;
-    }
-    op->st_matvecs += s;
-    return 0;
-}
-
-}  // namespace
-
-namespace nlg {
-bool linop_can_block(const nlg_linop *op) { return op && !op->is_lane; }
-}
-
-extern "C" {
-
-int nlg_linop_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vec_in, nlg_vec *const *vec_out, int transpose) {
-    return do_matvec_block(op, s, vec_in, vec_out, transpose ? 1 : 0);
 }
 
 int nlg_op_conv(nlg_mesh *m, const nlg_vec *base, const nlg_vec *in, nlg_vec *out, int adjoint) {

@@ -265,7 +265,7 @@ print("RESULT", st["p_iters"], st["v_iters"], " ".join("%%.15e" %% float(np.sum(
 
 
 def test_single_reduction_pcg_matches_the_two_reduction_pcg():
-    """NLG_PCG_SINGLE_RED=1 (the default with several ranks): the velocity and scalar solves run Chronopoulos & Gear's PCG -- one reduction per
+    """NLG_PCG_SINGLE_RED=1 (opt-in): the velocity and scalar solves run Chronopoulos & Gear's PCG -- one reduction per
     iteration carrying (w, u), (r, u) and |r|^2, p and s = A p as recurrences (csrc/lns.hip cg_post_logic mode 4; oracle twin
     oracle/lns.py pcg_helm_single_reduction).  The same propagator application in two processes, switch on and off: the same fields to the
     solver tolerance, the same Helmholtz iteration counts (the convergence is noticed one operator application later, the iterates
