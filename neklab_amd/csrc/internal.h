@@ -398,48 +398,43 @@ int halo_finish(nlg_mesh *m, double *const *fields, int nf, int layout, int nl =
 void halo_free(nlg_mesh *m);
 
 // ---- sem.hip (device-pointer level operators; all on ctx->stream) ----
-// nl / ld / ldg (everywhere below): nl lanes of a block step in ONE launch (gridDim.y = nl): lane v's fields sit v * ld doubles
-// behind the given (lane-0) pointers, its gate v * ldg doubles behind `gate`
+// Lanes (everywhere below): nl <= kMaxLanes vectors of a block step in one call.  Every pointer argument is lane 0's; lane v of a
+// per-lane field, flag or sum sits v * ld doubles behind it.  ldv: the same for the velocity-mesh fields of the pressure
+// operators (sem_opgradt, sem_opdiv), whose pressure-mesh arguments step by ld.  ldg: the gates of sem_gs.  Where a kernel has
+// no lane dimension the operator launches it once per lane.
 int sem_gs(nlg_mesh *m, double *const *fields, int nf, const double *gate = nullptr, int layout = 0, int nl = 1, int64_t ld = 0, int64_t ldg = 0);   // in place QQ^T; gate: device flag, non-zero = skip; layout: LAYOUT_NAT or LAYOUT_XP
 int sem_to_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl = 1, int64_t ld = 0, double *const *wts = nullptr);     // natural -> x-planes-first (out of place); wts: dst = wts * src
 int sem_from_xp(nlg_mesh *m, double *const *src, double *const *dst, int nf, int nl = 1, int64_t ld = 0);
 int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h1, double h2, double *pw_part = nullptr,
                double *const *zf = nullptr, const double *beta_p = nullptr, const double *done_p = nullptr, bool xp = false, int nl = 1, int64_t ld = 0, int64_t uoff = 0);   // uoff: the updated direction is stored uoff doubles behind u (direction history of the PCG); zf: fused u <- zf + beta u; xp: u, zf, w in the x-planes-first layout (3-D, lx1 <= 8)
-int sem_axhelm_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const *const *w, double h1, double h2, double *const *pw,
-                     double *const *const *zf, const double *const *beta, const double *const *done, bool xp);
 int sem_opdiv_blocks(const nlg_mesh *m);
 int sem_axhelm_blocks(nlg_mesh *m, int nf);   // 3-D: number of per-block sums of u . w_local written to pw_part
 int sem_helm_diag(nlg_mesh *m, double *out, double h1, double h2);   // local diag (not assembled)
-struct nlg_pupd;
-bool sem_opgradt_has_fg(const nlg_mesh *m);
-int sem_opgradt(nlg_mesh *m, const double *p, double *const *w, bool face_grouped = false, const double *gate = nullptr, const nlg_pupd *upd = nullptr);
-int sem_opdiv(nlg_mesh *m, double *const *u, double *out, double scale, double *const *wts = nullptr, bool face_grouped = false,
-              const double *pdot = nullptr, double *pw_part = nullptr, const double *gate = nullptr);
-int sem_opbinv(nlg_mesh *m, double *const *w, int nl = 1, int64_t ld = 0);                       // w_i <- mask_i binv QQ^T w_i
-// direction update of a PCG performed by the operator while it loads p:  p <- (z - zmean[0]) + beta[0] p   (device scalars)
+// direction update of a PCG performed by the operator while it loads p:  p <- (z - zmean[0]) + beta[0] p   (device scalars; per lane at ld)
 struct nlg_pupd {
     const double *z = nullptr, *beta = nullptr, *zmean = nullptr;
     double *p = nullptr;
 };
+bool sem_opgradt_has_fg(const nlg_mesh *m);
+int sem_opgradt(nlg_mesh *m, const double *p, double *const *w, bool face_grouped = false, const double *gate = nullptr, const nlg_pupd *upd = nullptr,
+                int nl = 1, int64_t ld = 0, int64_t ldv = 0);
+int sem_opdiv(nlg_mesh *m, double *const *u, double *out, double scale, double *const *wts = nullptr, bool face_grouped = false,
+              const double *pdot = nullptr, double *pw_part = nullptr, const double *gate = nullptr, int nl = 1, int64_t ld = 0, int64_t ldv = 0);
+int sem_opbinv(nlg_mesh *m, double *const *w, int nl = 1, int64_t ld = 0);                       // w_i <- mask_i binv QQ^T w_i
 bool sem_opgradt_fuses_pupdate(const nlg_mesh *m);
 bool sem_small_mesh(const nlg_mesh *m);   // local element count below the threshold of the strong-scaling kernel variants (NLG_SMALL_E)
-int sem_cdabdtp(nlg_mesh *m, const double *p, double *out, double *pw_part = nullptr, const double *gate = nullptr, const nlg_pupd *upd = nullptr);
-int sem_cdabdtp_lanes(nlg_mesh *m, int nl, const double *const *p, double *const *out, double *const *pw_part, const double *const *gate,
-                      const nlg_pupd *upd = nullptr);
-int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const *const *w, bool face_grouped, const double *const *gate,
-                      const nlg_pupd *upd = nullptr);
-int sem_opdiv_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const *out, double scale, double *const *wts, bool face_grouped,
-                    const double *const *pdot, double *const *pw_part, const double *const *gate);
+int sem_cdabdtp(nlg_mesh *m, const double *p, double *out, double *pw_part = nullptr, const double *gate = nullptr, const nlg_pupd *upd = nullptr,
+                int nl = 1, int64_t ld = 0);
 int sem_ediag(nlg_mesh *m, double *out);
 int sem_tensor(nlg_mesh *m, const double *in, double *out, int nin, int nout, const double *Mx, const double *My,
                const double *Mz, const double *wt);
 int sem_conv_setup(nlg_mesh *m, double *const *U, double **Ur, double **GU);
-int sem_conv_apply(nlg_mesh *m, double *const *Ur, double *const *GU, double *const *u, double *const *out, int adjoint);
-int sem_conv_apply_lanes(nlg_mesh *m, double *const *Ur, double *const *GU, int nl, double *const *const *ulanes, double *const *const *olanes, int adjoint);
+int sem_conv_apply(nlg_mesh *m, double *const *Ur, double *const *GU, double *const *u, double *const *out, int adjoint, int nl = 1, int64_t ld = 0);
 int sem_conv_apply_generic(nlg_mesh *m, double *const *Ur, double *const *GU, double *const *u, double *const *out, int adjoint);
 int sem_conv_scalar_setup(nlg_mesh *m, const double *Theta, double **GT);
-int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, double *const *u, const double *theta, double *out, int adjoint = 0);
-int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, double *const *out, double sgn);
+int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, double *const *u, const double *theta, double *out, int adjoint = 0,
+                          int nl = 1, int64_t ld = 0);
+int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, double *const *out, double sgn, int nl = 1, int64_t ld = 0);
 int sem_cfl(nlg_mesh *m, double *const *U, double dt, double *cfl_host);
 int sem_ortho(nlg_mesh *m, double *p, int nl = 1, int64_t ld = 0);
 double *sem_scratch1(nlg_mesh *m, int i);

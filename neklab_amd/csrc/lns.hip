@@ -1029,16 +1029,6 @@ inline F3 at_lane3(const nlg_linop *op, double *const *a, int v) {
     return r;
 }
 
-// the copies of a set of component fields in lanes 0 .. nl - 1, as the *_lanes functions of sem.hip take them
-struct LaneFields {
-    F3 f[kMaxLanes];
-    double *const *p[kMaxLanes];
-    LaneFields(const nlg_linop *op, double *const *a, int nl) {
-        for (int v = 0; v < nl; ++v) f[v] = at_lane3(op, a, v), p[v] = f[v].p;
-    }
-    LaneFields(const LaneFields &) = delete;
-};
-
 // rotate three levels (of every lane, by the lane-0 pointers): the oldest becomes the newest
 template <typename T>
 void rotate3(T (&levels)[3]) {
@@ -1430,17 +1420,15 @@ int heat_step(const Lanes &L, int k, double b0) {
     // explicit term into the oldest buffer, then rotate.  The transport term is one launch per lane (base-flow data shared); everything
     // after it -- right-hand side, operator, gather-scatter, the whole PCG -- is ONE launch for all lanes (gridDim.y), as in the velocity solve
     const int adj = (op->adjoint && !op->nonlinear) ? 1 : 0;
-    for (int v = 0; v < nl; ++v) {
-        const F3 u = at_lane3(op, op->ubuf[0], v);
-        double *ft = at_lane(op, op->ftbuf[2], v);
-        NLG_TRY(sem_conv_scalar_apply(m, op->Ur, op->GT, u.p, at_lane(op, op->tbuf[0], v), ft, adj));
-        if (adj) {
-            // adjoint temperature equation: rhocp theta+_t = rhocp (U.grad) theta+ + conductivity lap theta+ + rhocp b . u+
-            // (stored term N_t = -conv(U, theta+) - bm1 b . u+ ; oracle/lns.py advance, adjoint branch)
+    NLG_TRY(sem_conv_scalar_apply(m, op->Ur, op->GT, op->ubuf[0], op->tbuf[0], op->ftbuf[2], adj, nl, ld));
+    if (adj) {
+        // adjoint temperature equation: rhocp theta+_t = rhocp (U.grad) theta+ + conductivity lap theta+ + rhocp b . u+
+        // (stored term N_t = -conv(U, theta+) - bm1 b . u+ ; oracle/lns.py advance, adjoint branch)
+        for (int v = 0; v < nl; ++v)
             for (int i = 0; i < m->dim; ++i)
                 if (c.buoy[i] != 0.0)
-                    NLG_LAUNCH(k_mul3_acc, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, ft, (const double *)m->d_bm1, (const double *)u.p[i], -c.buoy[i]);
-        }
+                    NLG_LAUNCH(k_mul3_acc, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, at_lane(op, op->ftbuf[2], v), (const double *)m->d_bm1,
+                               (const double *)at_lane(op, op->ubuf[0][i], v), -c.buoy[i]);
     }
     rotate3(op->ftbuf);
     Hist h;
@@ -1660,25 +1648,10 @@ int pres_apply(const Lanes &L, const PresSolve &Q) {
         p_in = op->prh + (int64_t)si * Q.P.hist.stride;
         p_out = op->prh + (int64_t)so * Q.P.hist.stride;
     }
-    if (L.nl == 1) {
-        if (Q.P.fused_pupdate) {   // p <- (z - zmean) + beta p while the gradient kernel loads p
-            nlg_pupd u;
-            u.z = op->pr_z, u.beta = op->d_s + S_N + S_BETA, u.zmean = op->d_s + S_N + S_ZMEAN, u.p = p_out;
-            return sem_cdabdtp(op->mesh, p_in, op->pr_w, Q.pw_part, op->d_s + S_N + S_DONE, &u);
-        }
-        return sem_cdabdtp(op->mesh, op->pr_p, op->pr_w, Q.pw_part, op->d_s + S_N + S_DONE);
-    }
-    // E p for all lanes: the gradient and divergence kernels take the lanes in one launch each, so does the gather-scatter
-    const double *pp[kMaxLanes], *gg[kMaxLanes];
-    double *ww[kMaxLanes], *pw[kMaxLanes];
-    nlg_pupd pu[kMaxLanes];
-    const int64_t ld = L.ld();
-    for (int v = 0; v < L.nl; ++v) {
-        pp[v] = p_in + v * ld, ww[v] = op->pr_w + v * ld, pw[v] = Q.pw_part + v * ld, gg[v] = op->d_s + S_N + S_DONE + v * ld;
-        if (Q.P.fused_pupdate)
-            pu[v].z = op->pr_z + v * ld, pu[v].beta = op->d_s + S_N + S_BETA + v * ld, pu[v].zmean = op->d_s + S_N + S_ZMEAN + v * ld, pu[v].p = p_out + v * ld;
-    }
-    return sem_cdabdtp_lanes(op->mesh, L.nl, pp, ww, pw, gg, Q.P.fused_pupdate ? pu : nullptr);
+    // E p for all lanes; with the fused update p <- (z - zmean) + beta p while the gradient kernel loads p
+    nlg_pupd u;
+    u.z = op->pr_z, u.beta = op->d_s + S_N + S_BETA, u.zmean = op->d_s + S_N + S_ZMEAN, u.p = p_out;
+    return sem_cdabdtp(op->mesh, p_in, op->pr_w, Q.pw_part, op->d_s + S_N + S_DONE, Q.P.fused_pupdate ? &u : nullptr, L.nl, L.ld());
 }
 
 int pres_finish(const Lanes &L, const PresSolve &Q, const int *iters) {
@@ -1770,15 +1743,10 @@ int adv_a(const Lanes &L) {
     if (op->cfg.ifheat) NLG_TRY(heat_step(L, k, b0));   // scalar first: the fluid sees the new temperature (Nek5000's order)
     // F = -N(u): written into the oldest forcing buffer, then the buffers rotate
     double **Fnew = op->fbuf[2];
-    if (nl == 1) {
-        NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], Fnew, op->nonlinear ? 0 : op->adjoint));
-    } else {   // convective terms of all lanes against the shared base-flow fields: one launch
-        const LaneFields ul(op, op->ubuf[0], nl), ol(op, Fnew, nl);
-        NLG_TRY(sem_conv_apply_lanes(m, op->Ur, op->GU, nl, ul.p, ol.p, op->adjoint));
-    }
+    NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], Fnew, op->nonlinear ? 0 : op->adjoint, nl, ld));   // all lanes against the shared base flow
     if (op->cfg.ifheat && op->adjoint && !op->nonlinear) {
-        // adjoint momentum equation: - theta+ grad Theta with the new theta+ (stored F is +N: add the weak term); lane by lane
-        for (int v = 0; v < nl; ++v) NLG_TRY(sem_scalar_grad_apply(m, op->GT, at_lane(op, op->tbuf[0], v), at_lane3(op, Fnew, v).p, 1.0));
+        // adjoint momentum equation: - theta+ grad Theta with the new theta+ (stored F is +N: add the weak term)
+        NLG_TRY(sem_scalar_grad_apply(m, op->GT, op->tbuf[0], Fnew, 1.0, nl, ld));
     } else if (op->cfg.ifheat) {
         const double bs = op->nonlinear ? 2.0 : 1.0;   // the nonlinear step halves the whole stored term (F holds 2 N there)
         for (int v = 0; v < nl; ++v)
@@ -1808,14 +1776,7 @@ int adv_a(const Lanes &L) {
     }
     // residual form: res = mask QQ^T (rhs + D^T p - H u); the history sums and the two operator terms in ONE pass over the fields
     const double h2 = b0 / dt;
-    if (nl == 1) {
-        NLG_TRY(sem_opgradt(m, op->p, op->gp));
-    } else {
-        const double *pp[kMaxLanes];
-        for (int v = 0; v < nl; ++v) pp[v] = at_lane(op, op->p, v);
-        const LaneFields gl(op, op->gp, nl);
-        NLG_TRY(sem_opgradt_lanes(m, nl, pp, gl.p, false, nullptr));
-    }
+    NLG_TRY(sem_opgradt(m, op->p, op->gp, false, nullptr, nullptr, nl, ld, ld));
     NLG_TRY(sem_axhelm(m, op->ubuf[0], op->w, dim, nu, h2, nullptr, nullptr, nullptr, nullptr, false, nl, ld));
     if (op->use_xp > 0) {
         // slab-permuted velocity solve: the right-hand side is born masked in that layout (no permutation pass in helm_problem, and
@@ -1862,14 +1823,7 @@ int adv_b(const Lanes &L) {
                   cf3(op->x, dim), 1.0, none, 0.0, ld);
     }
     // pressure correction
-    if (nl == 1) {
-        NLG_TRY(sem_opdiv(m, unew, op->pr_r, -(b0 / dt)));
-    } else {
-        const LaneFields ul(op, unew, nl);
-        double *ol[kMaxLanes], *none[kMaxLanes] = {};
-        for (int v = 0; v < nl; ++v) ol[v] = at_lane(op, op->pr_r, v);
-        NLG_TRY(sem_opdiv_lanes(m, nl, ul.p, ol, -(b0 / dt), nullptr, false, nullptr, none, nullptr));
-    }
+    NLG_TRY(sem_opdiv(m, unew, op->pr_r, -(b0 / dt), nullptr, false, nullptr, nullptr, nullptr, nl, ld, ld));
     NLG_TRY(sem_ortho(m, op->pr_r, nl, ld));
     return 0;
 }
@@ -1887,14 +1841,7 @@ int adv_c(const Lanes &L) {
     // (3-D): its gather-scatter then moves whole faces (50 us against 100 us in the natural layout at 10^4 elements), and the update
     // below reads it through the element-local slot table
     const bool fg = sem_opgradt_has_fg(m);
-    if (nl == 1) {
-        NLG_TRY(sem_opgradt(m, op->pr_x, op->gp, fg));
-    } else {
-        const double *pp[kMaxLanes];
-        for (int v = 0; v < nl; ++v) pp[v] = at_lane(op, op->pr_x, v);
-        const LaneFields gl(op, op->gp, nl);
-        NLG_TRY(sem_opgradt_lanes(m, nl, pp, gl.p, fg, nullptr));
-    }
+    NLG_TRY(sem_opgradt(m, op->pr_x, op->gp, fg, nullptr, nullptr, nl, ld, ld));
     // u = uh + (dt / b0) mask binv QQ^T D^T dp: gather-scatter, then weights and update in one pass
     NLG_TRY(sem_gs(m, op->gp, dim, nullptr, fg ? LAYOUT_FG : LAYOUT_NAT, nl, ld, 0));
     {

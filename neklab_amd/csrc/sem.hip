@@ -686,145 +686,6 @@ __global__ __launch_bounds__(64 * kAxhelm3rWaves) void k_axhelm3r(int64_t E, int
     }
 }
 
-// The same for the NL <= 4 lanes of a block step: one block = one element, 3 NL waves = (lane, component) pairs, so the six
-// metric factors and the mass matrix of the element are fetched from HBM once and served to the other waves by L1.  Every
-// lane has its own direction update (beta), done flag and (p, w) sums -- one sum per (lane, element).
-struct HelmLanes {
-    const double *u[4][3];
-    double *w[4][3];
-    const double *z[4][3];
-    const double *beta[4];
-    const double *done[4];
-    double *pw[4];
-};
-template <int N, int NL, bool XP>
-__global__ __launch_bounds__(64 * 3 * NL) void k_axhelm3rb(int64_t E, const double *__restrict__ Dg,
-                                                       const double *__restrict__ G0, const double *__restrict__ G1,
-                                                       const double *__restrict__ G2, const double *__restrict__ G3,
-                                                       const double *__restrict__ G4, const double *__restrict__ G5,
-                                                       const double *__restrict__ bm1, HelmLanes L, double h1, double h2,
-                                                       const int *__restrict__ xptab) {
-    constexpr int WPB = 3 * NL;
-    static_assert(N * N <= 64, "one lane per (i, j)");
-    constexpr int NP = N * N * N, NS = N * N, NQ = N + 1;
-    __shared__ double sD[N * N];
-    __shared__ double sU[WPB][N * NQ], sR[WPB][N * NQ], sS[WPB][N * NQ];
-    __shared__ double sred[WPB];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: element, field and every base pointer stay scalar
-    for (int p = tid; p < NS; p += 64 * WPB) sD[p] = Dg[p];
-    __syncthreads();   // the only block-wide barrier: the derivative matrix
-    const int64_t e = blockIdx.x;
-    const int lv = wv / 3, c = wv - 3 * lv;
-    const double *done_p = L.done[lv], *beta_p = L.beta[lv];
-    const bool gated = done_p && done_p[0] != 0.0;   // this lane's PCG has converged: nothing consumes its w any more
-    const bool act = e < E && lane < NS && !gated;
-    const int ij = lane < NS ? lane : 0;
-    const int i = ij % N, j = ij / N;
-    const int64_t eoff = (e < E ? e : 0) * NP;
-    const int base = ij;   // offset inside the element, natural layout (metric factors)
-    // field offsets inside the element: vk[k]
-    int vk[N];   // field offsets inside the element; slab-permuted layout: from the element's slot table (internal.h xp_slot), any permutation
-    const int gen = XP ? xptab[N * N * N] : 0;   // entry N^3 of the table: 1 = general permutation, 0 = every slab permuted alike (one entry per lane)
-    const int v0 = XP ? xptab[ij] : ij;
-#pragma unroll
-    for (int k = 0; k < N; ++k) vk[k] = gen ? xptab[ij + NS * k] : v0 + NS * k;
-    const double *uc = L.u[lv][c] + eoff;
-    double *wc = L.w[lv][c] + eoff;
-    const double *zc = L.z[lv][c] + eoff;
-    G0 += eoff, G1 += eoff, G2 += eoff, G3 += eoff, G4 += eoff, G5 += eoff, bm1 += eoff;
-    const bool upd = beta_p != nullptr && !gated;
-    const double beta = upd ? beta_p[0] : 0.0;
-    double pw = 0.0;
-    if (!gated) {   // (a converged lane skips the work; its waves still take part in the block reduction below)
-    double uk[N], wk[N], di[N], dj[N], dti[N], dtj[N];
-    // all loads of the column first, then the stores of the fused direction update: with load / store alternating per point the
-    // compiler cannot hoist the later loads over the earlier stores (same array) and the wave pays N serialised round trips
-    {
-        double zk[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            uk[k] = act ? uc[vk[k]] : 0.0;
-            zk[k] = (upd && act) ? zc[vk[k]] : 0.0;
-            wk[k] = 0.0;
-        }
-        if (upd && act) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                uk[k] = zk[k] + beta * uk[k];
-                const_cast<double *>(uc)[vk[k]] = uk[k];
-            }
-        }
-    }
-#pragma unroll
-    for (int l = 0; l < N; ++l) {
-        di[l] = sD[i * N + l];
-        dj[l] = sD[j * N + l];
-        dti[l] = sD[l * N + i];
-        dtj[l] = sD[l * N + j];
-    }
-    double *mU = sU[wv], *mR = sR[wv], *mS = sS[wv];
-    // metric factors of slab k+1 are requested while slab k is computed; the compiler barrier at the end of every slab
-    // keeps it from hoisting ALL slabs' loads to the top (which costs 400 registers and the occupancy)
-    double gn[7];
-    gn[0] = G0[base], gn[1] = G1[base], gn[2] = G2[base], gn[3] = G3[base], gn[4] = G4[base], gn[5] = G5[base], gn[6] = bm1[base];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const double g0 = gn[0], g1 = gn[1], g2 = gn[2], g3 = gn[3], g4 = gn[4], g5 = gn[5], bm = gn[6];
-        if (k + 1 < N) {
-            const int q = base + (k + 1) * NS;
-            gn[0] = G0[q], gn[1] = G1[q], gn[2] = G2[q], gn[3] = G3[q], gn[4] = G4[q], gn[5] = G5[q], gn[6] = bm1[q];
-        }
-        if (lane < NS) mU[i + NQ * j] = uk[k];
-        wave_lds_sync();
-        // row k of D, wave-uniform: lane k (i = k, j = 0) holds it in di[] -> scalar registers, no LDS, no vector registers
-        double dk[N];
-#pragma unroll
-        for (int l = 0; l < N; ++l) dk[l] = readlane_f64(di[l], k);
-        double ur = 0.0, us = 0.0, ut = 0.0;
-#pragma unroll
-        for (int l = 0; l < N; ++l) {
-            ur += di[l] * mU[l + NQ * j];
-            us += dj[l] * mU[i + NQ * l];
-            ut += dk[l] * uk[l];
-        }
-        const double gr = h1 * (g0 * ur + g1 * us + g2 * ut);
-        const double gs = h1 * (g1 * ur + g3 * us + g4 * ut);
-        const double gt = h1 * (g2 * ur + g4 * us + g5 * ut);
-        if (lane < NS) {
-            mR[i + NQ * j] = gr;
-            mS[i + NQ * j] = gs;
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int l = 0; l < N; ++l) wk[l] += dk[l] * gt;
-        double a = h2 * bm * uk[k];
-#pragma unroll
-        for (int l = 0; l < N; ++l) a += dti[l] * mR[l + NQ * j] + dtj[l] * mS[i + NQ * l];
-        wk[k] += a;
-        // pin the accumulators here: otherwise the compiler sinks these sums into the guarded store at the end and keeps
-        // every slab's LDS operands alive until then (400 registers, one wave per SIMD)
-#pragma unroll
-        for (int l = 0; l < N; ++l) asm volatile("" : "+v"(wk[l]));
-        asm volatile("" ::: "memory");
-    }
-    if (act) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            wc[vk[k]] = wk[k];
-            pw += wk[k] * uk[k];
-        }
-    }
-    }
-    {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pw += __shfl_down(pw, o, 64);
-        if (lane == 0) sred[wv] = pw;
-        __syncthreads();
-        if (tid < NL && L.pw[tid] && !(L.done[tid] && L.done[tid][0] != 0.0)) L.pw[tid][e] = (sred[3 * tid] + sred[3 * tid + 1]) + sred[3 * tid + 2];
-    }
-}
-
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding global load (s_waitcnt vmcnt(0)
 // before s_barrier), which turns a prefetch issued ahead of it into a blocking load; with the fences restricted to the LDS address
 // space only the LDS counter is drained.  (An inline-asm barrier with a "memory" clobber does the same to the waits but makes the
@@ -3685,55 +3546,6 @@ int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h
     return 0;
 }
 
-// nl <= 4 lanes of the velocity PCG of a block step in one launch (3-D, lx1 <= 8); otherwise lane by lane.  pw[v]: E sums of
-// p . w per lane (one per element); zf / beta / done: the fused direction update and the done flag of every lane.
-int sem_axhelm_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const *const *w, double h1, double h2, double *const *pw,
-                     double *const *const *zf, const double *const *beta, const double *const *done, bool xp) {
-    if (!(m->dim == 3 && m->n <= 8 && nl >= 2 && nl <= 4)) {
-        for (int v = 0; v < nl; ++v) NLG_TRY(sem_axhelm(m, u[v], w[v], m->dim, h1, h2, pw[v], zf[v], beta[v], done[v], xp));
-        return 0;
-    }
-    ProfScope ps(m->ctx, P_AXHELM);
-    HelmLanes L;
-    for (int v = 0; v < 4; ++v) {
-        for (int c = 0; c < 3; ++c) {
-            L.u[v][c] = v < nl ? u[v][c] : nullptr;
-            L.w[v][c] = v < nl ? w[v][c] : nullptr;
-            L.z[v][c] = v < nl ? zf[v][c] : nullptr;
-        }
-        L.beta[v] = v < nl ? beta[v] : nullptr;
-        L.done[v] = v < nl ? done[v] : nullptr;
-        L.pw[v] = v < nl ? pw[v] : nullptr;
-    }
-    hipStream_t s = m->ctx->stream;
-    const int *tab = xp ? (const int *)m->d_slot_xp : nullptr;
-#define AXB(N_, NL_)                                                                                                         \
-    if (xp)                                                                                                                  \
-        NLG_LAUNCH((k_axhelm3rb<N_, NL_, true>), dim3((unsigned)m->E), dim3(64 * 3 * NL_), 0, s, m->E, m->d_D, m->d_G[0], m->d_G[1], \
-                           m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, L, h1, h2, tab);                          \
-    else                                                                                                                     \
-        NLG_LAUNCH((k_axhelm3rb<N_, NL_, false>), dim3((unsigned)m->E), dim3(64 * 3 * NL_), 0, s, m->E, m->d_D, m->d_G[0], m->d_G[1], \
-                           m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, L, h1, h2, tab);
-#define AXBN(N_)                        \
-    case N_:                            \
-        if (nl == 2) {                  \
-            AXB(N_, 2)                  \
-        } else if (nl == 3) {           \
-            AXB(N_, 3)                  \
-        } else {                        \
-            AXB(N_, 4)                  \
-        }                               \
-        break;
-    switch (m->n) {
-        AXBN(4) AXBN(5) AXBN(6) AXBN(7) AXBN(8)
-        default: set_error("sem_axhelm_lanes: lx1 = %d", m->n); return 1;
-    }
-#undef AXBN
-#undef AXB
-    NLG_HIP(hipGetLastError());
-    return 0;
-}
-
 int sem_helm_diag(nlg_mesh *m, double *out, double h1, double h2) {
     NLG_LAUNCH(k_helm_diag, dim3(grid_for(m->lvn)), dim3(NT), 0, m->ctx->stream, m->dim, m->n, m->E, m->d_D,
                        m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, out, h1, h2);
@@ -3767,10 +3579,15 @@ static CF9 rst2w_ptrs(const nlg_mesh *m) {
     return g;
 }
 
-int sem_opgradt(nlg_mesh *m, const double *p, double *const *w, bool face_grouped, const double *gate, const nlg_pupd *upd) {
-    const double *pl[1] = {p}, *gl[1] = {gate};
-    double *const *wl[1] = {w};
-    return sem_opgradt_lanes(m, 1, pl, wl, face_grouped, gl, upd);
+// lane v of a per-lane argument, v * ld doubles behind lane 0 (null stays null)
+template <typename T>
+static T *at_lane(T *p, int v, int64_t ld) {
+    return p ? p + v * ld : nullptr;
+}
+static F3 at_lane3(double *const *a, int nf, int v, int64_t ld) {
+    F3 r = {{nullptr, nullptr, nullptr}};
+    for (int c = 0; c < nf; ++c) r.p[c] = at_lane(a[c], v, ld);
+    return r;
 }
 
 // does sem_opgradt perform the PCG direction update itself when asked to (nlg_pupd)?  3-D, lx1 >= 8: the in-place kernels
@@ -3778,17 +3595,17 @@ int sem_opgradt(nlg_mesh *m, const double *p, double *const *w, bool face_groupe
 //  update kernel costs -- so the fusion stops at lx1 = 10)
 bool sem_opgradt_fuses_pupdate(const nlg_mesh *m) { return m->dim == 3 && m->n >= 8 && m->n <= 10; }
 
-// nl <= 4 pressure fields -> nl velocity-mesh field triples in one launch (block stepper); gates: per-lane done flags (may be null)
-int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const *const *w, bool face_grouped, const double *const *gate,
-                      const nlg_pupd *upd) {
+// 3-D: the nl <= 4 lanes in one launch; 2-D: one launch per lane.  gate: the done flags of the lanes (may be null)
+int sem_opgradt(nlg_mesh *m, const double *p, double *const *w, bool face_grouped, const double *gate, const nlg_pupd *upd, int nl, int64_t ld,
+                int64_t ldv) {
     NLG_CHECK(!upd || sem_opgradt_fuses_pupdate(m), "sem_opgradt: the fused direction update exists for 3-D, lx1 >= 8 only");
     PUpd pu;
     for (int v = 0; v < 4; ++v) {
-        const bool on = upd && v < nl && upd[v].z;
-        pu.z[v] = on ? upd[v].z : nullptr;
-        pu.beta[v] = on ? upd[v].beta : nullptr;
-        pu.zmean[v] = on ? upd[v].zmean : nullptr;
-        pu.p[v] = on ? upd[v].p : nullptr;
+        const bool on = upd && v < nl && upd->z;
+        pu.z[v] = on ? at_lane(upd->z, v, ld) : nullptr;
+        pu.beta[v] = on ? at_lane(upd->beta, v, ld) : nullptr;
+        pu.zmean[v] = on ? at_lane(upd->zmean, v, ld) : nullptr;
+        pu.p[v] = on ? at_lane(upd->p, v, ld) : nullptr;
     }
     // (the timed class is ONE kernel instantiation -- the face-grouped variant of the pressure operator in 3-D; the natural-layout
     //  launches of the right-hand sides, a few per time step, are booked under "vec_ops")
@@ -3799,23 +3616,22 @@ int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const
         CP4 pl, gl;
         F3L wl;
         for (int v = 0; v < 4; ++v) {
-            pl.p[v] = v < nl ? p[v] : nullptr;
-            gl.p[v] = (v < nl && gate) ? gate[v] : nullptr;
-            for (int c = 0; c < 3; ++c) wl.p[v][c] = v < nl ? w[v][c] : nullptr;
+            pl.p[v] = v < nl ? p + v * ld : nullptr;
+            gl.p[v] = v < nl ? at_lane(gate, v, ld) : nullptr;
+            for (int c = 0; c < 3; ++c) wl.p[v][c] = v < nl ? at_lane(w[c], v, ldv) : nullptr;
         }
         if (m->n == 8 && nl == 1 && sem_small_mesh(m)) {   // strong-scaling regime: three waves per element
-            const F3 w3 = {{w[0][0], w[0][1], w[0][2]}};
-            const double *g0 = gate ? gate[0] : nullptr;
+            const F3 w3 = {{w[0], w[1], w[2]}};
             if (upd) {
                 if (face_grouped)
-                    NLG_LAUNCH((k_opgradt3w<8, true, true>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p[0], w3, g0, pu);
+                    NLG_LAUNCH((k_opgradt3w<8, true, true>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, pu);
                 else
-                    NLG_LAUNCH((k_opgradt3w<8, false, true>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p[0], w3, g0, pu);
+                    NLG_LAUNCH((k_opgradt3w<8, false, true>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, pu);
             } else {
                 if (face_grouped)
-                    NLG_LAUNCH((k_opgradt3w<8, true, false>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p[0], w3, g0, NoPUpd{});
+                    NLG_LAUNCH((k_opgradt3w<8, true, false>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, NoPUpd{});
                 else
-                    NLG_LAUNCH((k_opgradt3w<8, false, false>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p[0], w3, g0, NoPUpd{});
+                    NLG_LAUNCH((k_opgradt3w<8, false, false>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, NoPUpd{});
             }
             NLG_HIP(hipGetLastError());
             return 0;
@@ -3850,8 +3666,8 @@ int sem_opgradt_lanes(nlg_mesh *m, int nl, const double *const *p, double *const
 #undef GT3_
     } else {
         for (int v = 0; v < nl; ++v) {
-            F3 cw = {{w[v][0], w[v][1], nullptr}};
-            const double *pv = p[v];
+            F3 cw = {{w[0] + v * ldv, w[1] + v * ldv, nullptr}};
+            const double *pv = p + v * ld;
 #define GT2(N_)                                                                                              \
     {                                                                                                        \
         constexpr int EPB = NT / (N_ * N_) > 0 ? NT / (N_ * N_) : 1;                                         \
@@ -3873,17 +3689,9 @@ int sem_opdiv_blocks(const nlg_mesh *m) {
     return (int)((m->E + epb - 1) / epb);
 }
 
-int sem_opdiv(nlg_mesh *m, double *const *u, double *out, double scale, double *const *wts, bool face_grouped,
-              const double *pdot, double *pw_part, const double *gate) {
-    double *const *ul[1] = {u};
-    double *ol[1] = {out}, *pl[1] = {pw_part};
-    const double *dl[1] = {pdot}, *gl[1] = {gate};
-    return sem_opdiv_lanes(m, 1, ul, ol, scale, wts, face_grouped, dl, pl, gl);
-}
-
-// nl <= 4 velocity-mesh field triples -> nl pressure fields in one launch (block stepper)
-int sem_opdiv_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const *out, double scale, double *const *wts, bool face_grouped,
-                    const double *const *pdot, double *const *pw_part, const double *const *gate) {
+// 3-D: the nl <= 4 lanes in one launch; 2-D: one launch per lane
+int sem_opdiv(nlg_mesh *m, double *const *u, double *out, double scale, double *const *wts, bool face_grouped, const double *pdot, double *pw_part,
+              const double *gate, int nl, int64_t ld, int64_t ldv) {
     ProfScope ps(m->ctx, (m->dim == 2 || face_grouped) ? P_OPDIV : P_VECOPS);
     CF3 wt = {{wts ? wts[0] : nullptr, wts ? wts[1] : nullptr, (wts && m->dim == 3) ? wts[2] : nullptr}};
     // face-grouped weights mask_i * binvm1: ONE array (binvm1) and one byte per point (bit i = mask_i) instead of three arrays
@@ -3903,20 +3711,18 @@ int sem_opdiv_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const 
         P4 ol, pl;
         CP4 dl, gl;
         for (int v = 0; v < 4; ++v) {
-            for (int c = 0; c < 3; ++c) ul.p[v][c] = v < nl ? u[v][c] : nullptr;
-            ol.p[v] = v < nl ? out[v] : nullptr;
-            pl.p[v] = (v < nl && pw_part) ? pw_part[v] : nullptr;
-            dl.p[v] = (v < nl && pdot) ? pdot[v] : nullptr;
-            gl.p[v] = (v < nl && gate) ? gate[v] : nullptr;
+            for (int c = 0; c < 3; ++c) ul.p[v][c] = v < nl ? at_lane(u[c], v, ldv) : nullptr;
+            ol.p[v] = v < nl ? out + v * ld : nullptr;
+            pl.p[v] = v < nl ? at_lane(pw_part, v, ld) : nullptr;
+            dl.p[v] = v < nl ? at_lane(pdot, v, ld) : nullptr;
+            gl.p[v] = v < nl ? at_lane(gate, v, ld) : nullptr;
         }
         if (m->n == 8 && nl == 1 && sem_small_mesh(m)) {   // strong-scaling regime: three waves per element
-            const CF3 u3 = {{u[0][0], u[0][1], u[0][2]}};
-            const double *g0 = gate ? gate[0] : nullptr, *d0 = pdot ? pdot[0] : nullptr;
-            double *p0 = pw_part ? pw_part[0] : nullptr;
+            const CF3 u3 = {{u[0], u[1], u[2]}};
             if (face_grouped)
-                NLG_LAUNCH((k_opdiv3w<8, true>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, u3, wt, out[0], scale, d0, p0, g0);
+                NLG_LAUNCH((k_opdiv3w<8, true>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, u3, wt, out, scale, pdot, pw_part, gate);
             else
-                NLG_LAUNCH((k_opdiv3w<8, false>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, u3, wt, out[0], scale, d0, p0, g0);
+                NLG_LAUNCH((k_opdiv3w<8, false>), dim3((unsigned)m->E), dim3(192), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, u3, wt, out, scale, pdot, pw_part, gate);
             NLG_HIP(hipGetLastError());
             return 0;
         }
@@ -3943,9 +3749,9 @@ int sem_opdiv_lanes(nlg_mesh *m, int nl, double *const *const *u, double *const 
 #undef DV3_
     } else {
         for (int v = 0; v < nl; ++v) {
-            CF3 cu = {{u[v][0], u[v][1], nullptr}};
-            double *ov = out[v], *pv = pw_part ? pw_part[v] : nullptr;
-            const double *dv = pdot ? pdot[v] : nullptr, *gv = gate ? gate[v] : nullptr;
+            CF3 cu = {{u[0] + v * ldv, u[1] + v * ldv, nullptr}};
+            double *ov = out + v * ld, *pv = at_lane(pw_part, v, ld);
+            const double *dv = at_lane(pdot, v, ld), *gv = at_lane(gate, v, ld);
 #define DV2(N_)                                                                                            \
     {                                                                                                      \
         constexpr int EPB = NT / (N_ * N_) > 0 ? NT / (N_ * N_) : 1;                                       \
@@ -3973,62 +3779,35 @@ int sem_opbinv(nlg_mesh *m, double *const *w, int nl, int64_t ld) {
     return 0;
 }
 
-// E applied to nl <= 4 pressure fields (block stepper): gradient, gather-scatter, divergence; the two element kernels take
-// all lanes in one launch
 // the intermediates of the pressure operator can be kept in the face-grouped element layout (tables, gather-scatter lists and, on
 // several ranks, halo index lists of that layout exist)
 bool sem_opgradt_has_fg(const nlg_mesh *m) { return m->dim == 3 && m->gs.d_indices_fg && m->d_slot_fg && (!m->halo.active || m->halo.d_send_idx_fg); }
 
-int sem_cdabdtp_lanes(nlg_mesh *m, int nl, const double *const *p, double *const *out, double *const *pw_part, const double *const *gate,
-                      const nlg_pupd *upd) {
+// E = D binv QQ^T D^T: gradient, gather-scatter, divergence, each one launch for all lanes (3-D).  In 3-D the intermediate
+// velocity-mesh fields use the face-grouped element layout where it exists: the copies of a shared face are contiguous runs
+// (coalesced gather-scatter), and the rank halo uses index lists in that layout.
+int sem_cdabdtp(nlg_mesh *m, const double *p, double *out, double *pw_part, const double *gate, const nlg_pupd *upd, int nl, int64_t ld) {
     const bool fg = sem_opgradt_has_fg(m);
-    // the intermediate velocity-mesh fields of all lanes in ONE allocation at a constant stride, so that their gather-scatter
-    // (and its halo exchange) is one launch with gridDim.y = lanes
+    // the intermediates: one lane in three scratch fields (the stride is not used); the lanes of a block step in ONE allocation at a
+    // constant stride, so that their gather-scatter (and its halo exchange) is one launch with gridDim.y = lanes
     const int64_t ldw = 3 * m->lvs;
-    if (!m->d_wlanes) {
-        NLG_HIP(hipMalloc(&m->d_wlanes, sizeof(double) * (size_t)(kMaxLanes * ldw)));
-        NLG_HIP(hipMemsetAsync(m->d_wlanes, 0, sizeof(double) * (size_t)(kMaxLanes * ldw), m->ctx->stream));
-    }
-    double *w[4][3];
-    double *const *wl[4];
-    for (int v = 0; v < nl; ++v) {
-        for (int c = 0; c < 3; ++c) w[v][c] = c < m->dim ? m->d_wlanes + v * ldw + c * m->lvs : nullptr;
-        wl[v] = w[v];
-    }
-    NLG_TRY(sem_opgradt_lanes(m, nl, p, wl, fg, gate, upd));
-    // the gates of the lanes are the done flags of their solver scalars: at a constant stride when the lanes share a slab
-    bool strided = true;
-    int64_t ldg = 0;
-    if (gate && nl > 1) {
-        ldg = gate[1] - gate[0];
-        for (int v = 1; v < nl; ++v) strided = strided && gate[v] && (gate[v] - gate[0]) == v * ldg;
-    }
-    if (strided) {
-        NLG_TRY(sem_gs(m, w[0], m->dim, gate ? gate[0] : nullptr, fg ? LAYOUT_FG : LAYOUT_NAT, nl, ldw, ldg));
+    double *w[3];
+    if (nl == 1) {
+        for (int c = 0; c < 3; ++c) w[c] = c < m->dim ? sem_scratch1(m, c) : nullptr;
+        NLG_CHECK(w[0] && w[1], "sem_cdabdtp: scratch allocation failed");
     } else {
-        for (int v = 0; v < nl; ++v) NLG_TRY(sem_gs(m, w[v], m->dim, gate ? gate[v] : nullptr, fg ? LAYOUT_FG : LAYOUT_NAT));
+        if (!m->d_wlanes) {
+            NLG_HIP(hipMalloc(&m->d_wlanes, sizeof(double) * (size_t)(kMaxLanes * ldw)));
+            NLG_HIP(hipMemsetAsync(m->d_wlanes, 0, sizeof(double) * (size_t)(kMaxLanes * ldw), m->ctx->stream));
+        }
+        for (int c = 0; c < 3; ++c) w[c] = c < m->dim ? m->d_wlanes + c * m->lvs : nullptr;
     }
-    // (p, E p): p AFTER the fused direction update, which may have gone to another buffer than the one it was read from (direction ring)
-    const double *pd[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int v = 0; v < nl; ++v) pd[v] = (upd && upd[v].z && upd[v].p) ? upd[v].p : p[v];
-    return sem_opdiv_lanes(m, nl, wl, out, 1.0, fg ? m->d_mbinv_fg : m->d_mbinv, fg, pd, pw_part, gate);
-}
-
-int sem_cdabdtp(nlg_mesh *m, const double *p, double *out, double *pw_part, const double *gate, const nlg_pupd *upd) {
-    double *w[3] = {sem_scratch1(m, 0), sem_scratch1(m, 1), m->dim == 3 ? sem_scratch1(m, 2) : nullptr};
-    NLG_CHECK(w[0] && w[1], "sem_cdabdtp: scratch allocation failed");
-    if (m->dim == 3 && m->gs.d_indices_fg && (!m->halo.active || m->halo.d_send_idx_fg)) {
-        // 3-D: the intermediate velocity-mesh fields use the face-grouped element layout, in which the copies of a
-        // shared face are contiguous runs -> coalesced gather-scatter; the rank halo uses index lists in that layout
-        NLG_TRY(sem_opgradt(m, p, w, true, gate, upd));
-        NLG_TRY(sem_gs(m, w, 3, gate, LAYOUT_FG));
-        NLG_TRY(sem_opdiv(m, w, out, 1.0, m->d_mbinv_fg, true, (upd && upd->z && upd->p) ? upd->p : p, pw_part, gate));   // (p, E p) with the UPDATED p
-        return 0;
-    }
-    NLG_TRY(sem_opgradt(m, p, w, false, gate, upd));
-    NLG_TRY(sem_gs(m, w, m->dim, gate));
-    NLG_TRY(sem_opdiv(m, w, out, 1.0, m->d_mbinv, false, p, pw_part, gate));   // mask * binvm1 fused into the load
-    return 0;
+    NLG_TRY(sem_opgradt(m, p, w, fg, gate, upd, nl, ld, ldw));
+    NLG_TRY(sem_gs(m, w, m->dim, gate, fg ? LAYOUT_FG : LAYOUT_NAT, nl, ldw, ld));
+    // (p, E p): p AFTER the fused direction update, which may have gone to another buffer than the one it was read from (direction ring);
+    // mask * binvm1 fused into the load
+    const double *pd = (upd && upd->z && upd->p) ? upd->p : p;
+    return sem_opdiv(m, w, out, 1.0, fg ? m->d_mbinv_fg : m->d_mbinv, fg, pd, pw_part, gate, nl, ld, ldw);
 }
 
 int sem_ortho(nlg_mesh *m, double *p, int nl, int64_t ld) {
@@ -4149,7 +3928,11 @@ __global__ void k_mul_fine(int64_t n, const double *a, const double *b, double *
 __global__ void k_axpy_field(int64_t n, double *y, const double *x, double s) {
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) y[q] += s * x[q];
 }
-int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, double *const *out, double sgn) {
+int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, double *const *out, double sgn, int nl, int64_t ld) {
+    if (nl > 1) {   // one lane at a time
+        for (int v = 0; v < nl; ++v) NLG_TRY(sem_scalar_grad_apply(m, GT, theta + v * ld, at_lane3(out, m->dim, v, ld).p, sgn));
+        return 0;
+    }
     ProfScope ps(m->ctx, P_CONV);
     const int dim = m->dim;
     double *tf = sem_scratchd(m, 0), *prod = sem_scratchd(m, 1), *back = sem_scratch1(m, 4);
@@ -4165,7 +3948,12 @@ int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, d
 }
 
 // adjoint != 0: out = - J^T [ Ur . grad theta ]  (the transport term of the adjoint temperature equation; no u . grad Theta)
-int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, double *const *u, const double *theta, double *out, int adjoint) {
+int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, double *const *u, const double *theta, double *out, int adjoint, int nl,
+                          int64_t ld) {
+    if (nl > 1) {   // the kernels have no lane dimension: one launch per lane
+        for (int v = 0; v < nl; ++v) NLG_TRY(sem_conv_scalar_apply(m, Ur, GT, at_lane3(u, m->dim, v, ld).p, theta + v * ld, out + v * ld, adjoint));
+        return 0;
+    }
     ProfScope ps(m->ctx, P_CONV);
     const int dim = m->dim;
     if (dim == 3 && m->n >= 8 && m->n <= 10 && m->nd == (3 * m->n) / 2) {
@@ -4210,17 +3998,12 @@ int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, dou
     return 0;
 }
 
-// out_i = weak linearised convective term (B-weighted, element-local), see oracle/sem.py lns_conv_weak
-int sem_conv_apply(nlg_mesh *m, double *const *Ur, double *const *GU, double *const *u, double *const *out, int adjoint) {
-    double *const *ul[1] = {u}, *const *ol[1] = {out};
-    return sem_conv_apply_lanes(m, Ur, GU, 1, ul, ol, adjoint);
-}
-
-// nl <= 4 vectors against the same base flow (block stepper): one launch where the fused kernel exists
-int sem_conv_apply_lanes(nlg_mesh *m, double *const *Ur, double *const *GU, int nl, double *const *const *ulanes, double *const *const *olanes, int adjoint) {
+// out_i = weak linearised convective term (B-weighted, element-local), see oracle/sem.py lns_conv_weak.  The nl <= 4 lanes of a
+// block step against the same base flow: one launch where the fused kernel exists, otherwise one generic pass per lane
+int sem_conv_apply(nlg_mesh *m, double *const *Ur, double *const *GU, double *const *u, double *const *out, int adjoint, int nl, int64_t ld) {
     const int dim = m->dim;
     if (!(dim == 3 && (m->n <= 10 || m->n == 12) && m->nd == (3 * m->n) / 2)) {
-        for (int v = 0; v < nl; ++v) NLG_TRY(sem_conv_apply_generic(m, Ur, GU, ulanes[v], olanes[v], adjoint));
+        for (int v = 0; v < nl; ++v) NLG_TRY(sem_conv_apply_generic(m, Ur, GU, at_lane3(u, dim, v, ld).p, at_lane3(out, dim, v, ld).p, adjoint));
         return 0;
     }
     ProfScope ps(m->ctx, P_CONV);
@@ -4231,8 +4014,8 @@ int sem_conv_apply_lanes(nlg_mesh *m, double *const *Ur, double *const *GU, int 
         F3L co;
         for (int v = 0; v < 4; ++v)
             for (int c = 0; c < 3; ++c) {
-                cu.p[v][c] = v < nl ? ulanes[v][c] : nullptr;
-                co.p[v][c] = v < nl ? olanes[v][c] : nullptr;
+                cu.p[v][c] = v < nl ? at_lane(u[c], v, ld) : nullptr;
+                co.p[v][c] = v < nl ? at_lane(out[c], v, ld) : nullptr;
             }
         CF9 cg;
         for (int q = 0; q < 9; ++q) cg.p[q] = GU[q];

@@ -370,7 +370,7 @@ print("RESULT", st["v_iters"], st["p_iters"], " ".join(words))
 
 def test_compact_divergence_weights_are_bit_identical():
     """k_opdiv3n reads the weights mask_i * binvm1 of the consistent Poisson operator as ONE array (binvm1) and one byte per point (bit i =
-    mask_i) instead of three arrays (csrc/sem.hip sem_opdiv_lanes; NLG_OPDIV_MASKB=0 = the three arrays).  Same products: a matvec gives the
+    mask_i) instead of three arrays (csrc/sem.hip sem_opdiv; NLG_OPDIV_MASKB=0 = the three arrays).  Same products: a matvec gives the
     same BITS either way, also where the three masks differ (a free-slip plane: tangential components free, normal component fixed).  The
     Jacobi preconditioner mask_i / diag(H) of the velocity PCG is read the same way (1 / diag and the mask bytes, NLG_PC_MASKB=0 = three arrays)."""
     import os
