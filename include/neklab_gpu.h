@@ -272,6 +272,15 @@ typedef struct nlg_exptA_config {
                           slightly different discretisation of exp(tau L) (start-up at first order: +4e-5 in the cylinder's leading
                           multiplier), but ONE linear map for every column of the Arnoldi relation.  0 (default): the reference's
                           protocol. */
+    double filter_weight; /* Nek5000's explicit modal filter (`filtering = explicit`, `filterWeight`; e.g. examples/back_fstep/
+                          transient_growth/bfs.par): > 0: at the end of every time step the velocity of every lane, and the temperature
+                          with ifheat, become (F x F [x F]) u element by element, F = Phi diag(d) Phi^-1 in the basis L_0, L_1,
+                          L_{k-1} - L_{k-3} with d = 1 - filter_weight ((k - k0) / filter_modes)^2 on the last filter_modes modes
+                          (DESIGN.md 3.2).  The pressure is never filtered; the same F serves direct, adjoint, nonlinear and forced
+                          integration.  0 (default): off -- the time step is launch for launch the unfiltered one.  Range [0, 1];
+                          kernels exist for lx1 = 6, 8, 10 (and 12 in 3-D). */
+    int filter_modes;  /* number of attenuated modes (what Nek5000's .par reader derives from `filterCutoffRatio`), 1 .. lx1 - 2;
+                          read only when filter_weight > 0 */
 } nlg_exptA_config;
 
 int nlg_exptA_config_default(nlg_exptA_config *cfg);
@@ -355,6 +364,9 @@ int nlg_op_pprec(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out, int overlap, i
 int nlg_op_opdiv(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_opgradt(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_conv(nlg_mesh *mesh, const nlg_vec *base, const nlg_vec *in, nlg_vec *out, int adjoint);
+/* the explicit modal filter of the time stepper (nlg_exptA_config.filter_weight / filter_modes) on its own, in place on the velocity
+ * fields (and scalars) of nvec <= 4 vectors, which go through the kernel together as the lanes of a block step do */
+int nlg_op_filter(nlg_mesh *mesh, int nvec, nlg_vec *const *vecs, double filter_weight, int filter_modes);
 int nlg_op_cfl(nlg_mesh *mesh, const nlg_vec *base, double dt, double *cfl);
 
 /* ---------------------------------------------------------------------------------------------- */

@@ -38,6 +38,7 @@ class ExptAConfig(C.Structure):
         ("fixed_iters_v", C.c_int), ("fixed_iters_p", C.c_int), ("pprecond", C.c_int), ("pproj", C.c_int),
         ("ifheat", C.c_int), ("conductivity", C.c_double), ("rhocp", C.c_double), ("buoy", C.c_double * 3),
         ("no_history", C.c_int),
+        ("filter_weight", C.c_double), ("filter_modes", C.c_int),
     ]
 
 
@@ -139,6 +140,7 @@ SIGNATURES = {
     "nlg_op_opdiv": (C.c_int, [vp, vp, vp]),
     "nlg_op_opgradt": (C.c_int, [vp, vp, vp]),
     "nlg_op_conv": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+    "nlg_op_filter": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_double, C.c_int]),
     "nlg_op_cfl": (C.c_int, [vp, vp, C.c_double, c_double_p]),
     "nlg_arnoldi_step": (C.c_int, [vp, vp, C.c_int, c_double_p, C.c_int, C.c_int]),
     "nlg_eigs_opts_default": (C.c_int, [C.POINTER(EigsOpts)]),

@@ -437,6 +437,13 @@ int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, dou
 int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, double *const *out, double sgn, int nl = 1, int64_t ld = 0);
 int sem_cfl(nlg_mesh *m, double *const *U, double dt, double *cfl_host);
 int sem_ortho(nlg_mesh *m, double *p, int nl = 1, int64_t ld = 0);
+// explicit modal filter: the dense 1-D matrix F (n x n, row-major, host; ncut attenuated modes, weight of the last one), and its
+// element-local action fields_c <- (F x F [x F]) fields_c on nf <= 4 fields of nl lanes in ONE launch.  upd_x: the velocity
+// correction fields_c += upd_s * upd_wt_c * upd_x_c (c < dim; x through the element-local table `slot` when given) rides in the load
+bool sem_filter_available(const nlg_mesh *m);   // kernels exist for 2-D lx1 = 6, 8, 10 and 3-D lx1 = 6, 8, 10, 12
+int sem_filter_matrix(const nlg_mesh *m, int ncut, double weight, std::vector<double> &F);
+int sem_filter(nlg_mesh *m, const double *F, double *const *fields, int nf, int nl = 1, int64_t ld = 0, double *const *upd_x = nullptr,
+               double *const *upd_wt = nullptr, double upd_s = 0.0, const int *slot = nullptr);
 double *sem_scratch1(nlg_mesh *m, int i);
 double *sem_scratchd(nlg_mesh *m, int i);
 double *sem_scratch2(nlg_mesh *m, int i);

@@ -951,6 +951,8 @@ struct nlg_linop {
     // BDF order, gradient of the base temperature on the fine mesh
     double *tbuf[3] = {}, *ftbuf[3] = {}, *trhs = nullptr, *tx = nullptr, *tz = nullptr, *tpv = nullptr, *tw = nullptr;
     double *pct[4] = {}, *GT[3] = {};
+    bool filt_fused = true;
+    double *d_filt = nullptr;  // explicit modal filter (cfg.filter_weight > 0): the dense 1-D matrix F, [n][n]; belongs to the operator, not the mesh
     int nonlinear = 0;         // 1: full Navier-Stokes step, N(u) = (u.grad)u = half of the linearised term about U = u
     int64_t st_steps = 0, st_viters = 0, st_piters = 0, st_titers = 0, st_matvecs = 0;   // summed over the lanes
 };
@@ -1844,7 +1846,8 @@ int adv_c(const Lanes &L) {
     NLG_TRY(sem_opgradt(m, op->pr_x, op->gp, fg, nullptr, nullptr, nl, ld, ld));
     // u = uh + (dt / b0) mask binv QQ^T D^T dp: gather-scatter, then weights and update in one pass
     NLG_TRY(sem_gs(m, op->gp, dim, nullptr, fg ? LAYOUT_FG : LAYOUT_NAT, nl, ld, 0));
-    {
+    const bool fused = op->d_filt && op->filt_fused;
+    if (!fused) {
         CF3 wt = {{m->d_mbinv[0], m->d_mbinv[1], m->d_mbinv[2]}};
         if (fg)
             launch_nf(dim, k_axpy_w<1, true>, k_axpy_w<2, true>, k_axpy_w<3, true>, lgrid(grid_for(m->lvn), nl), st, m->lvn, f3(unew, dim), cf3(op->gp, dim),
@@ -1852,6 +1855,16 @@ int adv_c(const Lanes &L) {
         else
             launch_nf(dim, k_axpy_w<1>, k_axpy_w<2>, k_axpy_w<3>, lgrid(grid_for(m->lvn), nl), st, m->lvn, f3(unew, dim), cf3(op->gp, dim), wt, dt / b0,
                       ld, (const int *)nullptr, 1);
+    }
+    if (op->d_filt) {
+        // explicit filter, the last thing a step does: the velocity of every lane and, coupled, the new temperature (which the fluid
+        // has seen unfiltered in its buoyancy term) in one launch; the pressure is never filtered
+        double *fl[4] = {unew[0], unew[1], dim == 3 ? unew[2] : op->tbuf[0], op->tbuf[0]};
+        const int nf = dim + (op->cfg.ifheat ? 1 : 0);
+        if (fused)   // the update above rides in the filter's load
+            NLG_TRY(sem_filter(m, op->d_filt, fl, nf, nl, ld, op->gp, m->d_mbinv, dt / b0, fg ? (const int *)m->d_slot_fg : nullptr));
+        else
+            NLG_TRY(sem_filter(m, op->d_filt, fl, nf, nl, ld));
     }
     NLG_HIP(hipGetLastError());
     // rotate velocity history: new -> current, current -> lag1, lag1 -> lag2
@@ -2133,6 +2146,8 @@ int nlg_exptA_config_default(nlg_exptA_config *c) {
     c->rhocp = 1.0;
     c->pproj = 1;   // residualProj = yes for the pressure, as in the reference's cylinder case (1cyl.par:23)
     c->no_history = 0;
+    c->filter_weight = 0.0;
+    c->filter_modes = 0;
     return 0;
 }
 
@@ -2143,9 +2158,23 @@ int nlg_linop_create(nlg_mesh *mesh, const nlg_exptA_config *cfg, const nlg_vec 
     NLG_CHECK(cfg->tau > 0.0 && cfg->re > 0.0, "nlg_linop_create: tau and re must be positive");
     NLG_CHECK(!cfg->ifheat || (baseflow->nscal >= 1 && cfg->conductivity > 0.0 && cfg->rhocp > 0.0),
               "nlg_linop_create: ifheat needs a base flow with its temperature (nscal >= 1) and positive conductivity / rhocp");
+    NLG_CHECK(cfg->filter_weight >= 0.0 && cfg->filter_weight <= 1.0, "nlg_linop_create: filter_weight %g outside [0, 1]", cfg->filter_weight);
+    std::vector<double> filt;
+    if (cfg->filter_weight > 0.0) {
+        NLG_CHECK(cfg->filter_modes >= 1 && cfg->filter_modes <= mesh->n - 2, "nlg_linop_create: filter_modes %d outside [1, lx1 - 2 = %d]",
+                  cfg->filter_modes, mesh->n - 2);
+        NLG_CHECK(sem_filter_available(mesh), "nlg_linop_create: the explicit filter has no kernel for lx1 = %d in %d-D (2-D: 6, 8, 10; 3-D: 6, 8, 10, 12)",
+                  mesh->n, mesh->dim);
+        NLG_TRY(sem_filter_matrix(mesh, cfg->filter_modes, cfg->filter_weight, filt));
+    }
     nlg_linop *op = new nlg_linop();
     op->mesh = mesh;
     op->cfg = *cfg;
+    if (!filt.empty()) {
+        op->filt_fused = !(getenv("NLG_FILTER_FUSED") && atoi(getenv("NLG_FILTER_FUSED")) == 0);
+        NLG_HIP(hipMalloc(&op->d_filt, sizeof(double) * filt.size()));
+        NLG_HIP(hipMemcpy(op->d_filt, filt.data(), sizeof(double) * filt.size(), hipMemcpyHostToDevice));
+    }
     NLG_TRY(nlg_vec_clone(baseflow, &op->baseflow));
     *out = op;
     return 0;
@@ -2158,6 +2187,7 @@ int nlg_linop_destroy(nlg_linop *op) {
         if (p) hipFree(p);
     };
     fr(op->slab);        // every per-lane work buffer (lane_buffers)
+    fr(op->d_filt);
     fr(op->d_red);
     for (int c = 0; c < 3; ++c) {
         fr(op->Ur[c]);
@@ -2534,6 +2564,44 @@ int nlg_op_conv(nlg_mesh *m, const nlg_vec *base, const nlg_vec *in, nlg_vec *ou
     hipStreamSynchronize(m->ctx->stream);
     for (int c = 0; c < dim; ++c) hipFree(Ur[c]);
     for (int q = 0; q < dim * dim; ++q) hipFree(GU[q]);
+    return rc;
+}
+
+// the copies in, the launch and the copies out of nlg_op_filter; its caller owns (and frees) the two buffers whatever this returns
+static int op_filter_run(nlg_mesh *m, int nvec, nlg_vec *const *vecs, const std::vector<double> &filt, double *dF, double *buf) {
+    // the kernel takes lanes as a stride: the fields of the vectors go through one buffer [nvec][ncomp][lvs]
+    const int nc = vecs[0]->ncomp;
+    const int64_t ld = (int64_t)nc * m->lvs;
+    hipStream_t st = m->ctx->stream;
+    NLG_HIP(hipMemcpyAsync(dF, filt.data(), sizeof(double) * filt.size(), hipMemcpyHostToDevice, st));
+    for (int v = 0; v < nvec; ++v)
+        NLG_HIP(hipMemcpyAsync(buf + v * ld, vecs[v]->vel(0), sizeof(double) * (size_t)ld, hipMemcpyDeviceToDevice, st));
+    double *f[4] = {};
+    for (int c = 0; c < nc; ++c) f[c] = buf + (int64_t)c * m->lvs;
+    NLG_TRY(sem_filter(m, dF, f, nc, nvec, ld));
+    for (int v = 0; v < nvec; ++v)
+        NLG_HIP(hipMemcpyAsync(vecs[v]->vel(0), buf + v * ld, sizeof(double) * (size_t)ld, hipMemcpyDeviceToDevice, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int nlg_op_filter(nlg_mesh *m, int nvec, nlg_vec *const *vecs, double filter_weight, int filter_modes) {
+    NLG_CHECK(m && vecs && nvec >= 1 && nvec <= kMaxLanes, "nlg_op_filter: bad arguments");
+    for (int v = 0; v < nvec; ++v)
+        NLG_CHECK(vecs[v] && vecs[v]->mesh == m && vecs[v]->ncomp == vecs[0]->ncomp && vecs[v]->ncomp <= 4, "nlg_op_filter: vector %d NULL, on another mesh or of another shape", v);
+    NLG_CHECK(filter_weight >= 0.0 && filter_weight <= 1.0, "nlg_op_filter: filter_weight %g outside [0, 1]", filter_weight);
+    std::vector<double> filt;
+    NLG_TRY(sem_filter_matrix(m, filter_modes, filter_weight, filt));
+    double *dF = nullptr, *buf = nullptr;
+    int rc = 1;
+    if (hipMalloc(&dF, sizeof(double) * filt.size()) == hipSuccess &&
+        hipMalloc(&buf, sizeof(double) * (size_t)vecs[0]->ncomp * m->lvs * nvec) == hipSuccess)
+        rc = op_filter_run(m, nvec, vecs, filt, dF, buf);
+    else
+        nlg::set_error("nlg_op_filter: out of device memory");
+    if (rc) hipStreamSynchronize(m->ctx->stream);   // nothing in flight may still use the buffers
+    if (dF) hipFree(dF);
+    if (buf) hipFree(buf);
     return rc;
 }
 

@@ -4138,6 +4138,239 @@ int sem_ediag(nlg_mesh *m, double *out) {
     return 0;
 }
 
+// =================================================================================================
+// Explicit modal filter (Nek5000 `filtering = explicit`): u <- (F x F [x F]) u on every element, F dense N x N.
+// Element-local, no gather-scatter.  Rows 0 and N-1 of F are unit vectors, so a face's points are filtered along the face only
+// (F x F of the face's own values; an edge by F, a vertex not at all).  Both neighbours of a face apply the same F to the same face
+// data: C0 continuity survives, and so does every boundary value that is zero (or a polynomial the filter reproduces); other
+// inhomogeneous boundary data of the nonlinear map is smoothed along the boundary like any other face.
+// =================================================================================================
+// F = I + Phi diag(d - 1) Phi^-1 (row-major) with Phi_jk = phi_k(z_j), phi_1 = L_0, phi_2 = L_1, phi_k = L_{k-1} - L_{k-3}, and
+// d_k = 1 - w ((k - k0) / ncut)^2 for k > k0 = n - ncut.  The identity is kept apart from the correction: phi_k(+-1) = 0 for
+// k >= 3 is exact in the recurrence, so the first and the last row of F are unit vectors to the bit.
+int sem_filter_matrix(const nlg_mesh *m, int ncut, double weight, std::vector<double> &F) {
+    const int n = m->n, k0 = n - ncut;
+    NLG_CHECK(ncut >= 1 && ncut <= n - 2, "sem_filter_matrix: %d filtered modes out of range 1..%d", ncut, n - 2);
+    const std::vector<double> &z = m->ops.z1;
+    std::vector<double> Phi((size_t)n * n), A((size_t)n * 2 * n, 0.0);
+    for (int j = 0; j < n; ++j) {
+        std::vector<double> L(n);
+        for (int k = 0; k < n; ++k) {
+            double pk, pkm1;
+            legendre(k, z[j], pk, pkm1);
+            L[k] = pk;
+        }
+        for (int k = 0; k < n; ++k) Phi[(size_t)j * n + k] = k < 2 ? L[k] : L[k] - L[k - 2];
+    }
+    // Phi^-1 by Gauss-Jordan with partial pivoting on [Phi | I]
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < n; ++k) A[(size_t)i * 2 * n + k] = Phi[(size_t)i * n + k];
+        A[(size_t)i * 2 * n + n + i] = 1.0;
+    }
+    for (int c = 0; c < n; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < n; ++r)
+            if (std::fabs(A[(size_t)r * 2 * n + c]) > std::fabs(A[(size_t)piv * 2 * n + c])) piv = r;
+        NLG_CHECK(A[(size_t)piv * 2 * n + c] != 0.0, "sem_filter_matrix: singular modal basis");
+        if (piv != c)
+            for (int k = 0; k < 2 * n; ++k) std::swap(A[(size_t)c * 2 * n + k], A[(size_t)piv * 2 * n + k]);
+        const double ip = 1.0 / A[(size_t)c * 2 * n + c];
+        for (int k = 0; k < 2 * n; ++k) A[(size_t)c * 2 * n + k] *= ip;
+        for (int r = 0; r < n; ++r) {
+            const double f = A[(size_t)r * 2 * n + c];
+            if (r == c || f == 0.0) continue;
+            for (int k = 0; k < 2 * n; ++k) A[(size_t)r * 2 * n + k] -= f * A[(size_t)c * 2 * n + k];
+        }
+    }
+    F.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) {
+        for (int j = 0; j < n; ++j) {
+            double s = 0.0;
+            for (int k = k0; k < n; ++k) {   // 0-based mode k is the issue's k + 1
+                const double a = (double)(k + 1 - k0) / ncut;
+                s += Phi[(size_t)i * n + k] * (-weight * a * a) * A[(size_t)k * 2 * n + n + j];
+            }
+            F[(size_t)i * n + j] = s;
+        }
+        F[(size_t)i * n + i] += 1.0;
+    }
+    return 0;
+}
+
+// Optional velocity correction riding in the load of the first `nu` fields: u_c = f_c + s * wt_c * x_c, x in the natural layout or
+// (slot != null) in an element-local permutation -- what k_axpy_w of the time stepper does in a pass of its own.
+struct FilterUpd {
+    CF3 x, wt;
+    double s;
+    const int *slot;
+    int nu;
+};
+
+// 3-D: one block per (element, lane, field), N x N threads.  Thread (i, j) loads its k-column (coalesced slabs), contracts along k
+// in registers against F read from LDS (uniform addresses), then the tile goes through LDS once per remaining direction with the
+// thread's rows F[i][:] and F[j][:] in registers.  Rows are padded to N + 1 like the slabs of k_axhelm3r.
+// Bytes per point and field: 8 in + 8 out (UPD: + 8 weight + 8 increment + 4 slot).  Flops: 6 N per point.
+template <int N, bool UPD>
+__global__ __launch_bounds__(((N * N + 63) / 64) * 64) void k_filter3(const double *__restrict__ Fg, P4 f, int64_t ld, FilterUpd U) {
+    constexpr int NS = N * N, NP = N * N * N, NQ = N + 1;
+    __shared__ double sF[NS];
+    __shared__ double sT[N * N * NQ];
+    const int t = threadIdx.x;
+    const bool act = t < NS;
+    const int i = act ? t % N : 0, j = act ? t / N : 0;
+    const int c = blockIdx.z;
+    const int64_t e = blockIdx.x;
+    const int64_t lo = (int64_t)blockIdx.y * ld, base = e * NP;
+    double *__restrict__ fp = f.p[c] + lo + base;
+    for (int q = t; q < NS; q += blockDim.x) sF[q] = Fg[q];
+    double u[N], v[N], Fi[N], Fj[N];
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) u[k] = fp[k * NS + t];
+        if (UPD) {
+            if (c < U.nu) {
+                const double *__restrict__ xp = U.x.p[c] + lo + base;
+                const double *__restrict__ wp = U.wt.p[c] + base;
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+                    const int q = U.slot ? U.slot[k * NS + t] : k * NS + t;
+                    u[k] += U.s * (wp[k * NS + t] * xp[q]);
+                }
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < N; ++l) {
+            Fi[l] = Fg[i * N + l];
+            Fj[l] = Fg[j * N + l];
+        }
+    }
+    __syncthreads();
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            double s = 0.0;
+#pragma unroll
+            for (int l = 0; l < N; ++l) s += sF[k * N + l] * u[l];
+            sT[(k * N + j) * NQ + i] = s;
+        }
+    }
+    __syncthreads();
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            double s = 0.0;
+#pragma unroll
+            for (int l = 0; l < N; ++l) s += Fi[l] * sT[(k * N + j) * NQ + l];
+            v[k] = s;
+        }
+    }
+    __syncthreads();
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) sT[(k * N + j) * NQ + i] = v[k];
+    }
+    __syncthreads();
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            double s = 0.0;
+#pragma unroll
+            for (int l = 0; l < N; ++l) s += Fj[l] * sT[(k * N + l) * NQ + i];
+            fp[k * NS + t] = s;
+        }
+    }
+}
+
+// 2-D: one thread per point, the tile goes through LDS once per direction
+template <int N, bool UPD>
+__global__ __launch_bounds__(((N * N + 63) / 64) * 64) void k_filter2(const double *__restrict__ Fg, P4 f, int64_t ld, FilterUpd U) {
+    constexpr int NS = N * N, NQ = N + 1;
+    __shared__ double sT[N * NQ];
+    const int t = threadIdx.x;
+    const bool act = t < NS;
+    const int i = act ? t % N : 0, j = act ? t / N : 0;
+    const int c = blockIdx.z;
+    const int64_t lo = (int64_t)blockIdx.y * ld, base = (int64_t)blockIdx.x * NS;
+    double *__restrict__ fp = f.p[c] + lo + base;
+    double u = 0.0, Fi[N], Fj[N];
+    if (act) {
+        u = fp[t];
+        if (UPD) {
+            if (c < U.nu) u += U.s * (U.wt.p[c][base + t] * U.x.p[c][lo + base + (U.slot ? U.slot[t] : t)]);
+        }
+#pragma unroll
+        for (int l = 0; l < N; ++l) {
+            Fi[l] = Fg[i * N + l];
+            Fj[l] = Fg[j * N + l];
+        }
+        sT[j * NQ + i] = u;
+    }
+    __syncthreads();
+    double s = 0.0;
+    if (act) {
+#pragma unroll
+        for (int l = 0; l < N; ++l) s += Fi[l] * sT[j * NQ + l];
+    }
+    __syncthreads();
+    if (act) sT[j * NQ + i] = s;
+    __syncthreads();
+    if (act) {
+        s = 0.0;
+#pragma unroll
+        for (int l = 0; l < N; ++l) s += Fj[l] * sT[l * NQ + i];
+        fp[t] = s;
+    }
+}
+
+// one block per (element, lane, field): the grid is exactly E x nl x nf, the kernels need no guard
+template <int N, bool UPD>
+static int filter_launch(nlg_mesh *m, const double *F, const P4 &f, int nf, int nl, int64_t ld, const FilterUpd &U) {
+    const dim3 grid((unsigned)m->E, (unsigned)nl, (unsigned)nf), block(((N * N + 63) / 64) * 64);
+    if (m->dim == 3) {
+        NLG_LAUNCH((k_filter3<N, UPD>), grid, block, 0, m->ctx->stream, F, f, ld, U);
+    } else if constexpr (N <= 10) {
+        NLG_LAUNCH((k_filter2<N, UPD>), grid, block, 0, m->ctx->stream, F, f, ld, U);
+    } else {
+        NLG_CHECK(false, "sem_filter: no 2-D kernel for lx1 = %d", N);
+    }
+    return 0;
+}
+
+bool sem_filter_available(const nlg_mesh *m) { return m->n == 6 || m->n == 8 || m->n == 10 || (m->n == 12 && m->dim == 3); }
+
+// fields[0 .. nf-1] <- (F x F [x F]) fields, nf <= 4, all fields and lanes in one launch.  upd_x != null: the first m->dim fields
+// are corrected on the way in, field_c += upd_s * upd_wt_c * upd_x_c (x per lane at ld, read through `slot` when given).
+int sem_filter(nlg_mesh *m, const double *F, double *const *fields, int nf, int nl, int64_t ld, double *const *upd_x, double *const *upd_wt,
+               double upd_s, const int *slot) {
+    NLG_CHECK(F && fields && nf >= 1 && nf <= 4 && nl >= 1 && nl <= kMaxLanes, "sem_filter: bad arguments (%d fields, %d lanes)", nf, nl);
+    NLG_CHECK(sem_filter_available(m), "sem_filter: no kernel for lx1 = %d in %d-D (2-D: 6, 8, 10; 3-D: 6, 8, 10, 12)", m->n, m->dim);
+    NLG_CHECK(m->E <= 0x7fffffff, "sem_filter: %lld elements exceed the launch grid", (long long)m->E);
+    ProfScope ps(m->ctx, P_VECOPS);
+    P4 f = {{fields[0], nf > 1 ? fields[1] : nullptr, nf > 2 ? fields[2] : nullptr, nf > 3 ? fields[3] : nullptr}};
+    FilterUpd U = {{{nullptr, nullptr, nullptr}}, {{nullptr, nullptr, nullptr}}, 0.0, nullptr, 0};
+    if (upd_x) {
+        NLG_CHECK(upd_wt && nf >= m->dim, "sem_filter: the fused update needs its weights and the %d velocity fields", m->dim);
+        for (int c = 0; c < m->dim; ++c) U.x.p[c] = upd_x[c], U.wt.p[c] = upd_wt[c];
+        U.s = upd_s, U.slot = slot, U.nu = m->dim;
+    }
+#define NLG_FILTER_CASE(N_)                                              \
+    case N_:                                                             \
+        if (upd_x)                                                       \
+            NLG_TRY((filter_launch<N_, true>(m, F, f, nf, nl, ld, U)));  \
+        else                                                             \
+            NLG_TRY((filter_launch<N_, false>(m, F, f, nf, nl, ld, U))); \
+        break;
+    switch (m->n) {
+        NLG_FILTER_CASE(6)
+        NLG_FILTER_CASE(8)
+        NLG_FILTER_CASE(10)
+        NLG_FILTER_CASE(12)
+    }
+#undef NLG_FILTER_CASE
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace nlg
 
 // =================================================================================================

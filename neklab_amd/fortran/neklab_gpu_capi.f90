@@ -32,6 +32,8 @@ module neklab_gpu_capi
       integer(c_int) :: ifheat = 0
       real(c_double) :: conductivity = 1.0_c_double, rhocp = 1.0_c_double, buoy(3) = 0.0_c_double
       integer(c_int) :: no_history = 0
+      real(c_double) :: filter_weight = 0.0_c_double   ! Nek5000 `filtering = explicit`: filterWeight, 0 = off
+      integer(c_int) :: filter_modes = 0               ! attenuated modes (from filterCutoffRatio), 1 .. lx1 - 2
    end type
 
    type, bind(C), public :: nlg_eigs_opts

@@ -294,6 +294,15 @@ class KrylovBasis:
             self.h = None
 
 
+def filter_modes_from_cutoff_ratio(lx1: int, ratio: float) -> int:
+    """`filter_modes` (the number of attenuated modes of the explicit filter) from Nek5000's `filterCutoffRatio`, by the rule of its
+    .par reader: max(nint(lx1 (1 - ratio)) - 1, 0) + 1 with nint rounding half away from zero.  At the reference's 0.84
+    (examples/back_fstep/transient_growth/bfs.par:17-19): lx1 = 6, 8 -> 1; 10, 12 -> 2."""
+    x = lx1 * (1.0 - ratio)
+    nint = int(np.floor(abs(x) + 0.5)) * (1 if x >= 0 else -1)
+    return max(nint - 1, 0) + 1
+
+
 class exptA_linop:
     """reference: type exptA_linop (neklab_linops.f90:35-44); constructor idiom `exptA_linop(tau, bf)`
     (examples/cylinder/stability/direct/1cyl.usr:20)."""
