@@ -336,6 +336,30 @@ int nlg_linop_project(nlg_linop *op, nlg_vec *v);
  * part from a quarter period) lives on the host: neklab_amd/host.py resolvent_linop. */
 int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, const nlg_vec *f_im, double omega, int adjoint,
                                nlg_vec *vec_out);
+/* Coupled (orbit) mode: the propagator about a base flow that moves in time -- the monodromy operator of a periodic orbit, whose
+ * eigenvalues are its Floquet multipliers (the time stepper under the reference's periodic-orbit Jacobian,
+ * src/systems/periodic_orbit.f90:59-92: setup_linear_solver(solve_baseflow = .true., endtime = period)).
+ * nlg_linop_set_orbit(op, X0, period): X0 (copied) becomes the state the base flow starts every matvec from, tau = period, dt / nsteps
+ *   by the usual rule applied to X0 (cfg.cfl_limit, or cfg.dt when positive).  From then on a matvec advances, in the same time
+ *   steps and the same kernel launches, the base flow U by the nonlinear step (impulsive start from X0, explicit term
+ *   -1/2 lns_conv(U^n; U^n)) and the 1 .. 3 perturbations by the step linearised about U^n, the level the step starts from (explicit
+ *   term -lns_conv(U^n; u^n)); the fine-mesh factors of U^n are built once per step for all of them.  BDF / EXT order
+ *   min(istep, torder) for every lane; the perturbations replay their restart history as in nlg_linop_matvec, the base flow does
+ *   not; the history steps after the result advance the base flow as well.  With cfg.no_history and a fixed cfg.dt this is the exact
+ *   derivative of the discrete map of nlg_linop_nonlinear_map.  nlg_linop_matvec, nlg_linop_matvec_block (s <= 3), nlg_arnoldi_step,
+ *   nlg_block_arnoldi_step and nlg_eigs work on such an operator unchanged.  Refused with a message that names the mode:
+ *   nlg_linop_rmatvec / transpose (the adjoint of a time-dependent linearisation needs U(T - t); the reference's forward-run adjoint,
+ *   periodic_orbit.f90:117-183, is not reproduced on purpose), cfg.ifheat, the wavenumber projection, nlg_linop_integrate_forced,
+ *   nlg_linop_set_tau, nlg_linop_set_baseflow, nlg_linop_nonlinear_map.  X0 = NULL (period ignored) leaves the mode: the operator is
+ *   the frozen propagator about X0 over tau = period again.
+ * nlg_linop_orbit_end(op, out): the base flow after the nsteps of the last matvec, before the history steps: Phi_T(X0), so that
+ *   |out - X0| tells how well the orbit closes.
+ * nlg_linop_lane_iters: Helmholtz and pressure iterations of one lane in the last matvec (block): of its time step istep (1-based, the
+ *   history steps follow the nsteps), or summed over its steps for istep = 0; in orbit mode the base flow is the lane after the last
+ *   perturbation.  (nlg_linop_get_stats sums over the lanes, the base-flow lane included.) */
+int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period);
+int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out);
+int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_iters, int64_t *p_iters);
 /* %tau read/written by the driver (src/neklab_analysis.f90:84; apply_exptA neklab_linops.f90:252) */
 int nlg_linop_set_tau(nlg_linop *op, double tau);
 int nlg_linop_get_info(const nlg_linop *op, double *tau, double *dt, int *nsteps, double *cfl);

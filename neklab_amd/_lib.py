@@ -131,6 +131,9 @@ SIGNATURES = {
     "nlg_linop_matvec": (C.c_int, [vp, vp, vp]),
     "nlg_linop_rmatvec": (C.c_int, [vp, vp, vp]),
     "nlg_linop_set_tau": (C.c_int, [vp, C.c_double]),
+    "nlg_linop_set_orbit": (C.c_int, [vp, vp, C.c_double]),
+    "nlg_linop_orbit_end": (C.c_int, [vp, vp]),
+    "nlg_linop_lane_iters": (C.c_int, [vp, C.c_int, C.c_int, c_int64_p, c_int64_p]),
     "nlg_linop_get_info": (C.c_int, [vp, c_double_p, c_double_p, c_int_p, c_double_p]),
     "nlg_linop_get_stats": (C.c_int, [vp, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "nlg_op_helmholtz": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int]),

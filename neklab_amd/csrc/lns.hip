@@ -736,6 +736,7 @@ struct Hist {
     const double *u[3][3];
     double ab[3], bd[3];
     int k;
+    int half_lane = -1;   // the lane whose explicit terms enter with a factor 1/2 (coupled mode: the base-flow lane, N(U) = 1/2 lns_conv(U; U))
 };
 // `gp` / `w` non-null: the residual form of the tentative-velocity problem in the same pass, rhs_i += gp_i - w_i (D^T p - H u)
 // XP: the result is written masked and in the slab-permuted layout of the velocity solve (slot = element-local table), so that its
@@ -749,6 +750,9 @@ __global__ __launch_bounds__(NT) void k_rhs(int64_t n, Hist h, const double *bm1
     //  where the runtime index j costs a scalar load, into scratch memory -- measured 123 -> 315 us)
     const int64_t lo = lane_lo(ld);
     rhs = lane_f3(rhs, lo);
+    // (1.0 and 0.5 scale the coefficients exactly: every other lane sums what it summed without the factor, bit for bit, and the
+    //  base-flow lane what the nonlinear step sums with its -1/2 EXT coefficients)
+    const double fs = (int)blockIdx.y == h.half_lane ? 0.5 : 1.0;
     for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
         const double b = bm1[i] * rdt;
         int64_t q = i;
@@ -760,7 +764,7 @@ __global__ __launch_bounds__(NT) void k_rhs(int64_t n, Hist h, const double *bm1
         for (int c = 0; c < NF; ++c) {
             double a = 0.0, u = 0.0;
             for (int j = 0; j < h.k; ++j) {
-                a += h.ab[j] * h.f[j][c][lo + i];
+                a += (fs * h.ab[j]) * h.f[j][c][lo + i];
                 u += h.bd[j] * h.u[j][c][lo + i];
             }
             double v = a + b * u;
@@ -954,6 +958,12 @@ struct nlg_linop {
     bool filt_fused = true;
     double *d_filt = nullptr;  // explicit modal filter (cfg.filter_weight > 0): the dense 1-D matrix F, [n][n]; belongs to the operator, not the mesh
     int nonlinear = 0;         // 1: full Navier-Stokes step, N(u) = (u.grad)u = half of the linearised term about U = u
+    // coupled (orbit) mode, nlg_linop_set_orbit: `baseflow` holds X0, the state the base-flow lane starts every matvec from; that lane
+    // is one more lane of the block step (the last one), advanced by the nonlinear step while the lanes before it are advanced by
+    // the step linearised about its current state.  orbit_end: its state after the nsteps of the last matvec, Phi_T(X0).
+    bool orbit = false, orbit_end_valid = false;
+    nlg_vec *orbit_end = nullptr;
+    int64_t lane_viters[kMaxLanes] = {}, lane_piters[kMaxLanes] = {};   // iterations per lane of the last matvec (block)
     int64_t st_steps = 0, st_viters = 0, st_piters = 0, st_titers = 0, st_matvecs = 0;   // summed over the lanes
 };
 
@@ -1296,6 +1306,7 @@ int run_pcg(nlg_linop *op, const CGProblem &P, Apply apply, int *iters_out) {
 struct Lanes {
     nlg_linop *op;
     int nl;
+    int lb = -1;   // coupled mode: the lane that carries the base flow (nl - 1); -1: the base flow is frozen
     int64_t ld() const { return nl > 1 ? op->slab_ld : 0; }   // the lane stride the kernels receive
 };
 
@@ -1403,6 +1414,7 @@ int helm_solve(const Lanes &L, int order, double h2) {
     // (slab-permuted solve: the increment stays in that layout, adv_b reads it through the slot table)
     for (int v = 0; v < L.nl; ++v) {
         op->st_viters += iters[v];
+        op->lane_viters[v] += iters[v];
         op->pred[v].v.record(op->istep, iters[v]);
     }
     return 0;
@@ -1664,6 +1676,7 @@ int pres_finish(const Lanes &L, const PresSolve &Q, const int *iters) {
     const int64_t ld = L.ld();
     for (int v = 0; v < nl; ++v) {
         op->st_piters += iters[v];
+        op->lane_piters[v] += iters[v];
         op->pred[v].p.record(op->istep, iters[v]);
     }
     if (Q.proj) {
@@ -1741,6 +1754,9 @@ int adv_a(const Lanes &L) {
     if (op->nonlinear) {   // the "base flow" is the current state (velocity, and temperature when coupled); one lane only
         NLG_TRY(sem_conv_setup(m, op->ubuf[0], op->Ur, op->GU));
         if (op->cfg.ifheat) NLG_TRY(sem_conv_scalar_setup(m, op->tbuf[0], op->GT));
+    } else if (L.lb >= 0) {
+        // coupled mode: the fine-mesh factors of the base-flow lane's velocity at the level this step starts from, once for all lanes
+        NLG_TRY(sem_conv_setup(m, at_lane3(op, op->ubuf[0], L.lb).p, op->Ur, op->GU));
     }
     if (op->cfg.ifheat) NLG_TRY(heat_step(L, k, b0));   // scalar first: the fluid sees the new temperature (Nek5000's order)
     // F = -N(u): written into the oldest forcing buffer, then the buffers rotate
@@ -1768,6 +1784,7 @@ int adv_a(const Lanes &L) {
     rotate3(op->fbuf);
     Hist h;
     h.k = k;
+    h.half_lane = L.lb;   // the base-flow lane's own term -1/2 lns_conv(U; U): a coefficient of the history sum, not a pass
     for (int j = 0; j < 3; ++j) {
         h.ab[j] = -(op->nonlinear ? 0.5 : 1.0) * EXT_C[k][j];   // F = -N ; nonlinear: (u.grad)u = 1/2 [(U.grad)u + (u.grad)U] at U = u
         h.bd[j] = BDF_C[k][j];
@@ -1997,6 +2014,11 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     NLG_CHECK(op && vin && vout, "exptA block matvec: NULL argument");
     NLG_CHECK(s >= 1 && s <= kMaxLanes, "exptA block matvec: %d vectors unsupported (1..%d)", s, kMaxLanes);
     NLG_CHECK(op->inited, "exptA block matvec: nlg_linop_init has not been called");
+    if (op->orbit) {
+        NLG_CHECK(s <= kMaxLanes - 1, "exptA block matvec: orbit mode advances the base flow as one of the %d lanes, %d vectors unsupported (1..%d)",
+                  kMaxLanes, s, kMaxLanes - 1);
+        NLG_CHECK(!adjoint, "exptA rmatvec: orbit mode has no adjoint (the adjoint of a time-dependent linearisation needs U(T - t); nlg_linop_set_orbit)");
+    }
     nlg_mesh *m = op->mesh;
     const int want_scal = op->cfg.ifheat ? 1 : 0;
     for (int v = 0; v < s; ++v) {
@@ -2008,9 +2030,13 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
         for (int u = 0; u < v; ++u) NLG_CHECK(vout[v] != vout[u], "exptA block matvec: the same output vector twice");
     }
     const int nrst = op->cfg.no_history ? 0 : op->cfg.torder - 1;   // no_history: impulsive start, no history steps (include/neklab_gpu.h)
-    NLG_TRY(reset_state(op, s));
+    // coupled (orbit) mode: lane s carries the base flow, from X0 (impulsive start, no history: periodic_orbit.f90:59-92 with
+    // solve_baseflow = .true.) through the same time steps and the same launches as the s perturbation lanes before it
+    const int nl = op->orbit ? s + 1 : s, lb = op->orbit ? s : -1;
+    NLG_TRY(reset_state(op, nl));
     op->istep = 0;
     op->adjoint = adjoint;
+    for (int v = 0; v < kMaxLanes; ++v) op->lane_viters[v] = op->lane_piters[v] = 0;
     // the projection space belongs to one matvec: the result must not depend on earlier calls.  (Keeping it across matvecs, as a
     // Nek5000 run does across time steps, was measured in round 4: 11.76 -> 11.40 pressure iterations per time step over 844 matvecs
     // of a real Arnoldi / Krylov-Schur run -- successive Krylov vectors are orthogonal, their pressure increments share little --
@@ -2020,7 +2046,11 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
         NLG_TRY(load_state(op, v, vin[v], 0));
         NLG_TRY(project_alpha(op, v, 0));   // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
     }
-    const Lanes L{op, s};
+    if (lb >= 0) {
+        op->orbit_end_valid = false;
+        NLG_TRY(load_state(op, lb, op->baseflow, 0));
+    }
+    const Lanes L{op, nl, lb};
     for (int istep = 1; istep <= op->nsteps; ++istep) {
         NLG_TRY(advance(L));
         if (istep <= nrst)
@@ -2040,6 +2070,11 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
         // vec_out is intent(out): default-initialised (history cleared, nrst = 0), then filled
         NLG_TRY(nlg_vec_zero(vout[v]));
         NLG_TRY(store_state(op, v, vout[v], 0));
+    }
+    if (lb >= 0) {   // Phi_T(X0), before the history steps (which advance the base flow as well, periodic_orbit.f90:185-213)
+        NLG_TRY(nlg_vec_zero(op->orbit_end));
+        NLG_TRY(store_state(op, lb, op->orbit_end, 0));
+        op->orbit_end_valid = true;
     }
     for (int irst = 1; irst <= nrst; ++irst) {   // compute_rst, :109-127
         NLG_TRY(advance(L));
@@ -2072,6 +2107,7 @@ int do_matvec(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout, int adjoint) {
 int do_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, const nlg_vec *f_im, double omega, int adjoint, nlg_vec *vout) {
     NLG_CHECK(op && f_re && vout, "integrate_forced: NULL argument");
     NLG_CHECK(op->inited, "integrate_forced: nlg_linop_init has not been called");
+    NLG_CHECK(!op->orbit, "integrate_forced: not available in orbit mode (the forced response about a time-periodic base flow is not built; nlg_linop_set_orbit)");
     nlg_mesh *m = op->mesh;
     NLG_CHECK(f_re->mesh == m && vout->mesh == m && (!ic || ic->mesh == m) && (!f_im || f_im->mesh == m), "integrate_forced: vector on a different mesh");
     NLG_CHECK(vout != f_re && vout != f_im && vout != ic, "integrate_forced: the output must be distinct from the inputs");
@@ -2105,6 +2141,7 @@ int do_nonlinear_map(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout) {
     NLG_CHECK(vin->nscal == (op->cfg.ifheat ? 1 : 0) && vout->nscal == vin->nscal,
               "nonlinear_map: the vectors carry %d scalar(s), the operator expects %d (cfg.ifheat)", vin->nscal, op->cfg.ifheat ? 1 : 0);
     NLG_CHECK(vin != vout, "nonlinear_map: vec_in and vec_out must be distinct");
+    NLG_CHECK(!op->orbit, "nonlinear_map: the operator is in orbit mode and holds X0 as its base flow (use a second operator, or nlg_linop_set_orbit(op, NULL, 0))");
     hipStream_t st = m->ctx->stream;
     // "setup_nonlinear_solver(recompute_dt = .true.)": the time step follows the state that is integrated
     NLG_TRY(nlg_vec_copy(op->baseflow, vin));
@@ -2218,6 +2255,7 @@ int nlg_linop_destroy(nlg_linop *op) {
     fr(op->nwp);
     if (op->h_s) hipHostFree(op->h_s);
     if (op->baseflow) nlg_vec_destroy(op->baseflow);
+    if (op->orbit_end) nlg_vec_destroy(op->orbit_end);
     delete op;
     return 0;
 }
@@ -2378,6 +2416,7 @@ int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *
 
 int nlg_linop_set_baseflow(nlg_linop *op, const nlg_vec *baseflow) {
     NLG_CHECK(op && baseflow && baseflow->mesh == op->mesh, "nlg_linop_set_baseflow: bad argument");
+    NLG_CHECK(!op->orbit, "nlg_linop_set_baseflow: the operator is in orbit mode; nlg_linop_set_orbit replaces X0");
     NLG_TRY(nlg_vec_copy(op->baseflow, baseflow));
     return nlg_linop_init(op);
 }
@@ -2388,6 +2427,7 @@ int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_
     nlg_mesh *m = op->mesh;
     NLG_CHECK(idir >= 1 && idir <= m->dim, "nlg_linop_set_projection: idir %d out of range", idir);
     NLG_CHECK(op->inited, "nlg_linop_set_projection: call init first");
+    NLG_CHECK(!op->orbit, "nlg_linop_set_projection: not available in orbit mode (the base-flow lane is a full state, not one wavenumber; nlg_linop_set_orbit)");
     NLG_CHECK((line_label2 == nullptr) == (x2 == nullptr), "nlg_linop_set_projection: pressure-mesh labels and coordinates go together");
     hipStream_t st = m->ctx->stream;
     int64_t proj_glob_cap = 0;
@@ -2525,10 +2565,63 @@ int nlg_linop_set_tolerances(nlg_linop *op, double vtol, double ptol) {
 
 int nlg_linop_set_tau(nlg_linop *op, double tau) {
     NLG_CHECK(op && tau > 0.0, "nlg_linop_set_tau: bad argument");
+    NLG_CHECK(!op->orbit || tau == op->cfg.tau, "nlg_linop_set_tau: in orbit mode tau is the period; set it with nlg_linop_set_orbit");
     if (tau != op->cfg.tau) {
         op->cfg.tau = tau;
         if (op->inited) return nlg_linop_init(op);
     }
+    return 0;
+}
+
+// Coupled (orbit) mode, see do_matvec_block.  X0 becomes the operator's base flow (dt / nsteps by the usual rule applied to it, the
+// preconditioners for that dt); the fine-mesh factors of the convective term are rebuilt every step from the base-flow lane, and from
+// X0 again when the mode is left.
+int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period) {
+    NLG_CHECK(op, "nlg_linop_set_orbit: NULL operator");
+    if (!X0) {
+        if (!op->orbit) return 0;
+        op->orbit = false;
+        op->orbit_end_valid = false;
+        return op->inited ? nlg_linop_init(op) : 0;   // the frozen operator about X0 with tau = period
+    }
+    NLG_CHECK(X0->mesh == op->mesh, "nlg_linop_set_orbit: X0 lives on a different mesh");
+    NLG_CHECK(period > 0.0, "nlg_linop_set_orbit: the period must be positive");
+    NLG_CHECK(!op->cfg.ifheat, "nlg_linop_set_orbit: orbit mode does not carry the temperature (cfg.ifheat); not built");
+    NLG_CHECK(op->proj_nlines == 0, "nlg_linop_set_orbit: orbit mode and the wavenumber projection exclude each other");
+    NLG_TRY(nlg_vec_copy(op->baseflow, X0));
+    if (!op->orbit_end) NLG_TRY(nlg_vec_clone(op->baseflow, &op->orbit_end));
+    op->orbit_end_valid = false;
+    op->cfg.tau = period;
+    op->orbit = true;
+    return nlg_linop_init(op);
+}
+
+int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out) {
+    NLG_CHECK(op && out && out->mesh == op->mesh, "nlg_linop_orbit_end: bad argument");
+    NLG_CHECK(op->orbit, "nlg_linop_orbit_end: the operator is not in orbit mode (nlg_linop_set_orbit)");
+    NLG_CHECK(op->orbit_end_valid, "nlg_linop_orbit_end: no matvec in orbit mode yet");
+    NLG_CHECK(out->nscal == 0, "nlg_linop_orbit_end: orbit mode carries no scalars");
+    NLG_TRY(nlg_vec_zero(out));
+    nlg_mesh *m = op->mesh;
+    hipStream_t st = m->ctx->stream;
+    for (int c = 0; c < m->dim; ++c)
+        NLG_HIP(hipMemcpyAsync(out->vel(c), op->orbit_end->vel(c), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
+    NLG_HIP(hipMemcpyAsync(out->pr(), op->orbit_end->pr(), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_iters, int64_t *p_iters) {
+    NLG_CHECK(op && lane >= 0 && lane < kMaxLanes && istep >= 0, "nlg_linop_lane_iters: bad argument");
+    if (istep == 0) {
+        if (v_iters) *v_iters = op->lane_viters[lane];
+        if (p_iters) *p_iters = op->lane_piters[lane];
+        return 0;
+    }
+    // (the per-step counts are the ones the iteration predictor keeps from the last matvec)
+    const LanePred &lp = op->pred[lane];
+    NLG_CHECK(istep < (int)lp.v.hist.size() && istep < (int)lp.p.hist.size(), "nlg_linop_lane_iters: lane %d has not run a time step %d", lane, istep);
+    if (v_iters) *v_iters = lp.v.hist[istep];
+    if (p_iters) *p_iters = lp.p.hist[istep];
     return 0;
 }
 

@@ -259,6 +259,17 @@ module neklab_gpu_capi
          real(c_double), value :: tau
          integer(c_int) :: rc
       end function
+      function c_linop_set_orbit(op, X0, period) bind(C, name="nlg_linop_set_orbit") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: op, X0
+         real(c_double), value :: period
+         integer(c_int) :: rc
+      end function
+      function c_linop_orbit_end(op, vout) bind(C, name="nlg_linop_orbit_end") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: op, vout
+         integer(c_int) :: rc
+      end function
       function c_linop_matvec(op, vin, vout) bind(C, name="nlg_linop_matvec") result(rc)
          import c_int, c_ptr
          type(c_ptr), value :: op, vin, vout

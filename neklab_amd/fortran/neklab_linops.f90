@@ -76,6 +76,17 @@ module neklab_linops
       procedure, pass(self), public :: proj => proj_apply
    end type exptA_proj_linop
 
+   !> exptA_orbit_linop(T, X0): the propagator over one period T about the time-periodic base flow through X0 (held in `baseflow`),
+   !! the time stepper under the reference's periodic-orbit Jacobian (src/systems/periodic_orbit.f90:59-92: the nonlinear equations
+   !! and the perturbation integrated together, cfl_limit = 0.4).  Its eigenvalues are the Floquet multipliers of the orbit.  The
+   !! base flow rides as one more lane of the perturbation's kernel launches (nlg_linop_set_orbit).  No adjoint: rmatvec stops.
+   type, extends(exptA_linop), public :: exptA_orbit_linop
+   contains
+      procedure, pass(self), public :: init => init_exptA_orbit
+      procedure, pass(self), public :: rmatvec => exptA_orbit_rmatvec
+      procedure, pass(self), public :: orbit_end => exptA_orbit_end
+   end type exptA_orbit_linop
+
    !--------------------------------------
    !-----     RESOLVENT OPERATOR     -----
    !--------------------------------------
@@ -134,6 +145,43 @@ contains
       end if
       self%cfg_set = .true.
       call init_exptA(self)
+   end subroutine
+
+   subroutine init_exptA_orbit(self)
+      class(exptA_orbit_linop), intent(inout) :: self
+      if (.not. self%cfg_set) then
+         self%cfg = nek_case
+         self%cfg%cfl_limit = 0.4_dp                ! periodic_orbit.f90:73
+         self%cfg_set = .true.
+      end if
+      call init_exptA(self)
+      call nlg_check(c_linop_set_orbit(exptA_handle(self), nek_dvector_handle(self%baseflow), self%tau), 'init_exptA_orbit')
+   end subroutine
+
+   !> the adjoint of a time-dependent linearisation needs U(T - t); the reference's forward-run adjoint (periodic_orbit.f90:117-183)
+   !! is not reproduced on purpose.  The library refuses with its own message; this stops with it.
+   subroutine exptA_orbit_rmatvec(self, vec_in, vec_out)
+      class(exptA_orbit_linop), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      select type (vec_in)
+      type is (nek_dvector)
+         select type (vec_out)
+         type is (nek_dvector)
+            call nek_dvector_ensure(vec_out)
+            call nlg_check(c_linop_rmatvec(exptA_handle(self), nek_dvector_handle(vec_in), vec_out%h), 'exptA_orbit_rmatvec')
+         end select
+      end select
+      write (*, '(A)') 'ERROR in '//this_module//': exptA_orbit_linop has no adjoint (orbit mode)'
+      error stop 1
+   end subroutine
+
+   !> Phi_T(X0): the base flow after the time steps of the last matvec (how well the orbit closes)
+   subroutine exptA_orbit_end(self, vec_out)
+      class(exptA_orbit_linop), intent(in) :: self
+      type(nek_dvector), intent(inout) :: vec_out
+      call nek_dvector_ensure(vec_out)
+      call nlg_check(c_linop_orbit_end(exptA_handle(self), vec_out%h), 'exptA_orbit_end')
    end subroutine
 
    subroutine sync_tau(self, where)

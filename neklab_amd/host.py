@@ -369,6 +369,39 @@ class exptA_linop:
             self.h = None
 
 
+class exptA_orbit_linop(exptA_linop):
+    """Propagator over one period about a time-periodic base flow: the monodromy operator of the orbit through `X0`, whose
+    eigenvalues are the Floquet multipliers (the time stepper under the reference's periodic-orbit Jacobian,
+    src/systems/periodic_orbit.f90:59-92).  A matvec advances the base flow (nonlinear step, from X0) and 1 to 3 perturbations
+    (step linearised about the base flow's current state) in the same time steps and the same kernel launches
+    (nlg_linop_set_orbit).  cfl_limit defaults to 0.4, as in the reference's call.  No adjoint: rmatvec raises."""
+
+    def __init__(self, period: float, X0: nek_dvector, **cfg):
+        cfg.setdefault("cfl_limit", 0.4)
+        super().__init__(period, X0, **cfg)
+        self.period, self.X0 = float(period), X0
+        check(self.lib.nlg_linop_set_orbit(self.h, X0.h, self.period))     # (includes init)
+
+    def orbit_end(self, out: nek_dvector | None = None) -> nek_dvector:
+        """Phi_T(X0): the base flow after the time steps of the last matvec."""
+        out = out if out is not None else nek_dvector(self.mesh, 0, self.X0.lorder)
+        check(self.lib.nlg_linop_orbit_end(self.h, out.h))
+        return out
+
+    def closure(self) -> float:
+        """|Phi_T(X0) - X0| / |X0| in the norm of the vector space, from the last matvec."""
+        d = self.orbit_end()
+        d.axpby(-1.0, self.X0, 1.0)
+        return d.norm() / self.X0.norm()
+
+    def lane_iters(self, lane: int, istep: int = 0) -> dict:
+        """Iterations of one lane in the last matvec (block), of time step `istep` (1-based) or summed (0); the base flow is the
+        lane after the last perturbation."""
+        a, b = C.c_int64(), C.c_int64()
+        check(self.lib.nlg_linop_lane_iters(self.h, int(lane), int(istep), C.byref(a), C.byref(b)))
+        return {"v_iters": a.value, "p_iters": b.value}
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Resolvent operator by time stepping (SURVEY.md 8f row 4).  Reference: resolvent_linop (src/linops/neklab_linops.f90:198-205,
 # src/linops/resolvent.f90) acting on nek_zvector = (re, im) pairs of nek_dvector (src/vectors/neklab_vectors.f90).
@@ -844,3 +877,23 @@ def linear_stability_analysis_fixed_point(exptA: exptA_linop, kdim: int, nev: in
     if outpost:
         outpost_dnek(eigvecs, prefix, session, outdir)               # :93
     return eigvals, residuals, eigvecs, mu, info
+
+
+def linear_stability_analysis_periodic_orbit(op: exptA_orbit_linop, kdim: int, nev: int, X0: nek_dvector | None = None,
+                                             tol: float = 0.0, outdir: str = ".", seed: int = 0, outpost: bool = False,
+                                             session: str = "neklab", block_size: int = 0, max_restarts: int = 50):
+    """Floquet analysis of the orbit `op` was built about: the device Krylov loop of linear_stability_analysis_fixed_point
+    (nlg_eigs) on the coupled propagator.  Returns (mu, exponents, residuals, eigvecs, info): the Floquet multipliers mu, the
+    Floquet exponents log(mu) / T and the residuals nlg_eigs reports.  block_size <= 3 (the base flow takes one lane)."""
+    mesh = op.mesh
+    eigvecs = [nek_dvector(mesh, 0, 3) for _ in range(nev)]
+    for v in eigvecs:
+        v.zero()
+    mu, residuals, info = eigs(op, eigvecs, kdim=kdim, x0=X0, transpose=False, write_intermediate=True,
+                               logfile=os.path.join(outdir, "eigs_output.txt"), tol=tol, seed=seed, block_size=block_size,
+                               max_restarts=max_restarts)
+    exponents = np.log(mu.astype(complex)) / op.info()["tau"]
+    save_eigenspectrum(exponents, residuals, os.path.join(outdir, "floquet_eigenspectrum.npy"))
+    if outpost:
+        outpost_dnek(eigvecs, "flq", session, outdir)
+    return mu, exponents, residuals, eigvecs, info
