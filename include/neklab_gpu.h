@@ -360,6 +360,36 @@ int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *
 int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period);
 int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out);
 int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_iters, int64_t *p_iters);
+/* Optimally time-dependent (OTD) modes (nek_otd, src/neklab_otd.f90; otd_analysis, src/neklab_analysis.f90:214-344): r <= 4
+ * perturbations u_1 .. u_r, orthonormal in the inner product of the vector space, follow dU/dt = L(t) U - U C with C = Lr - Phi,
+ * Lr_ij = <u_i, L u_j> and Phi skew-symmetric such that C is upper triangular (C_jj = Lr_jj, C_ij = Lr_ij + Lr_ji for i < j): mode j
+ * is forced by the modes i <= j only.  The modes are lanes of the operator's block step; Lr comes from what the step has in memory
+ * anyway (D^T p, (nu A + h2 B) u and the convective term of every lane: one reduction pass), the forcing -bm1 U C joins the explicit
+ * term (extrapolated like the convective term), both without a copy to the host.  Steps before `startstep` are plain block steps.
+ * After every step istep >= startstep with istep <= startstep + 10 or istep % orthostep == 0, and in nlg_otd_reduced, the lanes
+ * are re-orthonormalised with T = chol(G)^-T, G_ij = <u_i, u_j>, applied to every stored level (velocities, pressure, explicit
+ * terms); at creation twice.  DESIGN.md 3.2 "OTD mode"; section 8 lists where this departs from the reference's literal loop.
+ *   create  op is initialised if it is not; dt by its usual rule (cfg.dt, or CFL with cfg.cfl_limit); impulsive start, order
+ *           min(istep, torder).  basis0: r vectors (copied), NULL = nlg_vec_rand with seeds 1 .. r.  solve_baseflow (r <= 3): the
+ *           operator's base flow becomes one more lane, advanced by the nonlinear step as in nlg_linop_set_orbit.  trans: the
+ *           adjoint equations (frozen base flow only).  Refused with a message that names the reason: trans with solve_baseflow,
+ *           cfg.ifheat, a wavenumber projection, an operator in orbit mode, r out of range, a second nlg_otd on the operator.
+ *           While the nlg_otd lives, every matvec, set_*, init, integrate_forced and nonlinear_map call on op is refused, and so is
+ *           nlg_linop_destroy (it returns an error and frees nothing: destroy the nlg_otd first).
+ *   advance a Gram matrix that is not positive definite (dependent or non-finite modes) is an error of the call that met it.
+ *   destroy after a run with solve_baseflow the operator's base-flow set-up is rebuilt from its own base flow: matvecs on op are
+ *           what they were before the run.
+ *   reduced orthonormalise, then evaluate Lr (column-major r x r) on the current state; G = the Gram matrix BEFORE that. */
+typedef struct nlg_otd nlg_otd;
+typedef struct nlg_otd_opts { int r; int startstep; int orthostep; int trans; int solve_baseflow; } nlg_otd_opts;
+int nlg_otd_opts_default(nlg_otd_opts *o);                 /* r = 2, startstep = 1, orthostep = 10, trans = 0, solve_baseflow = 0 */
+int nlg_otd_create(nlg_linop *op, const nlg_otd_opts *o, const nlg_vec *const *basis0, nlg_otd **out);
+int nlg_otd_advance(nlg_otd *otd, int nsteps);
+int nlg_otd_reduced(nlg_otd *otd, double *Lr, double *G);
+int nlg_otd_get_basis(nlg_otd *otd, int i, nlg_vec *out);   /* i 0-based */
+int nlg_otd_get_baseflow(nlg_otd *otd, nlg_vec *out);       /* its current state (the operator's base flow when it is frozen) */
+int nlg_otd_info(const nlg_otd *otd, int64_t *istep, double *time, double *dt);
+int nlg_otd_destroy(nlg_otd *otd);
 /* %tau read/written by the driver (src/neklab_analysis.f90:84; apply_exptA neklab_linops.f90:252) */
 int nlg_linop_set_tau(nlg_linop *op, double tau);
 int nlg_linop_get_info(const nlg_linop *op, double *tau, double *dt, int *nsteps, double *cfl);

@@ -49,6 +49,10 @@ class EigsOpts(C.Structure):
     ]
 
 
+class OtdOpts(C.Structure):
+    _fields_ = [("r", C.c_int), ("startstep", C.c_int), ("orthostep", C.c_int), ("trans", C.c_int), ("solve_baseflow", C.c_int)]
+
+
 # every symbol include/neklab_gpu.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "nlg_last_error": (C.c_char_p, []),
@@ -134,6 +138,14 @@ SIGNATURES = {
     "nlg_linop_set_orbit": (C.c_int, [vp, vp, C.c_double]),
     "nlg_linop_orbit_end": (C.c_int, [vp, vp]),
     "nlg_linop_lane_iters": (C.c_int, [vp, C.c_int, C.c_int, c_int64_p, c_int64_p]),
+    "nlg_otd_opts_default": (C.c_int, [C.POINTER(OtdOpts)]),
+    "nlg_otd_create": (C.c_int, [vp, C.POINTER(OtdOpts), C.POINTER(vp), C.POINTER(vp)]),
+    "nlg_otd_advance": (C.c_int, [vp, C.c_int]),
+    "nlg_otd_reduced": (C.c_int, [vp, c_double_p, c_double_p]),
+    "nlg_otd_get_basis": (C.c_int, [vp, C.c_int, vp]),
+    "nlg_otd_get_baseflow": (C.c_int, [vp, vp]),
+    "nlg_otd_info": (C.c_int, [vp, c_int64_p, c_double_p, c_double_p]),
+    "nlg_otd_destroy": (C.c_int, [vp]),
     "nlg_linop_get_info": (C.c_int, [vp, c_double_p, c_double_p, c_int_p, c_double_p]),
     "nlg_linop_get_stats": (C.c_int, [vp, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "nlg_op_helmholtz": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int]),

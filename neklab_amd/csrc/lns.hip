@@ -705,6 +705,168 @@ __global__ __launch_bounds__(NT) void k_add_force(int64_t n, F3 F, const double 
     }
 }
 
+// ---- optimally time-dependent modes (nlg_otd_*): R <= 4 lanes of the slab, lane v at v * ld behind the lane-0 pointers ----
+// device block of an nlg_otd: the reduced sums S and G (what the all-reduce carries), then Lr, C, T, the Gram matrix the last
+// transform was made from, and a flag (non-zero: that matrix was not positive definite); all R x R column-major, 16 doubles each
+enum { OTD_S = 0, OTD_G = 16, OTD_LR = 32, OTD_C = 48, OTD_T = 64, OTD_G0 = 80, OTD_FLAG = 96, OTD_N = 128 };
+
+// First stage of the 2 R^2 sums  S_ij = sum_c sum u_i,c (gp_j,c - w_j,c - N_j,c)  and  G_ij = sum_c sum bm1 u_i,c u_j,c  (WITH_S =
+// false: G only): every field is read once for all (i, j); partial[q * NB + block], q = i + R j (S), R^2 + i + R j (G).  Fixed grid
+// and fixed summation order, no atomics.
+template <int DIM, int R, bool WITH_S>
+__global__ __launch_bounds__(NT) void k_otd_reduce(int64_t n, CF3 u, CF3 gp, CF3 w, CF3 N, const double *__restrict__ bm1, int64_t ld,
+                                                   double *__restrict__ partial) {
+    __shared__ double sm[2 * R * R][NT / 64];
+    double S[R * R], G[R * R];
+#pragma unroll
+    for (int q = 0; q < R * R; ++q) S[q] = G[q] = 0.0;
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
+        const double b = bm1[i];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            double uv[R], Wv[R];
+#pragma unroll
+            for (int v = 0; v < R; ++v) {
+                const int64_t q = v * ld + i;
+                uv[v] = u.p[c][q];
+                Wv[v] = WITH_S ? (gp.p[c][q] - w.p[c][q]) - N.p[c][q] : 0.0;
+            }
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const double bu = b * uv[j];
+#pragma unroll
+                for (int a = 0; a < R; ++a) {
+                    if (WITH_S) S[a + R * j] += uv[a] * Wv[j];
+                    if (a <= j) G[a + R * j] += uv[a] * bu;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+#pragma unroll
+        for (int a = j + 1; a < R; ++a) G[a + R * j] = G[j + R * a];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < R * R; ++q) {
+        const double s = wave_sum(S[q]), g = wave_sum(G[q]);
+        if (lane == 0) {
+            sm[q][wid] = s;
+            sm[R * R + q][wid] = g;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * R * R) {
+        double t = 0.0;
+        for (int k = 0; k < NT / 64; ++k) t += sm[threadIdx.x][k];
+        partial[threadIdx.x * NB + blockIdx.x] = t;
+    }
+}
+// second stage: block q sums its row of first-stage sums; out[q] for q < R^2, out[OTD_G + q - R^2] above
+__global__ __launch_bounds__(NT) void k_otd_reduce2(const double *__restrict__ partial, int nblk, int rr, double *__restrict__ out) {
+    static_assert(NT == 256, "the pairwise sum of the four wave sums below is written out for 256 threads");
+    __shared__ double sm[NT / 64];
+    const int q = blockIdx.x;
+    double t = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += NT) t += partial[q * NB + i];
+    t = wave_sum(t);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) out[q < rr ? OTD_S + q : OTD_G + (q - rr)] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+// Lr = S + h2 G (the w of the time step carries h2 B u) and the upper-triangular C = Lr - Phi of the forcing, Phi skew:
+// C_jj = Lr_jj, C_ij = Lr_ij + Lr_ji (i < j), 0 below the diagonal.  One thread.
+__global__ void k_otd_coef(double *d, int r, double h2) {
+    for (int j = 0; j < r; ++j)
+        for (int i = 0; i < r; ++i) d[OTD_LR + i + r * j] = d[OTD_S + i + r * j] + h2 * d[OTD_G + i + r * j];
+    for (int j = 0; j < r; ++j)
+        for (int i = 0; i < r; ++i)
+            d[OTD_C + i + r * j] = i == j ? d[OTD_LR + i + r * j] : (i < j ? d[OTD_LR + i + r * j] + d[OTD_LR + j + r * i] : 0.0);
+}
+// F_j += bm1 sum_{i <= j} u_i C_ij for all lanes (the stored F is +N and enters the right-hand side with -EXT: this is -bm1 U C)
+template <int DIM, int R>
+__global__ __launch_bounds__(NT) void k_otd_force(int64_t n, F3 F, CF3 u, const double *__restrict__ bm1, const double *__restrict__ d, int64_t ld) {
+    double C[R * R];
+#pragma unroll
+    for (int q = 0; q < R * R; ++q) C[q] = d[OTD_C + q];
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
+        const double b = bm1[i];
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            double uv[R];
+#pragma unroll
+            for (int v = 0; v < R; ++v) uv[v] = u.p[c][v * ld + i];
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                double a = 0.0;
+#pragma unroll
+                for (int v = 0; v <= j; ++v) a += uv[v] * C[v + R * j];
+                F.p[c][j * ld + i] += b * a;
+            }
+        }
+    }
+}
+// T = chol(G)^-T, upper triangular (G = L L^T, T = L^-T: the columns of U T are orthonormal, and the leading k x k block of T is the
+// T of the first k modes); G is kept in OTD_G0.  One thread; a pivot that is not positive raises the flag and leaves T = I.
+__global__ void k_otd_chol(double *d, int r) {
+    double L[16], Li[16];
+    bool ok = true;
+    for (int q = 0; q < r * r; ++q) {
+        d[OTD_G0 + q] = d[OTD_G + q];
+        L[q] = Li[q] = 0.0;
+    }
+    for (int j = 0; j < r && ok; ++j) {
+        double s = d[OTD_G + j + r * j];
+        for (int k = 0; k < j; ++k) s -= L[j + r * k] * L[j + r * k];
+        if (!(s > 0.0)) {
+            ok = false;
+            break;
+        }
+        L[j + r * j] = sqrt(s);
+        for (int i = j + 1; i < r; ++i) {
+            double t = d[OTD_G + i + r * j];
+            for (int k = 0; k < j; ++k) t -= L[i + r * k] * L[j + r * k];
+            L[i + r * j] = t / L[j + r * j];
+        }
+    }
+    for (int j = 0; j < r && ok; ++j) {   // column j of L^-1 by forward substitution
+        Li[j + r * j] = 1.0 / L[j + r * j];
+        for (int i = j + 1; i < r; ++i) {
+            double t = 0.0;
+            for (int k = j; k < i; ++k) t -= L[i + r * k] * Li[k + r * j];
+            Li[i + r * j] = t / L[i + r * i];
+        }
+    }
+    if (!ok) d[OTD_FLAG] = 1.0;
+    for (int j = 0; j < r; ++j)
+        for (int i = 0; i < r; ++i) d[OTD_T + i + r * j] = ok ? Li[j + r * i] : (i == j ? 1.0 : 0.0);
+}
+// X <- X T in place for a list of slab levels (blockIdx.y): every point loads its R lane values, combines them and stores them
+struct OtdLevels {
+    double *p[20];
+    int64_t n[20];
+};
+template <int R>
+__global__ __launch_bounds__(NT) void k_otd_transform(OtdLevels lv, const double *__restrict__ d, int64_t ld) {
+    double T[R * R];
+#pragma unroll
+    for (int q = 0; q < R * R; ++q) T[q] = d[OTD_T + q];
+    double *__restrict__ x = lv.p[blockIdx.y];
+    const int64_t n = lv.n[blockIdx.y];
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
+        double xv[R];
+#pragma unroll
+        for (int v = 0; v < R; ++v) xv[v] = x[v * ld + i];
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            double a = 0.0;
+#pragma unroll
+            for (int v = 0; v <= j; ++v) a += xv[v] * T[v + R * j];
+            x[j * ld + i] = a;
+        }
+    }
+}
+
 // F_i -= bm1 * buoy_i * theta : Boussinesq buoyancy in the explicit term (the stored F is +N)
 template <int NF>
 __global__ __launch_bounds__(NT) void k_buoyancy(int64_t n, F3 F, const double *__restrict__ bm1, const double *__restrict__ theta,
@@ -884,8 +1046,11 @@ struct LanePred {
 
 }  // namespace
 
+struct nlg_otd;
+
 struct nlg_linop {
     nlg_mesh *mesh = nullptr;
+    nlg_otd *otd = nullptr;    // an OTD run lives on this operator: the lanes of the slab hold its state (nlg_otd_create)
     nlg_exptA_config cfg;
     nlg_vec *baseflow = nullptr;
     bool inited = false;
@@ -966,6 +1131,18 @@ struct nlg_linop {
     int64_t lane_viters[kMaxLanes] = {}, lane_piters[kMaxLanes] = {};   // iterations per lane of the last matvec (block)
     int64_t st_steps = 0, st_viters = 0, st_piters = 0, st_titers = 0, st_matvecs = 0;   // summed over the lanes
 };
+
+// Optimally time-dependent modes: r lanes of the operator's slab advanced as ONE continuous run (no restart-history protocol), the
+// base flow as lane r when it is solved alongside (coupled mode of the block step).  d: the device block OTD_*; part: first-stage sums.
+struct nlg_otd {
+    nlg_linop *op = nullptr;
+    nlg_otd_opts o;
+    int r = 0, nl = 0, lb = -1;
+    double *d = nullptr, *part = nullptr;
+    double time = 0.0;
+};
+// every entry point that would overwrite the lanes refuses while an OTD run lives on the operator
+#define NLG_NO_OTD(op, who) NLG_CHECK(!(op)->otd, "%s: an nlg_otd lives on this operator and its lanes hold the OTD state; nlg_otd_destroy it first", who)
 
 namespace {
 
@@ -1737,6 +1914,107 @@ int pres_solve(const Lanes &L, double scale) {
     return pres_finish(L, Q, iters);
 }
 
+// ---- OTD modes: the device side of nlg_otd_* ------------------------------------------------------------------------------
+// the 2 r^2 sums of k_otd_reduce over the r OTD lanes (Nf = null: the Gram matrix alone), second stage, ONE all-reduce
+int otd_sums(const nlg_otd *ot, double *const *gp, double *const *w, double *const *Nf) {
+    nlg_linop *op = ot->op;
+    nlg_mesh *m = op->mesh;
+    hipStream_t st = m->ctx->stream;
+    ProfScope ps(m->ctx, P_VECOPS);
+    const int dim = m->dim, r = ot->r, g = red_grid(m->lvn);
+    const CF3 u = cf3(op->ubuf[0], dim), none = {{nullptr, nullptr, nullptr}};
+    const CF3 a = Nf ? cf3(gp, dim) : none, b = Nf ? cf3(w, dim) : none, c = Nf ? cf3(Nf, dim) : none;
+#define OTD_RED(D_, R_)                                                                                                                              \
+    if (Nf)                                                                                                                                          \
+        NLG_LAUNCH((k_otd_reduce<D_, R_, true>), dim3(g), dim3(NT), 0, st, m->lvn, u, a, b, c, (const double *)m->d_bm1, op->slab_ld, ot->part);    \
+    else                                                                                                                                             \
+        NLG_LAUNCH((k_otd_reduce<D_, R_, false>), dim3(g), dim3(NT), 0, st, m->lvn, u, a, b, c, (const double *)m->d_bm1, op->slab_ld, ot->part)
+#define OTD_RED_D(D_)          \
+    if (r == 1) {              \
+        OTD_RED(D_, 1);        \
+    } else if (r == 2) {       \
+        OTD_RED(D_, 2);        \
+    } else if (r == 3) {       \
+        OTD_RED(D_, 3);        \
+    } else {                   \
+        OTD_RED(D_, 4);        \
+    }
+    if (dim == 3) {
+        OTD_RED_D(3)
+    } else {
+        OTD_RED_D(2)
+    }
+#undef OTD_RED_D
+#undef OTD_RED
+    NLG_LAUNCH(k_otd_reduce2, dim3(2 * r * r), dim3(NT), 0, st, (const double *)ot->part, g, r * r, ot->d);
+    // (S and G are 16 doubles each in the block whatever r is: one call carries both)
+    NLG_TRY(allreduce_sum(m->ctx, ot->d + OTD_S, 32));
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// U <- U chol(G)^-T on every stored level of the OTD lanes: current and lagged velocities, explicit-term levels, pressure
+int otd_orthonormalise(const nlg_otd *ot) {
+    nlg_linop *op = ot->op;
+    nlg_mesh *m = op->mesh;
+    hipStream_t st = m->ctx->stream;
+    NLG_TRY(otd_sums(ot, nullptr, nullptr, nullptr));
+    ProfScope ps(m->ctx, P_VECOPS);
+    NLG_LAUNCH(k_otd_chol, dim3(1), dim3(1), 0, st, ot->d, ot->r);
+    OtdLevels lv;
+    int nf = 0;
+    for (int s = 0; s < 3; ++s)
+        for (int c = 0; c < m->dim; ++c) {
+            lv.p[nf] = op->ubuf[s][c], lv.n[nf++] = m->lvn;
+            lv.p[nf] = op->fbuf[s][c], lv.n[nf++] = m->lvn;
+        }
+    lv.p[nf] = op->p, lv.n[nf++] = m->lpn;
+    for (int q = nf; q < 20; ++q) lv.p[q] = nullptr, lv.n[q] = 0;
+    const dim3 g(grid_for(m->lvn), nf);
+    if (ot->r == 1)
+        NLG_LAUNCH(k_otd_transform<1>, g, dim3(NT), 0, st, lv, (const double *)ot->d, op->slab_ld);
+    else if (ot->r == 2)
+        NLG_LAUNCH(k_otd_transform<2>, g, dim3(NT), 0, st, lv, (const double *)ot->d, op->slab_ld);
+    else if (ot->r == 3)
+        NLG_LAUNCH(k_otd_transform<3>, g, dim3(NT), 0, st, lv, (const double *)ot->d, op->slab_ld);
+    else
+        NLG_LAUNCH(k_otd_transform<4>, g, dim3(NT), 0, st, lv, (const double *)ot->d, op->slab_ld);
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// inside a time step: Lr from the step's own D^T p, (nu A + h2 B) u and N of every lane, then F_j += bm1 sum_{i <= j} u_i C_ij
+int otd_force(const nlg_otd *ot, double *const *Fnew, double h2) {
+    nlg_linop *op = ot->op;
+    nlg_mesh *m = op->mesh;
+    hipStream_t st = m->ctx->stream;
+    NLG_TRY(otd_sums(ot, op->gp, op->w, Fnew));
+    ProfScope ps(m->ctx, P_VECOPS);
+    NLG_LAUNCH(k_otd_coef, dim3(1), dim3(1), 0, st, ot->d, ot->r, h2);
+    const int dim = m->dim, g = grid_for(m->lvn);
+    const F3 F = f3(Fnew, dim);
+    const CF3 u = cf3(op->ubuf[0], dim);
+#define OTD_F(D_, R_) NLG_LAUNCH((k_otd_force<D_, R_>), dim3(g), dim3(NT), 0, st, m->lvn, F, u, (const double *)m->d_bm1, (const double *)ot->d, op->slab_ld)
+#define OTD_F_D(D_)      \
+    if (ot->r == 1)      \
+        OTD_F(D_, 1);    \
+    else if (ot->r == 2) \
+        OTD_F(D_, 2);    \
+    else if (ot->r == 3) \
+        OTD_F(D_, 3);    \
+    else                 \
+        OTD_F(D_, 4)
+    if (dim == 3) {
+        OTD_F_D(3);
+    } else {
+        OTD_F_D(2);
+    }
+#undef OTD_F_D
+#undef OTD_F
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
 // one restated nek_advance step (perturbation mode), see oracle/lns.py ExptA.advance; three phases around the two solves
 int adv_a(const Lanes &L) {
     nlg_linop *op = L.op;
@@ -1781,6 +2059,14 @@ int adv_a(const Lanes &L) {
         launch_nf(dim, k_add_force<1>, k_add_force<2>, k_add_force<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(Fnew, dim),
                   (const double *)m->d_bm1, fr, fi, std::cos(ph), -std::sin(ph));
     }
+    // OTD modes: D^T p and H u are computed before the explicit term is final, because the forcing needs the reduced operator they give
+    const double h2 = b0 / dt;
+    const bool otd_on = op->otd && op->istep >= op->otd->o.startstep;
+    if (otd_on) {
+        NLG_TRY(sem_opgradt(m, op->p, op->gp, false, nullptr, nullptr, nl, ld, ld));
+        NLG_TRY(sem_axhelm(m, op->ubuf[0], op->w, dim, nu, h2, nullptr, nullptr, nullptr, nullptr, false, nl, ld));
+        NLG_TRY(otd_force(op->otd, Fnew, h2));
+    }
     rotate3(op->fbuf);
     Hist h;
     h.k = k;
@@ -1794,9 +2080,10 @@ int adv_a(const Lanes &L) {
         }
     }
     // residual form: res = mask QQ^T (rhs + D^T p - H u); the history sums and the two operator terms in ONE pass over the fields
-    const double h2 = b0 / dt;
-    NLG_TRY(sem_opgradt(m, op->p, op->gp, false, nullptr, nullptr, nl, ld, ld));
-    NLG_TRY(sem_axhelm(m, op->ubuf[0], op->w, dim, nu, h2, nullptr, nullptr, nullptr, nullptr, false, nl, ld));
+    if (!otd_on) {
+        NLG_TRY(sem_opgradt(m, op->p, op->gp, false, nullptr, nullptr, nl, ld, ld));
+        NLG_TRY(sem_axhelm(m, op->ubuf[0], op->w, dim, nu, h2, nullptr, nullptr, nullptr, nullptr, false, nl, ld));
+    }
     if (op->use_xp > 0) {
         // slab-permuted velocity solve: the right-hand side is born masked in that layout (no permutation pass in helm_problem, and
         // its gather-scatter moves the layout's 64-byte runs instead of the natural layout's single points)
@@ -2014,6 +2301,7 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     NLG_CHECK(op && vin && vout, "exptA block matvec: NULL argument");
     NLG_CHECK(s >= 1 && s <= kMaxLanes, "exptA block matvec: %d vectors unsupported (1..%d)", s, kMaxLanes);
     NLG_CHECK(op->inited, "exptA block matvec: nlg_linop_init has not been called");
+    NLG_NO_OTD(op, "exptA matvec");
     if (op->orbit) {
         NLG_CHECK(s <= kMaxLanes - 1, "exptA block matvec: orbit mode advances the base flow as one of the %d lanes, %d vectors unsupported (1..%d)",
                   kMaxLanes, s, kMaxLanes - 1);
@@ -2107,6 +2395,7 @@ int do_matvec(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout, int adjoint) {
 int do_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, const nlg_vec *f_im, double omega, int adjoint, nlg_vec *vout) {
     NLG_CHECK(op && f_re && vout, "integrate_forced: NULL argument");
     NLG_CHECK(op->inited, "integrate_forced: nlg_linop_init has not been called");
+    NLG_NO_OTD(op, "integrate_forced");
     NLG_CHECK(!op->orbit, "integrate_forced: not available in orbit mode (the forced response about a time-periodic base flow is not built; nlg_linop_set_orbit)");
     nlg_mesh *m = op->mesh;
     NLG_CHECK(f_re->mesh == m && vout->mesh == m && (!ic || ic->mesh == m) && (!f_im || f_im->mesh == m), "integrate_forced: vector on a different mesh");
@@ -2136,6 +2425,7 @@ int do_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, c
 // dt from the CFL number of vec_in itself, no restart-history replay, no history in the result
 int do_nonlinear_map(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout) {
     NLG_CHECK(op && vin && vout, "nonlinear_map: NULL argument");
+    NLG_NO_OTD(op, "nonlinear_map");
     nlg_mesh *m = op->mesh;
     NLG_CHECK(vin->mesh == m && vout->mesh == m, "nonlinear_map: vector on a different mesh (reference: type_error, fixed_point.f90:31-36)");
     NLG_CHECK(vin->nscal == (op->cfg.ifheat ? 1 : 0) && vout->nscal == vin->nscal,
@@ -2219,6 +2509,7 @@ int nlg_linop_create(nlg_mesh *mesh, const nlg_exptA_config *cfg, const nlg_vec 
 
 int nlg_linop_destroy(nlg_linop *op) {
     if (!op) return 0;
+    NLG_NO_OTD(op, "nlg_linop_destroy");
     hipDeviceSynchronize();
     auto fr = [](double *p) {
         if (p) hipFree(p);
@@ -2262,6 +2553,7 @@ int nlg_linop_destroy(nlg_linop *op) {
 
 int nlg_linop_init(nlg_linop *op) {
     NLG_CHECK(op, "nlg_linop_init: NULL");
+    NLG_NO_OTD(op, "nlg_linop_init");
     nlg_mesh *m = op->mesh;
     nlg_ctx *ctx = m->ctx;
     hipStream_t st = ctx->stream;
@@ -2416,6 +2708,7 @@ int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *
 
 int nlg_linop_set_baseflow(nlg_linop *op, const nlg_vec *baseflow) {
     NLG_CHECK(op && baseflow && baseflow->mesh == op->mesh, "nlg_linop_set_baseflow: bad argument");
+    NLG_NO_OTD(op, "nlg_linop_set_baseflow");
     NLG_CHECK(!op->orbit, "nlg_linop_set_baseflow: the operator is in orbit mode; nlg_linop_set_orbit replaces X0");
     NLG_TRY(nlg_vec_copy(op->baseflow, baseflow));
     return nlg_linop_init(op);
@@ -2424,6 +2717,7 @@ int nlg_linop_set_baseflow(nlg_linop *op, const nlg_vec *baseflow) {
 int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
                              const double *x2) {
     NLG_CHECK(op && line_label, "nlg_linop_set_projection: NULL argument");
+    NLG_NO_OTD(op, "nlg_linop_set_projection");
     nlg_mesh *m = op->mesh;
     NLG_CHECK(idir >= 1 && idir <= m->dim, "nlg_linop_set_projection: idir %d out of range", idir);
     NLG_CHECK(op->inited, "nlg_linop_set_projection: call init first");
@@ -2558,6 +2852,7 @@ int nlg_linop_project(nlg_linop *op, nlg_vec *v) {
 
 int nlg_linop_set_tolerances(nlg_linop *op, double vtol, double ptol) {
     NLG_CHECK(op && vtol > 0.0 && ptol > 0.0, "nlg_linop_set_tolerances: bad argument");
+    NLG_NO_OTD(op, "nlg_linop_set_tolerances");
     op->cfg.vtol = vtol;
     op->cfg.ptol = ptol;
     return 0;
@@ -2565,6 +2860,7 @@ int nlg_linop_set_tolerances(nlg_linop *op, double vtol, double ptol) {
 
 int nlg_linop_set_tau(nlg_linop *op, double tau) {
     NLG_CHECK(op && tau > 0.0, "nlg_linop_set_tau: bad argument");
+    NLG_NO_OTD(op, "nlg_linop_set_tau");
     NLG_CHECK(!op->orbit || tau == op->cfg.tau, "nlg_linop_set_tau: in orbit mode tau is the period; set it with nlg_linop_set_orbit");
     if (tau != op->cfg.tau) {
         op->cfg.tau = tau;
@@ -2578,6 +2874,7 @@ int nlg_linop_set_tau(nlg_linop *op, double tau) {
 // X0 again when the mode is left.
 int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period) {
     NLG_CHECK(op, "nlg_linop_set_orbit: NULL operator");
+    NLG_NO_OTD(op, "nlg_linop_set_orbit");
     if (!X0) {
         if (!op->orbit) return 0;
         op->orbit = false;
@@ -2622,6 +2919,180 @@ int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_it
     NLG_CHECK(istep < (int)lp.v.hist.size() && istep < (int)lp.p.hist.size(), "nlg_linop_lane_iters: lane %d has not run a time step %d", lane, istep);
     if (v_iters) *v_iters = lp.v.hist[istep];
     if (p_iters) *p_iters = lp.p.hist[istep];
+    return 0;
+}
+
+// ---- OTD modes (include/neklab_gpu.h; nek_otd / otd_analysis of the reference) ----------------------------------------------------
+int nlg_otd_opts_default(nlg_otd_opts *o) {
+    NLG_CHECK(o, "nlg_otd_opts_default: NULL");
+    o->r = 2;
+    o->startstep = 1;
+    o->orthostep = 10;
+    o->trans = 0;
+    o->solve_baseflow = 0;
+    return 0;
+}
+
+static int otd_check_flag(nlg_otd *ot, const char *who) {
+    double flag = 0.0;
+    hipStream_t st = ot->op->mesh->ctx->stream;
+    NLG_HIP(hipMemcpyAsync(&flag, ot->d + OTD_FLAG, sizeof(double), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    NLG_CHECK(flag == 0.0, "%s: the Gram matrix of the OTD basis is not positive definite (dependent or non-finite modes)", who);
+    return 0;
+}
+
+int nlg_otd_destroy(nlg_otd *ot) {
+    if (!ot) return 0;
+    hipDeviceSynchronize();
+    nlg_linop *op = ot->op;
+    const bool live = op && op->otd == ot;
+    if (live) op->otd = nullptr;
+    if (ot->d) hipFree(ot->d);
+    if (ot->part) hipFree(ot->part);
+    const bool moved = live && ot->lb >= 0;
+    delete ot;
+    if (moved) {
+        // the base-flow lane rebuilt the fine-mesh factors of the convective term in every step: they belong to the operator's own
+        // (frozen) base flow again, so that a later matvec is the one it was before the run
+        nlg_mesh *m = op->mesh;
+        double *U[3] = {op->baseflow->vel(0), op->baseflow->vel(1), m->dim == 3 ? op->baseflow->vel(2) : nullptr};
+        NLG_TRY(sem_conv_setup(m, U, op->Ur, op->GU));
+    }
+    return 0;
+}
+
+int nlg_otd_create(nlg_linop *op, const nlg_otd_opts *o, const nlg_vec *const *basis0, nlg_otd **out) {
+    NLG_CHECK(op && o && out, "nlg_otd_create: NULL argument");
+    const int rmax = o->solve_baseflow ? kMaxLanes - 1 : kMaxLanes;
+    NLG_CHECK(o->r >= 1 && o->r <= rmax, "nlg_otd_create: r = %d out of range (1..%d%s)", o->r, rmax,
+              o->solve_baseflow ? ": with solve_baseflow the base flow takes one of the lanes" : "");
+    NLG_CHECK(!(o->trans && o->solve_baseflow), "nlg_otd_create: trans with solve_baseflow: the adjoint about a moving base flow needs U(T - t) and is not built");
+    NLG_CHECK(!op->cfg.ifheat, "nlg_otd_create: OTD modes do not carry the temperature (cfg.ifheat); not built");
+    NLG_CHECK(op->proj_nlines == 0, "nlg_otd_create: OTD modes and the wavenumber projection exclude each other");
+    NLG_CHECK(!op->orbit, "nlg_otd_create: the operator is in orbit mode (nlg_linop_set_orbit); use solve_baseflow on a frozen operator");
+    NLG_CHECK(!op->otd, "nlg_otd_create: an nlg_otd already lives on this operator");
+    NLG_CHECK(o->startstep >= 1 && o->orthostep >= 1, "nlg_otd_create: startstep and orthostep must be positive");
+    nlg_mesh *m = op->mesh;
+    if (basis0)
+        for (int v = 0; v < o->r; ++v)
+            NLG_CHECK(basis0[v] && basis0[v]->mesh == m && basis0[v]->nscal == 0, "nlg_otd_create: basis vector %d NULL, on a different mesh or with scalars", v);
+    if (!op->inited) NLG_TRY(nlg_linop_init(op));
+    nlg_otd *ot = new nlg_otd();
+    ot->op = op;
+    ot->o = *o;
+    ot->r = o->r;
+    ot->nl = o->r + (o->solve_baseflow ? 1 : 0);
+    ot->lb = o->solve_baseflow ? o->r : -1;
+    auto fail = [&](int rc) {
+        nlg_otd_destroy(ot);
+        return rc;
+    };
+    hipStream_t st = m->ctx->stream;
+    if (hipMalloc(&ot->d, sizeof(double) * OTD_N) != hipSuccess || hipMalloc(&ot->part, sizeof(double) * 32 * NB) != hipSuccess) {
+        set_error("nlg_otd_create: out of device memory");
+        return fail(1);
+    }
+    int rc = 0;
+    if (hipMemsetAsync(ot->d, 0, sizeof(double) * OTD_N, st) != hipSuccess) rc = 1;
+    if (!rc) rc = reset_state(op, ot->nl);
+    op->istep = 0;
+    op->adjoint = o->trans ? 1 : 0;
+    op->nproj = 0;
+    for (int v = 0; v < kMaxLanes; ++v) op->lane_viters[v] = op->lane_piters[v] = 0;
+    for (int v = 0; v < ot->r && !rc; ++v) {
+        if (basis0) {
+            rc = load_state(op, v, basis0[v], 0);
+        } else {   // rand_basis of init_OTD
+            nlg_vec *tmp = nullptr;
+            rc = nlg_vec_create(m, 0, 1, &tmp);
+            if (!rc) rc = nlg_vec_rand(tmp, 1, (uint64_t)(v + 1));
+            if (!rc) rc = load_state(op, v, tmp, 0);
+            if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = 1;
+            if (tmp) nlg_vec_destroy(tmp);
+        }
+    }
+    if (!rc && ot->lb >= 0) rc = load_state(op, ot->lb, op->baseflow, 0);
+    // at creation the basis may be far from orthonormal: twice
+    if (!rc) rc = otd_orthonormalise(ot);
+    if (!rc) rc = otd_orthonormalise(ot);
+    if (!rc) rc = otd_check_flag(ot, "nlg_otd_create");
+    if (rc) return fail(rc);
+    op->otd = ot;
+    *out = ot;
+    return 0;
+}
+
+int nlg_otd_advance(nlg_otd *ot, int nsteps) {
+    NLG_CHECK(ot && nsteps >= 0, "nlg_otd_advance: bad argument");
+    nlg_linop *op = ot->op;
+    const Lanes L{op, ot->nl, ot->lb};
+    bool ortho = false;
+    for (int s = 0; s < nsteps; ++s) {
+        NLG_TRY(advance(L));
+        ot->time += op->dt;
+        const int is = op->istep, s0 = ot->o.startstep;
+        if (is >= s0 && (is <= s0 + 10 || is % ot->o.orthostep == 0)) {
+            NLG_TRY(otd_orthonormalise(ot));
+            ortho = true;
+        }
+    }
+    // a Gram matrix that was not positive definite left T = I: say so here, not at the next read-out (one small copy per call)
+    if (ortho) NLG_TRY(otd_check_flag(ot, "nlg_otd_advance"));
+    return 0;
+}
+
+int nlg_otd_reduced(nlg_otd *ot, double *Lr, double *G) {
+    NLG_CHECK(ot && Lr, "nlg_otd_reduced: NULL argument");
+    nlg_linop *op = ot->op;
+    nlg_mesh *m = op->mesh;
+    hipStream_t st = m->ctx->stream;
+    const int dim = m->dim, r = ot->r;
+    const int64_t ld = r > 1 ? op->slab_ld : 0;
+    NLG_TRY(otd_orthonormalise(ot));
+    // L u_j in weak form from the operators of the time step, on the state as it stands (h2 = 0: the viscous term alone)
+    NLG_TRY(sem_ortho(m, op->p, r, ld));
+    if (ot->lb >= 0) NLG_TRY(sem_conv_setup(m, at_lane3(op, op->ubuf[0], ot->lb).p, op->Ur, op->GU));
+    NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], op->rhs, op->adjoint, r, ld));
+    NLG_TRY(sem_opgradt(m, op->p, op->gp, false, nullptr, nullptr, r, ld, ld));
+    NLG_TRY(sem_axhelm(m, op->ubuf[0], op->w, dim, 1.0 / op->cfg.re, 0.0, nullptr, nullptr, nullptr, nullptr, false, r, ld));
+    NLG_TRY(otd_sums(ot, op->gp, op->w, op->rhs));
+    NLG_LAUNCH(k_otd_coef, dim3(1), dim3(1), 0, st, ot->d, r, 0.0);
+    double h[OTD_N];
+    NLG_HIP(hipMemcpyAsync(h, ot->d, sizeof(double) * OTD_N, hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    NLG_CHECK(h[OTD_FLAG] == 0.0, "nlg_otd_reduced: the Gram matrix of the OTD basis is not positive definite (dependent or non-finite modes)");
+    for (int q = 0; q < r * r; ++q) {
+        Lr[q] = h[OTD_LR + q];
+        if (G) G[q] = h[OTD_G0 + q];
+    }
+    return 0;
+}
+
+int nlg_otd_get_basis(nlg_otd *ot, int i, nlg_vec *out) {
+    NLG_CHECK(ot && out && out->mesh == ot->op->mesh && out->nscal == 0, "nlg_otd_get_basis: bad argument");
+    NLG_CHECK(i >= 0 && i < ot->r, "nlg_otd_get_basis: mode %d out of range (0..%d)", i, ot->r - 1);
+    NLG_TRY(nlg_vec_zero(out));
+    return store_state(ot->op, i, out, 0);
+}
+
+int nlg_otd_get_baseflow(nlg_otd *ot, nlg_vec *out) {
+    NLG_CHECK(ot && out && out->mesh == ot->op->mesh && out->nscal == 0, "nlg_otd_get_baseflow: bad argument");
+    NLG_TRY(nlg_vec_zero(out));
+    if (ot->lb >= 0) return store_state(ot->op, ot->lb, out, 0);
+    nlg_mesh *m = ot->op->mesh;
+    const nlg_vec *bf = ot->op->baseflow;
+    for (int c = 0; c < m->dim; ++c)
+        NLG_HIP(hipMemcpyAsync(out->vel(c), bf->vel(c), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, m->ctx->stream));
+    NLG_HIP(hipMemcpyAsync(out->pr(), bf->pr(), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, m->ctx->stream));
+    return 0;
+}
+
+int nlg_otd_info(const nlg_otd *ot, int64_t *istep, double *time, double *dt) {
+    NLG_CHECK(ot, "nlg_otd_info: NULL");
+    if (istep) *istep = ot->op->istep;
+    if (time) *time = ot->time;
+    if (dt) *dt = ot->op->dt;
     return 0;
 }
 

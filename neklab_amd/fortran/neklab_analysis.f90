@@ -13,6 +13,8 @@ module neklab_analysis
    use LightKrylov, only: dp, eigs, svds, save_eigenspectrum, zero_basis, initialize_krylov_subspace, newton, gmres_rdp, &
                           newton_dp_opts, newton_dp_metadata
    use LightKrylov, only: abstract_vector_rdp, abstract_exptA_linop_rdp, abstract_system_rdp
+   use iso_c_binding, only: c_int
+   use neklab_gpu_capi, only: nlg_check, c_vec_get_field, c_vec_set_field, nek_lpn
    use neklab_vectors
    use neklab_linops
    use neklab_utils
@@ -21,6 +23,7 @@ module neklab_analysis
    private
 
    public :: linear_stability_analysis_fixed_point, transient_growth_analysis_fixed_point, newton_fixed_point_iteration
+   public :: otd_analysis
    !> .true.: Arnoldi / Lanczos on the device; .false.: LightKrylov's loops over the type-bound procedures
    logical, save, public :: device_eigs = .false.
 
@@ -125,5 +128,74 @@ contains
       call sys%finalize_timer()
       call sys%jacobian%finalize_timer()
    end subroutine newton_fixed_point_iteration
+
+   !> otd_analysis (src/neklab_analysis.f90:214-344): nsteps device time steps of the OTD modes in chunks that end at the next print /
+   !! io / restart step; there the basis is orthonormalised and Lr read out, Ls.dat / Lr.dat are appended in the reference's formats,
+   !! the projected modes (prefixes m01, m02, ..) and the basis (rst) written.
+   subroutine otd_analysis(OTD, nsteps, opts_)
+      type(nek_otd), intent(inout) :: OTD
+      integer, intent(in) :: nsteps
+      type(otd_opts), optional, intent(in) :: opts_
+      type(otd_opts) :: opts
+      real(dp), allocatable :: Lr(:, :), sigma(:), svec(:, :), pr(:)
+      complex(dp), allocatable :: lambda(:), eigvec(:, :)
+      type(nek_dvector) :: mode
+      character(len=3) :: prefix
+      real(dp) :: time, dt
+      integer :: r, istep, nxt, i, j, is, u
+      logical :: hp, hi, hr
+
+      opts = otd_opts()
+      if (present(opts_)) opts = opts_
+      call OTD%init(opts)
+      r = OTD%r
+      allocate (Lr(r, r), sigma(r), svec(r, r), lambda(r), eigvec(r, r), pr(nek_lpn))
+      open (newunit=u, file='Ls.dat', status='replace', action='write'); close (u)
+      open (newunit=u, file='Lr.dat', status='replace', action='write'); close (u)
+      istep = 0
+      do while (istep < nsteps)
+         nxt = nsteps
+         if (opts%printstep > 0) nxt = min(nxt, (istep/opts%printstep + 1)*opts%printstep)
+         if (opts%iostep > 0) nxt = min(nxt, (istep/opts%iostep + 1)*opts%iostep)
+         if (opts%iorststep > 0) nxt = min(nxt, (istep/opts%iorststep + 1)*opts%iorststep)
+         call OTD%advance(nxt - istep)
+         istep = nxt
+         if (istep < opts%startstep) cycle
+         hp = .false.; hi = .false.; hr = .false.
+         if (opts%printstep > 0) hp = mod(istep, opts%printstep) == 0
+         if (opts%iostep > 0) hi = mod(istep, opts%iostep) == 0
+         if (opts%iorststep > 0) hr = mod(istep, opts%iorststep) == 0
+         if (.not. (hp .or. hi .or. hr)) cycle
+         call OTD%info(is, time, dt)
+         if (hp .or. hi) then
+            call OTD%reduced(Lr)
+            call OTD%spectral_analysis(Lr, sigma, svec, lambda, eigvec)
+         end if
+         if (hp) then
+            open (newunit=u, file='Ls.dat', status='old', action='write', position='append')
+            write (u, '(I8,1X,F15.8,A,*(1X,E15.8))') istep, time, ' Ls ', sigma
+            close (u)
+            open (newunit=u, file='Lr.dat', status='old', action='write', position='append')
+            write (u, '(I8,1X,F15.8,A,*(1X,E15.8))', advance='no') istep, time, ' Lr%Re ', real(lambda)
+            write (u, '(A,*(1X,E15.8))') ' Lr%Im ', aimag(lambda)
+            close (u)
+         end if
+         if (hi .or. hr) call OTD%get_basis()
+         if (hi) then                            ! outpost_OTDmodes: mode i = sum_j u_j Re(eigvec_ji), pressure of basis vector i
+            do i = 1, r
+               mode = OTD%basis(i)
+               call mode%scal(real(eigvec(i, i)))
+               do j = 1, r
+                  if (j /= i) call mode%axpby(real(eigvec(j, i)), OTD%basis(j), 1.0_dp)
+               end do
+               call nlg_check(c_vec_get_field(nek_dvector_handle(OTD%basis(i)), 3_c_int, 0_c_int, pr, nek_lpn), 'otd_analysis pr')
+               call nlg_check(c_vec_set_field(mode%h, 3_c_int, 0_c_int, pr, nek_lpn), 'otd_analysis pr')
+               write (prefix, '(A,I2.2)') 'm', i
+               call outpost_dnek(mode, prefix)
+            end do
+         end if
+         if (hr) call outpost_dnek(OTD%basis, 'rst')
+      end do
+   end subroutine otd_analysis
 
 end module neklab_analysis

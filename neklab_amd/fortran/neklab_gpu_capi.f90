@@ -44,6 +44,11 @@ module neklab_gpu_capi
       integer(c_int) :: block_size = 0, warm_start = 0
    end type
 
+   !> nlg_otd_opts with the defaults of nlg_otd_opts_default
+   type, bind(C), public :: nlg_otd_opts
+      integer(c_int) :: r = 2, startstep = 1, orthostep = 10, trans = 0, solve_baseflow = 0
+   end type
+
    !> what the reference reads from Nek5000's `param(.)` / logical flags: the template every exptA_linop starts from,
    !! the number of active scalars (ifto / ifpsco) and `lorder` of SIZE for every nek_dvector
    type(nlg_exptA_config), save, public :: nek_case
@@ -268,6 +273,62 @@ module neklab_gpu_capi
       function c_linop_orbit_end(op, vout) bind(C, name="nlg_linop_orbit_end") result(rc)
          import c_int, c_ptr
          type(c_ptr), value :: op, vout
+         integer(c_int) :: rc
+      end function
+      function c_dense_eig(n, A, lda, wr, wi, vr, ldvr) bind(C, name="nlg_dense_eig") result(rc)
+         import c_int, c_double
+         integer(c_int), value :: n, lda, ldvr
+         real(c_double), intent(in) :: A(*)
+         real(c_double), intent(out) :: wr(*), wi(*), vr(*)
+         integer(c_int) :: rc
+      end function
+      ! OTD modes (include/neklab_gpu.h, nlg_otd_*)
+      function c_otd_opts_default(o) bind(C, name="nlg_otd_opts_default") result(rc)
+         import c_int, nlg_otd_opts
+         type(nlg_otd_opts), intent(out) :: o
+         integer(c_int) :: rc
+      end function
+      function c_otd_create(op, o, basis0, otd) bind(C, name="nlg_otd_create") result(rc)
+         import c_int, c_ptr, nlg_otd_opts
+         type(c_ptr), value :: op
+         type(nlg_otd_opts), intent(in) :: o
+         type(c_ptr), value :: basis0      ! address of an array of r vector handles, or c_null_ptr
+         type(c_ptr), intent(out) :: otd
+         integer(c_int) :: rc
+      end function
+      function c_otd_advance(otd, nsteps) bind(C, name="nlg_otd_advance") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: otd
+         integer(c_int), value :: nsteps
+         integer(c_int) :: rc
+      end function
+      function c_otd_reduced(otd, Lr, G) bind(C, name="nlg_otd_reduced") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: otd
+         real(c_double), intent(out) :: Lr(*), G(*)
+         integer(c_int) :: rc
+      end function
+      function c_otd_get_basis(otd, i, vout) bind(C, name="nlg_otd_get_basis") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: otd, vout
+         integer(c_int), value :: i
+         integer(c_int) :: rc
+      end function
+      function c_otd_get_baseflow(otd, vout) bind(C, name="nlg_otd_get_baseflow") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: otd, vout
+         integer(c_int) :: rc
+      end function
+      function c_otd_info(otd, istep, time, dt) bind(C, name="nlg_otd_info") result(rc)
+         import c_int, c_ptr, c_double, c_int64_t
+         type(c_ptr), value :: otd
+         integer(c_int64_t), intent(out) :: istep
+         real(c_double), intent(out) :: time, dt
+         integer(c_int) :: rc
+      end function
+      function c_otd_destroy(otd) bind(C, name="nlg_otd_destroy") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: otd
          integer(c_int) :: rc
       end function
       function c_linop_matvec(op, vin, vout) bind(C, name="nlg_linop_matvec") result(rc)

@@ -103,6 +103,48 @@ module neklab_linops
       procedure, pass(self), public :: rmatvec => resolvent_rmatvec
    end type
 
+   !---------------------------------------------------
+   !-----     OPTIMALLY TIME-DEPENDENT MODES      -----
+   !---------------------------------------------------
+   !> otd_opts (src/neklab_otd.f90:51-72), same components and defaults
+   type, public :: otd_opts
+      integer :: startstep = 1
+      integer :: printstep = 5
+      integer :: orthostep = 10
+      integer :: iostep = 100
+      integer :: iorststep = 100
+      integer :: n_usrIC = 0
+      logical :: trans = .false.
+      logical :: solve_baseflow = .true.
+      logical :: if_output_initial_conditions = .false.
+      character(len=128) :: OTDIC_basename = 'OTDIC_'
+   end type otd_opts
+
+   !> nek_otd (src/neklab_otd.f90:37-49): r OTD modes about `baseflow` as lanes of the device block step (nlg_otd_*).  The reduced
+   !! operator, the forcing (generate_forcing) and the re-orthonormalisation run inside the device time step; `basis` is filled by
+   !! get_basis.  cfg as for exptA_linop (from the case unless cfg_set), cfl_limit 0.4 as in init_OTD.  User initial conditions
+   !! (n_usrIC) are handed over in `basis` before init(); the reference reads them with Nek5000's load_fld.
+   type, public :: nek_otd
+      integer :: r = 2
+      type(nek_dvector) :: baseflow
+      type(nek_dvector), allocatable :: basis(:)
+      type(nlg_exptA_config) :: cfg = nlg_exptA_config()
+      logical :: cfg_set = .false.
+      type(c_ptr), private :: hop = c_null_ptr, h = c_null_ptr
+      integer(c_intptr_t), private :: owner = 0
+   contains
+      private
+      procedure, pass(self), public :: init => init_OTD
+      procedure, pass(self), public :: advance => otd_advance
+      procedure, pass(self), public :: reduced => otd_reduced
+      procedure, pass(self), public :: get_basis => otd_get_basis
+      procedure, pass(self), public :: get_baseflow => otd_get_baseflow
+      procedure, pass(self), public :: info => otd_info
+      procedure, pass(self), public :: spectral_analysis => otd_spectral_analysis
+      procedure, pass(self), public :: close => otd_close
+      final :: finalize_otd
+   end type nek_otd
+
 contains
 
    function exptA_handle(self) result(h)
@@ -324,6 +366,162 @@ contains
       integer(c_int) :: rc
       if (c_associated(self%h) .and. self%owner == loc(self)) rc = c_linop_destroy(self%h)
       self%h = c_null_ptr; self%owner = 0
+   end subroutine
+
+   !---- nek_otd ------------------------------------------------------------------------------------------------------
+   function otd_handle(self) result(h)
+      class(nek_otd), intent(in) :: self
+      type(c_ptr) :: h
+      if (.not. c_associated(self%h) .or. self%owner /= loc(self)) then
+         write (*, '(A)') 'ERROR in '//this_module//': OTD%init() has not been called on this object'
+         error stop 1
+      end if
+      h = self%h
+   end function
+
+   subroutine otd_close(self)
+      class(nek_otd), intent(inout) :: self
+      integer(c_int) :: rc
+      if (self%owner == loc(self)) then
+         if (c_associated(self%h)) rc = c_otd_destroy(self%h)
+         if (c_associated(self%hop)) rc = c_linop_destroy(self%hop)
+      end if
+      self%h = c_null_ptr; self%hop = c_null_ptr; self%owner = 0
+   end subroutine
+
+   subroutine finalize_otd(self)
+      type(nek_otd), intent(inout) :: self
+      call otd_close(self)
+   end subroutine
+
+   !> init_OTD (src/neklab_otd.f90:118-204).  `basis` allocated with r vectors on entry: they are the initial conditions;
+   !! otherwise the library draws r random modes (seeds 1 .. r).  Either way the basis is orthonormalised (twice).
+   subroutine init_OTD(self, opts)
+      class(nek_otd), intent(inout) :: self
+      type(otd_opts), intent(in) :: opts
+      type(nlg_otd_opts) :: o
+      type(c_ptr), allocatable, target :: hb(:)
+      integer :: i
+      call otd_close(self)
+      if (.not. self%cfg_set) then
+         self%cfg = nek_case
+         self%cfg%cfl_limit = 0.4_dp                ! setup_linear_solver(cfl_limit = 0.4_dp), neklab_otd.f90:203
+      end if
+      if (self%cfg%dt > 0.0_dp) self%cfg%tau = self%cfg%dt      ! OTD has no tau: the step is the given one, not tau / ceil(tau / dt)
+      call nlg_check(c_linop_create(nlg_mesh, self%cfg, nek_dvector_handle(self%baseflow), self%hop), 'init_OTD')
+      self%owner = loc(self)
+      o%r = self%r; o%startstep = opts%startstep; o%orthostep = opts%orthostep
+      o%trans = merge(1, 0, opts%trans); o%solve_baseflow = merge(1, 0, opts%solve_baseflow)
+      if (allocated(self%basis)) then
+         if (size(self%basis) /= self%r) then
+            write (*, '(A,I0,A,I0)') 'ERROR in '//this_module//': init_OTD: ', size(self%basis), ' initial conditions for r = ', self%r
+            error stop 1
+         end if
+         allocate (hb(self%r))
+         do i = 1, self%r
+            hb(i) = nek_dvector_handle(self%basis(i))
+         end do
+         call nlg_check(c_otd_create(self%hop, o, c_loc(hb), self%h), 'init_OTD')
+      else
+         call nlg_check(c_otd_create(self%hop, o, c_null_ptr, self%h), 'init_OTD')
+         allocate (self%basis(self%r))
+      end if
+      call otd_get_basis(self)
+   end subroutine
+
+   subroutine otd_advance(self, nsteps)
+      class(nek_otd), intent(inout) :: self
+      integer, intent(in) :: nsteps
+      call nlg_check(c_otd_advance(otd_handle(self), int(nsteps, c_int)), 'otd_advance')
+   end subroutine
+
+   !> orthonormalise, then Lr_ij = <u_i, L u_j> on the current state; G (optional): the Gram matrix before
+   subroutine otd_reduced(self, Lr, G)
+      class(nek_otd), intent(inout) :: self
+      real(dp), intent(out) :: Lr(self%r, self%r)
+      real(dp), intent(out), optional :: G(self%r, self%r)
+      real(dp) :: Gl(self%r, self%r)
+      call nlg_check(c_otd_reduced(otd_handle(self), Lr, Gl), 'otd_reduced')
+      if (present(G)) G = Gl
+   end subroutine
+
+   !> the current modes -> self%basis
+   subroutine otd_get_basis(self)
+      class(nek_otd), intent(inout) :: self
+      integer :: i
+      do i = 1, self%r
+         call nek_dvector_ensure(self%basis(i))
+         call nlg_check(c_otd_get_basis(otd_handle(self), int(i - 1, c_int), self%basis(i)%h), 'otd_get_basis')
+      end do
+   end subroutine
+
+   subroutine otd_get_baseflow(self, vec_out)
+      class(nek_otd), intent(in) :: self
+      type(nek_dvector), intent(inout) :: vec_out
+      call nek_dvector_ensure(vec_out)
+      call nlg_check(c_otd_get_baseflow(otd_handle(self), vec_out%h), 'otd_get_baseflow')
+   end subroutine
+
+   subroutine otd_info(self, istep, time, dt)
+      class(nek_otd), intent(in) :: self
+      integer, intent(out) :: istep
+      real(dp), intent(out) :: time, dt
+      integer(c_int64_t) :: is
+      call nlg_check(c_otd_info(otd_handle(self), is, time, dt), 'otd_info')
+      istep = int(is)
+   end subroutine
+
+   !> spectral_analysis (src/neklab_otd.f90:206-265) without the log files (otd_analysis writes them): sigma = eigenvalues of
+   !! (Lr + Lr^T) / 2, descending, with vectors; lambda = eigenvalues of Lr by real part, descending, with vectors
+   subroutine otd_spectral_analysis(self, Lr, sigma, svec, lambda, eigvec)
+      class(nek_otd), intent(in) :: self
+      real(dp), intent(in) :: Lr(self%r, self%r)
+      real(dp), intent(out) :: sigma(self%r), svec(self%r, self%r)
+      complex(dp), intent(out) :: lambda(self%r), eigvec(self%r, self%r)
+      real(dp) :: A(self%r, self%r), wr(self%r), wi(self%r), vr(self%r, self%r)
+      complex(dp) :: l(self%r), v(self%r, self%r)
+      integer :: r, j, idx(self%r)
+      r = self%r
+      A = 0.5_dp*(Lr + transpose(Lr))
+      call nlg_check(c_dense_eig(int(r, c_int), A, int(r, c_int), wr, wi, vr, int(r, c_int)), 'otd_spectral_analysis')
+      call order_desc(wr, idx)
+      do j = 1, r
+         sigma(j) = wr(idx(j)); svec(:, j) = vr(:, idx(j))
+      end do
+      A = Lr
+      call nlg_check(c_dense_eig(int(r, c_int), A, int(r, c_int), wr, wi, vr, int(r, c_int)), 'otd_spectral_analysis')
+      j = 1
+      do while (j <= r)                       ! LAPACK's real convention: a complex pair is (Re, Im) in consecutive columns
+         if (wi(j) /= 0.0_dp .and. j < r) then
+            l(j) = cmplx(wr(j), wi(j), dp); l(j + 1) = cmplx(wr(j + 1), wi(j + 1), dp)
+            v(:, j) = cmplx(vr(:, j), vr(:, j + 1), dp); v(:, j + 1) = conjg(v(:, j))
+            j = j + 2
+         else
+            l(j) = cmplx(wr(j), 0.0_dp, dp); v(:, j) = cmplx(vr(:, j), 0.0_dp, dp)
+            j = j + 1
+         end if
+      end do
+      call order_desc(wr, idx)
+      do j = 1, r
+         lambda(j) = l(idx(j)); eigvec(:, j) = v(:, idx(j))
+      end do
+   contains
+      subroutine order_desc(x, ix)          ! stable insertion sort of the indices, largest first
+         real(dp), intent(in) :: x(:)
+         integer, intent(out) :: ix(:)
+         integer :: a, b, t
+         do a = 1, size(x)
+            ix(a) = a
+         end do
+         do a = 2, size(x)
+            t = ix(a); b = a - 1
+            do while (b >= 1)
+               if (x(ix(b)) >= x(t)) exit
+               ix(b + 1) = ix(b); b = b - 1
+            end do
+            ix(b + 1) = t
+         end do
+      end subroutine
    end subroutine
 
    !---- exptA_proj_linop ---------------------------------------------------------------------------------------------

@@ -897,3 +897,193 @@ def linear_stability_analysis_periodic_orbit(op: exptA_orbit_linop, kdim: int, n
     if outpost:
         outpost_dnek(eigvecs, "flq", session, outdir)
     return mu, exponents, residuals, eigvecs, info
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Optimally time-dependent (OTD) modes.  Reference: otd_opts / nek_otd (src/neklab_otd.f90), otd_analysis
+# (src/neklab_analysis.f90:214-344).  The time stepping, the reduced operator, the forcing and the re-orthonormalisation are
+# device work (nlg_otd_*, DESIGN.md 3.2 "OTD mode"); the r x r spectral analysis and the log files are host work, as in the
+# reference.
+class otd_opts:
+    """reference: type otd_opts (src/neklab_otd.f90:51-72), same fields and defaults."""
+
+    def __init__(self, startstep: int = 1, printstep: int = 5, orthostep: int = 10, iostep: int = 100, iorststep: int = 100,
+                 n_usrIC: int = 0, trans: bool = False, solve_baseflow: bool = True, OTDIC_basename: str = "OTDIC_"):
+        self.startstep, self.printstep, self.orthostep = int(startstep), int(printstep), int(orthostep)
+        self.iostep, self.iorststep, self.n_usrIC = int(iostep), int(iorststep), int(n_usrIC)
+        self.trans, self.solve_baseflow, self.OTDIC_basename = bool(trans), bool(solve_baseflow), str(OTDIC_basename)
+
+
+def _fortran_e(x: float, w: int = 15, d: int = 8) -> str:
+    """Fortran's Ew.d edit descriptor: 0.dddddddd E+ee, right-justified in w characters."""
+    x = float(x)
+    if x == 0.0 or not np.isfinite(x):
+        body = ("0." + "0" * d + "E+00") if x == 0.0 else str(x)
+        return body.rjust(w)
+    mant, exp = ("%.*e" % (d - 1, abs(x))).split("e")          # d significant digits: m.ddd e ee with 1 <= m < 10
+    digits, e = mant.replace(".", ""), int(exp) + 1
+    body = "%s0.%sE%s%02d" % ("-" if x < 0 else "", digits, "-" if e < 0 else "+", abs(e))
+    return body.rjust(w)
+
+
+def otd_log_line(istep: int, time: float, *tagged) -> str:
+    """One line of Ls.dat / Lr.dat: '(I8,1X,F15.8,A,*(1X,E15.8))', the (tag, values) groups following each other
+    (spectral_analysis, src/neklab_otd.f90:225, :242, :262)."""
+    s = "%8d %15.8f" % (istep, time)
+    for tag, vals in tagged:
+        s += tag + "".join(" " + _fortran_e(v) for v in vals)
+    return s
+
+
+class nek_otd:
+    """reference: type nek_otd (src/neklab_otd.f90:37-49): r OTD modes about `baseflow`.  Keyword arguments are the options
+    of exptA_linop (re, torder, dt, tolerances, filter ...); cfl_limit defaults to 0.4 as in init_OTD."""
+
+    def __init__(self, baseflow: nek_dvector, r: int = 2, **cfg):
+        cfg.setdefault("cfl_limit", 0.4)
+        self.mesh, self.lib, self.baseflow, self.r = baseflow.mesh, baseflow.lib, baseflow, int(r)
+        # OTD has no tau, but the operator's rule snaps dt to tau / ceil(tau / dt): with a given dt, tau = dt keeps the step as given;
+        # with the CFL rule (dt = 0) the step is tau / ceil(tau c / cfl_limit), at most the CFL step, for tau = 1 unless `tau` is passed
+        tau = cfg.pop("tau", None)
+        if cfg.get("dt", 0.0) > 0.0:
+            tau = cfg["dt"]
+        self.op = exptA_linop(1.0 if tau is None else tau, baseflow, **cfg)
+        self.h = None
+        self.opts = None
+
+    def init(self, opts: "otd_opts | None" = None, basis0: "list | None" = None, icdir: str = "."):
+        """init_OTD (src/neklab_otd.f90:118-204): random basis (seeds 1 .. r), the first n_usrIC modes from
+        `<OTDIC_basename>nn.fld`, orthonormalised; `basis0` (r vectors) replaces both."""
+        opts = opts if opts is not None else otd_opts()
+        if not 0 <= opts.n_usrIC <= self.r:
+            raise ValueError("init_OTD: inconsistent number of IC fields to load: nIC = %d, r = %d" % (opts.n_usrIC, self.r))
+        if basis0 is None and opts.n_usrIC > 0:
+            from . import nekio
+            basis0 = []
+            for i in range(self.r):
+                v = nek_dvector(self.mesh, 0, 1)
+                if i < opts.n_usrIC:
+                    path = os.path.join(icdir, "%s%02d.fld" % (opts.OTDIC_basename, i + 1))
+                    if not os.path.exists(path):
+                        raise FileNotFoundError("init_OTD: cannot find IC file: %s" % path)
+                    f = nekio.read_fld(path)
+                    nek2vec(v, f["ux"], f["uy"], f.get("uz"), pressure_from_mesh1(self.mesh, f["p"]) if "p" in f else None)
+                else:
+                    v.rand(True, seed=i + 1)
+                basis0.append(v)
+        o = _lib.OtdOpts()
+        check(self.lib.nlg_otd_opts_default(C.byref(o)))
+        o.r, o.startstep, o.orthostep = self.r, opts.startstep, opts.orthostep
+        o.trans, o.solve_baseflow = int(opts.trans), int(opts.solve_baseflow)
+        arr = None
+        if basis0 is not None:
+            if len(basis0) != self.r:
+                raise ValueError("init_OTD: %d basis vectors for r = %d" % (len(basis0), self.r))
+            arr = (vp * self.r)(*[x.h for x in basis0])
+        h = vp()
+        check(self.lib.nlg_otd_create(self.op.h, C.byref(o), arr, C.byref(h)))
+        self.h, self.opts = h, opts
+
+    def advance(self, n: int = 1):
+        check(self.lib.nlg_otd_advance(self.h, int(n)))
+
+    def reduced(self):
+        """(Lr, G): the basis is orthonormalised, then Lr_ij = <u_i, L u_j> on the current state; G is the Gram matrix before."""
+        Lr, G = np.zeros((self.r, self.r), order="F"), np.zeros((self.r, self.r), order="F")
+        check(self.lib.nlg_otd_reduced(self.h, dptr(Lr), dptr(G)))
+        return Lr, G
+
+    def basis(self, i: int, out: "nek_dvector | None" = None) -> nek_dvector:
+        out = out if out is not None else nek_dvector(self.mesh)
+        check(self.lib.nlg_otd_get_basis(self.h, int(i), out.h))
+        return out
+
+    def current_baseflow(self, out: "nek_dvector | None" = None) -> nek_dvector:
+        out = out if out is not None else nek_dvector(self.mesh)
+        check(self.lib.nlg_otd_get_baseflow(self.h, out.h))
+        return out
+
+    def info(self) -> dict:
+        a, t, dt = C.c_int64(), C.c_double(), C.c_double()
+        check(self.lib.nlg_otd_info(self.h, C.byref(a), C.byref(t), C.byref(dt)))
+        return {"istep": a.value, "time": t.value, "dt": dt.value}
+
+    @staticmethod
+    def spectral_analysis(Lr):
+        """spectral_analysis (src/neklab_otd.f90:206-265), pure numpy: (sigma, svec, lambda, eigvec) -- the eigenvalues of
+        (Lr + Lr^T) / 2 in descending order with their vectors, and the eigenvalues of Lr sorted by real part, descending, with
+        theirs."""
+        Lr = np.asarray(Lr, dtype=np.float64)
+        s, v = np.linalg.eigh(0.5 * (Lr + Lr.T))
+        idx = np.argsort(-s, kind="stable")
+        lam, ev = np.linalg.eig(Lr)
+        jdx = np.argsort(-lam.real, kind="stable")
+        return s[idx], v[:, idx], lam[jdx].astype(complex), ev[:, jdx].astype(complex)
+
+    def outpost_OTDmodes(self, eigvec, outdir: str = ".", session: str = "neklab", index: int = 1, time: float = 0.0):
+        """outpost_OTDmodes (src/neklab_otd.f90:267-300): mode i = sum_j u_j Re(eigvec_ji) with the pressure of basis vector
+        i, written as `m<ii><session>0.f<index>`."""
+        B = [self.basis(j) for j in range(self.r)]
+        paths = []
+        for i in range(self.r):
+            m = B[i].copy()
+            m.scal(float(np.real(eigvec[i, i])))
+            for j in range(self.r):
+                if j != i:
+                    m.axpby(float(np.real(eigvec[j, i])), B[j], 1.0)
+            m.set_field(PR, B[i].get_field(PR))
+            paths += outpost_dnek(m, "m%02d" % (i + 1), session, outdir, first_index=index, time=time)
+        return paths
+
+    def close(self):
+        if self.h:
+            self.lib.nlg_otd_destroy(self.h)
+            self.h = None
+        if self.op is not None:
+            self.op.close()
+            self.op = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def otd_analysis(OTD: nek_otd, opts: "otd_opts | None" = None, nsteps: int = 100, outdir: str = ".", session: str = "neklab",
+                 basis0: "list | None" = None):
+    """reference: otd_analysis (src/neklab_analysis.f90:214-344).  The time loop runs on the device in chunks that end at the next
+    print / io / restart step; there the basis is orthonormalised, Lr read out, and Ls.dat / Lr.dat, the projected modes
+    (`m01`, ...) and the basis (`rst`) written.  Returns the logged rows: dicts of istep, time, sigma, lambda."""
+    opts = opts if opts is not None else otd_opts()
+    OTD.init(opts, basis0=basis0, icdir=outdir)
+    for name in ("Ls.dat", "Lr.dat"):
+        open(os.path.join(outdir, name), "w").close()
+    every = [s for s in (opts.printstep, opts.iostep, opts.iorststep) if s > 0]
+    rows, istep, nio, nrst = [], 0, 0, 0
+    while istep < nsteps:
+        nxt = min([nsteps] + [(istep // s + 1) * s for s in every])
+        OTD.advance(nxt - istep)
+        istep = nxt
+        if istep < opts.startstep:
+            continue
+        hit = {k: getattr(opts, k) > 0 and istep % getattr(opts, k) == 0 for k in ("printstep", "iostep", "iorststep")}
+        if not any(hit.values()):
+            continue
+        time = OTD.info()["time"]
+        if hit["printstep"] or hit["iostep"]:
+            Lr, _ = OTD.reduced()
+            sigma, svec, lam, eigvec = OTD.spectral_analysis(Lr)
+        if hit["printstep"]:
+            with open(os.path.join(outdir, "Ls.dat"), "a") as f:
+                f.write(otd_log_line(istep, time, (" Ls ", sigma)) + "\n")
+            with open(os.path.join(outdir, "Lr.dat"), "a") as f:
+                f.write(otd_log_line(istep, time, (" Lr%Re ", lam.real), (" Lr%Im ", lam.imag)) + "\n")
+            rows.append({"istep": istep, "time": time, "sigma": sigma, "lambda": lam})
+        if hit["iostep"]:
+            nio += 1
+            OTD.outpost_OTDmodes(eigvec, outdir, session, index=nio, time=time)
+        if hit["iorststep"]:
+            outpost_dnek([OTD.basis(j) for j in range(OTD.r)], "rst", session, outdir, first_index=nrst * OTD.r + 1, time=time)
+            nrst += 1
+    return rows
