@@ -360,6 +360,33 @@ int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *
 int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period);
 int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out);
 int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_iters, int64_t *p_iters);
+/* Periodic orbits: Newton-Krylov for the state X0 and the period T (nek_ext_dvector, src/vectors/real_extended_vectors.f90;
+ * nek_upo_system / nek_upo_jacobian, src/systems/periodic_orbit.f90, neklab_systems.f90:147-223).  Every entry point below works on an
+ * operator in orbit mode and refuses any other with a message that names nlg_linop_set_orbit.  One perturbation per call; no adjoint.
+ * nlg_linop_set_orbit_steps: nlg_linop_set_orbit with a fixed step count, dt = period / nsteps; nsteps = 0 is nlg_linop_set_orbit itself
+ *   (CFL rule with cfg.cfl_limit, or cfg.dt).  A Newton iteration calls it with its new (X, T); the count is held through the
+ *   iteration's GMRES, so that the residual does not jump where ceil() does (the reference recomputes it in every call,
+ *   periodic_orbit.f90:63-69).
+ * nlg_upo_residual: out = Phi_T(X0) - X0, pressure included (nonlinear_map_UPO, :4-45): the base-flow lane alone through the nonlinear
+ *   step with the operator's dt / nsteps; equal to orbit_end - X0 of a coupled matvec on the same operator.
+ * nlg_upo_fdot: the two time derivatives of the base flow (the reference's compute_fdot), taken from the last run -- any coupled matvec
+ *   or nlg_upo_residual -- and kept by the operator.  which = 0: f0 = (U^1 - U^0) / dt from the first step, compute_fdot at X0
+ *   literally (one impulsive first-order step; velocity and pressure).  which = 1: fT = the BDF-k derivative of the base flow at level
+ *   nsteps, k = min(nsteps, torder), from the time levels of the last step -- the derivative the scheme itself uses, at no extra time
+ *   step (the reference restarts impulsively from X(T): DESIGN.md 8); its pressure part is the first difference (p^N - p^{N-1}) / dt,
+ *   the one pressure level a step keeps.  An error before the first run.
+ * nlg_upo_jac_matvec: the bordered Jacobian (jac_direct_map, :47-115): v_out = M v_in - v_in + t_in fT, *t_out = <f0, v_in> in the
+ *   inner product of the vector space (velocity only); M = nlg_linop_matvec, unchanged.  nlg_upo_border: the border alone on w = M v_in
+ *   (in place) -- one fused pass when neither vector carries restart history (and composed == 0), else the vector operations
+ *   sub / axpby / dot, whose history semantics then apply.
+ * nlg_upo_arnoldi_step: nlg_upo_jac_matvec on column k of the basis, whose period components live in the host array tcol[0 .. k+1],
+ *   then CGS2 in the extended inner product <u, v> + t_u t_v; H(0:k+1, k) as nlg_arnoldi_step. */
+int nlg_linop_set_orbit_steps(nlg_linop *op, const nlg_vec *X0, double period, int nsteps);
+int nlg_upo_residual(nlg_linop *op, nlg_vec *out);
+int nlg_upo_fdot(nlg_linop *op, int which, nlg_vec *out);
+int nlg_upo_jac_matvec(nlg_linop *op, const nlg_vec *v_in, double t_in, nlg_vec *v_out, double *t_out);
+int nlg_upo_border(nlg_linop *op, const nlg_vec *v_in, double t_in, nlg_vec *w, double *t_out, int composed);
+int nlg_upo_arnoldi_step(nlg_linop *op, nlg_basis *basis, double *tcol, int k, double *H, int ldh);
 /* Optimally time-dependent (OTD) modes (nek_otd, src/neklab_otd.f90; otd_analysis, src/neklab_analysis.f90:214-344): r <= 4
  * perturbations u_1 .. u_r, orthonormal in the inner product of the vector space, follow dU/dt = L(t) U - U C with C = Lr - Phi,
  * Lr_ij = <u_i, L u_j> and Phi skew-symmetric such that C is upper triangular (C_jj = Lr_jj, C_ij = Lr_ij + Lr_ji for i < j): mode j

@@ -138,6 +138,12 @@ SIGNATURES = {
     "nlg_linop_set_orbit": (C.c_int, [vp, vp, C.c_double]),
     "nlg_linop_orbit_end": (C.c_int, [vp, vp]),
     "nlg_linop_lane_iters": (C.c_int, [vp, C.c_int, C.c_int, c_int64_p, c_int64_p]),
+    "nlg_linop_set_orbit_steps": (C.c_int, [vp, vp, C.c_double, C.c_int]),
+    "nlg_upo_residual": (C.c_int, [vp, vp]),
+    "nlg_upo_fdot": (C.c_int, [vp, C.c_int, vp]),
+    "nlg_upo_jac_matvec": (C.c_int, [vp, vp, C.c_double, vp, c_double_p]),
+    "nlg_upo_border": (C.c_int, [vp, vp, C.c_double, vp, c_double_p, C.c_int]),
+    "nlg_upo_arnoldi_step": (C.c_int, [vp, vp, c_double_p, C.c_int, c_double_p, C.c_int]),
     "nlg_otd_opts_default": (C.c_int, [C.POINTER(OtdOpts)]),
     "nlg_otd_create": (C.c_int, [vp, C.POINTER(OtdOpts), C.POINTER(vp), C.POINTER(vp)]),
     "nlg_otd_advance": (C.c_int, [vp, C.c_int]),

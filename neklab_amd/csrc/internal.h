@@ -357,6 +357,8 @@ struct ProfScope {
 int reduce_ws_reserve(nlg_ctx *ctx, int nvec);
 // weighted dot over the inner-product part, result left on device at ctx->d_scalars[slot]; allreduced
 int dev_dot(const nlg_vec *a, const nlg_vec *b, int slot);
+// border of the periodic-orbit Jacobian in one pass: w <- w - v + t fT (main block), <f0, v> at ctx->d_scalars[slot]; allreduced
+int upo_border_dev(nlg_vec *w, const nlg_vec *v, const nlg_vec *fT, const nlg_vec *f0, double t, int slot);
 int scalars_to_host(nlg_ctx *ctx, int first, int count, double *out);   // syncs the stream
 int allreduce_sum(nlg_ctx *ctx, double *d_buf, int count);
 int allreduce_max(nlg_ctx *ctx, double *d_buf, int count);

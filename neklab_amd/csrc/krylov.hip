@@ -164,6 +164,39 @@ int nlg_arnoldi_step(nlg_linop *op, nlg_basis *basis, int k, double *H, int ldh,
     return 0;
 }
 
+// One Arnoldi step of the bordered Jacobian of a periodic orbit on extended vectors (field, T): column k of the basis with period
+// component tcol[k] -> column k + 1 / tcol[k + 1], CGS2 in the extended inner product <u, v> + t_u t_v (the reference's
+// nek_ext_dvector dot, src/vectors/real_extended_vectors.f90), from the block projections of the basis with the scalar terms added on
+// the host.
+int nlg_upo_arnoldi_step(nlg_linop *op, nlg_basis *basis, double *tcol, int k, double *H, int ldh) {
+    NLG_CHECK(op, "nlg_upo_arnoldi_step: NULL operator, one in orbit mode is needed (nlg_linop_set_orbit)");
+    NLG_CHECK(basis && tcol && H, "nlg_upo_arnoldi_step: NULL argument");
+    NLG_CHECK(k >= 0 && k + 1 < basis->nvec, "nlg_upo_arnoldi_step: k=%d needs basis columns %d, %d (nvec=%d)", k, k, k + 1, basis->nvec);
+    NLG_CHECK(ldh >= k + 2, "nlg_upo_arnoldi_step: ldh=%d too small for k=%d", ldh, k);
+    nlg_vec *vk = basis->views[k], *w = basis->views[k + 1];
+    double tw = 0.0;
+    NLG_TRY(nlg_upo_jac_matvec(op, vk, tcol[k], w, &tw));   // (refuses an operator that is not in orbit mode)
+    const int kk = k + 1;
+    std::vector<double> h(kk, 0.0), hp(kk);
+    for (int pass = 0; pass < 2; ++pass) {
+        NLG_TRY(nlg_basis_block_dot(basis, kk, w, hp.data()));
+        for (int j = 0; j < kk; ++j) hp[j] += tcol[j] * tw;
+        NLG_TRY(nlg_basis_block_axpy(basis, kk, hp.data(), w));
+        for (int j = 0; j < kk; ++j) {
+            tw -= hp[j] * tcol[j];
+            h[j] += hp[j];
+        }
+    }
+    double ww = 0.0;
+    NLG_TRY(nlg_vec_dot(w, w, &ww));
+    const double beta = std::sqrt(ww + tw * tw);
+    if (beta > 0.0) NLG_TRY(nlg_vec_scal(w, 1.0 / beta));
+    tcol[k + 1] = beta > 0.0 ? tw / beta : 0.0;
+    for (int j = 0; j < kk; ++j) H[(size_t)k * ldh + j] = h[j];
+    H[(size_t)k * ldh + k + 1] = beta;
+    return 0;
+}
+
 int nlg_block_arnoldi_step(nlg_linop *op, nlg_basis *basis, int k, int s, double *H, int ldh, int transpose) {
     NLG_CHECK(op && basis && H, "nlg_block_arnoldi_step: NULL argument");
     NLG_CHECK(s >= 1 && s <= 4, "nlg_block_arnoldi_step: block size %d unsupported (1..4)", s);

@@ -1010,6 +1010,32 @@ __global__ __launch_bounds__(NT) void k_mul3(int64_t n, double *y, const double 
     for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) y[i] = s * a[i] * b[i];
 }
 
+// Time derivative of a state from the levels a time step keeps (periodic-orbit Newton, nlg_upo_fdot): field f = blockIdx.y of
+// `nf` fields (the velocity components, then the pressure) in ONE launch,
+//   out_f = (acc ? out_f : 0) + sum_j c[f][j] src[f][j]        (a null source is skipped),
+// so that the BDF-k sum over the velocity levels and the first difference of the pressure are the same pass.
+struct DdtArgs {
+    double *out[4];
+    const double *src[4][3];
+    double c[4][3];
+    int64_t n[4];
+    int acc;
+};
+__global__ __launch_bounds__(NT) void k_bdf_ddt(DdtArgs A) {
+    const int f = blockIdx.y;
+    const int64_t n = A.n[f];
+    double *__restrict__ out = A.out[f];
+    const double *s0 = A.src[f][0], *s1 = A.src[f][1], *s2 = A.src[f][2];
+    const double c0 = A.c[f][0], c1 = A.c[f][1], c2 = A.c[f][2];
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
+        double v = A.acc ? out[i] : 0.0;
+        if (s0) v += c0 * s0[i];
+        if (s1) v += c1 * s1[i];
+        if (s2) v += c2 * s2[i];
+        out[i] = v;
+    }
+}
+
 inline int grid_for(int64_t n) {
     int64_t g = (n + NT - 1) / NT;
     if (g > 2048) g = 2048;
@@ -1128,6 +1154,11 @@ struct nlg_linop {
     // the step linearised about its current state.  orbit_end: its state after the nsteps of the last matvec, Phi_T(X0).
     bool orbit = false, orbit_end_valid = false;
     nlg_vec *orbit_end = nullptr;
+    // periodic-orbit Newton (nlg_upo_*): a fixed step count for the orbit (0 = the usual rule) and the two time derivatives of the
+    // base flow taken from the run, upo_f0 = (U^1 - U^0) / dt and upo_fT = BDF-k derivative at level nsteps (capture_fdot)
+    int orbit_nsteps = 0;
+    bool upo_fdot_valid = false;
+    nlg_vec *upo_f0 = nullptr, *upo_fT = nullptr;
     int64_t lane_viters[kMaxLanes] = {}, lane_piters[kMaxLanes] = {};   // iterations per lane of the last matvec (block)
     int64_t st_steps = 0, st_viters = 0, st_piters = 0, st_titers = 0, st_matvecs = 0;   // summed over the lanes
 };
@@ -2209,6 +2240,8 @@ int load_state(nlg_linop *op, int lane, const nlg_vec *v, int irst) {
     return 0;
 }
 
+// (nlg_upo_residual reads the same buffers -- ubuf[0] and p of lane 0 -- directly, to difference them against X0 in one pass: a change
+// of where a lane keeps its current state belongs in both places)
 int store_state(nlg_linop *op, int lane, nlg_vec *v, int irst) {
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
@@ -2217,6 +2250,45 @@ int store_state(nlg_linop *op, int lane, nlg_vec *v, int irst) {
     NLG_HIP(hipMemcpyAsync(v->pr(irst), at_lane(op, op->p, lane), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
     if (op->cfg.ifheat)
         NLG_HIP(hipMemcpyAsync(v->theta(0, irst), at_lane(op, op->tbuf[0], lane), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// The two time derivatives of the base flow that the bordered Jacobian of a periodic orbit needs (the reference's compute_fdot,
+// src/systems/periodic_orbit.f90:96-102), taken from the run of lane `lane` instead of from two extra impulsive restarts:
+//   FDOT_START (after the first step)  f0 = (U^1 - U^0) / dt, velocity and pressure: compute_fdot at X0 literally;
+//   FDOT_PRE   (before the last step)  fT = -sum_{j<k} bd_j U^{N-1-j} / dt, while the step still holds the level it overwrites;
+//   FDOT_END   (after the last step)   fT += b0 U^N / dt: the BDF-k derivative the step itself used, k = min(nsteps, torder);
+//                                      its pressure is (p^N - p^{N-1}) / dt = dp / dt, the one pressure level a step keeps.
+enum { FDOT_START = 0, FDOT_PRE, FDOT_END };
+int capture_fdot(nlg_linop *op, int lane, int phase) {
+    nlg_mesh *m = op->mesh;
+    const int dim = m->dim;
+    const double idt = 1.0 / op->dt;
+    nlg_vec *o = phase == FDOT_START ? op->upo_f0 : op->upo_fT;
+    DdtArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int c = 0; c < dim; ++c) A.out[c] = o->vel(c), A.n[c] = m->lvn;
+    A.out[dim] = o->pr(), A.n[dim] = m->lpn;
+    if (phase == FDOT_START) {
+        for (int c = 0; c < dim; ++c) {
+            A.src[c][0] = at_lane(op, op->ubuf[0][c], lane), A.c[c][0] = idt;
+            A.src[c][1] = op->baseflow->vel(c), A.c[c][1] = -idt;
+        }
+        A.src[dim][0] = at_lane(op, op->p, lane), A.c[dim][0] = idt;
+        A.src[dim][1] = op->baseflow->pr(), A.c[dim][1] = -idt;
+    } else if (phase == FDOT_PRE) {
+        const int k = std::min(op->nsteps, op->cfg.torder);
+        for (int c = 0; c < dim; ++c)
+            for (int j = 0; j < k; ++j) A.src[c][j] = at_lane(op, op->ubuf[j][c], lane), A.c[c][j] = -BDF_C[k][j] * idt;
+    } else {
+        const int k = std::min(op->nsteps, op->cfg.torder);
+        A.acc = 1;
+        for (int c = 0; c < dim; ++c) A.src[c][0] = at_lane(op, op->ubuf[0][c], lane), A.c[c][0] = BDF_B0[k] * idt;
+        A.src[dim][0] = at_lane(op, op->pr_x, lane), A.c[dim][0] = idt;
+        op->upo_fdot_valid = true;
+    }
+    NLG_LAUNCH(k_bdf_ddt, dim3(grid_for(m->lvn), dim + 1), dim3(NT), 0, m->ctx->stream, A);
+    NLG_HIP(hipGetLastError());
     return 0;
 }
 
@@ -2336,11 +2408,14 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     }
     if (lb >= 0) {
         op->orbit_end_valid = false;
+        op->upo_fdot_valid = false;
         NLG_TRY(load_state(op, lb, op->baseflow, 0));
     }
     const Lanes L{op, nl, lb};
     for (int istep = 1; istep <= op->nsteps; ++istep) {
+        if (lb >= 0 && istep == op->nsteps) NLG_TRY(capture_fdot(op, lb, FDOT_PRE));
         NLG_TRY(advance(L));
+        if (lb >= 0 && istep == 1) NLG_TRY(capture_fdot(op, lb, FDOT_START));
         if (istep <= nrst)
             for (int v = 0; v < s; ++v)
                 if (vin[v]->nrst > 0) {
@@ -2363,6 +2438,7 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
         NLG_TRY(nlg_vec_zero(op->orbit_end));
         NLG_TRY(store_state(op, lb, op->orbit_end, 0));
         op->orbit_end_valid = true;
+        NLG_TRY(capture_fdot(op, lb, FDOT_END));
     }
     for (int irst = 1; irst <= nrst; ++irst) {   // compute_rst, :109-127
         NLG_TRY(advance(L));
@@ -2547,6 +2623,8 @@ int nlg_linop_destroy(nlg_linop *op) {
     if (op->h_s) hipHostFree(op->h_s);
     if (op->baseflow) nlg_vec_destroy(op->baseflow);
     if (op->orbit_end) nlg_vec_destroy(op->orbit_end);
+    if (op->upo_f0) nlg_vec_destroy(op->upo_f0);
+    if (op->upo_fT) nlg_vec_destroy(op->upo_fT);
     delete op;
     return 0;
 }
@@ -2591,7 +2669,11 @@ int nlg_linop_init(nlg_linop *op) {
     }
     double *U[3] = {op->baseflow->vel(0), op->baseflow->vel(1), dim == 3 ? op->baseflow->vel(2) : nullptr};
     // dt / nsteps (reference: neklab_nek_setup.f90:195-198)
-    if (op->cfg.dt > 0.0) {
+    if (op->orbit && op->orbit_nsteps > 0) {   // nlg_linop_set_orbit_steps: the count is given, dt follows the period
+        op->nsteps = op->orbit_nsteps;
+        op->dt = op->cfg.tau / op->nsteps;
+        NLG_TRY(sem_cfl(m, U, op->dt, &op->cfl));
+    } else if (op->cfg.dt > 0.0) {
         op->nsteps = (int)std::ceil(op->cfg.tau / op->cfg.dt - 1e-12);
         op->dt = op->cfg.tau / op->nsteps;
         NLG_TRY(sem_cfl(m, U, op->dt, &op->cfl));
@@ -2879,6 +2961,8 @@ int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period) {
         if (!op->orbit) return 0;
         op->orbit = false;
         op->orbit_end_valid = false;
+        op->upo_fdot_valid = false;
+        op->orbit_nsteps = 0;
         return op->inited ? nlg_linop_init(op) : 0;   // the frozen operator about X0 with tau = period
     }
     NLG_CHECK(X0->mesh == op->mesh, "nlg_linop_set_orbit: X0 lives on a different mesh");
@@ -2887,10 +2971,116 @@ int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period) {
     NLG_CHECK(op->proj_nlines == 0, "nlg_linop_set_orbit: orbit mode and the wavenumber projection exclude each other");
     NLG_TRY(nlg_vec_copy(op->baseflow, X0));
     if (!op->orbit_end) NLG_TRY(nlg_vec_clone(op->baseflow, &op->orbit_end));
+    for (nlg_vec **f : {&op->upo_f0, &op->upo_fT})
+        if (!*f) {
+            NLG_TRY(nlg_vec_clone(op->baseflow, f));
+            NLG_TRY(nlg_vec_zero(*f));
+        }
     op->orbit_end_valid = false;
+    op->upo_fdot_valid = false;
+    op->orbit_nsteps = 0;
     op->cfg.tau = period;
     op->orbit = true;
     return nlg_linop_init(op);
+}
+
+// ---- periodic-orbit Newton (include/neklab_gpu.h; nek_upo_system / nek_upo_jacobian of the reference) ------------------------------
+#define NLG_NEED_ORBIT(op, who) NLG_CHECK((op) && (op)->orbit, "%s: %s (nlg_linop_set_orbit)", who, (op) ? "the operator is not in orbit mode" : "NULL operator, one in orbit mode is needed")
+
+int nlg_linop_set_orbit_steps(nlg_linop *op, const nlg_vec *X0, double period, int nsteps) {
+    NLG_NEED_ORBIT(op, "nlg_linop_set_orbit_steps");
+    NLG_CHECK(X0, "nlg_linop_set_orbit_steps: NULL argument");
+    NLG_CHECK(nsteps >= 0, "nlg_linop_set_orbit_steps: nsteps %d is negative (0 = CFL rule / cfg.dt)", nsteps);
+    if (nsteps == 0) return nlg_linop_set_orbit(op, X0, period);
+    NLG_NO_OTD(op, "nlg_linop_set_orbit_steps");
+    NLG_CHECK(X0->mesh == op->mesh, "nlg_linop_set_orbit_steps: X0 lives on a different mesh");
+    NLG_CHECK(period > 0.0, "nlg_linop_set_orbit_steps: the period must be positive");
+    NLG_TRY(nlg_vec_copy(op->baseflow, X0));
+    op->orbit_end_valid = false;
+    op->upo_fdot_valid = false;
+    op->orbit_nsteps = nsteps;
+    op->cfg.tau = period;
+    return nlg_linop_init(op);
+}
+
+// Phi_T(X0) - X0 with the base-flow lane alone: the nonlinear step from X0 with the operator's dt / nsteps (nonlinear_map_UPO,
+// periodic_orbit.f90:4-45; the pressure is differenced as well, vec_out%sub(vec_in))
+int nlg_upo_residual(nlg_linop *op, nlg_vec *out) {
+    NLG_NEED_ORBIT(op, "nlg_upo_residual");
+    NLG_CHECK(out, "nlg_upo_residual: NULL argument");
+    NLG_NO_OTD(op, "nlg_upo_residual");
+    NLG_CHECK(op->inited, "nlg_upo_residual: nlg_linop_init has not been called");
+    nlg_mesh *m = op->mesh;
+    NLG_CHECK(out->mesh == m && out->nscal == 0, "nlg_upo_residual: the output lives on a different mesh or carries scalars");
+    NLG_TRY(reset_state(op, 1));
+    op->istep = 0;
+    op->adjoint = 0;
+    op->nproj = 0;
+    op->upo_fdot_valid = false;
+    for (int v = 0; v < kMaxLanes; ++v) op->lane_viters[v] = op->lane_piters[v] = 0;
+    op->nonlinear = 1;
+    int rc = load_state(op, 0, op->baseflow, 0);
+    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) {
+        if (istep == op->nsteps) rc = capture_fdot(op, 0, FDOT_PRE);
+        if (rc == 0) rc = advance(Lanes{op, 1});
+        if (rc == 0 && istep == 1) rc = capture_fdot(op, 0, FDOT_START);
+    }
+    op->nonlinear = 0;
+    if (rc) return rc;
+    NLG_TRY(capture_fdot(op, 0, FDOT_END));
+    NLG_TRY(nlg_vec_zero(out));
+    DdtArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int c = 0; c <= m->dim; ++c) {
+        const bool pr = c == m->dim;
+        A.out[c] = pr ? out->pr() : out->vel(c), A.n[c] = pr ? m->lpn : m->lvn;
+        A.src[c][0] = pr ? op->p : op->ubuf[0][c], A.c[c][0] = 1.0;
+        A.src[c][1] = pr ? op->baseflow->pr() : op->baseflow->vel(c), A.c[c][1] = -1.0;
+    }
+    NLG_LAUNCH(k_bdf_ddt, dim3(grid_for(m->lvn), m->dim + 1), dim3(NT), 0, m->ctx->stream, A);
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+int nlg_upo_fdot(nlg_linop *op, int which, nlg_vec *out) {
+    NLG_NEED_ORBIT(op, "nlg_upo_fdot");
+    NLG_CHECK(out, "nlg_upo_fdot: NULL argument");
+    NLG_CHECK(which == 0 || which == 1, "nlg_upo_fdot: which = %d (0: f0 at X0, 1: fT at the end of the period)", which);
+    NLG_CHECK(op->upo_fdot_valid, "nlg_upo_fdot: no run yet (a matvec in orbit mode or nlg_upo_residual fills the derivatives)");
+    nlg_mesh *m = op->mesh;
+    NLG_CHECK(out->mesh == m && out->nscal == 0, "nlg_upo_fdot: the output lives on a different mesh or carries scalars");
+    const nlg_vec *f = which == 0 ? op->upo_f0 : op->upo_fT;
+    NLG_TRY(nlg_vec_zero(out));
+    hipStream_t st = m->ctx->stream;
+    NLG_HIP(hipMemcpyAsync(out->d, f->d, sizeof(double) * (size_t)out->main_len, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// The border of the orbit's Jacobian on an existing w = M v_in (jac_direct_map, periodic_orbit.f90:91-103): w <- w - v_in + t_in fT,
+// t_out = <f0, v_in>.  Without restart history on either vector it is one pass (upo_border_dev, vec.hip: six streams); with it, the
+// vector operations, whose history semantics the result then follows.  composed != 0 forces the vector operations.
+int nlg_upo_border(nlg_linop *op, const nlg_vec *v_in, double t_in, nlg_vec *w, double *t_out, int composed) {
+    NLG_NEED_ORBIT(op, "nlg_upo_border");
+    NLG_CHECK(v_in && w && t_out, "nlg_upo_border: NULL argument");
+    NLG_CHECK(op->upo_fdot_valid, "nlg_upo_border: no run yet (a matvec in orbit mode or nlg_upo_residual fills the derivatives)");
+    NLG_CHECK(v_in->mesh == op->mesh && w->mesh == op->mesh && v_in->nscal == 0 && w->nscal == 0 && v_in != w,
+              "nlg_upo_border: the vectors live on a different mesh, carry scalars or are the same");
+    NLG_CHECK(op->upo_fT->nscal == 0, "nlg_upo_border: the operator's base flow carries scalars; orbit mode does not");
+    if (!composed && v_in->nrst == 0 && w->nrst == 0) {
+        NLG_TRY(upo_border_dev(w, v_in, op->upo_fT, op->upo_f0, t_in, 0));
+    } else {
+        NLG_TRY(nlg_vec_axpby(-1.0, v_in, 1.0, w));
+        NLG_TRY(nlg_vec_axpby(t_in, op->upo_fT, 1.0, w));
+        NLG_TRY(dev_dot(v_in, op->upo_f0, 0));
+    }
+    return scalars_to_host(op->mesh->ctx, 0, 1, t_out);
+}
+
+int nlg_upo_jac_matvec(nlg_linop *op, const nlg_vec *v_in, double t_in, nlg_vec *v_out, double *t_out) {
+    NLG_NEED_ORBIT(op, "nlg_upo_jac_matvec");
+    NLG_CHECK(v_in && v_out && t_out, "nlg_upo_jac_matvec: NULL argument");
+    NLG_TRY(do_matvec(op, v_in, v_out, 0));
+    return nlg_upo_border(op, v_in, t_in, v_out, t_out, 0);
 }
 
 int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out) {

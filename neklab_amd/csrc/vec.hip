@@ -118,6 +118,42 @@ __global__ __launch_bounds__(NT) void k_dot_partial(const double *a, const doubl
     if (threadIdx.x == 0) partial[c * nblk + blockIdx.x] = s;
 }
 
+// Border of the periodic-orbit Jacobian in one pass (nlg_upo_border): over the main block of the vectors, field c = blockIdx.y of
+// ncomp + 1 (the pressure last),  w_c <- (w_c - v_c) + t fT_c  with the rounding of the two axpby sweeps it replaces, and over the
+// ncomp inner-product fields the first stage of <f0, v> in the partition and summation order of k_dot_partial:
+// partial[c*nblk + blk] = sum v_c f0_c bm1.  Reads w, v, fT, f0, bm1 and writes w: six streams against the nine of sub + axpby + dot.
+__global__ __launch_bounds__(NT) void k_upo_border(double *w, const double *v, const double *fT, const double *f0, const double *bm1,
+                                                   double t, int64_t lvs, int64_t lps, int ncomp, int nblk, double *partial) {
+    __shared__ double sm[4];
+    const int c = blockIdx.y;
+    const bool ip = c < ncomp;
+    const int64_t n2 = (ip ? lvs : lps) >> 1;
+    const int64_t per = (n2 + nblk - 1) / nblk;
+    const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
+    const int64_t off = (int64_t)c * lvs;
+    double2 *w2 = reinterpret_cast<double2 *>(w + off);
+    const double2 *v2 = reinterpret_cast<const double2 *>(v + off);
+    const double2 *t2 = reinterpret_cast<const double2 *>(fT + off);
+    const double2 *f2 = reinterpret_cast<const double2 *>(f0 + off);
+    const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
+    double acc = 0.0;
+    for (int64_t i = beg + threadIdx.x; i < end; i += NT) {
+        const double2 vv = v2[i], tv = t2[i];
+        double2 wv = w2[i];
+        wv.x = __dadd_rn(__dadd_rn(wv.x, -vv.x), __dmul_rn(t, tv.x));
+        wv.y = __dadd_rn(__dadd_rn(wv.y, -vv.y), __dmul_rn(t, tv.y));
+        w2[i] = wv;
+        if (ip) {
+            const double2 fv = f2[i], mv = m2[i];
+            acc += vv.x * fv.x * mv.x + vv.y * fv.y * mv.y;
+        }
+    }
+    if (ip) {   // (uniform per block)
+        const double s = block_sum(acc, sm);
+        if (threadIdx.x == 0) partial[c * nblk + blockIdx.x] = s;
+    }
+}
+
 // second stage, fixed order => deterministic: out[row] (+)= sum_b partial[row*nper + b]
 __global__ __launch_bounds__(NT) void k_reduce_rows(const double *partial, int nper, double *out, int accumulate,
                                                     double *out2) {
@@ -515,6 +551,19 @@ int dev_dot(const nlg_vec *a, const nlg_vec *b, int slot) {
                        a->mesh->lvs, nblk, ctx->d_partial);
     NLG_LAUNCH(k_reduce_rows, dim3(1), dim3(NT), 0, ctx->stream, ctx->d_partial, nblk * a->ncomp,
                        ctx->d_scalars + slot, 0, (double *)nullptr);
+    NLG_HIP(hipGetLastError());
+    NLG_TRY(allreduce_sum(ctx, ctx->d_scalars + slot, 1));
+    return 0;
+}
+
+// w <- w - v + t fT on the main block, <f0, v> left on device at ctx->d_scalars[slot] (allreduced); no vector carries history
+int upo_border_dev(nlg_vec *w, const nlg_vec *v, const nlg_vec *fT, const nlg_vec *f0, double t, int slot) {
+    nlg_mesh *m = w->mesh;
+    nlg_ctx *ctx = m->ctx;
+    const int nblk = dot_nblk(w);
+    NLG_LAUNCH(k_upo_border, dim3(nblk, w->ncomp + 1), dim3(NT), 0, ctx->stream, w->d, (const double *)v->d, (const double *)fT->d,
+               (const double *)f0->d, (const double *)m->d_bm1, t, m->lvs, m->lps, w->ncomp, nblk, ctx->d_partial);
+    NLG_LAUNCH(k_reduce_rows, dim3(1), dim3(NT), 0, ctx->stream, ctx->d_partial, nblk * w->ncomp, ctx->d_scalars + slot, 0, (double *)nullptr);
     NLG_HIP(hipGetLastError());
     NLG_TRY(allreduce_sum(ctx, ctx->d_scalars + slot, 1));
     return 0;

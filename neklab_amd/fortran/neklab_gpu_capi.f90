@@ -275,6 +275,65 @@ module neklab_gpu_capi
          type(c_ptr), value :: op, vout
          integer(c_int) :: rc
       end function
+      ! periodic-orbit Newton (include/neklab_gpu.h, nlg_upo_*) and the Krylov basis its GMRES keeps on the device
+      function c_linop_set_orbit_steps(op, X0, period, nsteps) bind(C, name="nlg_linop_set_orbit_steps") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: op, X0
+         real(c_double), value :: period
+         integer(c_int), value :: nsteps
+         integer(c_int) :: rc
+      end function
+      function c_upo_residual(op, vout) bind(C, name="nlg_upo_residual") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: op, vout
+         integer(c_int) :: rc
+      end function
+      function c_upo_fdot(op, which, vout) bind(C, name="nlg_upo_fdot") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: op, vout
+         integer(c_int), value :: which
+         integer(c_int) :: rc
+      end function
+      function c_upo_jac_matvec(op, vin, t_in, vout, t_out) bind(C, name="nlg_upo_jac_matvec") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: op, vin, vout
+         real(c_double), value :: t_in
+         real(c_double), intent(out) :: t_out
+         integer(c_int) :: rc
+      end function
+      function c_upo_arnoldi_step(op, basis, tcol, k, H, ldh) bind(C, name="nlg_upo_arnoldi_step") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: op, basis
+         real(c_double), intent(inout) :: tcol(*), H(*)
+         integer(c_int), value :: k, ldh
+         integer(c_int) :: rc
+      end function
+      function c_basis_create(mesh, nscal, lorder, nvec, b) bind(C, name="nlg_basis_create") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: mesh
+         integer(c_int), value :: nscal, lorder, nvec
+         type(c_ptr), intent(out) :: b
+         integer(c_int) :: rc
+      end function
+      function c_basis_destroy(b) bind(C, name="nlg_basis_destroy") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: b
+         integer(c_int) :: rc
+      end function
+      function c_basis_vec(b, i, v) bind(C, name="nlg_basis_vec") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: b
+         integer(c_int), value :: i
+         type(c_ptr), intent(out) :: v
+         integer(c_int) :: rc
+      end function
+      function c_basis_combine(b, k, c, vout) bind(C, name="nlg_basis_combine") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: b, vout
+         integer(c_int), value :: k
+         real(c_double), intent(in) :: c(*)
+         integer(c_int) :: rc
+      end function
       function c_dense_eig(n, A, lda, wr, wi, vr, ldvr) bind(C, name="nlg_dense_eig") result(rc)
          import c_int, c_double
          integer(c_int), value :: n, lda, ldvr

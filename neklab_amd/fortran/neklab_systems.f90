@@ -5,6 +5,7 @@
 !!        reference's umbrella module and its thermosyphon case spell them nek_system_temp / nek_jacobian_temp,
 !!        src/neklab.f90:63-64, examples/thermosyphon/baseflow/tsyphon.usr:13,38-39 -- both spellings exist here)
 !!   nek_constant_tol / nek_dynamic_tol  neklab_systems.f90:229-335
+!!   nek_upo_system / nek_upo_jacobian    neklab_systems.f90:147-223, periodic_orbit.f90 (below, with gmres_upo)
 !! The reference integrates with Nek5000's global solver state; here each system / Jacobian owns a device propagator
 !! (exptA_linop) over the horizon `endtime` of the case (neklab_gpu_set_case(endtime=..): Nek5000's endTime, which
 !! setup_nonlinear_solver integrates to) and forwards:
@@ -13,7 +14,7 @@
 !!                              (fixed_point.f90:40-96); rmatvec likewise with the adjoint propagator
 module neklab_systems
    use iso_c_binding
-   use LightKrylov, only: dp, atol_dp, abstract_vector_rdp, abstract_system_rdp, abstract_jacobian_linop_rdp, type_error
+   use LightKrylov, only: dp, atol_dp, abstract_vector_rdp, abstract_linop_rdp, abstract_system_rdp, abstract_jacobian_linop_rdp, type_error
    use neklab_gpu_capi
    use neklab_vectors
    use neklab_linops
@@ -48,6 +49,44 @@ module neklab_systems
    end type
    type, extends(nek_jacobian), public :: nek_jacobian_temp
    end type
+
+   !> nek_upo_system / nek_upo_jacobian (neklab_systems.f90:147-223, src/systems/periodic_orbit.f90): Newton-Krylov for a periodic
+   !! orbit on nek_ext_dvector = (state, period).  Each owns one device propagator in orbit mode and forwards
+   !!   response(X, F, atol)  ->  nlg_linop_set_orbit_steps(X, T), tolerances 0.1 atol, nlg_upo_residual; F%T = 0      (:4-45)
+   !!   jacobian%matvec       ->  the same state call about self%X, tolerances 0.1 of the scheduler's, nlg_upo_jac_matvec:
+   !!                              (M - I) dx + dT fT, <f0, dx>                                                        (:47-115)
+   !!   jacobian%rmatvec      ->  stops: orbit mode has no adjoint (jac_adjoint_map is not built)
+   !! compute_rst / get_rst as exptA_linop has them: the device matvec does both internally.  The umbrella's names
+   !! nek_system_upo / nek_jacobian_upo (src/neklab.f90:63-64) exist as well.  upo_fixed_nsteps > 0 pins the step count of the orbit
+   !! (0: the CFL rule with cfl_limit 0.4, or the case's dt, applied to every new (X, T)).  The system and the Jacobian are separate
+   !! objects here as in the reference, so each holds an operator of its own (work buffers and the two derivative vectors twice);
+   !! matvec sets the state about self%X -- a full operator set-up -- on every application, gmres_upo once per solve.
+   type, extends(abstract_system_rdp), public :: nek_upo_system
+      type(exptA_orbit_linop), allocatable, private :: prop
+      logical, private :: ready = .false.
+   contains
+      private
+      procedure, pass(self), public :: response => nonlinear_map_upo
+   end type nek_upo_system
+
+   type, extends(abstract_jacobian_linop_rdp), public :: nek_upo_jacobian
+      type(exptA_orbit_linop), allocatable, private :: prop
+      logical, private :: ready = .false.
+   contains
+      private
+      procedure, pass(self), public :: matvec => jac_direct_map
+      procedure, pass(self), public :: rmatvec => jac_adjoint_map
+      procedure, pass(self), public :: compute_rst => jac_compute_rst
+      procedure, pass(self), public :: get_rst => jac_get_rst
+   end type nek_upo_jacobian
+
+   type, extends(nek_upo_system), public :: nek_system_upo
+   end type
+   type, extends(nek_upo_jacobian), public :: nek_jacobian_upo
+   end type
+
+   integer, save, public :: upo_fixed_nsteps = 0, upo_gmres_kdim = 30
+   public :: gmres_upo
 
    !> the solver tolerance the schedulers last chose = what Nek5000 keeps in param(21) / param(22) (neklab_systems.f90:261-264)
    !> the reference's param(22) (Nek5000's velocity tolerance), which its schedulers, nonlinear_map and the Jacobian products read and
@@ -142,6 +181,233 @@ contains
       class(abstract_vector_rdp), intent(out) :: vec_out
       call jac_apply(self, vec_in, vec_out, .true.)
    end subroutine
+
+   !---- periodic orbits ------------------------------------------------------------------------------------------------------
+   !> the operator in orbit mode about (X, T): created on first use, afterwards nlg_linop_set_orbit_steps with the new state
+   subroutine orbit_state(prop, ready, X)
+      type(exptA_orbit_linop), allocatable, intent(inout) :: prop
+      logical, intent(inout) :: ready
+      type(nek_ext_dvector), intent(in) :: X
+      if (.not. ready) then
+         allocate (prop)
+         prop%tau = X%T
+         prop%baseflow = X%vec
+         call prop%init()                              ! cfl_limit 0.4 (periodic_orbit.f90:18, :67), nlg_linop_set_orbit
+         ready = .true.
+         if (upo_fixed_nsteps <= 0) return              ! the count is left to the rule: set_orbit has set this state already
+      end if
+      prop%tau = X%T
+      call nlg_check(c_linop_set_orbit_steps(prop%handle(), nek_dvector_handle(X%vec), X%T, int(upo_fixed_nsteps, c_int)), 'nek_upo: state')
+   end subroutine
+
+   subroutine nonlinear_map_upo(self, vec_in, vec_out, atol)
+      class(nek_upo_system), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      real(dp), intent(in) :: atol
+      select type (vec_in)
+      type is (nek_ext_dvector)
+         select type (vec_out)
+         type is (nek_ext_dvector)
+            call orbit_state(self%prop, self%ready, vec_in)
+            call self%prop%set_tolerances(0.1_dp*atol, 0.1_dp*atol)
+            call nek_dvector_ensure(vec_out%vec)
+            call nlg_check(c_upo_residual(self%prop%handle(), vec_out%vec%h), 'nonlinear_map_upo')      ! Phi_T(X) - X
+            vec_out%T = 0.0_dp
+         class default
+            call type_error('vec_out', 'nek_ext_dvector', 'OUT', this_module, 'nonlinear_map_upo')
+         end select
+      class default
+         call type_error('vec_in', 'nek_ext_dvector', 'IN', this_module, 'nonlinear_map_upo')
+      end select
+   end subroutine
+
+   !> handle of the Jacobian's operator, set about self%X at the scheduler's tolerance
+   function upo_jacobian_handle(self) result(h)
+      class(nek_upo_jacobian), intent(inout) :: self
+      type(c_ptr) :: h
+      if (.not. allocated(self%X)) then
+         write (*, '(A)') 'ERROR in '//this_module//': jacobian%X is not set'
+         error stop 1
+      end if
+      h = c_null_ptr
+      select type (state => self%X)
+      type is (nek_ext_dvector)
+         call orbit_state(self%prop, self%ready, state)
+         call self%prop%set_tolerances(0.1_dp*solver_tol, 0.1_dp*solver_tol)
+         h = self%prop%handle()
+      class default
+         call type_error('self%X', 'nek_ext_dvector', 'IN', this_module, 'nek_upo_jacobian')
+      end select
+   end function
+
+   subroutine jac_direct_map(self, vec_in, vec_out)
+      class(nek_upo_jacobian), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      type(c_ptr) :: h
+      ! about the current X on every application, as the reference does (abs_ext_vec2nek(.., self%X), periodic_orbit.f90:60)
+      h = upo_jacobian_handle(self)
+      select type (vec_in)
+      type is (nek_ext_dvector)
+         select type (vec_out)
+         type is (nek_ext_dvector)
+            call nek_dvector_ensure(vec_out%vec)
+            call nlg_check(c_upo_jac_matvec(h, nek_dvector_handle(vec_in%vec), vec_in%T, vec_out%vec%h, vec_out%T), 'jac_direct_map')
+         class default
+            call type_error('vec_out', 'nek_ext_dvector', 'OUT', this_module, 'jac_direct_map')
+         end select
+      class default
+         call type_error('vec_in', 'nek_ext_dvector', 'IN', this_module, 'jac_direct_map')
+      end select
+   end subroutine
+
+   !> the library's refusal, then stop (as exptA_orbit_linop%rmatvec)
+   subroutine jac_adjoint_map(self, vec_in, vec_out)
+      class(nek_upo_jacobian), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      type(c_ptr) :: h
+      h = upo_jacobian_handle(self)
+      select type (vec_in)
+      type is (nek_ext_dvector)
+         select type (vec_out)
+         type is (nek_ext_dvector)
+            call self%prop%rmatvec(vec_in%vec, vec_out%vec)
+         end select
+      end select
+      write (*, '(A)') 'ERROR in '//this_module//': nek_upo_jacobian has no adjoint (orbit mode)'
+      error stop 1
+   end subroutine
+
+   subroutine jac_compute_rst(self, vec_out, nrst)
+      class(nek_upo_jacobian), intent(inout) :: self
+      class(abstract_vector_rdp), intent(inout) :: vec_out
+      integer, intent(in) :: nrst
+      select type (vec_out)
+      type is (nek_ext_dvector)
+         if (allocated(self%prop)) call self%prop%compute_rst(vec_out%vec, nrst)
+      class default
+         call type_error('vec_out', 'nek_ext_dvector', 'OUT', this_module, 'jac_compute_rst')
+      end select
+   end subroutine
+
+   !> Replay of vec_in's history slot: with restart history on (no_history = 0 in the case) the device matvec performs it inside its
+   !! time loop for the field part, as for exptA_linop; the period component of the slots (nek_ext_dvector%Trst) is carried by the
+   !! vector algebra only, the Jacobian does not read it.  Under the drivers' default, no_history = 1, there is nothing to replay.
+   subroutine jac_get_rst(self, vec_in, istep)
+      class(nek_upo_jacobian), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      integer, intent(in) :: istep
+      select type (vec_in)
+      type is (nek_ext_dvector)
+      class default
+         call type_error('vec_in', 'nek_ext_dvector', 'IN', this_module, 'jac_get_rst')
+      end select
+   end subroutine
+
+   !> Restarted GMRES(kdim) for the bordered Jacobian J x = b on extended vectors, zero initial guess, stop at |r| <= atol: a linear
+   !! solver with LightKrylov's interface (newton(sys, X, gmres_upo, ..)) whose Krylov loop runs on the device -- the basis in one
+   !! allocation, nlg_upo_arnoldi_step (Jacobian matvec + CGS2 in the extended inner product) per step, Givens rotations on the host.
+   !! No restart-history replay: every new Krylov vector is stripped of its history.  Krylov dimension upo_gmres_kdim, at most 10
+   !! cycles.  info = Jacobian matvecs.
+   subroutine gmres_upo(A, b, x, info, atol)
+      class(abstract_linop_rdp), intent(inout) :: A
+      class(abstract_vector_rdp), intent(in) :: b
+      class(abstract_vector_rdp), intent(inout) :: x
+      integer, intent(out) :: info
+      real(dp), intent(in) :: atol
+      integer, parameter :: nmax = 10
+      type(c_ptr) :: h, basis, col
+      type(nek_ext_dvector) :: r, dx, Jx
+      real(dp), allocatable :: Hm(:, :), Rm(:, :), cs(:), sn(:), g(:), hk(:), y(:), tcol(:)
+      real(dp) :: res, beta, t, d
+      integer :: kd, k, i, j, cyc
+      kd = upo_gmres_kdim
+      info = 0
+      select type (A)
+      class is (nek_upo_jacobian)
+         h = upo_jacobian_handle(A)
+      class default
+         call type_error('A', 'nek_upo_jacobian', 'IN', this_module, 'gmres_upo')
+      end select
+      select type (b)
+      type is (nek_ext_dvector)
+         r = b
+      class default
+         call type_error('b', 'nek_ext_dvector', 'IN', this_module, 'gmres_upo')
+      end select
+      call x%zero()
+      call nlg_check(c_basis_create(nlg_mesh, 0_c_int, int(nek_lorder, c_int), int(kd + 1, c_int), basis), 'gmres_upo')
+      allocate (Hm(kd + 2, kd + 1), Rm(kd + 1, kd), cs(kd), sn(kd), g(kd + 1), hk(kd + 2), y(kd), tcol(kd + 2))
+      res = r%norm()
+      do cyc = 1, nmax
+         beta = res
+         if (beta <= atol) exit
+         tcol = 0.0_dp
+         call nlg_check(c_basis_vec(basis, 0_c_int, col), 'gmres_upo')
+         call nlg_check(c_vec_copy(col, nek_dvector_handle(r%vec)), 'gmres_upo')
+         call nlg_check(c_vec_scal(col, 1.0_dp/beta), 'gmres_upo')
+         tcol(1) = r%T/beta
+         Hm = 0.0_dp; Rm = 0.0_dp; cs = 0.0_dp; sn = 0.0_dp; g = 0.0_dp
+         g(1) = beta
+         k = 0
+         do while (k < kd)
+            call nlg_check(c_upo_arnoldi_step(h, basis, tcol, int(k, c_int), Hm, int(kd + 2, c_int)), 'gmres_upo')
+            info = info + 1
+            call nlg_check(c_basis_vec(basis, int(k + 1, c_int), col), 'gmres_upo')
+            call nlg_check(c_vec_clear_rst(col), 'gmres_upo')
+            hk(1:k + 2) = Hm(1:k + 2, k + 1)
+            do i = 1, k                                    ! previous rotations
+               t = cs(i)*hk(i) + sn(i)*hk(i + 1)
+               hk(i + 1) = -sn(i)*hk(i) + cs(i)*hk(i + 1)
+               hk(i) = t
+            end do
+            d = sqrt(hk(k + 1)*hk(k + 1) + hk(k + 2)*hk(k + 2))
+            if (d == 0.0_dp) then
+               cs(k + 1) = 1.0_dp; sn(k + 1) = 0.0_dp
+            else
+               cs(k + 1) = hk(k + 1)/d; sn(k + 1) = hk(k + 2)/d
+            end if
+            hk(k + 1) = d; hk(k + 2) = 0.0_dp
+            Rm(1:k + 1, k + 1) = hk(1:k + 1)
+            g(k + 2) = -sn(k + 1)*g(k + 1)
+            g(k + 1) = cs(k + 1)*g(k + 1)
+            k = k + 1
+            res = abs(g(k + 1))
+            if (res <= atol) exit
+         end do
+         do i = k, 1, -1                                   ! R y = g, summed in the order of the Python driver
+            t = g(i)
+            do j = i + 1, k
+               t = t - Rm(i, j)*y(j)
+            end do
+            y(i) = t/Rm(i, i)
+         end do
+         call nek_dvector_ensure(dx%vec)
+         call nlg_check(c_basis_combine(basis, int(k, c_int), y, dx%vec%h), 'gmres_upo')
+         dx%T = 0.0_dp
+         do j = 1, k
+            dx%T = dx%T + tcol(j)*y(j)
+         end do
+         call x%axpby(1.0_dp, dx, 1.0_dp)
+         if (res <= atol) exit
+         select type (x)                                   ! true residual for the restart
+         type is (nek_ext_dvector)
+            call nek_dvector_ensure(Jx%vec)
+            call nlg_check(c_upo_jac_matvec(h, nek_dvector_handle(x%vec), x%T, Jx%vec%h, Jx%T), 'gmres_upo')
+            info = info + 1
+            call Jx%vec%clear_rst_fields()
+         end select
+         select type (b)
+         type is (nek_ext_dvector)
+            r = b
+         end select
+         call r%axpby(-1.0_dp, Jx, 1.0_dp)
+         res = r%norm()
+      end do
+      call nlg_check(c_basis_destroy(basis), 'gmres_upo')
+   end subroutine gmres_upo
 
    !> constant solver tolerance = the target, never below 10 atol_dp
    subroutine nek_constant_tol(tol, target_tol, rnorm, iter, info)

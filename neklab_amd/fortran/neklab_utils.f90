@@ -12,10 +12,18 @@ module neklab_utils
    implicit none
    private
    public :: nek2vec, vec2nek, outpost_dnek, set_outpost_session
+   public :: nek2ext_vec, ext_vec2nek, outpost_ext_dnek, get_period
 
    interface outpost_dnek
       module procedure outpost_dnek_vector
       module procedure outpost_dnek_basis
+   end interface
+
+   !> nek_ext_dvector (the state of a periodic orbit): the same movers on its field part (src/neklab_utils.f90:174-224), the field file
+   !! with the period in the header's time
+   interface outpost_ext_dnek
+      module procedure outpost_ext_dnek_vector
+      module procedure outpost_ext_dnek_basis
    end interface
 
    character(len=80), save :: session = 'neklab'
@@ -54,10 +62,49 @@ contains
       if (nek_nscal > 0) call nlg_check(c_vec_get_field(h, 4_c_int, 0_c_int, t_, nek_lvn), 'vec2nek t')
    end subroutine
 
-   !> one field file per call, numbered per prefix like Nek5000's outpost; the coordinates go into the first file of a prefix
+   subroutine nek2ext_vec(vec, vx_, vy_, vz_, pr_, t_)
+      type(nek_ext_dvector), intent(inout) :: vec
+      real(dp), intent(in) :: vx_(*), vy_(*), vz_(*), pr_(*), t_(*)
+      call nek2vec(vec%vec, vx_, vy_, vz_, pr_, t_)      ! (the period is not a Nek5000 field: vec%T stays)
+   end subroutine
+
+   subroutine ext_vec2nek(vx_, vy_, vz_, pr_, t_, vec)
+      real(dp), intent(inout) :: vx_(*), vy_(*), vz_(*), pr_(*), t_(*)
+      type(nek_ext_dvector), intent(in) :: vec
+      call vec2nek(vx_, vy_, vz_, pr_, t_, vec%vec)
+   end subroutine
+
+   pure real(dp) function get_period(vec) result(period)
+      type(nek_ext_dvector), intent(in) :: vec
+      period = vec%T
+   end function
+
+   subroutine outpost_ext_dnek_vector(vec, prefix)
+      type(nek_ext_dvector), intent(in) :: vec
+      character(len=3), intent(in) :: prefix
+      call outpost_one(vec%vec, prefix, vec%T)
+   end subroutine
+
+   subroutine outpost_ext_dnek_basis(vec, prefix)
+      type(nek_ext_dvector), intent(in) :: vec(:)
+      character(len=3), intent(in) :: prefix
+      integer :: i
+      do i = 1, size(vec)
+         call outpost_one(vec(i)%vec, prefix, vec(i)%T)
+      end do
+   end subroutine
+
    subroutine outpost_dnek_vector(vec, prefix)
       type(nek_dvector), intent(in) :: vec
       character(len=3), intent(in) :: prefix
+      call outpost_one(vec, prefix, 0.0_dp)
+   end subroutine
+
+   !> one field file per call, numbered per prefix like Nek5000's outpost; the coordinates go into the first file of a prefix
+   subroutine outpost_one(vec, prefix, time)
+      type(nek_dvector), intent(in) :: vec
+      character(len=3), intent(in) :: prefix
+      real(dp), intent(in) :: time
       character(len=256) :: fname
       integer :: i, slot
       slot = 0
@@ -71,7 +118,7 @@ contains
       seen_count(slot) = seen_count(slot) + 1
       write (fname, '(A,A,A,I5.5)') prefix, trim(session), '0.f', seen_count(slot)
       call nlg_check(c_vec_outpost(nek_dvector_handle(vec), trim(fname)//c_null_char, merge(1, 0, seen_count(slot) == 1), &
-                                   0.0_c_double, int(seen_count(slot), c_int)), 'outpost_dnek')
+                                   real(time, c_double), int(seen_count(slot), c_int)), 'outpost_dnek')
    end subroutine
 
    subroutine outpost_dnek_basis(vec, prefix)

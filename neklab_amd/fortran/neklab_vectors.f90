@@ -6,6 +6,7 @@
 !!   constructor nek_dvector(vx, vy, ..)  src/vectors/neklab_vectors.f90:53-61
 !!   zero/rand/scal/axpby/dot/get_size    src/vectors/real_vectors.f90:37-247
 !!   save_rst/get_rst/has_rst_fields/clear_rst_fields               :249-346
+!!   type nek_ext_dvector (+ T)           src/vectors/real_extended_vectors.f90
 !!
 !! Object semantics.  The reference's vectors are plain static arrays: intrinsic assignment, sourced allocation and
 !! structure constructors deep-copy them (SURVEY.md 7.3 item 5).  Here the fields live in HBM behind an opaque handle, so
@@ -69,6 +70,26 @@ module neklab_vectors
       procedure, pass(self), public :: dot => nek_zdot
       procedure, pass(self), public :: get_size => nek_zsize
    end type nek_zvector
+
+   !> nek_ext_dvector (src/vectors/neklab_vectors.f90, real_extended_vectors.f90): the state of a periodic orbit, a nek_dvector (`vec`,
+   !! fields in HBM) plus the period `T`; the inner product adds T T.  Trst: the period component of the restart-history slots.
+   type, extends(abstract_vector_rdp), public :: nek_ext_dvector
+      type(nek_dvector) :: vec
+      real(dp) :: T = 0.0_dp
+      real(dp) :: Trst(4) = 0.0_dp
+   contains
+      private
+      procedure, pass(self), public :: zero => nek_ext_dzero
+      procedure, pass(self), public :: rand => nek_ext_drand
+      procedure, pass(self), public :: scal => nek_ext_dscal
+      procedure, pass(self), public :: axpby => nek_ext_daxpby
+      procedure, pass(self), public :: dot => nek_ext_ddot
+      procedure, pass(self), public :: get_size => nek_ext_dsize
+      procedure, pass(self), public :: save_rst => ext_dsave_rst
+      procedure, pass(self), public :: get_rst => ext_dget_rst
+      procedure, pass(self), public :: has_rst_fields => ext_dhas_rst_fields
+      procedure, pass(self), public :: clear_rst_fields => ext_dclear_rst_fields
+   end type nek_ext_dvector
 
    ! --> Constructor (reference: construct_nek_dvector, neklab_vectors.f90:53-61; not pure: it allocates device memory)
    interface nek_dvector
@@ -312,6 +333,106 @@ contains
       integer :: n
       n = 2*self%re%get_size()
    end function
+
+   !---- nek_ext_dvector: the field part through the real vector's procedures, the period on the host ---------------------------
+   subroutine nek_ext_dzero(self)
+      class(nek_ext_dvector), intent(inout) :: self
+      call self%vec%zero()
+      self%T = 0.0_dp; self%Trst = 0.0_dp
+   end subroutine
+
+   subroutine nek_ext_drand(self, ifnorm)
+      class(nek_ext_dvector), intent(inout) :: self
+      logical, optional, intent(in) :: ifnorm
+      real(dp) :: nrm
+      call self%vec%rand(.false.)
+      call random_number(self%T)                    ! real_extended_vectors.f90:117
+      if (present(ifnorm)) then
+         if (ifnorm) then
+            nrm = sqrt(nek_ext_ddot(self, self))
+            call nek_ext_dscal(self, 1.0_dp/nrm)
+         end if
+      end if
+   end subroutine
+
+   subroutine nek_ext_dscal(self, alpha)
+      class(nek_ext_dvector), intent(inout) :: self
+      real(dp), intent(in) :: alpha
+      call self%vec%scal(alpha)
+      self%T = alpha*self%T; self%Trst = alpha*self%Trst
+   end subroutine
+
+   subroutine nek_ext_daxpby(alpha, vec, beta, self)
+      class(nek_ext_dvector), intent(inout) :: self
+      real(dp), intent(in) :: alpha
+      class(abstract_vector_rdp), intent(in) :: vec
+      real(dp), intent(in) :: beta
+      select type (vec)
+      type is (nek_ext_dvector)
+         call self%vec%axpby(alpha, vec%vec, beta)
+         self%T = beta*self%T + alpha*vec%T
+         self%Trst = beta*self%Trst + alpha*vec%Trst
+      class default
+         call type_error('vec', 'nek_ext_dvector', 'IN', this_module, 'nek_ext_daxpby')      ! real_extended_vectors.f90:216-218
+      end select
+   end subroutine
+
+   function nek_ext_ddot(self, vec) result(alpha)
+      class(nek_ext_dvector), intent(in) :: self
+      class(abstract_vector_rdp), intent(in) :: vec
+      real(dp) :: alpha
+      alpha = 0.0_dp
+      select type (vec)
+      type is (nek_ext_dvector)
+         alpha = self%vec%dot(vec%vec) + self%T*vec%T
+      class default
+         call type_error('vec', 'nek_ext_dvector', 'IN', this_module, 'nek_ext_ddot')        ! real_extended_vectors.f90:245-247
+      end select
+   end function
+
+   pure function nek_ext_dsize(self) result(n)
+      class(nek_ext_dvector), intent(in) :: self
+      integer :: n
+      n = self%vec%get_size() + 1
+   end function
+
+   subroutine ext_dsave_rst(self, vec_rst, irst)
+      class(nek_ext_dvector), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_rst
+      integer, intent(in) :: irst
+      select type (vec_rst)
+      type is (nek_ext_dvector)
+         call self%vec%save_rst(vec_rst%vec, irst)
+         if (irst >= 1 .and. irst <= size(self%Trst)) self%Trst(irst) = vec_rst%T
+      class default
+         call type_error('vec_rst', 'nek_ext_dvector', 'IN', this_module, 'ext_dsave_rst')
+      end select
+   end subroutine
+
+   subroutine ext_dget_rst(self, vec_rst, irst)
+      class(nek_ext_dvector), intent(in) :: self
+      class(abstract_vector_rdp), intent(inout) :: vec_rst
+      integer, intent(in) :: irst
+      select type (vec_rst)
+      type is (nek_ext_dvector)
+         call self%vec%get_rst(vec_rst%vec, irst)
+         if (irst >= 1 .and. irst <= size(self%Trst)) vec_rst%T = self%Trst(irst)
+      class default
+         call type_error('vec_rst', 'nek_ext_dvector', 'OUT', this_module, 'ext_dget_rst')
+      end select
+   end subroutine
+
+   pure function ext_dhas_rst_fields(self) result(has_rst_fields)
+      class(nek_ext_dvector), intent(in) :: self
+      logical :: has_rst_fields
+      has_rst_fields = self%vec%has_rst_fields()
+   end function
+
+   subroutine ext_dclear_rst_fields(self)
+      class(nek_ext_dvector), intent(inout) :: self
+      call self%vec%clear_rst_fields()
+      self%Trst = 0.0_dp
+   end subroutine
 
    !> intrinsic-assignment semantics of the reference's by-value vectors: deep copy
    subroutine assign_dvector(lhs, rhs)

@@ -717,6 +717,253 @@ def newton_fixed_point_iteration(sys: nek_system, bf: nek_dvector, tol: float, t
             "evals": sys.n_eval, "gmres_residuals": gmres_hist}
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Periodic orbits: Newton-Krylov for the state and the period.  Reference: nek_ext_dvector (src/vectors/real_extended_vectors.f90),
+# nek_upo_system / nek_upo_jacobian (src/systems/periodic_orbit.f90, neklab_systems.f90:147-223), driven by
+# examples/cylinder/newton/Re180_periodic_orbit/1cyl.usr.  The Jacobian's time stepping is the coupled (orbit) matvec; the border
+# (period column, phase row), the two time derivatives and the extended Arnoldi step are device work (nlg_upo_*); GMRES and Newton
+# are the host loops of `gmres` / `newton_fixed_point_iteration` on extended vectors.  DESIGN.md 3.2 "Periodic-orbit Newton".
+class nek_ext_dvector:
+    """reference: type nek_ext_dvector: a nek_dvector (`vec`) plus the period `T`; the inner product adds T T."""
+
+    def __init__(self, mesh: Mesh, lorder: int = 3, T: float = 0.0, _vec: "nek_dvector | None" = None):
+        self.vec = _vec if _vec is not None else nek_dvector(mesh, 0, lorder)
+        self.mesh, self.lib, self.lorder = mesh, mesh.lib, self.vec.lorder
+        self.T = float(T)
+
+    def zero(self):
+        self.vec.zero()
+        self.T = 0.0
+
+    def rand(self, ifnorm: bool = False, seed: int = 0):
+        """the field as nek_dvector.rand; T uniform in [0, 1) from the same seed (the reference draws it from the compiler's RNG)"""
+        self.vec.rand(False, seed)
+        self.T = float(np.random.default_rng(seed).random())
+        if ifnorm:
+            self.scal(1.0 / self.norm())
+
+    def scal(self, alpha: float):
+        self.vec.scal(alpha)
+        self.T *= float(alpha)
+
+    def axpby(self, alpha: float, vec: "nek_ext_dvector", beta: float):
+        """self = alpha*vec + beta*self"""
+        if not isinstance(vec, nek_ext_dvector):
+            raise TypeError("type_error: vec must be nek_ext_dvector (reference: real_extended_vectors.f90:216-218)")
+        self.vec.axpby(alpha, vec.vec, beta)
+        self.T = float(beta) * self.T + float(alpha) * vec.T
+
+    def dot(self, vec: "nek_ext_dvector") -> float:
+        if not isinstance(vec, nek_ext_dvector):
+            raise TypeError("type_error: vec must be nek_ext_dvector (reference: real_extended_vectors.f90:245-247)")
+        return self.vec.dot(vec.vec) + self.T * vec.T
+
+    def norm(self) -> float:
+        return float(np.sqrt(self.dot(self)))
+
+    def sub(self, vec: "nek_ext_dvector"):
+        self.axpby(-1.0, vec, 1.0)
+
+    def copy(self) -> "nek_ext_dvector":
+        return nek_ext_dvector(self.mesh, self.lorder, self.T, _vec=self.vec.copy())
+
+    def assign(self, other: "nek_ext_dvector"):
+        self.vec.assign(other.vec)
+        self.T = other.T
+
+
+def outpost_ext_dnek(vecs, prefix: str, session: str = "neklab", outdir: str = ".", first_index: int = 1):
+    """reference: outpost_ext_dnek (src/neklab_utils.f90): the field file of outpost_dnek with the period in the header's time."""
+    if isinstance(vecs, nek_ext_dvector):
+        vecs = [vecs]
+    return outpost_dnek([v.vec for v in vecs], prefix, session, outdir, first_index=first_index, time=[v.T for v in vecs])
+
+
+class nek_upo_system:
+    """One operator in orbit mode for F(X, T) = Phi_T(X) - X and its bordered Jacobian
+    [M - I, fT; f0^T, 0] (nek_upo_system / nek_upo_jacobian).  cfl_limit defaults to 0.4, as in both of the reference's calls
+    (periodic_orbit.f90:18, :67).  The step count follows the CFL rule once per `set_jacobian_state` and is held through the GMRES of
+    that iteration; fixed_nsteps > 0 pins it for good.  no_history = 1 by default: every matvec starts impulsively, like the map
+    whose derivative it is (see `gmres`), and the border is then the fused device pass."""
+
+    def __init__(self, X: nek_ext_dvector, re: float, torder: int = 3, fixed_nsteps: int = 0, **cfg):
+        cfg.setdefault("cfl_limit", 0.4)
+        cfg.setdefault("no_history", 1)
+        self.mesh, self.lib = X.mesh, X.lib
+        self.fixed_nsteps = int(fixed_nsteps)
+        self.op = exptA_orbit_linop(X.T, X.vec, re=re, torder=torder, **cfg)
+        self.h = self.op.h
+        if self.fixed_nsteps:                      # (with the count left to the rule the constructor's set_orbit is this state already)
+            self._state(X)
+        self.n_eval = 0
+
+    def _state(self, X: nek_ext_dvector):
+        check(self.lib.nlg_linop_set_orbit_steps(self.h, X.vec.h, float(X.T), self.fixed_nsteps))
+
+    def set_tolerance(self, tol: float):
+        """both maps solve to 0.1 tol (periodic_orbit.f90:19-20, :68-69)"""
+        check(self.lib.nlg_linop_set_tolerances(self.h, 0.1 * tol, 0.1 * tol))
+
+    def eval(self, X: nek_ext_dvector, out: nek_ext_dvector):
+        """out = (Phi_T(X) - X, 0)"""
+        self._state(X)
+        check(self.lib.nlg_upo_residual(self.h, out.vec.h))
+        out.T = 0.0
+        self.n_eval += 1
+
+    def set_jacobian_state(self, X: nek_ext_dvector):
+        self._state(X)
+
+    def jac_matvec(self, v: nek_ext_dvector, out: nek_ext_dvector):
+        t = C.c_double()
+        check(self.lib.nlg_upo_jac_matvec(self.h, v.vec.h, float(v.T), out.vec.h, C.byref(t)))
+        out.T = t.value
+
+    def fdot(self, which: int, out: "nek_dvector | None" = None) -> nek_dvector:
+        """f0 (which = 0) or fT (which = 1) of the last run"""
+        out = out if out is not None else nek_dvector(self.mesh, 0, self.op.X0.lorder)
+        check(self.lib.nlg_upo_fdot(self.h, int(which), out.h))
+        return out
+
+    def info(self) -> dict:
+        return self.op.info()
+
+    def close(self):
+        self.op.close()
+
+
+def upo_arnoldi_step(sys: nek_upo_system, basis: KrylovBasis, tcol: np.ndarray, k: int, H: np.ndarray):
+    """nlg_upo_arnoldi_step: column k -> k + 1 of the extended basis (fields in `basis`, period components in `tcol`)."""
+    assert H.flags.f_contiguous and tcol.dtype == np.float64 and tcol.flags.c_contiguous and tcol.size >= k + 2
+    check(sys.lib.nlg_upo_arnoldi_step(sys.h, basis.h, dptr(tcol), int(k), dptr(H), H.shape[0]))
+
+
+def gmres_upo(sys: nek_upo_system, b: nek_ext_dvector, x: nek_ext_dvector, atol: float, kdim: int = 30, maxiter: int = 10,
+              history: "list | None" = None, replay_history: bool = False, basis: "KrylovBasis | None" = None):
+    """The loop of `gmres` for J x = b on extended vectors, J the bordered Jacobian of `sys` (which contains -I: no shift), on the
+    device's extended Arnoldi step.  replay_history = False for the reason measured in `gmres`'s docstring.  Returns (residual
+    norm, number of Jacobian matvecs)."""
+    mesh = b.mesh
+    B = basis if basis is not None else KrylovBasis(mesh, kdim + 1, 0, b.lorder)
+    x.zero()
+    r = b.copy()
+    nmv = 0
+    res = r.norm()
+    if history is not None:
+        history.append(res)
+    for _ in range(maxiter):
+        beta = res
+        if beta <= atol:
+            break
+        tcol = np.zeros(kdim + 2)
+        B[0].assign(r.vec)
+        B[0].scal(1.0 / beta)
+        tcol[0] = r.T / beta
+        H = np.zeros((kdim + 2, kdim + 1), order="F")
+        R = np.zeros((kdim + 1, kdim))
+        cs, sn = np.zeros(kdim), np.zeros(kdim)
+        g = np.zeros(kdim + 1)
+        g[0] = beta
+        k = 0
+        while k < kdim:
+            upo_arnoldi_step(sys, B, tcol, k, H)
+            nmv += 1
+            if not replay_history:
+                B[k + 1].clear_rst_fields()
+            h = H[: k + 2, k].copy()
+            for i in range(k):                                   # previous rotations
+                t = cs[i] * h[i] + sn[i] * h[i + 1]
+                h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1]
+                h[i] = t
+            d = np.sqrt(h[k] * h[k] + h[k + 1] * h[k + 1])
+            cs[k], sn[k] = (1.0, 0.0) if d == 0.0 else (h[k] / d, h[k + 1] / d)
+            h[k], h[k + 1] = d, 0.0
+            R[: k + 1, k] = h[: k + 1]
+            g[k + 1] = -sn[k] * g[k]
+            g[k] = cs[k] * g[k]
+            k += 1
+            res = abs(g[k])
+            if history is not None:
+                history.append(res)
+            if res <= atol:
+                break
+        y = np.zeros(k)                                          # R y = g; plain sequential sums, here and for dx.T, so that the
+        for i in range(k - 1, -1, -1):                           # Fortran shim's gmres_upo is the same arithmetic operation by operation
+            t = g[i]
+            for j in range(i + 1, k):
+                t = t - R[i, j] * y[j]
+            y[i] = t / R[i, i]
+        dx = nek_ext_dvector(mesh, b.lorder)
+        B.combine(k, y, dx.vec)
+        dx.T = 0.0
+        for j in range(k):
+            dx.T = dx.T + float(tcol[j] * y[j])
+        x.axpby(1.0, dx, 1.0)
+        if res <= atol:
+            break
+        Jx = nek_ext_dvector(mesh, b.lorder)                     # true residual for the restart
+        sys.jac_matvec(x, Jx)
+        nmv += 1
+        if not replay_history:
+            Jx.vec.clear_rst_fields()
+        r.assign(b)
+        r.axpby(-1.0, Jx, 1.0)
+        res = r.norm()
+    return res, nmv
+
+
+def newton_periodic_orbit(sys: nek_upo_system, X: nek_ext_dvector, tol: float, tol_mode: int = 1, maxiter: int = 40,
+                          kdim: int = 30, offset: "nek_ext_dvector | None" = None, fixed_nsteps: int = 0,
+                          outdir: str | None = None, session: str = "neklab", log=None):
+    """The loop of `newton_fixed_point_iteration` on extended vectors: Newton on F(X, T) = Phi_T(X) - X (= offset, when given: a
+    manufactured root, or the continuation from a nearly closed orbit) with GMRES on the bordered Jacobian; same schedulers, same
+    convergence rule.  `X` is updated in place.  fixed_nsteps > 0 pins the step count of the orbit.  On convergence the orbit is
+    written as `upo<session>0.f00001` with the period as the header's time.  The result feeds Floquet analysis as
+    `exptA_orbit_linop(X.T, X.vec)`.  Returns the dictionary of newton_fixed_point_iteration plus `periods`, one per iteration."""
+    sched = nek_constant_tol if tol_mode == 1 else nek_dynamic_tol
+    mesh = X.mesh
+    if fixed_nsteps:
+        sys.fixed_nsteps = int(fixed_nsteps)
+    r = nek_ext_dvector(mesh, X.lorder)
+    dx = nek_ext_dvector(mesh, X.lorder)
+    B = KrylovBasis(mesh, kdim + 1, 0, X.lorder)
+    final = sched(0.0, tol, 0.0)
+    cur, rnorm = 0.0, 1.0
+    residuals, periods, nmv_total, converged = [], [], 0, False
+    gmres_hist = []
+    for it in range(maxiter + 1):
+        new = sched(cur, tol, rnorm)
+        if new != cur:
+            cur = new
+            sys.set_tolerance(cur)
+        if X.T <= 0.0:
+            raise NlgError("newton_periodic_orbit: the period estimate became %g" % X.T)
+        sys.eval(X, r)
+        if offset is not None:
+            r.axpby(-1.0, offset, 1.0)
+        rnorm = r.norm()
+        residuals.append(rnorm)
+        periods.append(X.T)
+        if log is not None:
+            log("newton %2d  |F(X, T)| = %.6e  T = %.9f  solver tol %.3e" % (it, rnorm, X.T, cur))
+        if rnorm < tol and cur <= final:
+            converged = True
+            break
+        if it == maxiter:
+            break
+        sys.set_jacobian_state(X)
+        r.scal(-1.0)
+        gh = []
+        res, nmv = gmres_upo(sys, r, dx, atol=sched(cur, tol, rnorm), kdim=kdim, basis=B, history=gh)
+        gmres_hist.append(gh)
+        nmv_total += nmv
+        X.axpby(1.0, dx, 1.0)
+    if converged and outdir is not None:
+        outpost_ext_dnek(X, "upo", session, outdir)
+    return {"converged": converged, "iterations": len(residuals) - 1, "residuals": residuals, "periods": periods,
+            "gmres_matvecs": nmv_total, "evals": sys.n_eval, "gmres_residuals": gmres_hist}
+
+
 def arnoldi_step(exptA: exptA_linop, basis: KrylovBasis, k: int, H: np.ndarray, transpose: bool = False):
     """H is Fortran-ordered (kdim+1, kdim)."""
     assert H.flags.f_contiguous
@@ -830,7 +1077,8 @@ def pressure_to_mesh1(vec: nek_dvector) -> np.ndarray:
 def outpost_dnek(vecs, prefix: str, session: str = "neklab", outdir: str = ".", first_index: int = 1, time: float = 0.0):
     """reference: outpost_dnek (src/neklab_utils.f90:305-333, called at neklab_analysis.f90:93,146,147): every vector
     becomes one Nek5000 field file `<prefix><session>0.f%05d` with the GLL coordinates in the first file only (Nek5000's
-    default `ifxyo` behaviour), velocity and the pressure mapped to the velocity mesh.  Single-rank writer."""
+    default `ifxyo` behaviour), velocity and the pressure mapped to the velocity mesh.  `time`: the header's time, one value or one
+    per vector.  Single-rank writer."""
     from . import nekio
     if isinstance(vecs, nek_dvector):
         vecs = [vecs]
@@ -846,7 +1094,7 @@ def outpost_dnek(vecs, prefix: str, session: str = "neklab", outdir: str = ".", 
             coords = [np.asarray(c).reshape(E, -1) for c in coords]
         vel = [v.get_field(c).reshape(E, -1) for c in range(dim)]
         path = os.path.join(outdir, "%s%s0.f%05d" % (prefix, session, first_index + i))
-        nekio.write_fld(path, n, dim, coords=coords, vel=vel, p=pressure_to_mesh1(v).reshape(E, -1), time=time,
+        nekio.write_fld(path, n, dim, coords=coords, vel=vel, p=pressure_to_mesh1(v).reshape(E, -1), time=time[i] if np.ndim(time) else time,
                         istep=first_index + i)
         paths.append(path)
     return paths
