@@ -354,9 +354,10 @@ int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *
  *   the frozen propagator about X0 over tau = period again.
  * nlg_linop_orbit_end(op, out): the base flow after the nsteps of the last matvec, before the history steps: Phi_T(X0), so that
  *   |out - X0| tells how well the orbit closes.
- * nlg_linop_lane_iters: Helmholtz and pressure iterations of one lane in the last matvec (block): of its time step istep (1-based, the
- *   history steps follow the nsteps), or summed over its steps for istep = 0; in orbit mode the base flow is the lane after the last
- *   perturbation.  (nlg_linop_get_stats sums over the lanes, the base-flow lane included.) */
+ * nlg_linop_lane_iters: Helmholtz and pressure iterations of one lane in the last run on the operator, whatever kind it was (a matvec
+ *   or block, nlg_linop_integrate_forced, nlg_linop_nonlinear_map, nlg_upo_residual, an OTD run): of its time step istep (1-based,
+ *   the history steps of a matvec follow the nsteps), or summed over its steps for istep = 0; in orbit mode the base flow is the lane
+ *   after the last perturbation.  Valid for any operator.  (nlg_linop_get_stats sums over the lanes, the base-flow lane included.) */
 int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period);
 int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out);
 int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_iters, int64_t *p_iters);

@@ -360,6 +360,7 @@ int dev_dot(const nlg_vec *a, const nlg_vec *b, int slot);
 // border of the periodic-orbit Jacobian in one pass: w <- w - v + t fT (main block), <f0, v> at ctx->d_scalars[slot]; allreduced
 int upo_border_dev(nlg_vec *w, const nlg_vec *v, const nlg_vec *fT, const nlg_vec *f0, double t, int slot);
 int scalars_to_host(nlg_ctx *ctx, int first, int count, double *out);   // syncs the stream
+int vec_copy_main(nlg_vec *dst, const nlg_vec *src);   // dst <- 0, then velocity and pressure of src's main block
 int allreduce_sum(nlg_ctx *ctx, double *d_buf, int count);
 int allreduce_max(nlg_ctx *ctx, double *d_buf, int count);
 int allgather_f64(nlg_ctx *ctx, const double *d_in, double *d_out, int64_t count);   // count doubles per rank

@@ -1070,6 +1070,22 @@ struct LanePred {
     int last_titers = 8;    // scalar solve
 };
 
+// wavenumber projection on one mesh: lines along the homogeneous direction (groups of local dofs, off / idx), cos / sin of alpha x,
+// 1 / sum of the weights of a line; several ranks: slot of every local line in the global line list, number of global lines and
+// the all-reduce buffer ([nglob][2][nf])
+struct ProjLines {
+    int nlines = 0;
+    int *off = nullptr, *idx = nullptr, *gslot = nullptr;
+    int64_t nglob = 0;
+    double *cv = nullptr, *sv = nullptr, *iden = nullptr, *glob = nullptr;
+    const double *weight = nullptr;   // the mesh's mass matrix (not owned)
+    void free() {
+        for (int *q : {off, idx, gslot}) (void)hipFree(q);
+        for (double *q : {cv, sv, iden, glob}) (void)hipFree(q);
+        *this = ProjLines();
+    }
+};
+
 }  // namespace
 
 struct nlg_otd;
@@ -1127,28 +1143,17 @@ struct nlg_linop {
     double *slab = nullptr;
     int64_t slab_ld = 0;
     int slab_cap = 0;
-    int istep = 0, adjoint = 0;   // the lanes of a block step advance in lockstep: one time-step index for all
+    int istep = 0;   // the lanes of a block step advance in lockstep: one time-step index for all (the mode of the run: struct Lanes)
     LanePred pred[kMaxLanes];
     int adv_k = 1;             // state handed from one phase of a time step to the next (adv_a / adv_b / adv_c)
     double adv_b0 = 1.0, adv_h2 = 0.0;
-    // wavenumber projection (exptA_proj_linop): lines along the homogeneous direction, cos / sin of alpha x, 1 / sum bm1
-    int proj_nlines = 0, proj_nlines2 = 0;     // velocity-mesh lines; pressure-mesh lines (0 = pressure not projected)
-    int *proj_off = nullptr, *proj_idx = nullptr, *proj_off2 = nullptr, *proj_idx2 = nullptr;
-    // several ranks: slot of every local line in the global line list, number of global lines, all-reduce buffer
-    int *proj_gslot = nullptr, *proj_gslot2 = nullptr;
-    int64_t proj_nglob = 0, proj_nglob2 = 0;
-    double *proj_glob = nullptr;
-    double *proj_cv = nullptr, *proj_sv = nullptr, *proj_iden = nullptr, *proj_cv2 = nullptr, *proj_sv2 = nullptr, *proj_iden2 = nullptr;
-    // time-harmonic body force Re(f exp(i s omega t)) of the resolvent integrations (null = none)
-    const nlg_vec *force_re = nullptr, *force_im = nullptr;
-    double force_omega = 0.0, force_sign = 1.0;
+    ProjLines proj_v, proj_p;   // wavenumber projection (exptA_proj_linop) on the velocity mesh and on the pressure mesh (no lines = not projected)
     // Boussinesq coupling (cfg.ifheat): temperature levels, its explicit terms, PCG work fields, Jacobi preconditioners per
     // BDF order, gradient of the base temperature on the fine mesh
     double *tbuf[3] = {}, *ftbuf[3] = {}, *trhs = nullptr, *tx = nullptr, *tz = nullptr, *tpv = nullptr, *tw = nullptr;
     double *pct[4] = {}, *GT[3] = {};
     bool filt_fused = true;
     double *d_filt = nullptr;  // explicit modal filter (cfg.filter_weight > 0): the dense 1-D matrix F, [n][n]; belongs to the operator, not the mesh
-    int nonlinear = 0;         // 1: full Navier-Stokes step, N(u) = (u.grad)u = half of the linearised term about U = u
     // coupled (orbit) mode, nlg_linop_set_orbit: `baseflow` holds X0, the state the base-flow lane starts every matvec from; that lane
     // is one more lane of the block step (the last one), advanced by the nonlinear step while the lanes before it are advanced by
     // the step linearised about its current state.  orbit_end: its state after the nsteps of the last matvec, Phi_T(X0).
@@ -1159,7 +1164,7 @@ struct nlg_linop {
     int orbit_nsteps = 0;
     bool upo_fdot_valid = false;
     nlg_vec *upo_f0 = nullptr, *upo_fT = nullptr;
-    int64_t lane_viters[kMaxLanes] = {}, lane_piters[kMaxLanes] = {};   // iterations per lane of the last matvec (block)
+    int64_t lane_viters[kMaxLanes] = {}, lane_piters[kMaxLanes] = {};   // iterations per lane of the last run (begin_run)
     int64_t st_steps = 0, st_viters = 0, st_piters = 0, st_titers = 0, st_matvecs = 0;   // summed over the lanes
 };
 
@@ -1510,11 +1515,16 @@ int run_pcg(nlg_linop *op, const CGProblem &P, Apply apply, int *iters_out) {
 }
 
 // The lanes 0 .. nl - 1 of a time step in the operator's slab; nl = 1 is the single-vector path.  Every phase launches once for
-// all lanes and keeps the iteration predictions per lane.
+// all lanes and keeps the iteration predictions per lane.  The mode of the run travels with them, by value: the operator keeps none.
 struct Lanes {
     nlg_linop *op;
     int nl;
-    int lb = -1;   // coupled mode: the lane that carries the base flow (nl - 1); -1: the base flow is frozen
+    int lb = -1;         // coupled mode: the lane that carries the base flow (nl - 1); -1: the base flow is frozen
+    int adjoint = 0;     // the adjoint equations (never together with nonlinear)
+    int nonlinear = 0;   // 1: full Navier-Stokes step, N(u) = (u.grad)u = half of the linearised term about U = u; one lane
+    // time-harmonic body force Re[(f_re + i f_im) exp(i sign omega t)] of the resolvent integrations (null = none)
+    const nlg_vec *f_re = nullptr, *f_im = nullptr;
+    double omega = 0.0, sign = 1.0;
     int64_t ld() const { return nl > 1 ? op->slab_ld : 0; }   // the lane stride the kernels receive
 };
 
@@ -1641,7 +1651,7 @@ int heat_step(const Lanes &L, int k, double b0) {
     const double dt = op->dt, rc = c.rhocp;
     // explicit term into the oldest buffer, then rotate.  The transport term is one launch per lane (base-flow data shared); everything
     // after it -- right-hand side, operator, gather-scatter, the whole PCG -- is ONE launch for all lanes (gridDim.y), as in the velocity solve
-    const int adj = (op->adjoint && !op->nonlinear) ? 1 : 0;
+    const int adj = L.adjoint;
     NLG_TRY(sem_conv_scalar_apply(m, op->Ur, op->GT, op->ubuf[0], op->tbuf[0], op->ftbuf[2], adj, nl, ld));
     if (adj) {
         // adjoint temperature equation: rhocp theta+_t = rhocp (U.grad) theta+ + conductivity lap theta+ + rhocp b . u+
@@ -1656,7 +1666,7 @@ int heat_step(const Lanes &L, int k, double b0) {
     Hist h;
     h.k = k;
     for (int j = 0; j < 3; ++j) {
-        h.ab[j] = -(op->nonlinear ? 0.5 : 1.0) * rc * EXT_C[k][j];   // nonlinear: (u.grad)theta = 1/2 [(U.grad)theta + (u.grad)Theta] at U = u, Theta = theta
+        h.ab[j] = -(L.nonlinear ? 0.5 : 1.0) * rc * EXT_C[k][j];   // nonlinear: (u.grad)theta = 1/2 [(U.grad)theta + (u.grad)Theta] at U = u, Theta = theta
         h.bd[j] = BDF_C[k][j];
         for (int q = 0; q < 3; ++q) {
             h.f[j][q] = q == 0 ? op->ftbuf[j] : nullptr;
@@ -2060,7 +2070,7 @@ int adv_a(const Lanes &L) {
     const int k = std::min(op->istep, op->cfg.torder);
     const double b0 = BDF_B0[k];
     op->adv_k = k, op->adv_b0 = b0, op->adv_h2 = b0 / dt;
-    if (op->nonlinear) {   // the "base flow" is the current state (velocity, and temperature when coupled); one lane only
+    if (L.nonlinear) {   // the "base flow" is the current state (velocity, and temperature when coupled); one lane only
         NLG_TRY(sem_conv_setup(m, op->ubuf[0], op->Ur, op->GU));
         if (op->cfg.ifheat) NLG_TRY(sem_conv_scalar_setup(m, op->tbuf[0], op->GT));
     } else if (L.lb >= 0) {
@@ -2070,23 +2080,23 @@ int adv_a(const Lanes &L) {
     if (op->cfg.ifheat) NLG_TRY(heat_step(L, k, b0));   // scalar first: the fluid sees the new temperature (Nek5000's order)
     // F = -N(u): written into the oldest forcing buffer, then the buffers rotate
     double **Fnew = op->fbuf[2];
-    NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], Fnew, op->nonlinear ? 0 : op->adjoint, nl, ld));   // all lanes against the shared base flow
-    if (op->cfg.ifheat && op->adjoint && !op->nonlinear) {
+    NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], Fnew, L.adjoint, nl, ld));   // all lanes against the shared base flow
+    if (op->cfg.ifheat && L.adjoint) {
         // adjoint momentum equation: - theta+ grad Theta with the new theta+ (stored F is +N: add the weak term)
         NLG_TRY(sem_scalar_grad_apply(m, op->GT, op->tbuf[0], Fnew, 1.0, nl, ld));
     } else if (op->cfg.ifheat) {
-        const double bs = op->nonlinear ? 2.0 : 1.0;   // the nonlinear step halves the whole stored term (F holds 2 N there)
+        const double bs = L.nonlinear ? 2.0 : 1.0;   // the nonlinear step halves the whole stored term (F holds 2 N there)
         for (int v = 0; v < nl; ++v)
             launch_nf(dim, k_buoyancy<1>, k_buoyancy<2>, k_buoyancy<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(at_lane3(op, Fnew, v).p, dim),
                       (const double *)m->d_bm1, (const double *)at_lane(op, op->tbuf[0], v), bs * op->cfg.buoy[0], bs * op->cfg.buoy[1], bs * op->cfg.buoy[2]);
     }
-    if (op->force_re) {
+    if (L.f_re) {
         // forcing of this step: evaluated at the time level the step starts from, (istep - 1) dt, like the explicit terms
         // (resolvent.f90:97-103: alpha = exp(sign i omega time) before nek_advance)
-        const double ph = op->force_sign * op->force_omega * (op->istep - 1) * dt;
-        CF3 fr = {{op->force_re->vel(0), op->force_re->vel(1), dim == 3 ? op->force_re->vel(2) : nullptr}};
+        const double ph = L.sign * L.omega * (op->istep - 1) * dt;
+        CF3 fr = {{L.f_re->vel(0), L.f_re->vel(1), dim == 3 ? L.f_re->vel(2) : nullptr}};
         CF3 fi = {{nullptr, nullptr, nullptr}};
-        if (op->force_im) fi = CF3{{op->force_im->vel(0), op->force_im->vel(1), dim == 3 ? op->force_im->vel(2) : nullptr}};
+        if (L.f_im) fi = CF3{{L.f_im->vel(0), L.f_im->vel(1), dim == 3 ? L.f_im->vel(2) : nullptr}};
         launch_nf(dim, k_add_force<1>, k_add_force<2>, k_add_force<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(Fnew, dim),
                   (const double *)m->d_bm1, fr, fi, std::cos(ph), -std::sin(ph));
     }
@@ -2103,7 +2113,7 @@ int adv_a(const Lanes &L) {
     h.k = k;
     h.half_lane = L.lb;   // the base-flow lane's own term -1/2 lns_conv(U; U): a coefficient of the history sum, not a pass
     for (int j = 0; j < 3; ++j) {
-        h.ab[j] = -(op->nonlinear ? 0.5 : 1.0) * EXT_C[k][j];   // F = -N ; nonlinear: (u.grad)u = 1/2 [(U.grad)u + (u.grad)U] at U = u
+        h.ab[j] = -(L.nonlinear ? 0.5 : 1.0) * EXT_C[k][j];   // F = -N ; nonlinear: (u.grad)u = 1/2 [(U.grad)u + (u.grad)U] at U = u
         h.bd[j] = BDF_C[k][j];
         for (int c = 0; c < 3; ++c) {
             h.f[j][c] = op->fbuf[j][c];
@@ -2229,6 +2239,21 @@ int reset_state(nlg_linop *op, int nl) {
     return 0;
 }
 
+// Every run of the time stepper starts here: nl lanes at rest, time-step index 0, no per-lane iteration counts, nothing kept from
+// the run before -- neither the pressure projection space nor what an orbit run left for nlg_linop_orbit_end / nlg_upo_fdot.
+// (The projection space belongs to one run: the result must not depend on earlier calls.  Keeping it across matvecs, as a
+// Nek5000 run does across time steps, was measured in round 4: 11.76 -> 11.40 pressure iterations per time step over 844 matvecs
+// of a real Arnoldi / Krylov-Schur run -- successive Krylov vectors are orthogonal, their pressure increments share little --
+// while bench.py, which re-applies the operator to the SAME column every step, would show 12.5 -> 6.5: an artefact, not adopted.)
+int begin_run(nlg_linop *op, int nl) {
+    NLG_TRY(reset_state(op, nl));
+    op->istep = 0;
+    op->nproj = 0;
+    for (int v = 0; v < kMaxLanes; ++v) op->lane_viters[v] = op->lane_piters[v] = 0;
+    op->orbit_end_valid = op->upo_fdot_valid = false;
+    return 0;
+}
+
 int load_state(nlg_linop *op, int lane, const nlg_vec *v, int irst) {
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
@@ -2240,8 +2265,6 @@ int load_state(nlg_linop *op, int lane, const nlg_vec *v, int irst) {
     return 0;
 }
 
-// (nlg_upo_residual reads the same buffers -- ubuf[0] and p of lane 0 -- directly, to difference them against X0 in one pass: a change
-// of where a lane keeps its current state belongs in both places)
 int store_state(nlg_linop *op, int lane, nlg_vec *v, int irst) {
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
@@ -2250,6 +2273,23 @@ int store_state(nlg_linop *op, int lane, nlg_vec *v, int irst) {
     NLG_HIP(hipMemcpyAsync(v->pr(irst), at_lane(op, op->p, lane), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
     if (op->cfg.ifheat)
         NLG_HIP(hipMemcpyAsync(v->theta(0, irst), at_lane(op, op->tbuf[0], lane), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// out (velocity and pressure of its main block) = c (state of lane `lane` - X0), X0 = the operator's base flow, in one pass
+int state_minus_x0(nlg_linop *op, int lane, double c, nlg_vec *out) {
+    nlg_mesh *m = op->mesh;
+    const int dim = m->dim;
+    DdtArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int f = 0; f <= dim; ++f) {
+        const bool pr = f == dim;
+        A.out[f] = pr ? out->pr() : out->vel(f), A.n[f] = pr ? m->lpn : m->lvn;
+        A.src[f][0] = at_lane(op, pr ? op->p : op->ubuf[0][f], lane), A.c[f][0] = c;
+        A.src[f][1] = pr ? op->baseflow->pr() : op->baseflow->vel(f), A.c[f][1] = -c;
+    }
+    NLG_LAUNCH(k_bdf_ddt, dim3(grid_for(m->lvn), dim + 1), dim3(NT), 0, m->ctx->stream, A);
+    NLG_HIP(hipGetLastError());
     return 0;
 }
 
@@ -2264,19 +2304,13 @@ int capture_fdot(nlg_linop *op, int lane, int phase) {
     nlg_mesh *m = op->mesh;
     const int dim = m->dim;
     const double idt = 1.0 / op->dt;
-    nlg_vec *o = phase == FDOT_START ? op->upo_f0 : op->upo_fT;
+    if (phase == FDOT_START) return state_minus_x0(op, lane, idt, op->upo_f0);
+    nlg_vec *o = op->upo_fT;
     DdtArgs A;
     memset(&A, 0, sizeof(A));
     for (int c = 0; c < dim; ++c) A.out[c] = o->vel(c), A.n[c] = m->lvn;
     A.out[dim] = o->pr(), A.n[dim] = m->lpn;
-    if (phase == FDOT_START) {
-        for (int c = 0; c < dim; ++c) {
-            A.src[c][0] = at_lane(op, op->ubuf[0][c], lane), A.c[c][0] = idt;
-            A.src[c][1] = op->baseflow->vel(c), A.c[c][1] = -idt;
-        }
-        A.src[dim][0] = at_lane(op, op->p, lane), A.c[dim][0] = idt;
-        A.src[dim][1] = op->baseflow->pr(), A.c[dim][1] = -idt;
-    } else if (phase == FDOT_PRE) {
+    if (phase == FDOT_PRE) {
         const int k = std::min(op->nsteps, op->cfg.torder);
         for (int c = 0; c < dim; ++c)
             for (int j = 0; j < k; ++j) A.src[c][j] = at_lane(op, op->ubuf[j][c], lane), A.c[c][j] = -BDF_C[k][j] * idt;
@@ -2292,70 +2326,55 @@ int capture_fdot(nlg_linop *op, int lane, int phase) {
     return 0;
 }
 
-// no-op unless nlg_linop_set_projection has been called: projects level `slot` of the state of lane `lane`
-int project_alpha(nlg_linop *op, int lane, int slot) {
-    if (op->proj_nlines == 0) return 0;
-    nlg_mesh *m = op->mesh;
-    const unsigned grid = (unsigned)((op->proj_nlines + NT / 64 - 1) / (NT / 64));
-    F3 u = f3(at_lane3(op, op->ubuf[slot], lane).p, m->dim);
-    if (op->proj_gslot) {
-        // several ranks: partial sums -> global slots -> all-reduce -> apply (the reference's planar_avg is a global
-        // operation, exponential_propagator_proj.f90:146-169)
-        hipStream_t st = m->ctx->stream;
-        auto pass = [&](int nf, int64_t nl, const int *off, const int *idx, const int *gs, int64_t nglob, const double *wt,
-                        const double *cv, const double *sv, const double *iden, F3 f) -> int {
-            const unsigned g = (unsigned)((nl + NT / 64 - 1) / (NT / 64));
-            const int64_t cnt = nglob * 2 * nf;
-            NLG_HIP(hipMemsetAsync(op->proj_glob, 0, sizeof(double) * (size_t)cnt, st));
-            CF3 cf = {{f.p[0], f.p[1], f.p[2]}};
-            if (nl > 0) {
-                if (nf == 3)
-                    NLG_LAUNCH(k_proj_sums<3>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, op->proj_glob);
-                else if (nf == 2)
-                    NLG_LAUNCH(k_proj_sums<2>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, op->proj_glob);
-                else
-                    NLG_LAUNCH(k_proj_sums<1>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, wt, cv, sv, cf, op->proj_glob);
-            }
-            NLG_TRY(allreduce_sum(m->ctx, op->proj_glob, (int)cnt));
-            if (nl > 0) {
-                if (nf == 3)
-                    NLG_LAUNCH(k_proj_apply<3>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)op->proj_glob, f);
-                else if (nf == 2)
-                    NLG_LAUNCH(k_proj_apply<2>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)op->proj_glob, f);
-                else
-                    NLG_LAUNCH(k_proj_apply<1>, dim3(g), dim3(NT), 0, st, nl, off, idx, gs, cv, sv, iden, (const double *)op->proj_glob, f);
-            }
-            return 0;
-        };
-        NLG_TRY(pass(m->dim, op->proj_nlines, op->proj_off, op->proj_idx, op->proj_gslot, op->proj_nglob, m->d_bm1, op->proj_cv, op->proj_sv,
-                     op->proj_iden, u));
-        if (op->proj_gslot2 && slot == 0) {
-            F3 pp = {{at_lane(op, op->p, lane), nullptr, nullptr}};
-            NLG_TRY(pass(1, op->proj_nlines2, op->proj_off2, op->proj_idx2, op->proj_gslot2, op->proj_nglob2, m->d_bm2, op->proj_cv2,
-                         op->proj_sv2, op->proj_iden2, pp));
-        }
-        NLG_HIP(hipGetLastError());
-        return 0;
+// The op->nsteps time steps of a run.  fdot_lane >= 0: that lane carries a base flow started from X0, and the three captures of its
+// time derivatives ride along (capture_fdot).  after_step(istep) is the caller's hook (the history replay of a matvec).
+template <typename Hook>
+int run_steps(const Lanes &L, int fdot_lane, Hook after_step) {
+    nlg_linop *op = L.op;
+    for (int istep = 1; istep <= op->nsteps; ++istep) {
+        if (fdot_lane >= 0 && istep == op->nsteps) NLG_TRY(capture_fdot(op, fdot_lane, FDOT_PRE));
+        NLG_TRY(advance(L));
+        if (fdot_lane >= 0 && istep == 1) NLG_TRY(capture_fdot(op, fdot_lane, FDOT_START));
+        NLG_TRY(after_step(istep));
     }
-    if (m->dim == 3)
-        NLG_LAUNCH(k_proj_alpha<3>, dim3(grid), dim3(NT), 0, m->ctx->stream, (int64_t)op->proj_nlines, (const int *)op->proj_off,
-                           (const int *)op->proj_idx, (const double *)m->d_bm1, (const double *)op->proj_cv, (const double *)op->proj_sv,
-                           (const double *)op->proj_iden, u);
-    else
-        NLG_LAUNCH(k_proj_alpha<2>, dim3(grid), dim3(NT), 0, m->ctx->stream, (int64_t)op->proj_nlines, (const int *)op->proj_off,
-                           (const int *)op->proj_idx, (const double *)m->d_bm1, (const double *)op->proj_cv, (const double *)op->proj_sv,
-                           (const double *)op->proj_iden, u);
-    if (op->proj_nlines2 > 0 && slot == 0) {
-        // the pressure is part of the state the integrator starts from (lagged pressure of the correction scheme) but not
-        // of the inner product: left unprojected it is a subspace the Arnoldi norm cannot see (observed: a spurious
-        // |mu| = 1.41 for plane Poiseuille flow at alpha = 2 instead of 0.945)
-        const unsigned grid2 = (unsigned)((op->proj_nlines2 + NT / 64 - 1) / (NT / 64));
-        F3 pp = {{at_lane(op, op->p, lane), nullptr, nullptr}};
-        NLG_LAUNCH(k_proj_alpha<1>, dim3(grid2), dim3(NT), 0, m->ctx->stream, (int64_t)op->proj_nlines2, (const int *)op->proj_off2,
-                           (const int *)op->proj_idx2, (const double *)m->d_bm2, (const double *)op->proj_cv2, (const double *)op->proj_sv2,
-                           (const double *)op->proj_iden2, pp);
+    if (fdot_lane >= 0) NLG_TRY(capture_fdot(op, fdot_lane, FDOT_END));
+    return 0;
+}
+int run_steps(const Lanes &L, int fdot_lane = -1) {
+    return run_steps(L, fdot_lane, [](int) { return 0; });
+}
+
+// the projection of nf fields on one mesh: one kernel; several ranks: partial sums -> global slots -> all-reduce -> apply (the
+// reference's planar_avg is a global operation, exponential_propagator_proj.f90:146-169)
+int project_lines(nlg_linop *op, const ProjLines &P, int nf, F3 f) {
+    nlg_mesh *m = op->mesh;
+    hipStream_t st = m->ctx->stream;
+    const int64_t nl = P.nlines;
+    const dim3 g((unsigned)((nl + NT / 64 - 1) / (NT / 64)));
+    const int *off = P.off, *idx = P.idx, *gs = P.gslot;
+    const double *cv = P.cv, *sv = P.sv, *iden = P.iden, *glob = P.glob;
+    if (!gs) {
+        launch_nf(nf, k_proj_alpha<1>, k_proj_alpha<2>, k_proj_alpha<3>, g, st, nl, off, idx, P.weight, cv, sv, iden, f);
+    } else {
+        const int64_t cnt = P.nglob * 2 * nf;
+        NLG_HIP(hipMemsetAsync(P.glob, 0, sizeof(double) * (size_t)cnt, st));
+        if (nl > 0) launch_nf(nf, k_proj_sums<1>, k_proj_sums<2>, k_proj_sums<3>, g, st, nl, off, idx, gs, P.weight, cv, sv, CF3{{f.p[0], f.p[1], f.p[2]}}, P.glob);
+        NLG_TRY(allreduce_sum(m->ctx, P.glob, (int)cnt));
+        if (nl > 0) launch_nf(nf, k_proj_apply<1>, k_proj_apply<2>, k_proj_apply<3>, g, st, nl, off, idx, gs, cv, sv, iden, glob, f);
     }
     NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// no-op unless nlg_linop_set_projection has been called: projects level `slot` of the state of lane `lane`
+int project_alpha(nlg_linop *op, int lane, int slot) {
+    if (op->proj_v.nlines == 0) return 0;
+    NLG_TRY(project_lines(op, op->proj_v, op->mesh->dim, f3(at_lane3(op, op->ubuf[slot], lane).p, op->mesh->dim)));
+    // the pressure is part of the state the integrator starts from (lagged pressure of the correction scheme) but not
+    // of the inner product: left unprojected it is a subspace the Arnoldi norm cannot see (observed: a spurious
+    // |mu| = 1.41 for plane Poiseuille flow at alpha = 2 instead of 0.945)
+    const ProjLines &Pp = op->proj_p;
+    if ((Pp.gslot || Pp.nlines > 0) && slot == 0) NLG_TRY(project_lines(op, Pp, 1, F3{{at_lane(op, op->p, lane), nullptr, nullptr}}));
     return 0;
 }
 
@@ -2393,36 +2412,23 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     // coupled (orbit) mode: lane s carries the base flow, from X0 (impulsive start, no history: periodic_orbit.f90:59-92 with
     // solve_baseflow = .true.) through the same time steps and the same launches as the s perturbation lanes before it
     const int nl = op->orbit ? s + 1 : s, lb = op->orbit ? s : -1;
-    NLG_TRY(reset_state(op, nl));
-    op->istep = 0;
-    op->adjoint = adjoint;
-    for (int v = 0; v < kMaxLanes; ++v) op->lane_viters[v] = op->lane_piters[v] = 0;
-    // the projection space belongs to one matvec: the result must not depend on earlier calls.  (Keeping it across matvecs, as a
-    // Nek5000 run does across time steps, was measured in round 4: 11.76 -> 11.40 pressure iterations per time step over 844 matvecs
-    // of a real Arnoldi / Krylov-Schur run -- successive Krylov vectors are orthogonal, their pressure increments share little --
-    // while bench.py, which re-applies the operator to the SAME column every step, would show 12.5 -> 6.5: an artefact, not adopted.)
-    op->nproj = 0;
+    NLG_TRY(begin_run(op, nl));
     for (int v = 0; v < s; ++v) {
         NLG_TRY(load_state(op, v, vin[v], 0));
         NLG_TRY(project_alpha(op, v, 0));   // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
     }
-    if (lb >= 0) {
-        op->orbit_end_valid = false;
-        op->upo_fdot_valid = false;
-        NLG_TRY(load_state(op, lb, op->baseflow, 0));
-    }
-    const Lanes L{op, nl, lb};
-    for (int istep = 1; istep <= op->nsteps; ++istep) {
-        if (lb >= 0 && istep == op->nsteps) NLG_TRY(capture_fdot(op, lb, FDOT_PRE));
-        NLG_TRY(advance(L));
-        if (lb >= 0 && istep == 1) NLG_TRY(capture_fdot(op, lb, FDOT_START));
+    if (lb >= 0) NLG_TRY(load_state(op, lb, op->baseflow, 0));
+    Lanes L{op, nl, lb};
+    L.adjoint = adjoint;
+    NLG_TRY(run_steps(L, lb, [&](int istep) -> int {
         if (istep <= nrst)
             for (int v = 0; v < s; ++v)
                 if (vin[v]->nrst > 0) {
                     NLG_TRY(load_state(op, v, vin[v], istep));   // get_rst, exponential_propagator.f90:129-142
                     NLG_TRY(project_alpha(op, v, 0));            // (projected operator: replayed states are projected as well, see below)
                 }
-    }
+        return 0;
+    }));
     // ... and the final state, :66.  The reference projects the initial condition and the final state only.  Here the
     // replayed history states and the lagged states of the multistep scheme are projected too: otherwise the extended map
     // (state, history) that the Arnoldi process iterates has a spurious unstable mode -- observed for plane Poiseuille flow
@@ -2438,7 +2444,6 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
         NLG_TRY(nlg_vec_zero(op->orbit_end));
         NLG_TRY(store_state(op, lb, op->orbit_end, 0));
         op->orbit_end_valid = true;
-        NLG_TRY(capture_fdot(op, lb, FDOT_END));
     }
     for (int irst = 1; irst <= nrst; ++irst) {   // compute_rst, :109-127
         NLG_TRY(advance(L));
@@ -2478,20 +2483,13 @@ int do_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, c
     NLG_CHECK(vout != f_re && vout != f_im && vout != ic, "integrate_forced: the output must be distinct from the inputs");
     NLG_CHECK(f_re->nscal == 0 && vout->nscal == 0, "integrate_forced: scalar (temperature) coupling is not built yet");
     hipStream_t st = m->ctx->stream;
-    NLG_TRY(reset_state(op, 1));
+    NLG_TRY(begin_run(op, 1));
     NLG_HIP(hipMemsetAsync(op->p, 0, sizeof(double) * (size_t)m->lps, st));
-    op->istep = 0;
-    op->adjoint = adjoint;
-    op->nproj = 0;
     if (ic) NLG_TRY(load_state(op, 0, ic, 0));
-    op->force_re = f_re;
-    op->force_im = f_im;
-    op->force_omega = omega;
-    op->force_sign = adjoint ? -1.0 : 1.0;
-    int rc = 0;
-    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) rc = advance(Lanes{op, 1});
-    op->force_re = op->force_im = nullptr;
-    if (rc) return rc;
+    Lanes L{op, 1};
+    L.adjoint = adjoint;
+    L.f_re = f_re, L.f_im = f_im, L.omega = omega, L.sign = adjoint ? -1.0 : 1.0;
+    NLG_TRY(run_steps(L));
     NLG_TRY(nlg_vec_zero(vout));
     NLG_TRY(store_state(op, 0, vout, 0));
     return 0;
@@ -2508,19 +2506,14 @@ int do_nonlinear_map(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout) {
               "nonlinear_map: the vectors carry %d scalar(s), the operator expects %d (cfg.ifheat)", vin->nscal, op->cfg.ifheat ? 1 : 0);
     NLG_CHECK(vin != vout, "nonlinear_map: vec_in and vec_out must be distinct");
     NLG_CHECK(!op->orbit, "nonlinear_map: the operator is in orbit mode and holds X0 as its base flow (use a second operator, or nlg_linop_set_orbit(op, NULL, 0))");
-    hipStream_t st = m->ctx->stream;
     // "setup_nonlinear_solver(recompute_dt = .true.)": the time step follows the state that is integrated
     NLG_TRY(nlg_vec_copy(op->baseflow, vin));
     NLG_TRY(nlg_linop_init(op));
-    NLG_TRY(reset_state(op, 1));
-    op->istep = 0;
-    op->adjoint = 0;
-    op->nproj = 0;
-    op->nonlinear = 1;
-    int rc = load_state(op, 0, vin, 0);
-    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) rc = advance(Lanes{op, 1});
-    op->nonlinear = 0;
-    if (rc) return rc;
+    NLG_TRY(begin_run(op, 1));
+    NLG_TRY(load_state(op, 0, vin, 0));
+    Lanes L{op, 1};
+    L.nonlinear = 1;
+    NLG_TRY(run_steps(L));
     NLG_TRY(nlg_vec_zero(vout));
     NLG_TRY(store_state(op, 0, vout, 0));
     NLG_TRY(nlg_vec_axpby(-1.0, vin, 1.0, vout));   // vec_out%sub(vec_in), fixed_point.f90:29
@@ -2604,19 +2597,8 @@ int nlg_linop_destroy(nlg_linop *op) {
     fr(op->pce);
     for (int q = 0; q < 3; ++q) fr(op->GT[q]);
     for (int k = 0; k < 4; ++k) fr(op->pct[k]);
-    fr(op->proj_cv);
-    fr(op->proj_sv);
-    fr(op->proj_iden);
-    fr(op->proj_cv2);
-    fr(op->proj_sv2);
-    fr(op->proj_iden2);
-    if (op->proj_off) hipFree(op->proj_off);
-    if (op->proj_idx) hipFree(op->proj_idx);
-    if (op->proj_off2) hipFree(op->proj_off2);
-    if (op->proj_idx2) hipFree(op->proj_idx2);
-    if (op->proj_gslot) hipFree(op->proj_gslot);
-    if (op->proj_gslot2) hipFree(op->proj_gslot2);
-    fr(op->proj_glob);
+    op->proj_v.free();
+    op->proj_p.free();
     fr(op->nwv);
     fr(op->nwv_xp);
     fr(op->nwp);
@@ -2626,6 +2608,16 @@ int nlg_linop_destroy(nlg_linop *op) {
     if (op->upo_f0) nlg_vec_destroy(op->upo_f0);
     if (op->upo_fT) nlg_vec_destroy(op->upo_fT);
     delete op;
+    return 0;
+}
+
+// dg = QQ^T diag(h1 A + h2 B), then the Jacobi preconditioners pc[c] = mask[c] / dg of nf fields
+static int jacobi_pc(nlg_mesh *m, double h1, double h2, int nf, double *const *mask, double *const *pc, double *dg) {
+    NLG_TRY(sem_helm_diag(m, dg, h1, h2));
+    double *f[1] = {dg};
+    NLG_TRY(sem_gs(m, f, 1));
+    for (int c = 0; c < nf; ++c)
+        NLG_LAUNCH(k_recipmask, dim3(grid_for(m->lvn)), dim3(NT), 0, m->ctx->stream, m->lvn, pc[c], (const double *)dg, (const double *)mask[c]);
     return 0;
 }
 
@@ -2688,36 +2680,19 @@ int nlg_linop_init(nlg_linop *op) {
     }
     // convective-term precomputation
     NLG_TRY(sem_conv_setup(m, U, op->Ur, op->GU));
-    // preconditioners
+    // Jacobi preconditioners of the velocity solve, per BDF order, all from one diagonal: pcv = mask_c / diag (pcv_xp: in the layout of
+    // the slab-permuted solve) and, in compact form for the streaming kernels of the PCG, pci = 1 / diag in the layout of the solve plus
+    // one mask byte per point.  The compact form needs masks of zeros and ones (sem.hip checked that when it built the byte masks of
+    // the pressure operator: m->d_maskb_fg exists) -- NLG_PC_MASKB=0 keeps the three arrays
     const double nu = 1.0 / op->cfg.re;
-    for (int k = 1; k <= op->cfg.torder; ++k) {
-        double *dg = sem_scratch1(m, 3);
-        NLG_CHECK(dg, "nlg_linop_init: scratch allocation failed");
-        NLG_TRY(sem_helm_diag(m, dg, nu, BDF_B0[k] / op->dt));
-        double *f[1] = {dg};
-        NLG_TRY(sem_gs(m, f, 1));
-        for (int c = 0; c < dim; ++c)
-            NLG_LAUNCH(k_recipmask, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, op->pcv[k][c], (const double *)dg,
-                               (const double *)m->d_mask[c]);
-    }
     if (op->use_xp < 0) op->use_xp = (dim == 3 && m->d_slot_xp && (m->gs.d_indices_xp || m->gs.ngroups == 0)) ? 1 : 0;
-    if (op->use_xp > 0) {
-        for (int k = 1; k <= op->cfg.torder; ++k) {
-            for (int c = 0; c < dim; ++c)
-                if (!op->pcv_xp[k][c]) NLG_TRY(lalloc(op, &op->pcv_xp[k][c], m->lvs));
-            NLG_TRY(sem_to_xp(m, op->pcv[k], op->pcv_xp[k], dim));
-        }
-    }
-    // compact form for the streaming kernels of the PCG: needs masks of zeros and ones (sem.hip checked that when it built the byte masks
-    // of the pressure operator: m->d_maskb_fg exists) -- NLG_PC_MASKB=0 keeps the three arrays
-    if (dim == 3 && m->d_maskb_fg && !op->use_sr && !(getenv("NLG_PC_MASKB") && atoi(getenv("NLG_PC_MASKB")) == 0)) {
-        double *t0 = sem_scratch1(m, 3), *t1 = sem_scratch1(m, 4);
-        NLG_CHECK(t0 && t1, "nlg_linop_init: scratch allocation failed");
-        const bool xp = op->use_xp > 0;
-        for (int k = 1; k <= op->cfg.torder; ++k) {
-            NLG_TRY(sem_helm_diag(m, t0, nu, BDF_B0[k] / op->dt));
-            double *f[1] = {t0};
-            NLG_TRY(sem_gs(m, f, 1));
+    const bool xp = op->use_xp > 0;
+    const bool compact = dim == 3 && m->d_maskb_fg && !op->use_sr && !(getenv("NLG_PC_MASKB") && atoi(getenv("NLG_PC_MASKB")) == 0);
+    double *t0 = sem_scratch1(m, 3), *t1 = compact ? sem_scratch1(m, 4) : nullptr;   // t0: the diagonal (jacobi_pc)
+    NLG_CHECK(t0 && (t1 || !compact), "nlg_linop_init: scratch allocation failed");
+    for (int k = 1; k <= op->cfg.torder; ++k) {
+        NLG_TRY(jacobi_pc(m, nu, BDF_B0[k] / op->dt, dim, m->d_mask, op->pcv[k], t0));
+        if (compact) {
             if (!op->pci[k]) NLG_TRY(lalloc(op, &op->pci[k], m->lvs));
             NLG_LAUNCH(k_recip1, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, xp ? t1 : op->pci[k], (const double *)t0);
             if (xp) {
@@ -2726,6 +2701,13 @@ int nlg_linop_init(nlg_linop *op) {
             }
             for (int c = 0; c < 3; ++c) op->pci_l[k][c] = op->pci[k];
         }
+        if (xp) {
+            for (int c = 0; c < dim; ++c)
+                if (!op->pcv_xp[k][c]) NLG_TRY(lalloc(op, &op->pcv_xp[k][c], m->lvs));
+            NLG_TRY(sem_to_xp(m, op->pcv[k], op->pcv_xp[k], dim));
+        }
+    }
+    if (compact) {
         NLG_LAUNCH(k_maskbits, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, t0, (const double *)m->d_mask[0], (const double *)m->d_mask[1],
                            (const double *)m->d_mask[2]);
         if (xp) {
@@ -2744,15 +2726,8 @@ int nlg_linop_init(nlg_linop *op) {
             for (int q = 0; q < dim; ++q) NLG_HIP(hipMalloc(&op->GT[q], sizeof(double) * (size_t)m->lfn));
         }
         NLG_TRY(sem_conv_scalar_setup(m, op->baseflow->theta(0), op->GT));
-        for (int k = 1; k <= op->cfg.torder; ++k) {
-            double *dg = sem_scratch1(m, 3);
-            NLG_CHECK(dg, "nlg_linop_init: scratch allocation failed");
-            NLG_TRY(sem_helm_diag(m, dg, op->cfg.conductivity, op->cfg.rhocp * BDF_B0[k] / op->dt));
-            double *f[1] = {dg};
-            NLG_TRY(sem_gs(m, f, 1));
-            NLG_LAUNCH(k_recipmask, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, op->pct[k], (const double *)dg,
-                               (const double *)m->d_tmask);
-        }
+        for (int k = 1; k <= op->cfg.torder; ++k)
+            NLG_TRY(jacobi_pc(m, op->cfg.conductivity, op->cfg.rhocp * BDF_B0[k] / op->dt, 1, &m->d_tmask, &op->pct[k], t0));
     }
     {
         double *ed = sem_scratch2(m, 5);
@@ -2796,6 +2771,99 @@ int nlg_linop_set_baseflow(nlg_linop *op, const nlg_vec *baseflow) {
     return nlg_linop_init(op);
 }
 
+struct DevBuf {   // a device temporary, released on every path out of its scope
+    double *p = nullptr;
+    ~DevBuf() { (void)hipFree(p); }
+};
+
+// the lines of one mesh into P (empty on entry; the caller frees it whatever this returns): lines = groups of local dofs with the same
+// label, ordered by label then by index.  The coordinate along the homogeneous direction is on the device (d_x) or on the host (h_x).
+static int proj_build(nlg_mesh *m, double alpha, int64_t n, const int64_t *lab, const double *d_x, const double *h_x, ProjLines &P) {
+    nlg_ctx *ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    std::vector<int> order((size_t)n);
+    for (int64_t i = 0; i < n; ++i) order[i] = (int)i;
+    std::sort(order.begin(), order.end(), [lab](int a, int b) { return lab[a] < lab[b] || (lab[a] == lab[b] && a < b); });
+    std::vector<int> off{0};
+    for (int64_t q = 1; q <= n; ++q)
+        if (q == n || lab[order[q]] != lab[order[q - 1]]) off.push_back((int)q);
+    const int nlines = (int)off.size() - 1;
+    std::vector<double> wt((size_t)n), iden((size_t)nlines);
+    NLG_HIP(hipMemcpyAsync(wt.data(), P.weight, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    for (int g = 0; g < nlines; ++g) {
+        double sum = 0.0;
+        for (int q = off[g]; q < off[g + 1]; ++q) sum += wt[order[q]];
+        NLG_CHECK(sum > 0.0, "nlg_linop_set_projection: empty line");
+        iden[g] = 1.0 / sum;
+    }
+    P.nlines = nlines;
+    NLG_HIP(hipMalloc(&P.off, sizeof(int) * off.size()));
+    NLG_HIP(hipMalloc(&P.idx, sizeof(int) * (size_t)n));
+    NLG_HIP(hipMalloc(&P.iden, sizeof(double) * (size_t)nlines));
+    NLG_HIP(hipMalloc(&P.cv, sizeof(double) * (size_t)n));
+    NLG_HIP(hipMalloc(&P.sv, sizeof(double) * (size_t)n));
+    NLG_HIP(hipMemcpy(P.off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
+    NLG_HIP(hipMemcpy(P.idx, order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    NLG_HIP(hipMemcpy(P.iden, iden.data(), sizeof(double) * (size_t)nlines, hipMemcpyHostToDevice));
+    DevBuf xs;
+    if (h_x) {   // (pressure mesh)
+        NLG_HIP(hipMalloc(&xs.p, sizeof(double) * (size_t)n));
+        NLG_HIP(hipMemcpy(xs.p, h_x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+        d_x = xs.p;
+    }
+    NLG_LAUNCH(k_cossin, dim3(grid_for(n)), dim3(NT), 0, st, n, d_x, alpha, P.cv, P.sv);
+    NLG_HIP(hipGetLastError());
+    NLG_HIP(hipStreamSynchronize(st));
+    if (!ctx->distributed()) return 0;
+    // the labels are global line names: gather every rank's distinct labels, number the union (identically on all
+    // ranks), and sum the weights of the parts of a line over the ranks for the denominators
+    const int nr = ctx->nranks;
+    const double mine = (double)nlines;
+    std::vector<double> cnts(nr);
+    int64_t maxc = 1;
+    {
+        DevBuf cnt;
+        NLG_HIP(hipMalloc(&cnt.p, sizeof(double) * (nr + 1)));
+        NLG_HIP(hipMemcpy(cnt.p + nr, &mine, sizeof(double), hipMemcpyHostToDevice));
+        NLG_TRY(allgather_f64(ctx, cnt.p + nr, cnt.p, 1));
+        NLG_HIP(hipMemcpyAsync(cnts.data(), cnt.p, sizeof(double) * nr, hipMemcpyDeviceToHost, st));
+        NLG_HIP(hipStreamSynchronize(st));
+    }
+    for (double c : cnts) maxc = std::max<int64_t>(maxc, (int64_t)c);
+    std::vector<int64_t> mylab((size_t)maxc, -1), all((size_t)maxc * nr);
+    for (int g = 0; g < nlines; ++g) mylab[g] = lab[order[off[g]]];
+    {
+        DevBuf labs;   // (labels travel as 8-byte words)
+        NLG_HIP(hipMalloc(&labs.p, sizeof(int64_t) * (size_t)maxc * (nr + 1)));
+        NLG_HIP(hipMemcpy(labs.p + (size_t)maxc * nr, mylab.data(), sizeof(int64_t) * (size_t)maxc, hipMemcpyHostToDevice));
+        NLG_TRY(allgather_f64(ctx, labs.p + (size_t)maxc * nr, labs.p, maxc));
+        NLG_HIP(hipMemcpyAsync(all.data(), labs.p, sizeof(int64_t) * (size_t)maxc * nr, hipMemcpyDeviceToHost, st));
+        NLG_HIP(hipStreamSynchronize(st));
+    }
+    std::vector<int64_t> uni;
+    for (int q = 0; q < nr; ++q)
+        for (int64_t g = 0; g < (int64_t)cnts[q]; ++g) uni.push_back(all[(size_t)q * maxc + g]);
+    std::sort(uni.begin(), uni.end());
+    uni.erase(std::unique(uni.begin(), uni.end()), uni.end());
+    std::vector<int> gs((size_t)std::max(nlines, 1));
+    for (int g = 0; g < nlines; ++g) gs[g] = (int)(std::lower_bound(uni.begin(), uni.end(), mylab[g]) - uni.begin());
+    NLG_HIP(hipMalloc(&P.gslot, sizeof(int) * gs.size()));
+    NLG_HIP(hipMemcpy(P.gslot, gs.data(), sizeof(int) * gs.size(), hipMemcpyHostToDevice));
+    P.nglob = (int64_t)uni.size();
+    NLG_HIP(hipMalloc(&P.glob, sizeof(double) * (size_t)(P.nglob * 2 * 3)));
+    NLG_HIP(hipMemsetAsync(P.glob, 0, sizeof(double) * (size_t)P.nglob, st));
+    const unsigned g1 = (unsigned)((nlines + NT / 64 - 1) / (NT / 64));
+    if (nlines > 0)
+        NLG_LAUNCH(k_proj_wsum, dim3(g1), dim3(NT), 0, st, (int64_t)nlines, (const int *)P.off, (const int *)P.idx, (const int *)P.gslot, P.weight, P.glob);
+    NLG_TRY(allreduce_sum(ctx, P.glob, (int)P.nglob));
+    if (nlines > 0)
+        NLG_LAUNCH(k_proj_iden, dim3(grid_for(nlines)), dim3(NT), 0, st, (int64_t)nlines, (const int *)P.gslot, (const double *)P.glob, P.iden);
+    NLG_HIP(hipGetLastError());
+    NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
                              const double *x2) {
     NLG_CHECK(op && line_label, "nlg_linop_set_projection: NULL argument");
@@ -2805,126 +2873,24 @@ int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_
     NLG_CHECK(op->inited, "nlg_linop_set_projection: call init first");
     NLG_CHECK(!op->orbit, "nlg_linop_set_projection: not available in orbit mode (the base-flow lane is a full state, not one wavenumber; nlg_linop_set_orbit)");
     NLG_CHECK((line_label2 == nullptr) == (x2 == nullptr), "nlg_linop_set_projection: pressure-mesh labels and coordinates go together");
-    hipStream_t st = m->ctx->stream;
-    int64_t proj_glob_cap = 0;
-    if (op->proj_glob) {
-        hipFree(op->proj_glob);
-        op->proj_glob = nullptr;
+    // built beside the operator's and swapped in on success: a call that fails leaves the operator as it was
+    ProjLines pv, pp;
+    pv.weight = m->d_bm1, pp.weight = m->d_bm2;
+    int rc = proj_build(m, alpha, m->lvn, line_label, m->d_x[idir - 1], nullptr, pv);
+    if (!rc && line_label2) rc = proj_build(m, alpha, m->lpn, line_label2, nullptr, x2, pp);
+    if (!rc) {
+        std::swap(op->proj_v, pv);
+        std::swap(op->proj_p, pp);
     }
-    // one set of lists per mesh: lines = groups of local dofs with the same label, ordered by label then by index
-    auto build = [&](int64_t n, const int64_t *lab, const double *d_w, const double *d_x, const double *h_x, int *nl, int **d_off, int **d_idx,
-                     double **d_cv, double **d_sv, double **d_iden, int **d_gslot, int64_t *nglob) -> int {
-        std::vector<int> order((size_t)n);
-        for (int64_t i = 0; i < n; ++i) order[i] = (int)i;
-        std::sort(order.begin(), order.end(), [lab](int a, int b) { return lab[a] < lab[b] || (lab[a] == lab[b] && a < b); });
-        std::vector<int> off{0};
-        for (int64_t q = 1; q <= n; ++q)
-            if (q == n || lab[order[q]] != lab[order[q - 1]]) off.push_back((int)q);
-        const int nlines = (int)off.size() - 1;
-        std::vector<double> wt((size_t)n), iden((size_t)nlines);
-        NLG_HIP(hipMemcpyAsync(wt.data(), d_w, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-        NLG_HIP(hipStreamSynchronize(st));
-        for (int g = 0; g < nlines; ++g) {
-            double sum = 0.0;
-            for (int q = off[g]; q < off[g + 1]; ++q) sum += wt[order[q]];
-            NLG_CHECK(sum > 0.0, "nlg_linop_set_projection: empty line");
-            iden[g] = 1.0 / sum;
-        }
-        if (*d_off) hipFree(*d_off);
-        if (*d_idx) hipFree(*d_idx);
-        if (*d_cv) hipFree(*d_cv);
-        if (*d_sv) hipFree(*d_sv);
-        if (*d_iden) hipFree(*d_iden);
-        NLG_HIP(hipMalloc(d_off, sizeof(int) * off.size()));
-        NLG_HIP(hipMalloc(d_idx, sizeof(int) * (size_t)n));
-        NLG_HIP(hipMalloc(d_iden, sizeof(double) * (size_t)nlines));
-        NLG_HIP(hipMalloc(d_cv, sizeof(double) * (size_t)n));
-        NLG_HIP(hipMalloc(d_sv, sizeof(double) * (size_t)n));
-        NLG_HIP(hipMemcpy(*d_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
-        NLG_HIP(hipMemcpy(*d_idx, order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-        NLG_HIP(hipMemcpy(*d_iden, iden.data(), sizeof(double) * (size_t)nlines, hipMemcpyHostToDevice));
-        const double *xs = d_x;
-        double *tmp = nullptr;
-        if (!xs) {   // coordinates given on the host (pressure mesh)
-            NLG_HIP(hipMalloc(&tmp, sizeof(double) * (size_t)n));
-            NLG_HIP(hipMemcpy(tmp, h_x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-            xs = tmp;
-        }
-        NLG_LAUNCH(k_cossin, dim3(grid_for(n)), dim3(NT), 0, st, n, xs, alpha, *d_cv, *d_sv);
-        NLG_HIP(hipGetLastError());
-        NLG_HIP(hipStreamSynchronize(st));
-        if (tmp) hipFree(tmp);
-        *nl = nlines;
-        if (*d_gslot) hipFree(*d_gslot);
-        *d_gslot = nullptr;
-        *nglob = 0;
-        if (m->ctx->distributed()) {
-            // the labels are global line names: gather every rank's distinct labels, number the union (identically on all
-            // ranks), and sum the weights of the parts of a line over the ranks for the denominators
-            nlg_ctx *ctx = m->ctx;
-            const int nr = ctx->nranks;
-            double *d_cnt = nullptr;
-            NLG_HIP(hipMalloc(&d_cnt, sizeof(double) * (nr + 1)));
-            const double mine = (double)nlines;
-            NLG_HIP(hipMemcpy(d_cnt + nr, &mine, sizeof(double), hipMemcpyHostToDevice));
-            NLG_TRY(allgather_f64(ctx, d_cnt + nr, d_cnt, 1));
-            std::vector<double> cnts(nr);
-            NLG_HIP(hipMemcpyAsync(cnts.data(), d_cnt, sizeof(double) * nr, hipMemcpyDeviceToHost, st));
-            NLG_HIP(hipStreamSynchronize(st));
-            hipFree(d_cnt);
-            int64_t maxc = 1;
-            for (double c : cnts) maxc = std::max<int64_t>(maxc, (int64_t)c);
-            std::vector<int64_t> mylab((size_t)maxc, -1), all((size_t)maxc * nr);
-            for (int g = 0; g < nlines; ++g) mylab[g] = lab[order[off[g]]];
-            int64_t *d_lab = nullptr;
-            NLG_HIP(hipMalloc(&d_lab, sizeof(int64_t) * (size_t)maxc * (nr + 1)));
-            NLG_HIP(hipMemcpy(d_lab + (size_t)maxc * nr, mylab.data(), sizeof(int64_t) * (size_t)maxc, hipMemcpyHostToDevice));
-            NLG_TRY(allgather_f64(ctx, reinterpret_cast<const double *>(d_lab + (size_t)maxc * nr), reinterpret_cast<double *>(d_lab), maxc));
-            NLG_HIP(hipMemcpyAsync(all.data(), d_lab, sizeof(int64_t) * (size_t)maxc * nr, hipMemcpyDeviceToHost, st));
-            NLG_HIP(hipStreamSynchronize(st));
-            hipFree(d_lab);
-            std::vector<int64_t> uni;
-            for (int q = 0; q < nr; ++q)
-                for (int64_t g = 0; g < (int64_t)cnts[q]; ++g) uni.push_back(all[(size_t)q * maxc + g]);
-            std::sort(uni.begin(), uni.end());
-            uni.erase(std::unique(uni.begin(), uni.end()), uni.end());
-            std::vector<int> gs((size_t)std::max(nlines, 1));
-            for (int g = 0; g < nlines; ++g) gs[g] = (int)(std::lower_bound(uni.begin(), uni.end(), mylab[g]) - uni.begin());
-            NLG_HIP(hipMalloc(d_gslot, sizeof(int) * gs.size()));
-            NLG_HIP(hipMemcpy(*d_gslot, gs.data(), sizeof(int) * gs.size(), hipMemcpyHostToDevice));
-            *nglob = (int64_t)uni.size();
-            const int64_t need = *nglob * 2 * 3;
-            if (need > proj_glob_cap) {
-                if (op->proj_glob) hipFree(op->proj_glob);
-                NLG_HIP(hipMalloc(&op->proj_glob, sizeof(double) * (size_t)need));
-                proj_glob_cap = need;
-            }
-            NLG_HIP(hipMemsetAsync(op->proj_glob, 0, sizeof(double) * (size_t)*nglob, st));
-            const unsigned g1 = (unsigned)((nlines + NT / 64 - 1) / (NT / 64));
-            if (nlines > 0)
-                NLG_LAUNCH(k_proj_wsum, dim3(g1), dim3(NT), 0, st, (int64_t)nlines, (const int *)*d_off, (const int *)*d_idx,
-                                   (const int *)*d_gslot, d_w, op->proj_glob);
-            NLG_TRY(allreduce_sum(ctx, op->proj_glob, (int)*nglob));
-            if (nlines > 0)
-                NLG_LAUNCH(k_proj_iden, dim3(grid_for(nlines)), dim3(NT), 0, st, (int64_t)nlines, (const int *)*d_gslot,
-                                   (const double *)op->proj_glob, *d_iden);
-            NLG_HIP(hipGetLastError());
-            NLG_HIP(hipStreamSynchronize(st));
-        }
-        return 0;
-    };
-    NLG_TRY(build(m->lvn, line_label, m->d_bm1, m->d_x[idir - 1], nullptr, &op->proj_nlines, &op->proj_off, &op->proj_idx, &op->proj_cv,
-                  &op->proj_sv, &op->proj_iden, &op->proj_gslot, &op->proj_nglob));
-    op->proj_nlines2 = 0;
-    if (line_label2)
-        NLG_TRY(build(m->lpn, line_label2, m->d_bm2, nullptr, x2, &op->proj_nlines2, &op->proj_off2, &op->proj_idx2, &op->proj_cv2,
-                      &op->proj_sv2, &op->proj_iden2, &op->proj_gslot2, &op->proj_nglob2));
-    return 0;
+    (void)hipStreamSynchronize(m->ctx->stream);   // nothing in flight may still use what is freed now
+    pv.free();
+    pp.free();
+    return rc;
 }
 
 int nlg_linop_project(nlg_linop *op, nlg_vec *v) {
     NLG_CHECK(op && v && v->mesh == op->mesh, "nlg_linop_project: bad argument");
-    NLG_CHECK(op->proj_nlines > 0, "nlg_linop_project: no projection set (nlg_linop_set_projection)");
+    NLG_CHECK(op->proj_v.nlines > 0, "nlg_linop_project: no projection set (nlg_linop_set_projection)");
     NLG_TRY(slab_ensure(op, 1));
     NLG_TRY(load_state(op, 0, v, 0));
     NLG_TRY(project_alpha(op, 0, 0));
@@ -2968,7 +2934,7 @@ int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period) {
     NLG_CHECK(X0->mesh == op->mesh, "nlg_linop_set_orbit: X0 lives on a different mesh");
     NLG_CHECK(period > 0.0, "nlg_linop_set_orbit: the period must be positive");
     NLG_CHECK(!op->cfg.ifheat, "nlg_linop_set_orbit: orbit mode does not carry the temperature (cfg.ifheat); not built");
-    NLG_CHECK(op->proj_nlines == 0, "nlg_linop_set_orbit: orbit mode and the wavenumber projection exclude each other");
+    NLG_CHECK(op->proj_v.nlines == 0, "nlg_linop_set_orbit: orbit mode and the wavenumber projection exclude each other");
     NLG_TRY(nlg_vec_copy(op->baseflow, X0));
     if (!op->orbit_end) NLG_TRY(nlg_vec_clone(op->baseflow, &op->orbit_end));
     for (nlg_vec **f : {&op->upo_f0, &op->upo_fT})
@@ -3012,34 +2978,13 @@ int nlg_upo_residual(nlg_linop *op, nlg_vec *out) {
     NLG_CHECK(op->inited, "nlg_upo_residual: nlg_linop_init has not been called");
     nlg_mesh *m = op->mesh;
     NLG_CHECK(out->mesh == m && out->nscal == 0, "nlg_upo_residual: the output lives on a different mesh or carries scalars");
-    NLG_TRY(reset_state(op, 1));
-    op->istep = 0;
-    op->adjoint = 0;
-    op->nproj = 0;
-    op->upo_fdot_valid = false;
-    for (int v = 0; v < kMaxLanes; ++v) op->lane_viters[v] = op->lane_piters[v] = 0;
-    op->nonlinear = 1;
-    int rc = load_state(op, 0, op->baseflow, 0);
-    for (int istep = 1; istep <= op->nsteps && rc == 0; ++istep) {
-        if (istep == op->nsteps) rc = capture_fdot(op, 0, FDOT_PRE);
-        if (rc == 0) rc = advance(Lanes{op, 1});
-        if (rc == 0 && istep == 1) rc = capture_fdot(op, 0, FDOT_START);
-    }
-    op->nonlinear = 0;
-    if (rc) return rc;
-    NLG_TRY(capture_fdot(op, 0, FDOT_END));
+    NLG_TRY(begin_run(op, 1));
+    NLG_TRY(load_state(op, 0, op->baseflow, 0));
+    Lanes L{op, 1};
+    L.nonlinear = 1;
+    NLG_TRY(run_steps(L, 0));
     NLG_TRY(nlg_vec_zero(out));
-    DdtArgs A;
-    memset(&A, 0, sizeof(A));
-    for (int c = 0; c <= m->dim; ++c) {
-        const bool pr = c == m->dim;
-        A.out[c] = pr ? out->pr() : out->vel(c), A.n[c] = pr ? m->lpn : m->lvn;
-        A.src[c][0] = pr ? op->p : op->ubuf[0][c], A.c[c][0] = 1.0;
-        A.src[c][1] = pr ? op->baseflow->pr() : op->baseflow->vel(c), A.c[c][1] = -1.0;
-    }
-    NLG_LAUNCH(k_bdf_ddt, dim3(grid_for(m->lvn), m->dim + 1), dim3(NT), 0, m->ctx->stream, A);
-    NLG_HIP(hipGetLastError());
-    return 0;
+    return state_minus_x0(op, 0, 1.0, out);
 }
 
 int nlg_upo_fdot(nlg_linop *op, int which, nlg_vec *out) {
@@ -3049,11 +2994,7 @@ int nlg_upo_fdot(nlg_linop *op, int which, nlg_vec *out) {
     NLG_CHECK(op->upo_fdot_valid, "nlg_upo_fdot: no run yet (a matvec in orbit mode or nlg_upo_residual fills the derivatives)");
     nlg_mesh *m = op->mesh;
     NLG_CHECK(out->mesh == m && out->nscal == 0, "nlg_upo_fdot: the output lives on a different mesh or carries scalars");
-    const nlg_vec *f = which == 0 ? op->upo_f0 : op->upo_fT;
-    NLG_TRY(nlg_vec_zero(out));
-    hipStream_t st = m->ctx->stream;
-    NLG_HIP(hipMemcpyAsync(out->d, f->d, sizeof(double) * (size_t)out->main_len, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return vec_copy_main(out, which == 0 ? op->upo_f0 : op->upo_fT);
 }
 
 // The border of the orbit's Jacobian on an existing w = M v_in (jac_direct_map, periodic_orbit.f90:91-103): w <- w - v_in + t_in fT,
@@ -3088,13 +3029,7 @@ int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out) {
     NLG_CHECK(op->orbit, "nlg_linop_orbit_end: the operator is not in orbit mode (nlg_linop_set_orbit)");
     NLG_CHECK(op->orbit_end_valid, "nlg_linop_orbit_end: no matvec in orbit mode yet");
     NLG_CHECK(out->nscal == 0, "nlg_linop_orbit_end: orbit mode carries no scalars");
-    NLG_TRY(nlg_vec_zero(out));
-    nlg_mesh *m = op->mesh;
-    hipStream_t st = m->ctx->stream;
-    for (int c = 0; c < m->dim; ++c)
-        NLG_HIP(hipMemcpyAsync(out->vel(c), op->orbit_end->vel(c), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, st));
-    NLG_HIP(hipMemcpyAsync(out->pr(), op->orbit_end->pr(), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return vec_copy_main(out, op->orbit_end);
 }
 
 int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_iters, int64_t *p_iters) {
@@ -3104,7 +3039,7 @@ int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_it
         if (p_iters) *p_iters = op->lane_piters[lane];
         return 0;
     }
-    // (the per-step counts are the ones the iteration predictor keeps from the last matvec)
+    // (the per-step counts are the ones the iteration predictor keeps from the last run)
     const LanePred &lp = op->pred[lane];
     NLG_CHECK(istep < (int)lp.v.hist.size() && istep < (int)lp.p.hist.size(), "nlg_linop_lane_iters: lane %d has not run a time step %d", lane, istep);
     if (v_iters) *v_iters = lp.v.hist[istep];
@@ -3159,7 +3094,7 @@ int nlg_otd_create(nlg_linop *op, const nlg_otd_opts *o, const nlg_vec *const *b
               o->solve_baseflow ? ": with solve_baseflow the base flow takes one of the lanes" : "");
     NLG_CHECK(!(o->trans && o->solve_baseflow), "nlg_otd_create: trans with solve_baseflow: the adjoint about a moving base flow needs U(T - t) and is not built");
     NLG_CHECK(!op->cfg.ifheat, "nlg_otd_create: OTD modes do not carry the temperature (cfg.ifheat); not built");
-    NLG_CHECK(op->proj_nlines == 0, "nlg_otd_create: OTD modes and the wavenumber projection exclude each other");
+    NLG_CHECK(op->proj_v.nlines == 0, "nlg_otd_create: OTD modes and the wavenumber projection exclude each other");
     NLG_CHECK(!op->orbit, "nlg_otd_create: the operator is in orbit mode (nlg_linop_set_orbit); use solve_baseflow on a frozen operator");
     NLG_CHECK(!op->otd, "nlg_otd_create: an nlg_otd already lives on this operator");
     NLG_CHECK(o->startstep >= 1 && o->orthostep >= 1, "nlg_otd_create: startstep and orthostep must be positive");
@@ -3185,11 +3120,7 @@ int nlg_otd_create(nlg_linop *op, const nlg_otd_opts *o, const nlg_vec *const *b
     }
     int rc = 0;
     if (hipMemsetAsync(ot->d, 0, sizeof(double) * OTD_N, st) != hipSuccess) rc = 1;
-    if (!rc) rc = reset_state(op, ot->nl);
-    op->istep = 0;
-    op->adjoint = o->trans ? 1 : 0;
-    op->nproj = 0;
-    for (int v = 0; v < kMaxLanes; ++v) op->lane_viters[v] = op->lane_piters[v] = 0;
+    if (!rc) rc = begin_run(op, ot->nl);   // the run goes on across the calls of nlg_otd_advance: op->istep is its time-step index
     for (int v = 0; v < ot->r && !rc; ++v) {
         if (basis0) {
             rc = load_state(op, v, basis0[v], 0);
@@ -3216,7 +3147,8 @@ int nlg_otd_create(nlg_linop *op, const nlg_otd_opts *o, const nlg_vec *const *b
 int nlg_otd_advance(nlg_otd *ot, int nsteps) {
     NLG_CHECK(ot && nsteps >= 0, "nlg_otd_advance: bad argument");
     nlg_linop *op = ot->op;
-    const Lanes L{op, ot->nl, ot->lb};
+    Lanes L{op, ot->nl, ot->lb};
+    L.adjoint = ot->o.trans ? 1 : 0;
     bool ortho = false;
     for (int s = 0; s < nsteps; ++s) {
         NLG_TRY(advance(L));
@@ -3243,7 +3175,7 @@ int nlg_otd_reduced(nlg_otd *ot, double *Lr, double *G) {
     // L u_j in weak form from the operators of the time step, on the state as it stands (h2 = 0: the viscous term alone)
     NLG_TRY(sem_ortho(m, op->p, r, ld));
     if (ot->lb >= 0) NLG_TRY(sem_conv_setup(m, at_lane3(op, op->ubuf[0], ot->lb).p, op->Ur, op->GU));
-    NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], op->rhs, op->adjoint, r, ld));
+    NLG_TRY(sem_conv_apply(m, op->Ur, op->GU, op->ubuf[0], op->rhs, ot->o.trans ? 1 : 0, r, ld));
     NLG_TRY(sem_opgradt(m, op->p, op->gp, false, nullptr, nullptr, r, ld, ld));
     NLG_TRY(sem_axhelm(m, op->ubuf[0], op->w, dim, 1.0 / op->cfg.re, 0.0, nullptr, nullptr, nullptr, nullptr, false, r, ld));
     NLG_TRY(otd_sums(ot, op->gp, op->w, op->rhs));
@@ -3268,14 +3200,9 @@ int nlg_otd_get_basis(nlg_otd *ot, int i, nlg_vec *out) {
 
 int nlg_otd_get_baseflow(nlg_otd *ot, nlg_vec *out) {
     NLG_CHECK(ot && out && out->mesh == ot->op->mesh && out->nscal == 0, "nlg_otd_get_baseflow: bad argument");
+    if (ot->lb < 0) return vec_copy_main(out, ot->op->baseflow);
     NLG_TRY(nlg_vec_zero(out));
-    if (ot->lb >= 0) return store_state(ot->op, ot->lb, out, 0);
-    nlg_mesh *m = ot->op->mesh;
-    const nlg_vec *bf = ot->op->baseflow;
-    for (int c = 0; c < m->dim; ++c)
-        NLG_HIP(hipMemcpyAsync(out->vel(c), bf->vel(c), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, m->ctx->stream));
-    NLG_HIP(hipMemcpyAsync(out->pr(), bf->pr(), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, m->ctx->stream));
-    return 0;
+    return store_state(ot->op, ot->lb, out, 0);
 }
 
 int nlg_otd_info(const nlg_otd *ot, int64_t *istep, double *time, double *dt) {

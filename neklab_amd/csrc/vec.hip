@@ -569,6 +569,16 @@ int upo_border_dev(nlg_vec *w, const nlg_vec *v, const nlg_vec *fT, const nlg_ve
     return 0;
 }
 
+// dst <- 0, then the velocity and the pressure of src's main block (no scalars, no restart history)
+int vec_copy_main(nlg_vec *dst, const nlg_vec *src) {
+    nlg_mesh *m = src->mesh;
+    NLG_TRY(nlg_vec_zero(dst));
+    for (int c = 0; c < m->dim; ++c)
+        NLG_HIP(hipMemcpyAsync(dst->vel(c), src->vel(c), sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToDevice, m->ctx->stream));
+    NLG_HIP(hipMemcpyAsync(dst->pr(), src->pr(), sizeof(double) * (size_t)m->lpn, hipMemcpyDeviceToDevice, m->ctx->stream));
+    return 0;
+}
+
 }  // namespace nlg
 
 static int g_axpby_consistent = 1;   // default reproduces the reference's published eigenvalue, see include/neklab_gpu.h

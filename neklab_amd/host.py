@@ -363,6 +363,13 @@ class exptA_linop:
         check(self.lib.nlg_linop_get_stats(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return {"steps": a.value, "v_iters": b.value, "p_iters": c.value, "matvecs": d.value}
 
+    def lane_iters(self, lane: int, istep: int = 0) -> dict:
+        """Iterations of one lane in the last run (a matvec or block, a forced integration, a nonlinear map), of time step
+        `istep` (1-based) or summed (0); in orbit mode the base flow is the lane after the last perturbation."""
+        a, b = C.c_int64(), C.c_int64()
+        check(self.lib.nlg_linop_lane_iters(self.h, int(lane), int(istep), C.byref(a), C.byref(b)))
+        return {"v_iters": a.value, "p_iters": b.value}
+
     def close(self):
         if self.h:
             self.lib.nlg_linop_destroy(self.h)
@@ -393,13 +400,6 @@ class exptA_orbit_linop(exptA_linop):
         d = self.orbit_end()
         d.axpby(-1.0, self.X0, 1.0)
         return d.norm() / self.X0.norm()
-
-    def lane_iters(self, lane: int, istep: int = 0) -> dict:
-        """Iterations of one lane in the last matvec (block), of time step `istep` (1-based) or summed (0); the base flow is the
-        lane after the last perturbation."""
-        a, b = C.c_int64(), C.c_int64()
-        check(self.lib.nlg_linop_lane_iters(self.h, int(lane), int(istep), C.byref(a), C.byref(b)))
-        return {"v_iters": a.value, "p_iters": b.value}
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -598,6 +598,62 @@ def nek_constant_tol(tol_old: float, target: float, rnorm: float):
     return max(target, 10.0 * 10.0 ** -12)
 
 
+def _gmres(b, x, atol: float, kdim: int, maxiter: int, history, first, column, assemble, residual):
+    """The restarted GMRES(kdim) loop of `gmres` and `gmres_upo`: Givens rotations, restarts, the residual history.  What differs
+    between the two comes in as four functions: first(r, beta) makes r / beta column 0 of the Krylov basis; column(k) makes column
+    k + 1 and returns column k of the Hessenberg matrix (k + 2 entries); assemble(k, y) returns the combination of the first k
+    columns; residual(x, r) writes the true residual b - A x into r.  The arithmetic is plain sequential sums and
+    sqrt(a * a + b * b), so that the Fortran shim's loop is the same operation by operation (tests/test_gpu_upo_fortran.py)."""
+    x.zero()
+    r = b.copy()
+    nmv = 0
+    res = r.norm()
+    if history is not None:
+        history.append(res)
+    for _ in range(maxiter):
+        beta = res
+        if beta <= atol:
+            break
+        first(r, beta)
+        R = np.zeros((kdim + 1, kdim))
+        cs, sn = np.zeros(kdim), np.zeros(kdim)
+        g = np.zeros(kdim + 1)
+        g[0] = beta
+        k = 0
+        while k < kdim:
+            h = column(k)
+            nmv += 1
+            for i in range(k):                                   # previous rotations
+                t = cs[i] * h[i] + sn[i] * h[i + 1]
+                h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1]
+                h[i] = t
+            d = np.sqrt(h[k] * h[k] + h[k + 1] * h[k + 1])
+            cs[k], sn[k] = (1.0, 0.0) if d == 0.0 else (h[k] / d, h[k + 1] / d)
+            h[k], h[k + 1] = d, 0.0
+            R[: k + 1, k] = h[: k + 1]
+            g[k + 1] = -sn[k] * g[k]
+            g[k] = cs[k] * g[k]
+            k += 1
+            res = abs(g[k])
+            if history is not None:
+                history.append(res)
+            if res <= atol:
+                break
+        y = np.zeros(k)                                          # R y = g
+        for i in range(k - 1, -1, -1):
+            t = g[i]
+            for j in range(i + 1, k):
+                t = t - R[i, j] * y[j]
+            y[i] = t / R[i, i]
+        x.axpby(1.0, assemble(k, y), 1.0)
+        if res <= atol:
+            break
+        residual(x, r)                                           # true residual for the restart
+        nmv += 1
+        res = r.norm()
+    return res, nmv
+
+
 def gmres(exptA: exptA_linop, b: nek_dvector, x: nek_dvector, atol: float, kdim: int = 30, maxiter: int = 10,
           shift: float = -1.0, basis: "KrylovBasis | None" = None, replay_history: bool = False, transpose: bool = False,
           history: "list | None" = None):
@@ -614,63 +670,75 @@ def gmres(exptA: exptA_linop, b: nek_dvector, x: nek_dvector, atol: float, kdim:
     derivative of the map being solved) and 3 without.  The converged fixed point is the same."""
     mesh = b.mesh
     B = basis if basis is not None else KrylovBasis(mesh, kdim + 1, b.nscal, b.lorder)
-    x.zero()
-    r = b.copy()
-    nmv = 0
-    res = r.norm()
-    if history is not None:
-        history.append(res)
-    for _ in range(maxiter):
-        beta = res
-        if beta <= atol:
-            break
-        v0 = B[0]
-        v0.assign(r)
-        v0.scal(1.0 / beta)
-        H = np.zeros((kdim + 2, kdim + 1), order="F")
-        R = np.zeros((kdim + 1, kdim))
-        cs, sn = np.zeros(kdim), np.zeros(kdim)
-        g = np.zeros(kdim + 1)
-        g[0] = beta
-        k = 0
-        while k < kdim:
-            arnoldi_step(exptA, B, k, H, transpose)
-            nmv += 1
-            if not replay_history:
-                B[k + 1].clear_rst_fields()
-            h = H[: k + 2, k].copy()
-            h[k] += shift
-            for i in range(k):                                   # previous rotations
-                t = cs[i] * h[i] + sn[i] * h[i + 1]
-                h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1]
-                h[i] = t
-            d = np.hypot(h[k], h[k + 1])
-            cs[k], sn[k] = (1.0, 0.0) if d == 0.0 else (h[k] / d, h[k + 1] / d)
-            h[k], h[k + 1] = d, 0.0
-            R[: k + 1, k] = h[: k + 1]
-            g[k + 1] = -sn[k] * g[k]
-            g[k] = cs[k] * g[k]
-            k += 1
-            res = abs(g[k])
-            if history is not None:
-                history.append(res)
-            if res <= atol:
-                break
-        y = np.linalg.solve(np.triu(R[:k, :k]), g[:k])
+    H = np.zeros((kdim + 2, kdim + 1), order="F")
+
+    def first(r, beta):
+        H[:] = 0.0
+        B[0].assign(r)
+        B[0].scal(1.0 / beta)
+
+    def column(k):
+        arnoldi_step(exptA, B, k, H, transpose)
+        if not replay_history:
+            B[k + 1].clear_rst_fields()
+        h = H[: k + 2, k].copy()
+        h[k] += shift
+        return h
+
+    def assemble(k, y):
         dx = nek_dvector(mesh, b.nscal, b.lorder)
         B.combine(k, y, dx)
-        x.axpby(1.0, dx, 1.0)
-        if res <= atol:
-            break
-        # true residual for the restart: r = b - (A + shift I) x
+        return dx
+
+    def residual(x, r):                                          # r = b - (A + shift I) x
         Ax = nek_dvector(mesh, b.nscal, b.lorder)
         (exptA.rmatvec if transpose else exptA.matvec)(x, Ax)
-        nmv += 1
         r.assign(b)
         r.axpby(-1.0, Ax, 1.0)
         r.axpby(-shift, x, 1.0)
-        res = r.norm()
-    return res, nmv
+
+    return _gmres(b, x, atol, kdim, maxiter, history, first, column, assemble, residual)
+
+
+def _newton(sys, X, r, solve, tol: float, tol_mode: int, maxiter: int, line, log=None, offset=None, each=None):
+    """The inexact Newton loop of `newton_fixed_point_iteration` and `newton_periodic_orbit` on F(X) = 0 (= offset, when given):
+    the tolerance scheduler nek_constant_tol (tol_mode 1) or nek_dynamic_tol called at the top of an iteration, as LightKrylov's
+    newton calls it; a residual below the target only counts when computed at the tightest level the scheduler will ever set;
+    maxiter iterations at most, no bisection.  r: work vector for the residual; solve(r, atol, history) -> (dx, matvecs) is the
+    GMRES on the Jacobian at X; line(it, rnorm, tol) the log line; each() runs before every evaluation.  `X` is updated in place."""
+    sched = nek_constant_tol if tol_mode == 1 else nek_dynamic_tol
+    final = sched(0.0, tol, 0.0)
+    cur, rnorm = 0.0, 1.0
+    residuals, nmv_total, converged = [], 0, False
+    gmres_hist = []
+    for it in range(maxiter + 1):
+        new = sched(cur, tol, rnorm)
+        if new != cur:
+            cur = new
+            sys.set_tolerance(cur)
+        if each is not None:
+            each()
+        sys.eval(X, r)
+        if offset is not None:
+            r.axpby(-1.0, offset, 1.0)
+        rnorm = r.norm()
+        residuals.append(rnorm)
+        if log is not None:
+            log(line(it, rnorm, cur))
+        if rnorm < tol and cur <= final:
+            converged = True
+            break
+        if it == maxiter:
+            break
+        sys.set_jacobian_state(X)
+        r.scal(-1.0)
+        gh = []
+        dx, nmv = solve(r, sched(cur, tol, rnorm), gh)
+        gmres_hist.append(gh)
+        nmv_total += nmv
+        X.axpby(1.0, dx, 1.0)
+    return {"converged": converged, "iterations": len(residuals) - 1, "residuals": residuals, "gmres_matvecs": nmv_total,
+            "evals": sys.n_eval, "gmres_residuals": gmres_hist}
 
 
 def newton_fixed_point_iteration(sys: nek_system, bf: nek_dvector, tol: float, tol_mode: int = 1, maxiter: int = 40,
@@ -679,42 +747,19 @@ def newton_fixed_point_iteration(sys: nek_system, bf: nek_dvector, tol: float, t
     """reference: newton_fixed_point_iteration (src/neklab_analysis.f90:158-205): Newton on F(X) = Phi_tau(X) - X with
     GMRES on the Jacobian exp(tau J) - I, tolerance scheduler nek_constant_tol (tol_mode 1) or nek_dynamic_tol, 40
     iterations at most, no bisection; on convergence the fixed point is written as `nwt<session>0.f00001`.
-    `bf` is updated in place.  Returns dict(converged, iterations, residuals, gmres_matvecs, evals)."""
-    sched = nek_constant_tol if tol_mode == 1 else nek_dynamic_tol
+    `bf` is updated in place.  Returns dict(converged, iterations, residuals, gmres_matvecs, evals, gmres_residuals)."""
     mesh = bf.mesh
-    r = nek_dvector(mesh, bf.nscal, bf.lorder)
     dx = nek_dvector(mesh, bf.nscal, bf.lorder)
     B = KrylovBasis(mesh, kdim + 1, bf.nscal, bf.lorder)     # (with the scalar of a temperature-coupled system)
-    final = sched(0.0, tol, 0.0)               # the tightest level the scheduler will ever set
-    cur, rnorm = 0.0, 1.0
-    residuals, nmv_total, converged = [], 0, False
-    gmres_hist = []
-    for it in range(maxiter + 1):
-        new = sched(cur, tol, rnorm)           # scheduler first, as LightKrylov's newton calls it at the top of an iteration
-        if new != cur:
-            cur = new
-            sys.set_tolerance(cur)
-        sys.eval(bf, r)
-        rnorm = r.norm()
-        residuals.append(rnorm)
-        if log is not None:
-            log("newton %2d  |F(X)| = %.6e  solver tol %.3e" % (it, rnorm, cur))
-        if rnorm < tol and cur <= final:       # a residual below the target only counts when computed at the final level
-            converged = True
-            break
-        if it == maxiter:
-            break
-        sys.set_jacobian_state(bf)
-        r.scal(-1.0)
-        gh = []
-        res, nmv = gmres(sys.jac, r, dx, atol=sched(cur, tol, rnorm), kdim=kdim, basis=B, replay_history=replay_history, history=gh)
-        gmres_hist.append(gh)
-        nmv_total += nmv
-        bf.axpby(1.0, dx, 1.0)
-    if converged and outdir is not None:
+
+    def solve(r, atol, gh):
+        return dx, gmres(sys.jac, r, dx, atol=atol, kdim=kdim, basis=B, replay_history=replay_history, history=gh)[1]
+
+    out = _newton(sys, bf, nek_dvector(mesh, bf.nscal, bf.lorder), solve, tol, tol_mode, maxiter,
+                  lambda it, rnorm, cur: "newton %2d  |F(X)| = %.6e  solver tol %.3e" % (it, rnorm, cur), log)
+    if out["converged"] and outdir is not None:
         outpost_dnek(bf, "nwt", session, outdir)
-    return {"converged": converged, "iterations": len(residuals) - 1, "residuals": residuals, "gmres_matvecs": nmv_total,
-            "evals": sys.n_eval, "gmres_residuals": gmres_hist}
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -722,7 +767,7 @@ def newton_fixed_point_iteration(sys: nek_system, bf: nek_dvector, tol: float, t
 # nek_upo_system / nek_upo_jacobian (src/systems/periodic_orbit.f90, neklab_systems.f90:147-223), driven by
 # examples/cylinder/newton/Re180_periodic_orbit/1cyl.usr.  The Jacobian's time stepping is the coupled (orbit) matvec; the border
 # (period column, phase row), the two time derivatives and the extended Arnoldi step are device work (nlg_upo_*); GMRES and Newton
-# are the host loops of `gmres` / `newton_fixed_point_iteration` on extended vectors.  DESIGN.md 3.2 "Periodic-orbit Newton".
+# run in the host loops `_gmres` / `_newton` on extended vectors.  DESIGN.md 3.2 "Periodic-orbit Newton".
 class nek_ext_dvector:
     """reference: type nek_ext_dvector: a nek_dvector (`vec`) plus the period `T`; the inner product adds T T."""
 
@@ -845,71 +890,39 @@ def gmres_upo(sys: nek_upo_system, b: nek_ext_dvector, x: nek_ext_dvector, atol:
     norm, number of Jacobian matvecs)."""
     mesh = b.mesh
     B = basis if basis is not None else KrylovBasis(mesh, kdim + 1, 0, b.lorder)
-    x.zero()
-    r = b.copy()
-    nmv = 0
-    res = r.norm()
-    if history is not None:
-        history.append(res)
-    for _ in range(maxiter):
-        beta = res
-        if beta <= atol:
-            break
-        tcol = np.zeros(kdim + 2)
+    H = np.zeros((kdim + 2, kdim + 1), order="F")
+    tcol = np.zeros(kdim + 2)                                    # the period components of the basis
+
+    def first(r, beta):
+        H[:] = 0.0
+        tcol[:] = 0.0
         B[0].assign(r.vec)
         B[0].scal(1.0 / beta)
         tcol[0] = r.T / beta
-        H = np.zeros((kdim + 2, kdim + 1), order="F")
-        R = np.zeros((kdim + 1, kdim))
-        cs, sn = np.zeros(kdim), np.zeros(kdim)
-        g = np.zeros(kdim + 1)
-        g[0] = beta
-        k = 0
-        while k < kdim:
-            upo_arnoldi_step(sys, B, tcol, k, H)
-            nmv += 1
-            if not replay_history:
-                B[k + 1].clear_rst_fields()
-            h = H[: k + 2, k].copy()
-            for i in range(k):                                   # previous rotations
-                t = cs[i] * h[i] + sn[i] * h[i + 1]
-                h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1]
-                h[i] = t
-            d = np.sqrt(h[k] * h[k] + h[k + 1] * h[k + 1])
-            cs[k], sn[k] = (1.0, 0.0) if d == 0.0 else (h[k] / d, h[k + 1] / d)
-            h[k], h[k + 1] = d, 0.0
-            R[: k + 1, k] = h[: k + 1]
-            g[k + 1] = -sn[k] * g[k]
-            g[k] = cs[k] * g[k]
-            k += 1
-            res = abs(g[k])
-            if history is not None:
-                history.append(res)
-            if res <= atol:
-                break
-        y = np.zeros(k)                                          # R y = g; plain sequential sums, here and for dx.T, so that the
-        for i in range(k - 1, -1, -1):                           # Fortran shim's gmres_upo is the same arithmetic operation by operation
-            t = g[i]
-            for j in range(i + 1, k):
-                t = t - R[i, j] * y[j]
-            y[i] = t / R[i, i]
+
+    def column(k):
+        upo_arnoldi_step(sys, B, tcol, k, H)
+        if not replay_history:
+            B[k + 1].clear_rst_fields()
+        return H[: k + 2, k].copy()
+
+    def assemble(k, y):
         dx = nek_ext_dvector(mesh, b.lorder)
         B.combine(k, y, dx.vec)
         dx.T = 0.0
-        for j in range(k):
+        for j in range(k):                                       # (a plain sequential sum, see _gmres)
             dx.T = dx.T + float(tcol[j] * y[j])
-        x.axpby(1.0, dx, 1.0)
-        if res <= atol:
-            break
-        Jx = nek_ext_dvector(mesh, b.lorder)                     # true residual for the restart
+        return dx
+
+    def residual(x, r):
+        Jx = nek_ext_dvector(mesh, b.lorder)
         sys.jac_matvec(x, Jx)
-        nmv += 1
         if not replay_history:
             Jx.vec.clear_rst_fields()
         r.assign(b)
         r.axpby(-1.0, Jx, 1.0)
-        res = r.norm()
-    return res, nmv
+
+    return _gmres(b, x, atol, kdim, maxiter, history, first, column, assemble, residual)
 
 
 def newton_periodic_orbit(sys: nek_upo_system, X: nek_ext_dvector, tol: float, tol_mode: int = 1, maxiter: int = 40,
@@ -920,48 +933,28 @@ def newton_periodic_orbit(sys: nek_upo_system, X: nek_ext_dvector, tol: float, t
     convergence rule.  `X` is updated in place.  fixed_nsteps > 0 pins the step count of the orbit.  On convergence the orbit is
     written as `upo<session>0.f00001` with the period as the header's time.  The result feeds Floquet analysis as
     `exptA_orbit_linop(X.T, X.vec)`.  Returns the dictionary of newton_fixed_point_iteration plus `periods`, one per iteration."""
-    sched = nek_constant_tol if tol_mode == 1 else nek_dynamic_tol
     mesh = X.mesh
     if fixed_nsteps:
         sys.fixed_nsteps = int(fixed_nsteps)
-    r = nek_ext_dvector(mesh, X.lorder)
     dx = nek_ext_dvector(mesh, X.lorder)
     B = KrylovBasis(mesh, kdim + 1, 0, X.lorder)
-    final = sched(0.0, tol, 0.0)
-    cur, rnorm = 0.0, 1.0
-    residuals, periods, nmv_total, converged = [], [], 0, False
-    gmres_hist = []
-    for it in range(maxiter + 1):
-        new = sched(cur, tol, rnorm)
-        if new != cur:
-            cur = new
-            sys.set_tolerance(cur)
+    periods = []
+
+    def each():
         if X.T <= 0.0:
             raise NlgError("newton_periodic_orbit: the period estimate became %g" % X.T)
-        sys.eval(X, r)
-        if offset is not None:
-            r.axpby(-1.0, offset, 1.0)
-        rnorm = r.norm()
-        residuals.append(rnorm)
         periods.append(X.T)
-        if log is not None:
-            log("newton %2d  |F(X, T)| = %.6e  T = %.9f  solver tol %.3e" % (it, rnorm, X.T, cur))
-        if rnorm < tol and cur <= final:
-            converged = True
-            break
-        if it == maxiter:
-            break
-        sys.set_jacobian_state(X)
-        r.scal(-1.0)
-        gh = []
-        res, nmv = gmres_upo(sys, r, dx, atol=sched(cur, tol, rnorm), kdim=kdim, basis=B, history=gh)
-        gmres_hist.append(gh)
-        nmv_total += nmv
-        X.axpby(1.0, dx, 1.0)
-    if converged and outdir is not None:
+
+    def solve(r, atol, gh):
+        return dx, gmres_upo(sys, r, dx, atol=atol, kdim=kdim, basis=B, history=gh)[1]
+
+    out = _newton(sys, X, nek_ext_dvector(mesh, X.lorder), solve, tol, tol_mode, maxiter,
+                  lambda it, rnorm, cur: "newton %2d  |F(X, T)| = %.6e  T = %.9f  solver tol %.3e" % (it, rnorm, X.T, cur),
+                  log, offset, each)
+    out["periods"] = periods
+    if out["converged"] and outdir is not None:
         outpost_ext_dnek(X, "upo", session, outdir)
-    return {"converged": converged, "iterations": len(residuals) - 1, "residuals": residuals, "periods": periods,
-            "gmres_matvecs": nmv_total, "evals": sys.n_eval, "gmres_residuals": gmres_hist}
+    return out
 
 
 def arnoldi_step(exptA: exptA_linop, basis: KrylovBasis, k: int, H: np.ndarray, transpose: bool = False):
