@@ -357,10 +357,15 @@ int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *
  * nlg_linop_lane_iters: Helmholtz and pressure iterations of one lane in the last run on the operator, whatever kind it was (a matvec
  *   or block, nlg_linop_integrate_forced, nlg_linop_nonlinear_map, nlg_upo_residual, an OTD run): of its time step istep (1-based,
  *   the history steps of a matvec follow the nsteps), or summed over its steps for istep = 0; in orbit mode the base flow is the lane
- *   after the last perturbation.  Valid for any operator.  (nlg_linop_get_stats sums over the lanes, the base-flow lane included.) */
+ *   after the last perturbation.  Valid for any operator.  (nlg_linop_get_stats sums over the lanes, the base-flow lane included.)
+ * nlg_linop_pcg_z_free: *out = 1 if the velocity PCG of this operator does not store z = M^-1 r (the Helmholtz kernel forms it from the
+ *   residual, 1 / diag and one mask byte per point while it updates the search direction), 0 if it stores it: before nlg_linop_init,
+ *   in 2-D, with NLG_PCG_SINGLE_RED=1, NLG_PC_MASKB=0 or NLG_PCG_STORE_Z=1 in the environment when the operator was initialised.  Same
+ *   results either way. */
 int nlg_linop_set_orbit(nlg_linop *op, const nlg_vec *X0, double period);
 int nlg_linop_orbit_end(nlg_linop *op, nlg_vec *out);
 int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_iters, int64_t *p_iters);
+int nlg_linop_pcg_z_free(const nlg_linop *op, int *out);
 /* Periodic orbits: Newton-Krylov for the state X0 and the period T (nek_ext_dvector, src/vectors/real_extended_vectors.f90;
  * nek_upo_system / nek_upo_jacobian, src/systems/periodic_orbit.f90, neklab_systems.f90:147-223).  Every entry point below works on an
  * operator in orbit mode and refuses any other with a message that names nlg_linop_set_orbit.  One perturbation per call; no adjoint.

@@ -138,6 +138,7 @@ SIGNATURES = {
     "nlg_linop_set_orbit": (C.c_int, [vp, vp, C.c_double]),
     "nlg_linop_orbit_end": (C.c_int, [vp, vp]),
     "nlg_linop_lane_iters": (C.c_int, [vp, C.c_int, C.c_int, c_int64_p, c_int64_p]),
+    "nlg_linop_pcg_z_free": (C.c_int, [vp, c_int_p]),
     "nlg_linop_set_orbit_steps": (C.c_int, [vp, vp, C.c_double, C.c_int]),
     "nlg_upo_residual": (C.c_int, [vp, vp]),
     "nlg_upo_fdot": (C.c_int, [vp, C.c_int, vp]),

@@ -100,10 +100,11 @@ __device__ __forceinline__ void block_sum3(double &a, double &b, double &c, doub
 
 // Projected PCG (P = I - 1 1^T / n on the mean-free subspace, see oracle/lns.py pcg_E): the means of
 // w = A p and of z = M^-1 r ride along as extra partial sums of kernels that exist anyway.
-// x = 0, r = b (in place), z = pc*r ; partial sums of (r,z)_ipw, (r,r)_nw and sum(z)
+// x = 0, r = b (in place), z = pc*r (stored unless store_z == 0) ; partial sums of (r,z)_ipw, (r,r)_nw and sum(z)
 template <int NF>
 __global__ __launch_bounds__(NT) void k_cg_init(int64_t n, F3 x, F3 r, F3 z, CF3 pc, const double *ipw,
-                                                const double *nw, double *partial, int64_t ld, const unsigned char *__restrict__ mb, int defer_x) {
+                                                const double *nw, double *partial, int64_t ld, const unsigned char *__restrict__ mb, int defer_x,
+                                                int store_z) {
     __shared__ double sm[12];
     const int64_t lo = lane_lo(ld);
     x = lane_f3(x, lo), r = lane_f3(r, lo), z = lane_f3(z, lo), partial += lo;
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(NT) void k_cg_init(int64_t n, F3 x, F3 r, F3 z, CF3
             b += rv * rv * wn;
             if (mb || pc.p[c]) {      // pointwise (Jacobi) preconditioner; otherwise z comes from an operator
                 const double zv = (mb ? (((mk >> c) & 1u) ? inv : 0.0) : pc.p[c][i]) * rv;
-                z.p[c][i] = zv;
+                if (store_z) z.p[c][i] = zv;   // (0: the operator kernel forms z from r and the same two operands, CGProblem::z_free)
                 a += rv * zv * wi;
                 c3 += zv;
             }
@@ -158,12 +159,14 @@ __global__ __launch_bounds__(NT) void k_cg_pw(const double *s, int64_t n, CF3 p,
 }
 
 // x += alpha p (unless deferred) ; r -= alpha (w - wmean) ; z = pc r ; partial (r,z)_ipw, (r,r)_nw, sum(z)
+// store_z == 0 (CGProblem::z_free): z lives in registers for the sums only -- its one reader, the direction update fused into the
+// operator kernel, forms it again from r, 1 / diag and the mask byte (three streams fewer here, 1 1/8 more there)
 // Two points per lane (16-byte accesses; every field length is a multiple of 32): eight streams per component are
 // what this kernel is, so the width of an access is its efficiency.
 template <int NF>
 __global__ __launch_bounds__(NT) void k_cg_update(const double *s, int64_t n, F3 x, F3 r, F3 z, CF3 p, CF3 w, CF3 pc,
                                                   const double *ipw, const double *nw, double *partial, int64_t ld, int defer_x,
-                                                  const unsigned char *__restrict__ mb) {
+                                                  const unsigned char *__restrict__ mb, int store_z) {
     __shared__ double sm[12];
     const int64_t lo = lane_lo(ld);
     s += lo, x = lane_f3(x, lo), r = lane_f3(r, lo), z = lane_f3(z, lo), p = lane_f3(p, lo), w = lane_f3(w, lo), partial += lo;
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(NT) void k_cg_update(const double *s, int64_t n, F3
                 double2 zv;
                 zv.x = pcv.x * rv.x;
                 zv.y = pcv.y * rv.y;
-                reinterpret_cast<double2 *>(z.p[c])[i] = zv;
+                if (store_z) reinterpret_cast<double2 *>(z.p[c])[i] = zv;
                 a += rv.x * zv.x * wi.x + rv.y * zv.y * wi.y;
                 c3 += zv.x + zv.y;
             }
@@ -223,7 +226,7 @@ __global__ __launch_bounds__(NT) void k_cg_update(const double *s, int64_t n, F3
             b += rv * rv * wn;
             if (mb || pc.p[c]) {
                 const double zv = pcv * rv;
-                z.p[c][i] = zv;
+                if (store_z) z.p[c][i] = zv;
                 a += rv * zv * wi;
                 c3 += zv;
             }
@@ -907,7 +910,9 @@ struct Hist {
 template <int NF, bool XP = false>
 __global__ __launch_bounds__(NT) void k_rhs(int64_t n, Hist h, const double *bm1, double rdt, F3 rhs, int64_t ld, CF3 gp = CF3{{nullptr, nullptr, nullptr}},
                                             CF3 w = CF3{{nullptr, nullptr, nullptr}}, const int *__restrict__ slot = nullptr, int np = 1,
-                                            CF3 mask = CF3{{nullptr, nullptr, nullptr}}) {
+                                            CF3 mask = CF3{{nullptr, nullptr, nullptr}}, const unsigned char *__restrict__ mb = nullptr) {
+    // mb (XP): the three masks as the bits of one byte per point, in the slab-permuted layout (the velocity solve's maskb_v), instead of
+    // `mask`; a product with 1.0 or 0.0 as before, so a masked entry keeps the sign of its zero
     // (the lane offset is added at the loads: writing it into `h` would move the by-value struct from the kernel-argument segment,
     //  where the runtime index j costs a scalar load, into scratch memory -- measured 123 -> 315 us)
     const int64_t lo = lane_lo(ld);
@@ -922,6 +927,7 @@ __global__ __launch_bounds__(NT) void k_rhs(int64_t n, Hist h, const double *bm1
             const int64_t e = i / np;
             q = e * np + slot[(int)(i - e * np)];
         }
+        const unsigned mk = (XP && mb) ? mb[q] : 0u;
 #pragma unroll
         for (int c = 0; c < NF; ++c) {
             double a = 0.0, u = 0.0;
@@ -931,7 +937,7 @@ __global__ __launch_bounds__(NT) void k_rhs(int64_t n, Hist h, const double *bm1
             }
             double v = a + b * u;
             if (gp.p[c]) v = (v + gp.p[c][lo + i]) - w.p[c][lo + i];
-            rhs.p[c][q] = XP ? mask.p[c][i] * v : v;
+            rhs.p[c][q] = XP ? (mb ? (((mk >> c) & 1u) ? 1.0 : 0.0) : mask.p[c][i]) * v : v;
         }
     }
 }
@@ -968,8 +974,11 @@ __global__ __launch_bounds__(NT) void k_add_xp(int64_t n, int np, const int *__r
 
 // y_c += s * wt_c * x_c  (velocity correction: the inverse mass / mask weights of opbinv ride in the update)
 template <int NF, bool SLOT = false>
-__global__ __launch_bounds__(NT) void k_axpy_w(int64_t n, F3 y, CF3 x, CF3 wt, double s, int64_t ld, const int *__restrict__ slot = nullptr, int np = 1) {
+__global__ __launch_bounds__(NT) void k_axpy_w(int64_t n, F3 y, CF3 x, CF3 wt, double s, int64_t ld, const int *__restrict__ slot = nullptr, int np = 1,
+                                               const unsigned char *__restrict__ mb = nullptr) {
     // SLOT: x is stored in an element-local permutation (the face-grouped layout of the pressure operator's intermediates)
+    // mb: wt_c = bit c of mb ? wt.p[0] : 0 with wt.p[0] = binvm1 and the mask bytes both in the layout of x (3 weight arrays -> 1 + 1/8;
+    // the masks are zeros and ones, so these are the values of mask_c * binvm1)
     const int64_t lo = lane_lo(ld);
     y = lane_f3(y, lo), x = lane_f3(x, lo);
     for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
@@ -978,8 +987,13 @@ __global__ __launch_bounds__(NT) void k_axpy_w(int64_t n, F3 y, CF3 x, CF3 wt, d
             const int64_t e = i / np;
             q = e * np + slot[(int)(i - e * np)];
         }
+        const double bv = mb ? wt.p[0][q] : 0.0;
+        const unsigned mk = mb ? mb[q] : 0u;
 #pragma unroll
-        for (int c = 0; c < NF; ++c) y.p[c][i] += s * (wt.p[c][i] * x.p[c][q]);
+        for (int c = 0; c < NF; ++c) {
+            const double wv = mb ? (((mk >> c) & 1u) ? bv : 0.0) : wt.p[c][i];
+            y.p[c][i] += s * (wv * x.p[c][q]);
+        }
     }
 }
 
@@ -1127,6 +1141,10 @@ struct nlg_linop {
     // layout of the velocity solve: what k_cg_init / k_cg_update read (3 streams -> 1 + 1/8); pci_l[k] = {pci[k], pci[k], pci[k]}
     double *pci[4] = {}, *pci_l[4][3] = {};
     unsigned char *maskb_v = nullptr;
+    // the velocity PCG does not store z = pc r: the operator kernel forms it (3-D, compact preconditioner, not the single-reduction
+    // variant, a size sem_axhelm_forms_z accepts; NLG_PCG_STORE_Z=1 restores the stored z).  Decided by nlg_linop_init
+    bool z_free = false;
+    bool store_z = false;   // NLG_PCG_STORE_Z=1
     double *pce = nullptr;     // 1 / diag(E)
     double *prX = nullptr, *prB = nullptr, *d_pc = nullptr;   // pressure residual projection: PROJ_L solution / image pairs, coefficients
     int nproj = 0;
@@ -1350,6 +1368,7 @@ struct CGProblem {
     int pw_n = 0;
     bool pw_sum = true;                // false: the sum of w is not provided (and not needed: inv_n == 0)
     bool fused_pupdate = false;        // `apply` itself performs p <- z + beta p (gated by the done flag) before w = A p
+    bool z_free = false;               // ... and forms z = pc r itself, from r and pc / pc_mb: k_cg_init and k_cg_update do not store z
     const double *rz_part = nullptr;   // [2][rz_n]: sum r.z , sum z   (written by `precond`)
     int rz_n = 0;
     const double *rr_part = nullptr;   // [rr_n]: sum r^2 nw, written by `precond`, which then also performs the update
@@ -1392,7 +1411,7 @@ int run_pcg(nlg_linop *op, const CGProblem &P, Apply apply, int *iters_out) {
         }
         return 0;
     };
-    launch_nf(nf, k_cg_init<1>, k_cg_init<2>, k_cg_init<3>, lgrid(g, nl), st, P.n, x, r, z, pc, P.ipw, P.nw, partial, ld, P.pc_mb, (int)(P.hist.ph > 0));
+    launch_nf(nf, k_cg_init<1>, k_cg_init<2>, k_cg_init<3>, lgrid(g, nl), st, P.n, x, r, z, pc, P.ipw, P.nw, partial, ld, P.pc_mb, (int)(P.hist.ph > 0), (int)!P.z_free);
     if (P.sd && P.apply_plain && !P.precond && P.pw_part) {
         // ---- single-reduction PCG (Chronopoulos-Gear): ONE reduction per iteration carries (w, u), (r, u) and |r|^2; several ranks: one
         // all-reduce instead of two.  u = M^-1 r lives in z, p and s = A p are recurrences.  Same iterates as the loop below in exact
@@ -1473,7 +1492,7 @@ int run_pcg(nlg_linop *op, const CGProblem &P, Apply apply, int *iters_out) {
         if (!P.rr_part) {
             ProfScope pu(ctx, P_CGUPDATE);   // the largest single kernel of a step by time: its own class inside cg_vec (bench.py quotes its roofline)
             launch_nf(nf, k_cg_update<1>, k_cg_update<2>, k_cg_update<3>, lgrid(g, nl), st, (const double *)s, P.n, x, r, z, cp, cw,
-                      pc, P.ipw, P.nw, partial, ld, (int)(P.hist.ph > 0), P.pc_mb);
+                      pc, P.ipw, P.nw, partial, ld, (int)(P.hist.ph > 0), P.pc_mb, (int)!P.z_free);
         }
         ++nbody;
         if (prof_cg) prof_end(ctx, P_CGVEC);
@@ -1586,6 +1605,8 @@ int helm_problem(const Lanes &L, int order, double h2, HelmSolve &H) {
     P.pw_n = sem_axhelm_blocks(m, dim);
     P.pw_sum = false;
     P.fused_pupdate = true;
+    // z = pc r is a pointwise product of what the operator kernel can read itself: it is not stored (NLG_PCG_STORE_Z=1 keeps it)
+    P.z_free = op->z_free;
     if (op->ph > 0) {
         for (int q = 0; q < dim; ++q) P.hist.p0[q] = op->phist + (int64_t)q * m->lvs;
         P.hist.stride = (int64_t)dim * m->lvs;
@@ -1598,6 +1619,10 @@ int helm_apply(const Lanes &L, const HelmSolve &H) {
     nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
     const int dim = m->dim;
+    // z-free: the kernel reads the residual where it read z, and 1 / diag and the mask bytes of the solve (H.P.pc, H.P.pc_mb)
+    double *const *zf = H.P.z_free ? H.P.r : op->z;
+    const double *pcinv = H.P.z_free ? H.P.pc[0] : nullptr;
+    const unsigned char *pcmb = H.P.z_free ? H.P.pc_mb : nullptr;
     if (H.P.hist.ph > 0) {
         // direction ring: read direction it - 1, store direction it one slot further (the first application multiplies slot ph - 1 by
         // beta = 0: the ring is zeroed with the slab and holds finite values ever after)
@@ -1605,10 +1630,10 @@ int helm_apply(const Lanes &L, const HelmSolve &H) {
         ++H.it;
         double *pin[3] = {nullptr, nullptr, nullptr};
         for (int q = 0; q < dim; ++q) pin[q] = op->phist + si * H.P.hist.stride + (int64_t)q * m->lvs;
-        NLG_TRY(sem_axhelm(m, pin, op->w, dim, H.nu, H.h2, H.pw_part, op->z, op->d_s + S_BETA, op->d_s + S_DONE, H.xp, L.nl, L.ld(),
-                           (so - si) * H.P.hist.stride));
+        NLG_TRY(sem_axhelm(m, pin, op->w, dim, H.nu, H.h2, H.pw_part, zf, op->d_s + S_BETA, op->d_s + S_DONE, H.xp, L.nl, L.ld(),
+                           (so - si) * H.P.hist.stride, pcinv, pcmb));
     } else {
-        NLG_TRY(sem_axhelm(m, op->pv, op->w, dim, H.nu, H.h2, H.pw_part, op->z, op->d_s + S_BETA, op->d_s + S_DONE, H.xp, L.nl, L.ld()));
+        NLG_TRY(sem_axhelm(m, op->pv, op->w, dim, H.nu, H.h2, H.pw_part, zf, op->d_s + S_BETA, op->d_s + S_DONE, H.xp, L.nl, L.ld(), 0, pcinv, pcmb));
     }
     NLG_TRY(sem_gs(m, op->w, dim, op->d_s + S_DONE, H.xp ? LAYOUT_XP : LAYOUT_NAT, L.nl, L.ld(), L.ld()));
     return 0;
@@ -2130,13 +2155,14 @@ int adv_a(const Lanes &L) {
         // its gather-scatter moves the layout's 64-byte runs instead of the natural layout's single points)
         CF3 mk = {{m->d_mask[0], m->d_mask[1], m->d_mask[2]}};
         launch_nf(dim, k_rhs<1, true>, k_rhs<2, true>, k_rhs<3, true>, lgrid(grid_for(m->lvn), nl), st, m->lvn, h, (const double *)m->d_bm1, 1.0 / dt,
-                  f3(op->rhs, dim), ld, cf3(op->gp, dim), cf3(op->w, dim), (const int *)m->d_slot_xp, m->np1, mk);
+                  f3(op->rhs, dim), ld, cf3(op->gp, dim), cf3(op->w, dim), (const int *)m->d_slot_xp, m->np1, mk,
+                  (const unsigned char *)op->maskb_v);   // (the bytes are in this layout: nlg_linop_init; null = the three mask arrays)
         NLG_TRY(sem_gs(m, op->rhs, dim, nullptr, LAYOUT_XP, nl, ld, 0));
         op->rhs_in_xp = true;
         return 0;
     }
     launch_nf(dim, k_rhs<1>, k_rhs<2>, k_rhs<3>, lgrid(grid_for(m->lvn), nl), st, m->lvn, h, (const double *)m->d_bm1, 1.0 / dt,
-              f3(op->rhs, dim), ld, cf3(op->gp, dim), cf3(op->w, dim), (const int *)nullptr, 1, CF3{{nullptr, nullptr, nullptr}});
+              f3(op->rhs, dim), ld, cf3(op->gp, dim), cf3(op->w, dim), (const int *)nullptr, 1, CF3{{nullptr, nullptr, nullptr}}, (const unsigned char *)nullptr);
     NLG_TRY(sem_gs(m, op->rhs, dim, nullptr, LAYOUT_NAT, nl, ld, 0));
     if (op->use_xp <= 0) {   // (slab-permuted velocity solve: the mask is applied by the permutation of the right-hand side, helm_problem)
         CF3 mk = {{m->d_mask[0], m->d_mask[1], m->d_mask[2]}};
@@ -2194,12 +2220,15 @@ int adv_c(const Lanes &L) {
     const bool fused = op->d_filt && op->filt_fused;
     if (!fused) {
         CF3 wt = {{m->d_mbinv[0], m->d_mbinv[1], m->d_mbinv[2]}};
+        // compact weights (as the velocity preconditioner's, and under its switch): binvm1 and the mask bytes in the face-grouped layout
+        const bool wb = fg && op->maskb_v && m->d_maskb_fg && m->d_binv_fg;
+        if (wb) wt.p[0] = m->d_binv_fg;
         if (fg)
             launch_nf(dim, k_axpy_w<1, true>, k_axpy_w<2, true>, k_axpy_w<3, true>, lgrid(grid_for(m->lvn), nl), st, m->lvn, f3(unew, dim), cf3(op->gp, dim),
-                      wt, dt / b0, ld, (const int *)m->d_slot_fg, m->np1);
+                      wt, dt / b0, ld, (const int *)m->d_slot_fg, m->np1, wb ? (const unsigned char *)m->d_maskb_fg : (const unsigned char *)nullptr);
         else
             launch_nf(dim, k_axpy_w<1>, k_axpy_w<2>, k_axpy_w<3>, lgrid(grid_for(m->lvn), nl), st, m->lvn, f3(unew, dim), cf3(op->gp, dim), wt, dt / b0,
-                      ld, (const int *)nullptr, 1);
+                      ld, (const int *)nullptr, 1, (const unsigned char *)nullptr);
     }
     if (op->d_filt) {
         // explicit filter, the last thing a step does: the velocity of every lane and, coupled, the new temperature (which the fluid
@@ -2655,6 +2684,8 @@ int nlg_linop_init(nlg_linop *op) {
         // (NLG_PCG_DEFER_XP=16): measured neutral at 10^4 elements -- the update kernel of the preconditioner drops 3 of its 9 streams
         // (preconditioner class 7.06 -> 6.83 ms per step), the assembly of x and the colder directions give it back (44.5 ms either way)
         op->php = (dim == 3 && sem_opgradt_fuses_pupdate(m) && getenv("NLG_PCG_DEFER_XP")) ? std::max(0, std::min(kAlphaRing, atoi(getenv("NLG_PCG_DEFER_XP")))) : 0;
+        // z = pc r of the velocity PCG formed by the operator kernel instead of stored and loaded back; NLG_PCG_STORE_Z=1 keeps the stored z
+        op->store_z = getenv("NLG_PCG_STORE_Z") && atoi(getenv("NLG_PCG_STORE_Z")) != 0;
         NLG_TRY(slab_ensure(op, 1));   // the work buffers of one lane; a block matvec grows the slab on first use
         NLG_TRY(lalloc(op, &op->d_red, 3 * kMaxLanes));
         op->set_up = true;
@@ -2720,6 +2751,8 @@ int nlg_linop_init(nlg_linop *op) {
         }
         NLG_LAUNCH(k_to_bytes, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, op->maskb_v, (const double *)(xp ? t1 : t0));
     }
+    // (the velocity solve always runs the direction update inside the operator kernel, helm_problem)
+    op->z_free = dim == 3 && op->maskb_v && !op->use_sr && !op->store_z && sem_axhelm_forms_z(m);
     if (op->cfg.ifheat) {
         if (!op->pct[1]) {
             for (int k = 1; k <= op->cfg.torder; ++k) NLG_TRY(lalloc(op, &op->pct[k], m->lvs));
@@ -3044,6 +3077,12 @@ int nlg_linop_lane_iters(const nlg_linop *op, int lane, int istep, int64_t *v_it
     NLG_CHECK(istep < (int)lp.v.hist.size() && istep < (int)lp.p.hist.size(), "nlg_linop_lane_iters: lane %d has not run a time step %d", lane, istep);
     if (v_iters) *v_iters = lp.v.hist[istep];
     if (p_iters) *p_iters = lp.p.hist[istep];
+    return 0;
+}
+
+int nlg_linop_pcg_z_free(const nlg_linop *op, int *out) {
+    NLG_CHECK(op && out, "nlg_linop_pcg_z_free: bad argument");
+    *out = op->z_free ? 1 : 0;
     return 0;
 }
 

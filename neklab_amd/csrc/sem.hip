@@ -551,7 +551,8 @@ __global__ __launch_bounds__(64 * kAxhelm3rWaves) void k_axhelm3r(int64_t E, int
                                                        const double *__restrict__ G4, const double *__restrict__ G5,
                                                        const double *__restrict__ bm1, CF3 u, F3 w, double h1, double h2,
                                                        double *__restrict__ pw_part, CF3 zf, const double *__restrict__ beta_p,
-                                                       const double *__restrict__ done_p, const int *__restrict__ xptab, int64_t ld, int64_t uoff) {
+                                                       const double *__restrict__ done_p, const int *__restrict__ xptab, int64_t ld, int64_t uoff,
+                                                       const double *__restrict__ pcinv, const unsigned char *__restrict__ pcmb) {
     static_assert(N * N <= 64, "one lane per (i, j)");
     constexpr int NP = N * N * N, NS = N * N, NQ = N + 1, WPB = kAxhelm3rWaves;
     __shared__ double sD[N * N];
@@ -597,18 +598,32 @@ __global__ __launch_bounds__(64 * kAxhelm3rWaves) void k_axhelm3r(int64_t E, int
     double uk[N], wk[N], di[N], dj[N], dti[N], dtj[N];
     // all loads of the column first, then the stores of the fused direction update: with load / store alternating per point the
     // compiler cannot hoist the later loads over the earlier stores (same array) and the wave pays N serialised round trips
+    // pcinv: zf carries the residual r of the Jacobi-preconditioned PCG and z = M^-1 r is formed here, from 1 / diag and the point's mask
+    // byte (both shared by the lanes, in the layout of zf) -- the product k_cg_update forms for its sums, so the same bits, and z is
+    // never stored.  A statement of its own: the product is rounded before the direction update adds to it, as the stored z was
     {
-        double zk[N];
+        double zk[N], ik[N];
+        unsigned mk[N];
+        const bool zfree = pcinv != nullptr;
+        const double *ic = zfree ? pcinv + eoff : nullptr;
+        const unsigned char *mc = zfree ? pcmb + eoff : nullptr;
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             uk[k] = act ? uc[vk[k]] : 0.0;
             zk[k] = (upd && act) ? zc[vk[k]] : 0.0;
+            ik[k] = (zfree && upd && act) ? ic[vk[k]] : 0.0;
+            mk[k] = (zfree && upd && act) ? mc[vk[k]] : 0u;
             wk[k] = 0.0;
         }
         if (upd && act) {
 #pragma unroll
             for (int k = 0; k < N; ++k) {
-                uk[k] = zk[k] + beta * uk[k];
+                double zv = zk[k];
+                if (zfree) {
+                    const double pcv = ((mk[k] >> c) & 1u) ? ik[k] : 0.0;
+                    zv = pcv * zk[k];
+                }
+                uk[k] = zv + beta * uk[k];
                 const_cast<double *>(uc)[uoff + vk[k]] = uk[k];
             }
         }
@@ -713,7 +728,8 @@ __global__ __launch_bounds__(((PPB * N * N + 63) / 64) * 64) void k_axhelm3c(int
                                                                         const double *__restrict__ G4, const double *__restrict__ G5,
                                                                         const double *__restrict__ bm1, CF3 u, F3 w, double h1, double h2,
                                                                         double *__restrict__ pw_part, CF3 zf, const double *__restrict__ beta_p,
-                                                                        const double *__restrict__ done_p, const int *__restrict__ xptab, int64_t ld, int64_t uoff) {
+                                                                        const double *__restrict__ done_p, const int *__restrict__ xptab, int64_t ld, int64_t uoff,
+                                                                        const double *__restrict__ pcinv, const unsigned char *__restrict__ pcmb) {
     constexpr int NP = N * N * N, NS = N * N, NQ = N + 1, NTB = ((PPB * NS + 63) / 64) * 64, NWB = NTB / 64;
     __shared__ double sD[NS];
     __shared__ double mUa[PPB][N * NQ], mRa[PPB][N * NQ], mSa[PPB][N * NQ];
@@ -768,18 +784,29 @@ __global__ __launch_bounds__(((PPB * N * N + 63) / 64) * 64) void k_axhelm3c(int
     const bool upd = beta_p != nullptr && done_p[0] == 0.0;
     const double beta = upd ? beta_p[0] : 0.0;
     double uk[N], wk[N], di[N], dj[N], dti[N], dtj[N];
-    {   // loads first, then the stores of the fused direction update (see k_axhelm3r)
-        double zk[N];
+    {   // loads first, then the stores of the fused direction update; pcinv: zf carries r and z = M^-1 r is formed here (see k_axhelm3r)
+        double zk[N], ik[N];
+        unsigned mk[N];
+        const bool zfree = pcinv != nullptr;
+        const double *ic = zfree ? pcinv + eoff : nullptr;
+        const unsigned char *mc = zfree ? pcmb + eoff : nullptr;
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             uk[k] = act ? uc[pk[k]] : 0.0;
             zk[k] = (upd && act) ? zc[pk[k]] : 0.0;
+            ik[k] = (zfree && upd && act) ? ic[pk[k]] : 0.0;
+            mk[k] = (zfree && upd && act) ? mc[pk[k]] : 0u;
             wk[k] = 0.0;
         }
         if (upd && act) {
 #pragma unroll
             for (int k = 0; k < N; ++k) {
-                uk[k] = zk[k] + beta * uk[k];
+                double zv = zk[k];
+                if (zfree) {
+                    const double pcv = ((mk[k] >> c) & 1u) ? ik[k] : 0.0;
+                    zv = pcv * zk[k];
+                }
+                uk[k] = zv + beta * uk[k];
                 const_cast<double *>(uc)[uoff + pk[k]] = uk[k];
             }
         }
@@ -3481,9 +3508,15 @@ int sem_axhelm_blocks(nlg_mesh *m, int nf) {
     return (int)((m->E * nf + slots - 1) / slots);
 }
 
+// z = M^-1 r inside the operator kernel (pcinv / pcmb of sem_axhelm): every 3-D size keeps its waves per SIMD and stays free of
+// scratch with the two extra columns in the prologue (register table: DESIGN section 5)
+bool sem_axhelm_forms_z(const nlg_mesh *m) { return m->dim == 3; }
+
 int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h1, double h2, double *pw_part,
-               double *const *zf, const double *beta_p, const double *done_p, bool xp, int nl, int64_t ld, int64_t uoff) {
+               double *const *zf, const double *beta_p, const double *done_p, bool xp, int nl, int64_t ld, int64_t uoff,
+               const double *pcinv, const unsigned char *pcmb) {
     NLG_CHECK(nf >= 1 && nf <= 3, "sem_axhelm: nf=%d unsupported", nf);
+    NLG_CHECK(!pcinv || (m->dim == 3 && pcmb && beta_p), "sem_axhelm: z = M^-1 r inside the operator needs 3-D, the mask bytes and the fused direction update");
     NLG_CHECK(uoff == 0 || beta_p, "sem_axhelm: an output offset for the direction without the fused direction update");
     if (nl > 1 && m->dim == 2) {
         // the 2-D kernel has no lane dimension: one launch per lane at the lane's offsets
@@ -3510,16 +3543,16 @@ int sem_axhelm(nlg_mesh *m, double *const *u, double *const *w, int nf, double h
         if constexpr (N_ <= 8) {                                                                                      \
             const dim3 grid((unsigned)((tot + kAxhelm3rWaves - 1) / kAxhelm3rWaves), nl), block(64 * kAxhelm3rWaves); \
             if (xp)                                                                                                   \
-                NLG_LAUNCH((k_axhelm3r<N_, true>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
+                NLG_LAUNCH((k_axhelm3r<N_, true>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff, pcinv, pcmb); \
             else                                                                                                      \
-                NLG_LAUNCH((k_axhelm3r<N_, false>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
+                NLG_LAUNCH((k_axhelm3r<N_, false>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff, pcinv, pcmb); \
         } else {                                                                                                      \
             constexpr int PPB_ = axhelm3c_ppb(N_);                                                                    \
             const dim3 grid((unsigned)((tot + PPB_ - 1) / PPB_), nl), block(((PPB_ * N_ * N_ + 63) / 64) * 64);       \
             if (xp)                                                                                                   \
-                NLG_LAUNCH((k_axhelm3c<N_, true, PPB_>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
+                NLG_LAUNCH((k_axhelm3c<N_, true, PPB_>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff, pcinv, pcmb); \
             else                                                                                                      \
-                NLG_LAUNCH((k_axhelm3c<N_, false, PPB_>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff); \
+                NLG_LAUNCH((k_axhelm3c<N_, false, PPB_>), grid, block, 0, s, m->E, nf, m->d_D, m->d_G[0], m->d_G[1], m->d_G[2], m->d_G[3], m->d_G[4], m->d_G[5], m->d_bm1, cu, cw, h1, h2, pw_part, cz, beta_p, done_p, tab, ld, uoff, pcinv, pcmb); \
         }                                                                                                             \
     }
         NLG_FOR_N(AX3)

@@ -356,7 +356,9 @@ class exptA_linop:
     def info(self) -> dict:
         tau, dt, cfl, ns = C.c_double(), C.c_double(), C.c_double(), C.c_int()
         check(self.lib.nlg_linop_get_info(self.h, C.byref(tau), C.byref(dt), C.byref(ns), C.byref(cfl)))
-        return {"tau": tau.value, "dt": dt.value, "nsteps": ns.value, "cfl": cfl.value}
+        zf = C.c_int()
+        check(self.lib.nlg_linop_pcg_z_free(self.h, C.byref(zf)))   # 1: the velocity PCG does not store z (NLG_PCG_STORE_Z=1 -> 0)
+        return {"tau": tau.value, "dt": dt.value, "nsteps": ns.value, "cfl": cfl.value, "pcg_z_free": zf.value}
 
     def stats(self) -> dict:
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
