@@ -121,6 +121,9 @@ int nlg_mesh_sizes(const nlg_mesh *mesh, int64_t *lvn, int64_t *lpn, int *dim, i
 /* read back a derived array by name for verification: "bm1", "binvm1", "vmult", "jac", "bm2",
  * "g11".."g33" (Nek g1m1..g6m1 ordering by index pair), "rxm1"... (as "rst11".."rst33") */
 int nlg_mesh_get(const nlg_mesh *mesh, const char *name, double *out, int64_t count);
+/* *out = 1 if single-vector launches of the pressure operator (opgradt, opdiv) on this mesh take the matrix-pipe kernels: 3-D, lx1 = 8,
+ * at least NLG_SMALL_E local elements, NLG_POP_MFMA not 0 */
+int nlg_mesh_pop_mfma(const nlg_mesh *mesh, int *out);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* nek_dvector                                                                                      */

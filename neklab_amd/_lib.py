@@ -88,6 +88,7 @@ SIGNATURES = {
     "nlg_mesh_destroy": (C.c_int, [vp]),
     "nlg_mesh_sizes": (C.c_int, [vp, c_int64_p, c_int64_p, c_int_p, c_int_p]),
     "nlg_mesh_get": (C.c_int, [vp, C.c_char_p, c_double_p, C.c_int64]),
+    "nlg_mesh_pop_mfma": (C.c_int, [vp, c_int_p]),
     "nlg_vec_create": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp)]),
     "nlg_vec_destroy": (C.c_int, [vp]),
     "nlg_vec_clone": (C.c_int, [vp, C.POINTER(vp)]),

@@ -428,6 +428,7 @@ int sem_opdiv(nlg_mesh *m, double *const *u, double *out, double scale, double *
 int sem_opbinv(nlg_mesh *m, double *const *w, int nl = 1, int64_t ld = 0);                       // w_i <- mask_i binv QQ^T w_i
 bool sem_opgradt_fuses_pupdate(const nlg_mesh *m);
 bool sem_small_mesh(const nlg_mesh *m);   // local element count below the threshold of the strong-scaling kernel variants (NLG_SMALL_E)
+bool sem_pop_mfma(const nlg_mesh *m);     // single-vector opgradt / opdiv launches take the matrix-pipe kernels (3-D, lx1 = 8, not a small mesh; NLG_POP_MFMA)
 int sem_cdabdtp(nlg_mesh *m, const double *p, double *out, double *pw_part = nullptr, const double *gate = nullptr, const nlg_pupd *upd = nullptr,
                 int nl = 1, int64_t ld = 0);
 int sem_ediag(nlg_mesh *m, double *out);

@@ -3586,6 +3586,343 @@ int sem_helm_diag(nlg_mesh *m, double *out, double h1, double h2) {
     return 0;
 }
 
+namespace {
+// ---- pressure operator at lx1 = 8 on the matrix pipe (single-vector launches of large meshes) --------------------------------
+// One wave per element as in k_opgradt3n / k_opdiv3n, the nine contractions of an element as v_mfma_f64_16x16x4_f64 tiles (operand
+// layouts: k_interp4_mfma).  fp64 MFMA has the peak rate of the vector pipe, so the flops gain nothing (the first form of these kernels,
+// with the memory accesses of the vector kernels, was no faster: DESIGN.md section 5); what the operand layouts buy is memory accesses in
+// whole `lane + 64 u` sweeps of the element where the vector kernels move 8 bytes per lane at a stride of 64.
+// Between the stages ONE LDS array holds the intermediate in two alternating layouts of stride 54:
+//   S1: the three z-side arrays A_j / C_j [i2][j2][k] at  (j * 6 + j2) * 54 + k * 6 + i2   (18 rows of 48)
+//   S2: the two x-side arrays  B_b [i2][j][k]         at  (b * 8 + j) * 54 + k * 6 + i2    (16 rows of 48)
+// A tile of the y stage reads and writes the same 16 columns (k, i2) of the rows, so that stage runs in place tile by tile.  Stride 54
+// puts the 16-lane groups of the z-stage ds_write_b64 of opgradt on 16 different double-words mod 16, and its y stage pairs K rows 8
+// apart in a half-wave (8 * 54 = 16 mod 32) for conflict-free reads; the other exchanges keep two-way conflicts on some banks.
+// opgradt: z stage K = 12 for the pair (A_0 | A_2) = [I^T 0; 0 D^T] [q_0; q_2] and K = 6 (+2 padding) for A_1: 5 MFMA per 16 columns, 3
+// tiles of the 36 columns, B operands = metric * p straight from the global loads; y stage the 16 x 18 block matrix [I^T 0 0; 0 D^T I^T],
+// K = 20, 3 tiles; x stage TRANSPOSED, the data as A operand and [D^T | I^T]^T as B operand, two rows j per tile (K = 24), 2 tiles: the D
+// registers are sweeps of the element.  15 + 15 + 12 = 42 MFMA per component, 126 per element.
+// opdiv (face-grouped layout with the compact weights only: in the natural layout without weights k_opdiv3n is faster): ONE A operand
+// [D; I] (rows 0 - 5 and 8 - 13, K = 8) serves all three stages.  x stage: the element arrives as eight sweeps, is weighted and goes
+// through an LDS cube into the B operands, 4 tiles x 2; y stage 3 tiles x (2 + 2): [D; I] B_1 = (C_1; C_2), the I half of [D; I] B_0 = C_0;
+// z stage 3 arrays x 3 tiles x 2, the metric products summed in the layout of the D registers.  8 + 12 + 18 = 38 per component, 114
+// per element.  Padded K entries: zero in A, a finite value in B.
+__device__ __forceinline__ v4f64 mfma4(double a, double b, v4f64 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+// gathers through a 32-bit byte offset from a wave-uniform base (scalar base + vector offset: no 64-bit address per lane and load)
+__device__ __forceinline__ double ld_off(const double *base, unsigned off) { return *(const double *)((const char *)base + off); }
+
+template <bool FG, bool PU>
+__global__ __launch_bounds__(64, 4) void k_opgradt3m8(int64_t E, const double *__restrict__ mIt, const double *__restrict__ mDt, const int *__restrict__ fgtab, CF9 g,
+                                                   const double *__restrict__ p, F3 w, const double *__restrict__ gate, std::conditional_t<PU, PUpd, NoPUpd> pu) {
+    constexpr int N = 8, N2 = 6, NS2 = 36, NP2 = 216, NP1 = 512, RW = 54, RY = 54;
+    __shared__ double sS[18 * RW];
+    if (gate && gate[0] != 0.0) return;
+    const int lane = threadIdx.x, l15 = lane & 15, lg = lane >> 4, r8 = l15 & 7;
+    const bool top = l15 < 8, lo = lg < 2;
+    const int64_t e = blockIdx.x;
+    const v4f64 zero = {0.0, 0.0, 0.0, 0.0};
+    // K order of the z stage: k2 = lg (all lanes) and k2 = 4 + (lg & 1); in the pair tile lanes lg < 2 carry q_0 and lanes lg >= 2 carry q_2 there
+    const int kA = lg, kB = 4 + (lg & 1);
+    const double zA0 = top ? mIt[r8 * N2 + kA] : 0.0;
+    const double zA1 = lo ? (top ? mIt[r8 * N2 + kB] : 0.0) : (top ? 0.0 : mDt[r8 * N2 + kB]);
+    const double zA2 = top ? 0.0 : mDt[r8 * N2 + kA];
+    // y stage: K row = (array, j2) = 6 array + j2.  Lanes lg and lg + 1 of a half-wave read rows 8 apart (8 * 54 = 16 mod 32): steps
+    // 0 - 3 take rows (2 s + (lg >> 1)) + 8 (lg & 1), step 4 rows 16, 17 on the even lg and padding on the odd ones
+    double yA[5];
+    int yoff[5];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        const bool pad = s == 4 && (lg & 1);
+        const int kr = s < 4 ? (2 * s + (lg >> 1)) + 8 * (lg & 1) : 16 + (lg >> 1);
+        const int arr = kr / N2, j2 = kr % N2;
+        const double v = top ? (arr == 0 ? mIt[r8 * N2 + j2] : 0.0) : (arr == 1 ? mDt[r8 * N2 + j2] : (arr == 2 ? mIt[r8 * N2 + j2] : 0.0));
+        yA[s] = pad ? 0.0 : v;
+        yoff[s] = kr * RW + l15;
+    }
+    // x stage, transposed so that the D registers are `lane + 64 u` sweeps of the element: the DATA are the A operand (row = (j pair
+    // l15 & 3, plane 4 tile + (l15 >> 2))), the matrix [D^T | I^T]^T the B operand (column = point a = l15 & 7).  Columns 0 - 7 take the
+    // even row j of the pair through K rows 0 - 11 (6 b + i2 = 4 s + lg), columns 8 - 15 the odd one through K rows 12 - 23
+    double xM[3];
+    int xoff[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int kr = 4 * s + lg, b = kr / N2, i2 = kr % N2;
+        xM[s] = b == 0 ? mDt[r8 * N2 + i2] : mIt[r8 * N2 + i2];
+        xoff[s] = (b * N + 2 * (l15 & 3)) * RY + (l15 >> 2) * N2 + i2;
+    }
+    // the z columns of this lane: col = 16 t + l15 (clamped: the padding columns carry p = 0 and finite metrics)
+    int ia[3], ib[3], zw[3];
+    bool cv[3];
+    double pA[3], pB[3];
+    const double *pe = p + e * NP2;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const int col = 16 * t + l15, cc = col < NS2 ? col : NS2 - 1;
+        cv[t] = col < NS2;
+        ia[t] = cc + NS2 * kA;
+        ib[t] = cc + NS2 * kB;
+        zw[t] = (cc / N2) * RW + cc % N2;
+        pA[t] = pe[ia[t]];
+        pB[t] = pe[ib[t]];
+    }
+    if constexpr (PU) if (pu.z[0]) {
+        const double beta = pu.beta[0][0], zmean = pu.zmean[0][0];
+        const double *ze = pu.z[0] + e * NP2;
+        double *po = pu.p[0] + e * NP2;
+        double zvA[3], zvB[3];   // loads first, stores afterwards (see k_opgradt3n)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            zvA[t] = ze[ia[t]];
+            zvB[t] = ze[ib[t]];
+        }
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            pA[t] = (zvA[t] - zmean) + beta * pA[t];
+            pB[t] = (zvB[t] - zmean) + beta * pB[t];
+            if (cv[t]) po[ia[t]] = pA[t];
+            if (cv[t] && lo) po[ib[t]] = pB[t];   // (lanes lg and lg + 2 hold the same two planes k2 = 4, 5)
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+        if (!cv[t]) pA[t] = pB[t] = 0.0;
+    // metric columns of a component: requested two LDS stages before their use.  [0] g_0i, [1] g_2i, [2] g_1i at k2 = kA;
+    // [3] g_0i (lg < 2) or g_2i at kB; [4] g_1i at kB
+    double gq[3][5];
+    auto load_g = [&](int i) {
+        const double *g0 = g.p[i] + e * NP2, *g1 = g.p[3 + i] + e * NP2, *g2 = g.p[6 + i] + e * NP2;
+        const double *gx = lo ? g0 : g2;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            gq[t][0] = g0[ia[t]];
+            gq[t][1] = g2[ia[t]];
+            gq[t][2] = g1[ia[t]];
+            gq[t][3] = gx[ib[t]];
+            gq[t][4] = g1[ib[t]];
+        }
+    };
+    load_g(0);
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i) {
+        if (i > 0) lds_barrier();   // the x stage of the previous component has read its columns
+        // z stage -> S1
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            v4f64 d = mfma4(zA0, gq[t][0] * pA[t], zero);
+            d = mfma4(zA1, gq[t][3] * pB[t], d);
+            d = mfma4(zA2, gq[t][1] * pA[t], d);
+            v4f64 d1 = mfma4(zA0, gq[t][2] * pA[t], zero);
+            d1 = mfma4(zA1, lo ? gq[t][4] * pB[t] : 0.0, d1);
+            if (cv[t]) {
+                double *r = sS + zw[t] + N2 * lg;
+                r[0] = d[0];
+                r[4 * N2] = d[1];
+                r[N2 * RW] = d1[0];
+                r[N2 * RW + 4 * N2] = d1[1];
+                r[2 * N2 * RW] = d[2];
+                r[2 * N2 * RW + 4 * N2] = d[3];
+            }
+        }
+        if (i < 2) load_g(i + 1);
+        lds_barrier();
+        // y stage: S1 -> S2, in place tile by tile (a tile reads and writes its own 16 columns of the rows)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            double yb[5];
+#pragma unroll
+            for (int s = 0; s < 5; ++s) yb[s] = sS[yoff[s] + 16 * t];
+            v4f64 d = mfma4(yA[0], yb[0], zero);
+#pragma unroll
+            for (int s = 1; s < 5; ++s) d = mfma4(yA[s], yb[s], d);
+            double *r = sS + lg * RY + 16 * t + l15;
+            r[0] = d[0];
+            r[4 * RY] = d[1];
+            r[8 * RY] = d[2];
+            r[12 * RY] = d[3];
+        }
+        lds_barrier();
+        // x stage: S2 -> HBM; tile t = planes 4 t .. 4 t + 3, register r of the result = points lane + 64 (4 t + r)
+        double *wp = w.p[i] + e * NP1;
+        int sl[2][4];   // face-grouped slots from the table (loads before the stores)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sl[t][r] = FG ? fgtab[lane + 64 * (4 * t + r)] : lane + 64 * (4 * t + r);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            v4f64 d = zero;
+#pragma unroll
+            for (int s = 0; s < 3; ++s) d = mfma4(sS[xoff[s] + 4 * t * N2], top ? xM[s] : 0.0, d);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) d = mfma4(sS[xoff[s] + RY + 4 * t * N2], top ? 0.0 : xM[s], d);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wp[sl[t][r]] = d[r];
+        }
+    }
+}
+
+__global__ __launch_bounds__(64, 4) void k_opdiv3m8(int64_t E, const double *__restrict__ mIm, const double *__restrict__ mDm, const int *__restrict__ fgtab, CF9 g, CF3 u,
+                                                 const double *__restrict__ binv, const unsigned char *__restrict__ mb, double *__restrict__ out, double scale,
+                                                 const double *__restrict__ pdot, double *__restrict__ part, const double *__restrict__ gate) {
+    constexpr int N = 8, N2 = 6, NS2 = 36, NP2 = 216, NP1 = 512, RW = 54, RY = 54;
+    __shared__ double sS[18 * RW];
+    if (gate && gate[0] != 0.0) return;
+    const int lane = threadIdx.x, l15 = lane & 15, lg = lane >> 4, r8 = l15 & 7;
+    const bool top = l15 < 8, lo = lg < 2;
+    const int64_t e = blockIdx.x;
+    const v4f64 zero = {0.0, 0.0, 0.0, 0.0};
+    // the A operand of every stage: [D; I], rows 0 - 5 and 8 - 13, K = 8 in two steps
+    const int r6 = r8 < N2 ? r8 : N2 - 1;
+    const double live = r8 < N2 ? 1.0 : 0.0;
+    const double aA = live * (top ? mDm[r6 * N + lg] : mIm[r6 * N + lg]);
+    const double aB = live * (top ? mDm[r6 * N + lg + 4] : mIm[r6 * N + lg + 4]);
+    // x stage: the element arrives as eight `lane + 64 u` sweeps and goes through LDS (x rows padded to 9 doubles) into the B operands
+    // of tile t: rows j = 2 t, 2 t + 1 of all eight planes, K = point a of the row
+    const int jx = l15 >> 3, kx = l15 & 7;
+    const int cw = lane + (lane >> 3), cr = lg + 9 * jx + 72 * kx;
+    // z columns: col = 16 t + l15 (clamped), points k2 = lg and 4 + (lg & 1) (the latter counted on lanes lg < 2 only)
+    int ia[3], ib[3], zr[3];
+    bool cv[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const int col = 16 * t + l15, cc = col < NS2 ? col : NS2 - 1;
+        cv[t] = col < NS2;
+        ia[t] = cc + NS2 * lg;
+        ib[t] = cc + NS2 * (4 + (lg & 1));
+        zr[t] = (cc / N2) * RW + cc % N2 + N2 * lg;
+    }
+    double acc[3][2];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) acc[t][0] = acc[t][1] = 0.0;
+    unsigned so[N];   // byte offsets of the lane's eight points lane + 64 u: face-grouped slots from the table
+#pragma unroll
+    for (int u8 = 0; u8 < N; ++u8) so[u8] = 8u * (unsigned)fgtab[lane + 64 * u8];
+    double ww[N];   // compact weights: binvm1 of the lane's points and their mask bits, loaded once for the three components
+    unsigned mk = 0u;
+    {
+        const double *wq = binv + e * NP1;
+        const unsigned char *mp = mb + e * NP1;
+#pragma unroll
+        for (int u8 = 0; u8 < N; ++u8) {
+            ww[u8] = ld_off(wq, so[u8]);
+            mk |= (unsigned)(mp[so[u8] >> 3] & 7u) << (3 * u8);
+        }
+    }
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i) {
+        if (i > 0) lds_barrier();   // the z stage of the previous component has read its columns
+        // x stage from HBM -> S2: B0 = D_x u, B1 = I_x u
+        const double *up = u.p[i] + e * NP1;
+        double uu[N];
+#pragma unroll
+        for (int u8 = 0; u8 < N; ++u8) uu[u8] = ld_off(up, so[u8]);
+        // weight = binvm1 where bit i of the point's mask byte is set, 0 elsewhere (= mask_i * binvm1)
+#pragma unroll
+        for (int u8 = 0; u8 < N; ++u8) uu[u8] *= ((mk >> (3 * u8 + i)) & 1u) ? ww[u8] : 0.0;
+#pragma unroll
+        for (int u8 = 0; u8 < N; ++u8) sS[cw + 72 * u8] = uu[u8];
+        lds_barrier();
+        double xb[4][2];   // every operand is read before the first result overwrites the cube
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            xb[t][0] = sS[cr + 18 * t];
+            xb[t][1] = sS[cr + 18 * t + 4];
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            v4f64 d = mfma4(aA, xb[t][0], zero);
+            d = mfma4(aB, xb[t][1], d);
+            double *r = sS + (2 * t + jx) * RY + kx * N2 + lg;
+            r[0] = d[0];
+            r[N * RY] = d[2];
+            if (lo) {
+                r[4] = d[1];
+                r[N * RY + 4] = d[3];
+            }
+        }
+        double gq[3][3][2];   // the metric columns of the component, requested two LDS stages before their use
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double *gp = g.p[j * 3 + i] + e * NP2;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                gq[j][t][0] = gp[ia[t]];
+                gq[j][t][1] = gp[ib[t]];
+            }
+        }
+        lds_barrier();
+        // y stage: S2 -> S1, in place tile by tile (a tile reads and writes its own 16 columns of the rows)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            double yb[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) yb[s] = sS[(4 * s + lg) * RY + 16 * t + l15];   // s = 0, 1: B0 rows j; s = 2, 3: B1 rows j
+            v4f64 d0 = mfma4(aA, yb[0], zero);
+            d0 = mfma4(aB, yb[1], d0);
+            v4f64 d1 = mfma4(aA, yb[2], zero);
+            d1 = mfma4(aB, yb[3], d1);
+            double *r = sS + lg * RW + 16 * t + l15;   // C0 = I_y B0 ; C1 = D_y B1 ; C2 = I_y B1
+            r[0] = d0[2];
+            r[N2 * RW] = d1[0];
+            r[2 * N2 * RW] = d1[2];
+            if (lo) {
+                r[4 * RW] = d0[3];
+                r[(N2 + 4) * RW] = d1[1];
+                r[(2 * N2 + 4) * RW] = d1[3];
+            }
+        }
+        lds_barrier();
+        // z stage: I_z C0, I_z C1 (rows 8 - 13), D_z C2 (rows 0 - 5); the metric products are summed in the D registers' layout
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const double *r = sS + j * N2 * RW + zr[t];
+                v4f64 d = mfma4(aA, r[0], zero);
+                d = mfma4(aB, r[4 * N2], d);
+                acc[t][0] += gq[j][t][0] * (j < 2 ? d[2] : d[0]);
+                acc[t][1] += gq[j][t][1] * (j < 2 ? d[3] : d[1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one array's three tiles at a time: 9 interleaved chains of 4-register results spill
+        }
+    }
+    double spw = 0.0, sw = 0.0;
+    {
+        double pd[3][2];   // loads before the stores (see k_axhelm3r)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            pd[t][0] = part ? pdot[e * NP2 + ia[t]] : 0.0;
+            pd[t][1] = part ? pdot[e * NP2 + ib[t]] : 0.0;
+        }
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const double v0 = scale * acc[t][0], v1 = scale * acc[t][1];
+            if (cv[t]) {
+                out[e * NP2 + ia[t]] = v0;
+                spw += pd[t][0] * v0;
+                sw += v0;
+                if (lo) {
+                    out[e * NP2 + ib[t]] = v1;
+                    spw += pd[t][1] * v1;
+                    sw += v1;
+                }
+            }
+        }
+    }
+    if (part) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            spw += __shfl_down(spw, o, 64);
+            sw += __shfl_down(sw, o, 64);
+        }
+        if (lane == 0) {
+            part[e] = spw;
+            part[E + e] = sw;
+        }
+    }
+}
+}  // namespace
+
 template <int N>
 static void fill_pmats(const nlg_mesh *m, PMats<N> &M) {
     const int n2 = N - 2;
@@ -3604,6 +3941,13 @@ static void fill_pmats(const nlg_mesh *m, PMats<N> &M) {
 bool sem_small_mesh(const nlg_mesh *m) {
     static const int64_t lim = getenv("NLG_SMALL_E") ? atoll(getenv("NLG_SMALL_E")) : 4096;
     return m->E < lim;
+}
+
+// single-vector launches of the pressure operator take the matrix-pipe kernels (k_opgradt3m8 / k_opdiv3m8): 3-D, lx1 = 8, not a small
+// mesh; NLG_POP_MFMA=0 keeps the vector kernels (A/B runs)
+bool sem_pop_mfma(const nlg_mesh *m) {
+    static const bool on = !(getenv("NLG_POP_MFMA") && atoi(getenv("NLG_POP_MFMA")) == 0);
+    return on && m->dim == 3 && m->n == 8 && !sem_small_mesh(m);
 }
 
 static CF9 rst2w_ptrs(const nlg_mesh *m) {
@@ -3669,7 +4013,23 @@ int sem_opgradt(nlg_mesh *m, const double *p, double *const *w, bool face_groupe
             NLG_HIP(hipGetLastError());
             return 0;
         }
-#define GT3_(N_, ML_)                                                                                                        \
+        if (nl == 1 && sem_pop_mfma(m)) {   // lx1 = 8, large mesh: the contractions on the matrix pipe
+            const F3 w3 = {{w[0], w[1], w[2]}};
+            if (upd) {
+                if (face_grouped)
+                    NLG_LAUNCH((k_opgradt3m8<true, true>), dim3((unsigned)m->E), dim3(64), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, pu);
+                else
+                    NLG_LAUNCH((k_opgradt3m8<false, true>), dim3((unsigned)m->E), dim3(64), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, pu);
+            } else {
+                if (face_grouped)
+                    NLG_LAUNCH((k_opgradt3m8<true, false>), dim3((unsigned)m->E), dim3(64), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, NoPUpd{});
+                else
+                    NLG_LAUNCH((k_opgradt3m8<false, false>), dim3((unsigned)m->E), dim3(64), 0, s, m->E, (const double *)m->d_I12t, (const double *)m->d_D12t, (const int *)m->d_slot_fg, g, p, w3, gate, NoPUpd{});
+            }
+            NLG_HIP(hipGetLastError());
+            return 0;
+        }
+#define GT3_(N_, ML_)                                                                                                       \
     if constexpr (N_ < 8) {                                                                                            \
         PMats<N_> M;                                                                                                   \
         fill_pmats<N_>(m, M);                                                                                          \
@@ -3759,7 +4119,15 @@ int sem_opdiv(nlg_mesh *m, double *const *u, double *out, double scale, double *
             NLG_HIP(hipGetLastError());
             return 0;
         }
-#define DV3_(N_, ML_)                                                                                                        \
+        // lx1 = 8, large mesh, face-grouped with the compact weights (the pressure operator of the solver): the contractions on the matrix
+        // pipe.  The natural layout without weights (right-hand sides, four launches per step) keeps k_opdiv3n, which is faster there
+        if (nl == 1 && sem_pop_mfma(m) && mb) {
+            const CF3 u3 = {{u[0], u[1], u[2]}};
+            NLG_LAUNCH(k_opdiv3m8, dim3((unsigned)m->E), dim3(64), 0, s, m->E, (const double *)m->d_I12, (const double *)m->d_D12, (const int *)m->d_slot_fg, g, u3, wtn.p[0], mb, out, scale, pdot, pw_part, gate);
+            NLG_HIP(hipGetLastError());
+            return 0;
+        }
+#define DV3_(N_, ML_)                                                                                                       \
     if constexpr (N_ < 8) {                                                                                            \
         PMats<N_> M;                                                                                                   \
         fill_pmats<N_>(m, M);                                                                                          \
@@ -4821,6 +5189,12 @@ int nlg_mesh_sizes(const nlg_mesh *m, int64_t *lvn, int64_t *lpn, int *dim, int 
     if (lpn) *lpn = m->lpn;
     if (dim) *dim = m->dim;
     if (n) *n = m->n;
+    return 0;
+}
+
+int nlg_mesh_pop_mfma(const nlg_mesh *m, int *out) {
+    NLG_CHECK(m && out, "nlg_mesh_pop_mfma: bad argument");
+    *out = sem_pop_mfma(m) ? 1 : 0;
     return 0;
 }
 

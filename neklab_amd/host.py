@@ -103,6 +103,12 @@ class Mesh:
         check(self.lib.nlg_mesh_get(self.h, name.encode(), dptr(out), npts))
         return out
 
+    def pop_mfma(self) -> int:
+        """1 if single-vector launches of the pressure operator on this mesh take the matrix-pipe kernels (NLG_POP_MFMA=0 -> 0)."""
+        out = C.c_int()
+        check(self.lib.nlg_mesh_pop_mfma(self.h, C.byref(out)))
+        return out.value
+
     def close(self):
         if self.h:
             self.lib.nlg_mesh_destroy(self.h)
