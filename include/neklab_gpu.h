@@ -339,6 +339,19 @@ int nlg_linop_project(nlg_linop *op, nlg_vec *v);
  * part from a quarter period) lives on the host: neklab_amd/host.py resolvent_linop. */
 int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, const nlg_vec *f_im, double omega, int adjoint,
                                nlg_vec *vec_out);
+/* s <= 4 forced integrations TOGETHER, as the lanes of one block run (evaluate_rhs / evaluate_imaginary_part of
+ * src/linops/resolvent.f90:80-111, :133-166 for s forcings at once; Nek5000 advances npert > 1 perturbations the same way,
+ * src/neklab_nek_setup.f90:39-247, src/neklab_otd.f90:37-49, see nlg_linop_matvec_block).  Lane v starts from ic[v] (ic == NULL or a
+ * NULL entry: rest, zero pressure), is forced by Re[(f_re[v] + i f_im[v]) exp(i s omega t)] (f_im == NULL or a NULL entry: a real
+ * forcing) and is stored into vec_out[v] exactly as the single call stores its result: forcing at the time level each step starts
+ * from, no restart-history replay, no history in the result.  omega, the adjoint flag and the operator's dt / nsteps are shared;
+ * every kernel of a time step, the forcing included, is launched once for all lanes, and each lane performs the iterations of the
+ * single call, which is the block of one.  Refused: what nlg_linop_integrate_forced refuses (orbit mode, a live nlg_otd, vectors
+ * with scalars, a foreign mesh, no nlg_linop_init), s outside 1 .. 4, a NULL f_re[v] or vec_out[v], an output that is also an
+ * input of any lane, the same output twice.  The block resolvent built on it lives on the host: neklab_amd/host.py
+ * resolvent_linop.matvec_block, resolvent_analysis. */
+int nlg_linop_integrate_forced_block(nlg_linop *op, int s, const nlg_vec *const *ic, const nlg_vec *const *f_re,
+                                     const nlg_vec *const *f_im, double omega, int adjoint, nlg_vec *const *vec_out);
 /* Coupled (orbit) mode: the propagator about a base flow that moves in time -- the monodromy operator of a periodic orbit, whose
  * eigenvalues are its Floquet multipliers (the time stepper under the reference's periodic-orbit Jacobian,
  * src/systems/periodic_orbit.f90:59-92: setup_linear_solver(solve_baseflow = .true., endtime = period)).

@@ -698,13 +698,20 @@ __global__ __launch_bounds__(NT) void k_cossin(int64_t n, const double *__restri
     }
 }
 
-// F -= bm1 (cr f_re + ci f_im): a body force in the explicit term (the stored F is +N, the right-hand side takes -EXT(F))
-template <int NF>
-__global__ __launch_bounds__(NT) void k_add_force(int64_t n, F3 F, const double *__restrict__ bm1, CF3 fre, CF3 fim, double cr, double ci) {
+// F_v -= bm1 (cr f_re,v + ci f_im,v) for the NL lanes of a forced run: a body force in the explicit term (the stored F is +N, the
+// right-hand side takes -EXT(F)).  Every lane has its own forcing vectors (by value: they are the caller's, not part of the slab;
+// a null f_im is a real forcing); lane v of F lies v * ld behind lane 0; bm1 is read once per point for all lanes.
+struct ForceLanes {
+    const double *re[kMaxLanes][3], *im[kMaxLanes][3];
+};
+template <int NF, int NL>
+__global__ __launch_bounds__(NT) void k_add_force(int64_t n, F3 F, const double *__restrict__ bm1, ForceLanes f, double cr, double ci, int64_t ld) {
     for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
         const double b = bm1[i];
 #pragma unroll
-        for (int c = 0; c < NF; ++c) F.p[c][i] -= b * (cr * fre.p[c][i] + (fim.p[c] ? ci * fim.p[c][i] : 0.0));
+        for (int v = 0; v < NL; ++v)
+#pragma unroll
+            for (int c = 0; c < NF; ++c) F.p[c][v * ld + i] -= b * (cr * f.re[v][c][i] + (f.im[v][c] ? ci * f.im[v][c][i] : 0.0));
     }
 }
 
@@ -1541,8 +1548,9 @@ struct Lanes {
     int lb = -1;         // coupled mode: the lane that carries the base flow (nl - 1); -1: the base flow is frozen
     int adjoint = 0;     // the adjoint equations (never together with nonlinear)
     int nonlinear = 0;   // 1: full Navier-Stokes step, N(u) = (u.grad)u = half of the linearised term about U = u; one lane
-    // time-harmonic body force Re[(f_re + i f_im) exp(i sign omega t)] of the resolvent integrations (null = none)
-    const nlg_vec *f_re = nullptr, *f_im = nullptr;
+    // time-harmonic body force Re[(f_re[v] + i f_im[v]) exp(i sign omega t)] of the resolvent integrations, one per lane (f_re[0]
+    // null = an unforced run; a null f_im[v] = a real forcing); omega and sign are shared
+    const nlg_vec *f_re[kMaxLanes] = {}, *f_im[kMaxLanes] = {};
     double omega = 0.0, sign = 1.0;
     int64_t ld() const { return nl > 1 ? op->slab_ld : 0; }   // the lane stride the kernels receive
 };
@@ -2115,15 +2123,34 @@ int adv_a(const Lanes &L) {
             launch_nf(dim, k_buoyancy<1>, k_buoyancy<2>, k_buoyancy<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(at_lane3(op, Fnew, v).p, dim),
                       (const double *)m->d_bm1, (const double *)at_lane(op, op->tbuf[0], v), bs * op->cfg.buoy[0], bs * op->cfg.buoy[1], bs * op->cfg.buoy[2]);
     }
-    if (L.f_re) {
+    if (L.f_re[0]) {
         // forcing of this step: evaluated at the time level the step starts from, (istep - 1) dt, like the explicit terms
-        // (resolvent.f90:97-103: alpha = exp(sign i omega time) before nek_advance)
+        // (resolvent.f90:97-103: alpha = exp(sign i omega time) before nek_advance); one launch for all lanes
         const double ph = L.sign * L.omega * (op->istep - 1) * dt;
-        CF3 fr = {{L.f_re->vel(0), L.f_re->vel(1), dim == 3 ? L.f_re->vel(2) : nullptr}};
-        CF3 fi = {{nullptr, nullptr, nullptr}};
-        if (L.f_im) fi = CF3{{L.f_im->vel(0), L.f_im->vel(1), dim == 3 ? L.f_im->vel(2) : nullptr}};
-        launch_nf(dim, k_add_force<1>, k_add_force<2>, k_add_force<3>, dim3(grid_for(m->lvn)), st, m->lvn, f3(Fnew, dim),
-                  (const double *)m->d_bm1, fr, fi, std::cos(ph), -std::sin(ph));
+        ForceLanes f;
+        memset(&f, 0, sizeof(f));
+        for (int v = 0; v < nl; ++v)
+            for (int c = 0; c < dim; ++c) {
+                f.re[v][c] = L.f_re[v]->vel(c);
+                if (L.f_im[v]) f.im[v][c] = L.f_im[v]->vel(c);
+            }
+#define ADD_F(D_, NL_) NLG_LAUNCH((k_add_force<D_, NL_>), dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, f3(Fnew, dim), (const double *)m->d_bm1, f, std::cos(ph), -std::sin(ph), ld)
+#define ADD_F_D(D_)   \
+    if (nl == 1)      \
+        ADD_F(D_, 1); \
+    else if (nl == 2) \
+        ADD_F(D_, 2); \
+    else if (nl == 3) \
+        ADD_F(D_, 3); \
+    else              \
+        ADD_F(D_, 4)
+        if (dim == 3) {
+            ADD_F_D(3);
+        } else {
+            ADD_F_D(2);
+        }
+#undef ADD_F_D
+#undef ADD_F
     }
     // OTD modes: D^T p and H u are computed before the explicit term is final, because the forcing needs the reduced operator they give
     const double h2 = b0 / dt;
@@ -2501,27 +2528,51 @@ int do_matvec(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout, int adjoint) {
 
 // vec_out = state after the nsteps of one application started from `ic` (null: rest) under the time-harmonic body force
 // Re[(f_re + i f_im) exp(i s omega t)], s = -1 for the adjoint equations: evaluate_rhs / evaluate_imaginary_part of the
-// resolvent (src/linops/resolvent.f90:80-111, :133-166).  No restart-history replay, no history in the result.
-int do_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, const nlg_vec *f_im, double omega, int adjoint, nlg_vec *vout) {
+// resolvent (src/linops/resolvent.f90:80-111, :133-166).  No restart-history replay, no history in the result.  s <= 4 such runs are
+// the lanes of one block run (lane v: ic[v], f_re[v], f_im[v] -> vout[v]; omega, the adjoint flag, dt and the step count are
+// shared), as Nek5000 advances npert > 1 perturbations together (src/neklab_nek_setup.f90:39-247).
+int do_integrate_forced_block(nlg_linop *op, int s, const nlg_vec *const *ic, const nlg_vec *const *f_re, const nlg_vec *const *f_im, double omega,
+                              int adjoint, nlg_vec *const *vout) {
     NLG_CHECK(op && f_re && vout, "integrate_forced: NULL argument");
+    NLG_CHECK(s >= 1 && s <= kMaxLanes, "integrate_forced: %d forcings unsupported (1..%d)", s, kMaxLanes);
     NLG_CHECK(op->inited, "integrate_forced: nlg_linop_init has not been called");
     NLG_NO_OTD(op, "integrate_forced");
     NLG_CHECK(!op->orbit, "integrate_forced: not available in orbit mode (the forced response about a time-periodic base flow is not built; nlg_linop_set_orbit)");
     nlg_mesh *m = op->mesh;
-    NLG_CHECK(f_re->mesh == m && vout->mesh == m && (!ic || ic->mesh == m) && (!f_im || f_im->mesh == m), "integrate_forced: vector on a different mesh");
-    NLG_CHECK(vout != f_re && vout != f_im && vout != ic, "integrate_forced: the output must be distinct from the inputs");
-    NLG_CHECK(f_re->nscal == 0 && vout->nscal == 0, "integrate_forced: scalar (temperature) coupling is not built yet");
+    Lanes L{op, s};
+    for (int v = 0; v < s; ++v) {
+        NLG_CHECK(f_re[v] && vout[v], "integrate_forced: NULL argument (forcing or output of lane %d)", v);
+        L.f_re[v] = f_re[v];
+        L.f_im[v] = f_im ? f_im[v] : nullptr;
+    }
+    for (int v = 0; v < s; ++v) {
+        const nlg_vec *icv = ic ? ic[v] : nullptr;
+        NLG_CHECK(L.f_re[v]->mesh == m && vout[v]->mesh == m && (!icv || icv->mesh == m) && (!L.f_im[v] || L.f_im[v]->mesh == m),
+                  "integrate_forced: vector on a different mesh");
+        for (int u = 0; u < s; ++u)
+            NLG_CHECK(vout[v] != L.f_re[u] && vout[v] != L.f_im[u] && !(ic && vout[v] == ic[u]), "integrate_forced: the output must be distinct from the inputs");
+        for (int u = 0; u < v; ++u) NLG_CHECK(vout[v] != vout[u], "integrate_forced: the same output vector twice");
+        NLG_CHECK(L.f_re[v]->nscal == 0 && vout[v]->nscal == 0, "integrate_forced: scalar (temperature) coupling is not built yet");
+    }
     hipStream_t st = m->ctx->stream;
-    NLG_TRY(begin_run(op, 1));
-    NLG_HIP(hipMemsetAsync(op->p, 0, sizeof(double) * (size_t)m->lps, st));
-    if (ic) NLG_TRY(load_state(op, 0, ic, 0));
-    Lanes L{op, 1};
+    NLG_TRY(begin_run(op, s));
+    for (int v = 0; v < s; ++v) {
+        NLG_HIP(hipMemsetAsync(at_lane(op, op->p, v), 0, sizeof(double) * (size_t)m->lps, st));
+        if (ic && ic[v]) NLG_TRY(load_state(op, v, ic[v], 0));
+    }
     L.adjoint = adjoint;
-    L.f_re = f_re, L.f_im = f_im, L.omega = omega, L.sign = adjoint ? -1.0 : 1.0;
+    L.omega = omega, L.sign = adjoint ? -1.0 : 1.0;
     NLG_TRY(run_steps(L));
-    NLG_TRY(nlg_vec_zero(vout));
-    NLG_TRY(store_state(op, 0, vout, 0));
+    for (int v = 0; v < s; ++v) {
+        NLG_TRY(nlg_vec_zero(vout[v]));
+        NLG_TRY(store_state(op, v, vout[v], 0));
+    }
     return 0;
+}
+
+int do_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, const nlg_vec *f_im, double omega, int adjoint, nlg_vec *vout) {
+    NLG_CHECK(op && f_re && vout, "integrate_forced: NULL argument");
+    return do_integrate_forced_block(op, 1, &ic, &f_re, &f_im, omega, adjoint, &vout);
 }
 
 // vec_out = Phi_tau(vec_in) - vec_in with the NONLINEAR integrator (reference: nonlinear_map, src/systems/fixed_point.f90:4-38):
@@ -2794,6 +2845,10 @@ int nlg_linop_nonlinear_map(nlg_linop *op, const nlg_vec *vec_in, nlg_vec *vec_o
 int nlg_linop_integrate_forced(nlg_linop *op, const nlg_vec *ic, const nlg_vec *f_re, const nlg_vec *f_im, double omega, int adjoint,
                                nlg_vec *vec_out) {
     return do_integrate_forced(op, ic, f_re, f_im, omega, adjoint, vec_out);
+}
+int nlg_linop_integrate_forced_block(nlg_linop *op, int s, const nlg_vec *const *ic, const nlg_vec *const *f_re, const nlg_vec *const *f_im, double omega,
+                                     int adjoint, nlg_vec *const *vec_out) {
+    return do_integrate_forced_block(op, s, ic, f_re, f_im, omega, adjoint, vec_out);
 }
 
 int nlg_linop_set_baseflow(nlg_linop *op, const nlg_vec *baseflow) {

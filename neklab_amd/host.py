@@ -444,20 +444,61 @@ class nek_zvector:
     def norm(self) -> float:
         return float(np.sqrt(self.re.dot(self.re) + self.im.dot(self.im)))
 
+    def rand(self, seed: int = 0):
+        """Admissible random real and imaginary parts (nek_dvector.rand), from the two seeds 2 seed + 1 and 2 seed + 2."""
+        self.re.rand(False, 2 * int(seed) + 1)
+        self.im.rand(False, 2 * int(seed) + 2)
+
+    def scal(self, alpha: complex):
+        a = complex(alpha)
+        if a.imag == 0.0:
+            self.re.scal(a.real)
+            self.im.scal(a.real)
+        else:
+            self.axpby(0.0, self, a)
+
+    def copy(self) -> "nek_zvector":
+        z = nek_zvector.__new__(nek_zvector)
+        z.mesh = self.mesh
+        z.re, z.im = self.re.copy(), self.im.copy()
+        return z
+
+    def conj(self):
+        """self = conj(self), in place."""
+        self.im.scal(-1.0)
+
 
 def integrate_forced(exptA: exptA_linop, ic, f_re: nek_dvector, f_im, omega: float, adjoint: bool, out: nek_dvector):
     check(exptA.lib.nlg_linop_integrate_forced(exptA.h, ic.h if ic is not None else None, f_re.h,
                                                f_im.h if f_im is not None else None, float(omega), int(bool(adjoint)), out.h))
 
 
+def integrate_forced_block(exptA: exptA_linop, ics, f_res: list, f_ims, omega: float, adjoint: bool, outs: list):
+    """len(f_res) <= 4 forced integrations as the lanes of one block run (nlg_linop_integrate_forced_block): lane v starts from
+    ics[v] (ics None, or a None entry: rest) under Re[(f_res[v] + i f_ims[v]) exp(i s omega t)] (f_ims None, or a None entry: a
+    real forcing) and is stored into outs[v]."""
+    s = len(f_res)
+    if len(outs) != s or (ics is not None and len(ics) != s) or (f_ims is not None and len(f_ims) != s):
+        raise ValueError("integrate_forced_block: %d forcings need as many initial conditions, imaginary parts and outputs" % s)
+
+    def arr(vs):
+        return (vp * max(s, 1))(*[x.h if x is not None else None for x in vs])
+
+    check(exptA.lib.nlg_linop_integrate_forced_block(exptA.h, s, arr(ics) if ics is not None else None, arr(f_res),
+                                                     arr(f_ims) if f_ims is not None else None, float(omega), int(bool(adjoint)), arr(outs)))
+
+
 class resolvent_linop:
     """R(omega) f: the time-periodic response to the forcing Re[f exp(i omega t)] about `baseflow`, by time stepping
     (resolvent_matvec, src/linops/resolvent.f90:17-44): b = one period from rest under the forcing (evaluate_rhs),
     Re x from (I - exp(T L)) x = b by GMRES(64), rtol 1e-6 (solve_resolvent_real_part, :113-131), Im part = the state a
-    quarter period later (evaluate_imaginary_part).  `rmatvec` integrates the adjoint equations with exp(-i omega t)."""
+    quarter period later (evaluate_imaginary_part).  `rmatvec` integrates the adjoint equations with exp(-i omega t).
+    rtol, kdim: of that GMRES (the reference's values by default).  `matvec_block` / `rmatvec_block` apply the operator to up to four
+    vectors as the lanes of one run (block GMRES), `apply_linear_block` is the linear pair (R, R^H) that `resolvent_analysis` uses."""
 
-    def __init__(self, omega: float, baseflow: nek_dvector, **cfg):
+    def __init__(self, omega: float, baseflow: nek_dvector, rtol: float = 1.0e-6, kdim: int = 64, **cfg):
         self.omega, self.baseflow, self.cfg = float(omega), baseflow, dict(cfg)
+        self.rtol, self.kdim = float(rtol), int(kdim)      # of the GMRES for the real part (the reference's: 1e-6, 64)
         self.mesh = baseflow.mesh
         self.gmres_matvecs = 0
 
@@ -471,7 +512,7 @@ class resolvent_linop:
         rhs = b.copy()
         rhs.scal(-1.0)
         x = nek_dvector(self.mesh)
-        res, nmv = gmres(A, rhs, x, atol=max(1.0e-6 * b.norm(), 1.0e-12), kdim=64, transpose=adjoint)
+        res, nmv = gmres(A, rhs, x, atol=max(self.rtol * b.norm(), 1.0e-12), kdim=self.kdim, transpose=adjoint)
         self.gmres_matvecs += nmv
         x.clear_rst_fields()
         vout.re.assign(x)
@@ -485,6 +526,118 @@ class resolvent_linop:
 
     def rmatvec(self, vin: nek_zvector, vout: nek_zvector):
         return self._apply(vin, vout, True)
+
+    def _apply_block(self, vins: list, vouts: list, adjoint: bool):
+        """`_apply` for s = len(vins) <= 4 forcings as the lanes of ONE operator: a forced block period from rest, block GMRES on
+        (exp(T L) - I) X = -B, a forced block quarter period from the X_v.  All lanes share omega, dt and the step count."""
+        s = len(vins)
+        if len(vouts) != s:
+            raise ValueError("resolvent block: %d inputs, %d outputs" % (s, len(vouts)))
+        tau = 1.0 if self.omega == 0.0 else 2.0 * np.pi / abs(self.omega)
+        A = exptA_linop(tau, self.baseflow, **self.cfg)
+        A.init()
+        f_re, f_im = [v.re for v in vins], [v.im for v in vins]
+        bs = [nek_dvector(self.mesh) for _ in range(s)]
+        integrate_forced_block(A, None, f_re, f_im, self.omega, adjoint, bs)
+        atols = [max(self.rtol * b.norm(), 1.0e-12) for b in bs]
+        for b in bs:
+            b.scal(-1.0)
+        xs = [nek_dvector(self.mesh) for _ in range(s)]
+        res, nmv = gmres_block(A, bs, xs, atols, kdim=self.kdim, transpose=adjoint)
+        self.gmres_matvecs += nmv
+        for v in range(s):
+            xs[v].clear_rst_fields()
+            vouts[v].re.assign(xs[v])
+        A.tau = tau / 4.0
+        integrate_forced_block(A, xs, f_re, f_im, self.omega, adjoint, [o.im for o in vouts])
+        self.last_operator = A
+        return res
+
+    def matvec_block(self, vins: list, vouts: list):
+        return self._apply_block(vins, vouts, False)
+
+    def rmatvec_block(self, vins: list, vouts: list):
+        return self._apply_block(vins, vouts, True)
+
+    def apply_linear_block(self, vs: list, outs: list, adjoint: bool = False):
+        """The LINEAR pair the analyses are built on: outs[v] = R vs[v] (adjoint: R^H vs[v]).  `matvec` returns conj(R f): the
+        response to Re[f exp(i omega t)] is Re[x exp(i omega t)] with x = R f, and its state a quarter period later is
+        Re[i x] = -Im x, which resolvent_matvec stores as the imaginary part; that map is antilinear in f, so the direct result
+        is conjugated here.  The adjoint run uses exp(-i omega t), its quarter-period state is +Im y: `rmatvec` is R^H itself."""
+        if adjoint:
+            return self.rmatvec_block(vs, outs)
+        res = self.matvec_block(vs, outs)
+        for o in outs:
+            o.conj()
+        return res
+
+
+def _zorth(Ys: list) -> np.ndarray:
+    """Modified Gram-Schmidt, applied twice, on a list of complex vectors in place, in the inner product of their `dot`
+    (<a, b> = sum conj(a) b).  Returns the upper-triangular T with Y_in = Y_out T."""
+    k = len(Ys)
+    T = np.eye(k, dtype=complex)
+    for _ in range(2):
+        S = np.zeros((k, k), dtype=complex)
+        for j in range(k):
+            for i in range(j):
+                c = Ys[i].dot(Ys[j])
+                Ys[j].axpby(-c, Ys[i], 1.0)
+                S[i, j] = c
+            nrm = Ys[j].norm()
+            S[j, j] = nrm
+            if nrm > 0.0:
+                Ys[j].scal(1.0 / nrm)
+        T = S @ T
+    return T
+
+
+def resolvent_analysis(R, nsv: int, power_iters: int = 1, seed: int = 1, Omega: "list | None" = None):
+    """The nsv <= 4 leading singular triplets of the resolvent R by a randomised SVD whose k = nsv samples are the lanes of block
+    applications (the reference's case file asks for `nsv = 4` next to resolvent_linop, examples/back_fstep/gramian/bfs.usr:8):
+    Y = R Omega; power_iters times Q = orth(Y), Z = R^H Q, Q' = orth(Z), Y = R Q'; then Q = orth(Y), Z = R^H Q = V^ T
+    (Gram-Schmidt), T^H = W Sigma P^H, U = Q W, V = V^ P: 2 power_iters + 2 block applications.  Returns (sigma descending,
+    U: the responses, V: the forcings), R v_j ~ sigma_j u_j and R^H u_j = sigma_j v_j.
+
+    R is touched through R.apply_linear_block(vs, outs, adjoint) only and the vectors through nek_zvector's methods (copy, dot,
+    norm, axpby, scal), so anything that offers those can stand in.  Omega: the k test forcings (default: nek_zvector.rand of
+    seed, seed + 1, ...); they are not modified."""
+    k = int(nsv)
+    if not 1 <= k <= 4:
+        raise ValueError("resolvent_analysis: nsv = %d unsupported (1..4: the singular vectors are the lanes of one block run)" % k)
+    if Omega is None:
+        Omega = []
+        for i in range(k):
+            z = nek_zvector(R.mesh)
+            z.rand(seed + i)
+            Omega.append(z)
+    if len(Omega) != k:
+        raise ValueError("resolvent_analysis: %d test forcings for nsv = %d" % (len(Omega), k))
+    Y = [z.copy() for z in Omega]
+    Z = [z.copy() for z in Omega]
+    R.apply_linear_block(Omega, Y, False)
+    for _ in range(int(power_iters)):
+        _zorth(Y)
+        R.apply_linear_block(Y, Z, True)
+        _zorth(Z)
+        R.apply_linear_block(Z, Y, False)
+    _zorth(Y)                                  # Y = Q
+    R.apply_linear_block(Y, Z, True)
+    T = _zorth(Z)                              # Z = V^
+    W, sigma, Ph = np.linalg.svd(T.conj().T)
+    P = Ph.conj().T
+
+    def combine(basis, C):
+        out = []
+        for j in range(k):
+            u = basis[0].copy()
+            u.scal(C[0, j])
+            for i in range(1, k):
+                u.axpby(C[i, j], basis[i], 1.0)
+            out.append(u)
+        return out
+
+    return sigma, combine(Y, W), combine(Z, P)
 
 
 def line_labels(mesh: "Mesh", idir: int, decimals: int = 9) -> np.ndarray:
@@ -706,6 +859,79 @@ def gmres(exptA: exptA_linop, b: nek_dvector, x: nek_dvector, atol: float, kdim:
         r.axpby(-shift, x, 1.0)
 
     return _gmres(b, x, atol, kdim, maxiter, history, first, column, assemble, residual)
+
+
+def _block_gmres_ls(H: np.ndarray, R0: np.ndarray, s: int, j: int, shift: float):
+    """The small problem of block GMRES after j block steps of size s: min | E1 R0 - (H~ + shift I~) Y | column by column, where
+    H~ = H[:(j + 1) s, :j s] is the block Hessenberg matrix of A (A Q_j = Q_{j+1} H~), I~ the identity on top of s zero rows and
+    R0 (s x s) the coefficients of the residual block on the first s basis vectors.  Returns Y (j s x s) and the s residual norms,
+    which are those of (A + shift I) Q_j Y - Q_0 R0 as long as the basis is orthonormal.  Least squares by SVD (numpy.linalg.lstsq,
+    minimum norm): a deflated basis column -- a zero vector, a zero column of H~ and a zero row of R0 -- gets the coefficient 0 and
+    needs no special case."""
+    m = j * s
+    Hs = np.array(H[: m + s, :m], dtype=np.float64)
+    Hs[np.arange(m), np.arange(m)] += shift
+    rhs = np.zeros((m + s, s))
+    rhs[:s, :] = R0
+    Y = np.linalg.lstsq(Hs, rhs, rcond=None)[0]
+    return Y, np.linalg.norm(rhs - Hs @ Y, axis=0)
+
+
+def gmres_block(exptA: exptA_linop, Bs: list, Xs: list, atols, kdim: int = 32, maxiter: int = 10, shift: float = -1.0,
+                transpose: bool = False, replay_history: bool = False):
+    """Restarted block GMRES for (A + shift I) X = B with s = len(Bs) <= 4 right-hand sides, zero initial guess, on the device's
+    block Krylov pieces: the residual block is orthonormalised by `nlg_basis_block_cgs2`, every block step is one
+    `nlg_block_arnoldi_step` (one `nlg_linop_matvec_block` of s lanes + block CGS2), `shift` goes on the diagonal of H as in
+    `gmres`, and the small least-squares problem is solved on the host after every block step (`_block_gmres_ls`).  A cycle has at
+    most `kdim` block steps and stops when every column's residual norm is at or below its atols[v]; a restart starts from the true
+    residual block (one more matvec_block).  replay_history as in `gmres`.  Returns (residual norms per column, matvecs)."""
+    s = len(Bs)
+    if not (1 <= s <= 4 and len(Xs) == s and len(atols) == s):
+        raise ValueError("gmres_block: 1..4 right-hand sides with as many solutions and tolerances, got %d, %d, %d" % (s, len(Xs), len(atols)))
+    atols = np.asarray(atols, dtype=np.float64)
+    mesh, nscal, lorder = Bs[0].mesh, Bs[0].nscal, Bs[0].lorder
+    basis = KrylovBasis(mesh, (kdim + 1) * s, nscal, lorder)
+    H = np.zeros(((kdim + 1) * s, kdim * s), order="F")
+    for x in Xs:
+        x.zero()
+    Rs = [b.copy() for b in Bs]
+    res = np.array([r.norm() for r in Rs])
+    nmv = 0
+    for _ in range(maxiter):
+        if np.all(res <= atols):
+            break
+        for v in range(s):
+            basis[v].assign(Rs[v])
+        R0 = basis.block_cgs2(0, s)
+        H[:] = 0.0
+        j, Y = 0, None
+        while j < kdim:
+            block_arnoldi_step(exptA, basis, j * s, s, H, transpose)
+            nmv += s
+            rank = basis.last_block_rank() if s > 1 else 1
+            if not replay_history:
+                for v in range(s):
+                    basis[(j + 1) * s + v].clear_rst_fields()
+            j += 1
+            Y, res = _block_gmres_ls(H, R0, s, j, shift)
+            if np.all(res <= atols) or rank == 0:
+                break
+        for v in range(s):
+            dx = nek_dvector(mesh, nscal, lorder)
+            basis.combine(j * s, Y[:, v], dx)
+            Xs[v].axpby(1.0, dx, 1.0)
+        if np.all(res <= atols):
+            break
+        AX = [nek_dvector(mesh, nscal, lorder) for _ in range(s)]            # true residual block for the restart
+        exptA.matvec_block(Xs, AX, transpose)
+        nmv += s
+        for v in range(s):
+            Rs[v].assign(Bs[v])
+            Rs[v].axpby(-1.0, AX[v], 1.0)
+            Rs[v].axpby(-shift, Xs[v], 1.0)
+        res = np.array([r.norm() for r in Rs])
+    basis.close()
+    return res, nmv
 
 
 def _newton(sys, X, r, solve, tol: float, tol_mode: int, maxiter: int, line, log=None, offset=None, each=None):
