@@ -219,6 +219,15 @@ int nlg_basis_block_axpy(const nlg_basis *b, int k, const double *h, nlg_vec *w)
 /* classical Gram-Schmidt with one re-orthogonalisation pass, then norm and scale:
  * h[0:k] accumulated coefficients, *beta = ||w|| before normalisation */
 int nlg_basis_cgs2(const nlg_basis *b, int k, nlg_vec *w, double *h, double *beta);
+/* The same for s <= 4 vectors, EACH against its own basis: for every lane l what nlg_basis_cgs2(b[l], k, w[l], h + l*ldh,
+ * beta + l) does (restart history and pressure as in the consistent history update, a zero norm leaves a zero vector), with
+ * the lane in the grid of every kernel: one launch per stage and one all-reduce per reduction (k*s, then s values) for all
+ * lanes.  The bases have equal shape (mesh, nscal, lorder, nvec) and are distinct; no w[l] may be one of the columns 0 .. k-1
+ * of any of them; the w[l] may differ in their number of valid history levels.  One variant for every k (the fused
+ * subtraction-and-projection sweep of the single-lane path at k >= 24 has no lane form), so the coefficients agree with the
+ * single-lane ones to rounding, not bit for bit.  With nlg_set_axpby_rst_consistent(0) the lanes go one by one through the
+ * path of nlg_basis_cgs2. */
+int nlg_basis_cgs2_batch(int s, nlg_basis *const *b, int k, nlg_vec *const *w, double *h, int ldh, double *beta);
 /* Block variant for s <= 4 NEW vectors held in the consecutive columns k .. k+s-1 (block Arnoldi, BASELINE.json config 5;
  * the reference advances several perturbations together through Nek5000's lpert / npert, src/neklab_nek_setup.f90:39-247,
  * src/neklab_otd.f90:37-49): classical Gram-Schmidt with one re-orthogonalisation pass against the columns 0 .. k-1 --
@@ -331,6 +340,22 @@ int nlg_linop_set_tolerances(nlg_linop *op, double vtol, double ptol);
 int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
                              const double *x2);
 int nlg_linop_project(nlg_linop *op, nlg_vec *v);
+/* Wavenumber lanes: one wavenumber per lane of a block run, for sweeps over alpha (dispersion relations, neutral curves) in
+ * lock-step.  nlg_linop_set_projection_lanes is nlg_linop_set_projection with nalpha = 1 .. 4 wavenumbers (same preconditions,
+ * same optional pressure-mesh pair, swapped in on success only): the lines are built once and shared, the cos / sin tables
+ * exist once per lane (each the table a single-alpha operator builds, bit for bit).  Afterwards lane l of
+ * nlg_linop_matvec_block (s <= nalpha vectors) projects onto alpha[l] wherever a projected run projects -- initial condition,
+ * replayed history states, final state with its lagged levels, pressure -- in ONE launch per level for all lanes, each lane
+ * with the result the single-alpha kernel gives (same summation order per line); several ranks: one all-reduce for all
+ * lanes.  nlg_linop_matvec / rmatvec / nlg_linop_project are the block of one and use alpha[0].  A later
+ * nlg_linop_set_projection returns the operator to one alpha for all lanes; calling this again replaces the set (fewer
+ * lanes: a sweep retires the wavenumbers that have converged).  Refused: nalpha outside 1..4, a NULL alpha, orbit mode, a
+ * live nlg_otd, cfg.ifheat (the projection does not touch the scalar); on such an operator: a block run of more than nalpha
+ * vectors and nlg_linop_integrate_forced*.  nlg_otd_create and nlg_linop_set_orbit refuse it as they refuse any projection.
+ * nlg_linop_project_block: v[l] <- P_{alpha[l]} v[l] for s <= nalpha distinct vectors. */
+int nlg_linop_set_projection_lanes(nlg_linop *op, int nalpha, const double *alpha, int idir, const int64_t *line_label,
+                                   const int64_t *line_label2, const double *x2);
+int nlg_linop_project_block(nlg_linop *op, int s, nlg_vec *const *v);
 /* Resolvent operator by time stepping (resolvent_linop, src/linops/resolvent.f90): the building
  * block of evaluate_rhs (:80-111) and evaluate_imaginary_part (:133-166): vec_out = state after the nsteps of one
  * application started from `ic` (NULL: rest, zero pressure) under the body force Re[(f_re + i f_im) exp(i s omega t)]
@@ -482,6 +507,15 @@ int nlg_arnoldi_step(nlg_linop *op, nlg_basis *basis, int k, double *H, int ldh,
 /* one BLOCK Arnoldi step: the s columns k .. k+s-1 of the basis -> columns k+s .. k+2s-1 (s matvecs, then
  * nlg_basis_block_cgs2 against the k+s columns before them); H(0:k+2s, k:k+s) written (column-major, ldh >= k+2s). */
 int nlg_block_arnoldi_step(nlg_linop *op, nlg_basis *basis, int k, int s, double *H, int ldh, int transpose);
+
+/* one Arnoldi step of s <= 4 SEPARATE eigenproblems in lock-step (wavenumber sweep): column k of basis[l] goes through
+ * nlg_linop_matvec_block, lane l at the operator's wavenumber alpha[l], into column k+1 of basis[l]; then
+ * nlg_basis_cgs2_batch orthogonalises every lane against its own k+1 columns.  Column k of lane l's Hessenberg matrix is
+ * written to H + l*hstride in the layout of nlg_arnoldi_step (H[k*ldh + 0..k], H[k*ldh + k+1] = beta); one device-to-host
+ * copy for all lanes.  Refused: an operator without wavenumber lanes (nlg_linop_set_projection_lanes), s > nalpha,
+ * k + 1 >= nvec. */
+int nlg_sweep_arnoldi_step(nlg_linop *op, int s, nlg_basis *const *basis, int k, double *H, int ldh, int64_t hstride,
+                           int transpose);
 
 typedef struct nlg_eigs_opts {
     int kdim;               /* kdim=  (1cyl.usr:11: 128)                                          */

@@ -132,6 +132,10 @@ SIGNATURES = {
     "nlg_linop_set_tolerances": (C.c_int, [vp, C.c_double, C.c_double]),
     "nlg_linop_set_projection": (C.c_int, [vp, C.c_double, C.c_int, c_int64_p, c_int64_p, c_double_p]),
     "nlg_linop_project": (C.c_int, [vp, vp]),
+    "nlg_linop_set_projection_lanes": (C.c_int, [vp, C.c_int, c_double_p, C.c_int, c_int64_p, c_int64_p, c_double_p]),
+    "nlg_linop_project_block": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "nlg_basis_cgs2_batch": (C.c_int, [C.c_int, C.POINTER(vp), C.c_int, C.POINTER(vp), c_double_p, C.c_int, c_double_p]),
+    "nlg_sweep_arnoldi_step": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_int, c_double_p, C.c_int, C.c_int64, C.c_int]),
     "nlg_linop_integrate_forced": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_int, vp]),
     "nlg_linop_integrate_forced_block": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_double, C.c_int, C.POINTER(vp)]),
     "nlg_linop_matvec": (C.c_int, [vp, vp, vp]),

@@ -373,6 +373,12 @@ int basis_block_dot_dev(const nlg_basis *b, int k, const nlg_vec *w, double *d_o
 int basis_block_axpy_dev(const nlg_basis *b, int k, const double *d_h, nlg_vec *w, double sign, const double *d_hh = nullptr,
                          bool main_only = false);
 int basis_cgs2_dev(nlg_basis *b, int k, nlg_vec *w);
+// CGS2 + norm + scale of s vectors, w[l] against columns 0 .. k-1 of its own basis b[l], one launch per stage for all lanes
+// (nlg_basis_cgs2_batch).  Results on device in b[0]->d_hb: lane l's k coefficients at [l * k], its |w|^2 before scaling at [s * k + l].
+int basis_cgs2_batch_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w);
+
+// ---- lns.hip ----
+int linop_proj_lanes(const nlg_linop *op);   // wavenumber lanes of the operator (nlg_linop_set_projection_lanes), 0 = none
 
 // ---- pprec.hip ----
 int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d);

@@ -222,6 +222,41 @@ int nlg_block_arnoldi_step(nlg_linop *op, nlg_basis *basis, int k, int s, double
     return 0;
 }
 
+// One Arnoldi step of s separate eigenproblems in lock-step (a wavenumber sweep): lane l's column k through the block propagator, at
+// lane l's wavenumber, into its column k + 1, then the batched CGS2 of every lane against its OWN basis.
+int nlg_sweep_arnoldi_step(nlg_linop *op, int s, nlg_basis *const *basis, int k, double *H, int ldh, int64_t hstride, int transpose) {
+    NLG_CHECK(op && basis && H, "nlg_sweep_arnoldi_step: NULL argument");
+    NLG_CHECK(s >= 1 && s <= kMaxLanes, "nlg_sweep_arnoldi_step: %d lanes unsupported (1..%d)", s, kMaxLanes);
+    const int nalpha = linop_proj_lanes(op);
+    NLG_CHECK(nalpha > 0, "nlg_sweep_arnoldi_step: the operator has no wavenumber lanes (nlg_linop_set_projection_lanes)");
+    NLG_CHECK(s <= nalpha, "nlg_sweep_arnoldi_step: %d lanes on an operator with %d wavenumber lanes", s, nalpha);
+    for (int l = 0; l < s; ++l) {
+        NLG_CHECK(basis[l], "nlg_sweep_arnoldi_step: NULL basis in lane %d", l);
+        NLG_CHECK(k >= 0 && k + 1 < basis[l]->nvec, "nlg_sweep_arnoldi_step: k=%d needs basis columns %d, %d (nvec=%d)", k, k, k + 1, basis[l]->nvec);
+        for (int u = 0; u < l; ++u) NLG_CHECK(basis[l] != basis[u], "nlg_sweep_arnoldi_step: the same basis in two lanes");
+    }
+    NLG_CHECK(ldh >= k + 2, "nlg_sweep_arnoldi_step: ldh=%d too small for k=%d", ldh, k);
+    const nlg_vec *vi[kMaxLanes];
+    nlg_vec *vo[kMaxLanes];
+    for (int l = 0; l < s; ++l) vi[l] = basis[l]->views[k], vo[l] = basis[l]->views[k + 1];
+    const int kk = k + 1;
+    for (int l = 1; l < s; ++l)
+        NLG_CHECK(basis[l]->mesh == basis[0]->mesh && basis[l]->nscal == basis[0]->nscal && basis[l]->lorder == basis[0]->lorder && basis[l]->nvec == basis[0]->nvec,
+                  "nlg_sweep_arnoldi_step: the bases differ in shape (lane %d)", l);
+    NLG_TRY(nlg_linop_matvec_block(op, s, vi, vo, transpose));
+    NLG_TRY(basis_cgs2_batch_dev(s, basis, kk, vo));
+    std::vector<double> tmp((size_t)s * kk + s);   // one copy for all lanes
+    hipStream_t st = basis[0]->mesh->ctx->stream;
+    NLG_HIP(hipMemcpyAsync(tmp.data(), basis[0]->d_hb, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    for (int l = 0; l < s; ++l) {
+        double *col = H + (size_t)l * hstride + (size_t)k * ldh;
+        for (int i = 0; i < kk; ++i) col[i] = tmp[(size_t)l * kk + i];
+        col[kk] = std::sqrt(tmp[(size_t)s * kk + l]);
+    }
+    return 0;
+}
+
 int nlg_eigs_opts_default(nlg_eigs_opts *o) {
     NLG_CHECK(o, "nlg_eigs_opts_default: NULL");
     o->kdim = 0;

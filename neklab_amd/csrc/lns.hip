@@ -674,6 +674,114 @@ __global__ __launch_bounds__(NT) void k_proj_apply(int64_t nlines, const int *__
         for (int c = 0; c < NF; ++c) u.p[c][i] = cv[i] * (src[2 * c] * id) + sv[i] * (src[2 * c + 1] * id);
     }
 }
+// Wavenumber lanes: the same three kernels for the lanes of a block run, each with its own cos / sin table.  The lane sits in
+// gridDim.y: lane l's fields lie l * ld behind lane 0's (the slab), its tables l * tld behind lane 0's; the lines, the weights and
+// the denominators are shared.  One wave per line, and the summation order of a line is that of k_proj_alpha, so a lane's result is
+// the one the single-wavenumber kernel gives with that lane's table.  Lanes whose bit in `mask` is clear are left alone (history
+// replay: only the lanes that carry a history level are reloaded and projected).  Several ranks: slot [gslot][lane] of the
+// all-reduce buffer, one all-reduce for all lanes.
+template <int NF>
+__global__ __launch_bounds__(NT) void k_proj_alpha_lanes(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
+                                                         const double *__restrict__ bm1, const double *__restrict__ cv,
+                                                         const double *__restrict__ sv, int64_t tld, const double *__restrict__ inv_den,
+                                                         F3 u, int64_t ld, unsigned mask) {
+    if (!((mask >> blockIdx.y) & 1u)) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (g >= nlines) return;
+    u = lane_f3(u, lane_lo(ld));
+    cv += lane_lo(tld), sv += lane_lo(tld);
+    const int b = off[g], e = off[g + 1];
+    double ac[NF], as[NF];
+#pragma unroll
+    for (int c = 0; c < NF; ++c) ac[c] = as[c] = 0.0;
+    for (int q = b + lane; q < e; q += 64) {
+        const int i = idx[q];
+        const double w = 2.0 * bm1[i], c0 = cv[i], s0 = sv[i];
+#pragma unroll
+        for (int c = 0; c < NF; ++c) {
+            const double v = u.p[c][i];
+            ac[c] += w * v * c0;
+            as[c] += w * v * s0;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NF; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            ac[c] += __shfl_xor(ac[c], o, 64);
+            as[c] += __shfl_xor(as[c], o, 64);
+        }
+    }
+    const double id = inv_den[g];
+    for (int q = b + lane; q < e; q += 64) {
+        const int i = idx[q];
+#pragma unroll
+        for (int c = 0; c < NF; ++c) u.p[c][i] = cv[i] * (ac[c] * id) + sv[i] * (as[c] * id);
+    }
+}
+template <int NF>
+__global__ __launch_bounds__(NT) void k_proj_sums_lanes(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
+                                                        const int *__restrict__ gslot, const double *__restrict__ bm1,
+                                                        const double *__restrict__ cv, const double *__restrict__ sv, int64_t tld, CF3 u,
+                                                        int64_t ld, unsigned mask, double *__restrict__ glob) {
+    if (!((mask >> blockIdx.y) & 1u)) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (g >= nlines) return;
+    u = lane_f3(u, lane_lo(ld));
+    cv += lane_lo(tld), sv += lane_lo(tld);
+    const int b = off[g], e = off[g + 1];
+    double ac[NF], as[NF];
+#pragma unroll
+    for (int c = 0; c < NF; ++c) ac[c] = as[c] = 0.0;
+    for (int q = b + lane; q < e; q += 64) {
+        const int i = idx[q];
+        const double w = 2.0 * bm1[i], c0 = cv[i], s0 = sv[i];
+#pragma unroll
+        for (int c = 0; c < NF; ++c) {
+            const double v = u.p[c][i];
+            ac[c] += w * v * c0;
+            as[c] += w * v * s0;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NF; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            ac[c] += __shfl_xor(ac[c], o, 64);
+            as[c] += __shfl_xor(as[c], o, 64);
+        }
+    }
+    if (lane == 0) {
+        double *dst = glob + ((int64_t)gslot[g] * gridDim.y + blockIdx.y) * (2 * NF);
+#pragma unroll
+        for (int c = 0; c < NF; ++c) {
+            dst[2 * c] = ac[c];
+            dst[2 * c + 1] = as[c];
+        }
+    }
+}
+template <int NF>
+__global__ __launch_bounds__(NT) void k_proj_apply_lanes(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
+                                                         const int *__restrict__ gslot, const double *__restrict__ cv,
+                                                         const double *__restrict__ sv, int64_t tld, const double *__restrict__ inv_den,
+                                                         const double *__restrict__ glob, F3 u, int64_t ld, unsigned mask) {
+    if (!((mask >> blockIdx.y) & 1u)) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (g >= nlines) return;
+    u = lane_f3(u, lane_lo(ld));
+    cv += lane_lo(tld), sv += lane_lo(tld);
+    const int b = off[g], e = off[g + 1];
+    const double *src = glob + ((int64_t)gslot[g] * gridDim.y + blockIdx.y) * (2 * NF);
+    const double id = inv_den[g];
+    for (int q = b + lane; q < e; q += 64) {
+        const int i = idx[q];
+#pragma unroll
+        for (int c = 0; c < NF; ++c) u.p[c][i] = cv[i] * (src[2 * c] * id) + sv[i] * (src[2 * c + 1] * id);
+    }
+}
 // weights of a rank's part of every line into the global slots (set-up: the denominators)
 __global__ __launch_bounds__(NT) void k_proj_wsum(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
                                                   const int *__restrict__ gslot, const double *__restrict__ w, double *__restrict__ glob) {
@@ -1093,11 +1201,14 @@ struct LanePred {
 
 // wavenumber projection on one mesh: lines along the homogeneous direction (groups of local dofs, off / idx), cos / sin of alpha x,
 // 1 / sum of the weights of a line; several ranks: slot of every local line in the global line list, number of global lines and
-// the all-reduce buffer ([nglob][2][nf])
+// the all-reduce buffer ([nglob][2][nf]).  Wavenumber lanes (nlg_linop_set_projection_lanes): the lines are shared, the cos / sin
+// tables exist once per lane, lane l's at cv + l * tld and sv + l * tld, and the all-reduce buffer is [nglob][lanes][2][nf].
 struct ProjLines {
     int nlines = 0;
     int *off = nullptr, *idx = nullptr, *gslot = nullptr;
     int64_t nglob = 0;
+    int nalpha = 1;
+    int64_t tld = 0;
     double *cv = nullptr, *sv = nullptr, *iden = nullptr, *glob = nullptr;
     const double *weight = nullptr;   // the mesh's mass matrix (not owned)
     void free() {
@@ -1173,6 +1284,7 @@ struct nlg_linop {
     int adv_k = 1;             // state handed from one phase of a time step to the next (adv_a / adv_b / adv_c)
     double adv_b0 = 1.0, adv_h2 = 0.0;
     ProjLines proj_v, proj_p;   // wavenumber projection (exptA_proj_linop) on the velocity mesh and on the pressure mesh (no lines = not projected)
+    int proj_lanes = 0;         // > 0: lane l of a block run projects onto its own wavenumber, proj_lanes of them (nlg_linop_set_projection_lanes)
     // Boussinesq coupling (cfg.ifheat): temperature levels, its explicit terms, PCG work fields, Jacobi preconditioners per
     // BDF order, gradient of the base temperature on the fine mesh
     double *tbuf[3] = {}, *ftbuf[3] = {}, *trhs = nullptr, *tx = nullptr, *tz = nullptr, *tpv = nullptr, *tw = nullptr;
@@ -2434,6 +2546,39 @@ int project_alpha(nlg_linop *op, int lane, int slot) {
     return 0;
 }
 
+// wavenumber lanes: project_lines for the lanes 0 .. s-1 of the slab whose bit in `mask` is set, lane l with table l, in one launch
+// (f: lane 0's fields); several ranks: one all-reduce for all lanes
+int project_lines_lanes(nlg_linop *op, const ProjLines &P, int nf, F3 f, int s, unsigned mask) {
+    nlg_mesh *m = op->mesh;
+    hipStream_t st = m->ctx->stream;
+    const int64_t nl = P.nlines, ld = op->slab_ld, tld = P.tld;
+    const dim3 g((unsigned)((nl + NT / 64 - 1) / (NT / 64)), (unsigned)s);
+    const int *off = P.off, *idx = P.idx, *gs = P.gslot;
+    const double *cv = P.cv, *sv = P.sv, *iden = P.iden, *glob = P.glob;
+    if (!gs) {
+        launch_nf(nf, k_proj_alpha_lanes<1>, k_proj_alpha_lanes<2>, k_proj_alpha_lanes<3>, g, st, nl, off, idx, P.weight, cv, sv, tld, iden, f, ld, mask);
+    } else {
+        const int64_t cnt = P.nglob * s * 2 * nf;
+        NLG_HIP(hipMemsetAsync(P.glob, 0, sizeof(double) * (size_t)cnt, st));
+        if (nl > 0)
+            launch_nf(nf, k_proj_sums_lanes<1>, k_proj_sums_lanes<2>, k_proj_sums_lanes<3>, g, st, nl, off, idx, gs, P.weight, cv, sv, tld,
+                      CF3{{f.p[0], f.p[1], f.p[2]}}, ld, mask, P.glob);
+        NLG_TRY(allreduce_sum(m->ctx, P.glob, (int)cnt));
+        if (nl > 0)
+            launch_nf(nf, k_proj_apply_lanes<1>, k_proj_apply_lanes<2>, k_proj_apply_lanes<3>, g, st, nl, off, idx, gs, cv, sv, tld, iden, glob, f, ld, mask);
+    }
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// level `slot` of the lanes 0 .. s-1 (those in `mask`), lane l onto wavenumber l: what s calls of project_alpha do, in one launch per mesh
+int project_alpha_lanes(nlg_linop *op, int s, int slot, unsigned mask) {
+    NLG_TRY(project_lines_lanes(op, op->proj_v, op->mesh->dim, f3(op->ubuf[slot], op->mesh->dim), s, mask));
+    const ProjLines &Pp = op->proj_p;
+    if ((Pp.gslot || Pp.nlines > 0) && slot == 0) NLG_TRY(project_lines_lanes(op, Pp, 1, F3{{op->p, nullptr, nullptr}}, s, mask));
+    return 0;
+}
+
 // =====================================================================================================================
 // Multi-vector (block) propagator: s <= 4 perturbations advanced together, time step by time step (the reference advances
 // several perturbations together through Nek5000's lpert / npert, src/neklab_nek_setup.f90:39-247, src/neklab_otd.f90:37-49).
@@ -2468,21 +2613,32 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     // coupled (orbit) mode: lane s carries the base flow, from X0 (impulsive start, no history: periodic_orbit.f90:59-92 with
     // solve_baseflow = .true.) through the same time steps and the same launches as the s perturbation lanes before it
     const int nl = op->orbit ? s + 1 : s, lb = op->orbit ? s : -1;
+    // wavenumber lanes: lane v projects onto its own wavenumber, all lanes of a level in one launch (project_alpha_lanes); otherwise
+    // lane by lane onto the one wavenumber of the operator, or not at all (project_alpha)
+    const bool wl = op->proj_lanes > 0;
+    NLG_CHECK(!wl || s <= op->proj_lanes, "exptA block matvec: %d vectors on an operator with %d wavenumber lanes (nlg_linop_set_projection_lanes)", s,
+              op->proj_lanes);
+    const unsigned all = (1u << s) - 1u;
     NLG_TRY(begin_run(op, nl));
     for (int v = 0; v < s; ++v) {
         NLG_TRY(load_state(op, v, vin[v], 0));
-        NLG_TRY(project_alpha(op, v, 0));   // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
+        if (!wl) NLG_TRY(project_alpha(op, v, 0));   // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
     }
+    if (wl) NLG_TRY(project_alpha_lanes(op, s, 0, all));
     if (lb >= 0) NLG_TRY(load_state(op, lb, op->baseflow, 0));
     Lanes L{op, nl, lb};
     L.adjoint = adjoint;
     NLG_TRY(run_steps(L, lb, [&](int istep) -> int {
-        if (istep <= nrst)
+        if (istep <= nrst) {
+            unsigned replayed = 0;
             for (int v = 0; v < s; ++v)
                 if (vin[v]->nrst > 0) {
                     NLG_TRY(load_state(op, v, vin[v], istep));   // get_rst, exponential_propagator.f90:129-142
-                    NLG_TRY(project_alpha(op, v, 0));            // (projected operator: replayed states are projected as well, see below)
+                    if (!wl) NLG_TRY(project_alpha(op, v, 0));   // (projected operator: replayed states are projected as well, see below)
+                    replayed |= 1u << v;
                 }
+            if (wl && replayed) NLG_TRY(project_alpha_lanes(op, s, 0, replayed));
+        }
         return 0;
     }));
     // ... and the final state, :66.  The reference projects the initial condition and the final state only.  Here the
@@ -2490,8 +2646,11 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     // (state, history) that the Arnoldi process iterates has a spurious unstable mode -- observed for plane Poiseuille flow
     // at alpha = 2, Re = 7500: a "converged" |mu| = 1.41 in front of the Orr-Sommerfeld pair |mu| = 0.9448; with the
     // consistent projection the leading pair is 0.94454.
+    if (wl)
+        for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha_lanes(op, s, slot, all));
     for (int v = 0; v < s; ++v) {
-        for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha(op, v, slot));
+        if (!wl)
+            for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha(op, v, slot));
         // vec_out is intent(out): default-initialised (history cleared, nrst = 0), then filled
         NLG_TRY(nlg_vec_zero(vout[v]));
         NLG_TRY(store_state(op, v, vout[v], 0));
@@ -2538,6 +2697,7 @@ int do_integrate_forced_block(nlg_linop *op, int s, const nlg_vec *const *ic, co
     NLG_CHECK(op->inited, "integrate_forced: nlg_linop_init has not been called");
     NLG_NO_OTD(op, "integrate_forced");
     NLG_CHECK(!op->orbit, "integrate_forced: not available in orbit mode (the forced response about a time-periodic base flow is not built; nlg_linop_set_orbit)");
+    NLG_CHECK(op->proj_lanes == 0, "integrate_forced: not available on an operator with wavenumber lanes (a forced run does not project; nlg_linop_set_projection_lanes)");
     nlg_mesh *m = op->mesh;
     Lanes L{op, s};
     for (int v = 0; v < s; ++v) {
@@ -2602,6 +2762,10 @@ int do_nonlinear_map(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout) {
 }
 
 }  // namespace
+
+namespace nlg {
+int linop_proj_lanes(const nlg_linop *op) { return op->proj_lanes; }
+}  // namespace nlg
 
 extern "C" {
 
@@ -2866,7 +3030,9 @@ struct DevBuf {   // a device temporary, released on every path out of its scope
 
 // the lines of one mesh into P (empty on entry; the caller frees it whatever this returns): lines = groups of local dofs with the same
 // label, ordered by label then by index.  The coordinate along the homogeneous direction is on the device (d_x) or on the host (h_x).
-static int proj_build(nlg_mesh *m, double alpha, int64_t n, const int64_t *lab, const double *d_x, const double *h_x, ProjLines &P) {
+// nalpha wavenumbers: the lines once, one cos / sin table per wavenumber (k_cossin each: table l is the table of a single alpha[l]).
+static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *alpha, int64_t n, const int64_t *lab, const double *d_x, const double *h_x,
+                      ProjLines &P) {
     nlg_ctx *ctx = m->ctx;
     hipStream_t st = ctx->stream;
     std::vector<int> order((size_t)n);
@@ -2882,15 +3048,17 @@ static int proj_build(nlg_mesh *m, double alpha, int64_t n, const int64_t *lab, 
     for (int g = 0; g < nlines; ++g) {
         double sum = 0.0;
         for (int q = off[g]; q < off[g + 1]; ++q) sum += wt[order[q]];
-        NLG_CHECK(sum > 0.0, "nlg_linop_set_projection: empty line");
+        NLG_CHECK(sum > 0.0, "%s: empty line", who);
         iden[g] = 1.0 / sum;
     }
     P.nlines = nlines;
+    P.nalpha = nalpha;
+    P.tld = n;
     NLG_HIP(hipMalloc(&P.off, sizeof(int) * off.size()));
     NLG_HIP(hipMalloc(&P.idx, sizeof(int) * (size_t)n));
     NLG_HIP(hipMalloc(&P.iden, sizeof(double) * (size_t)nlines));
-    NLG_HIP(hipMalloc(&P.cv, sizeof(double) * (size_t)n));
-    NLG_HIP(hipMalloc(&P.sv, sizeof(double) * (size_t)n));
+    NLG_HIP(hipMalloc(&P.cv, sizeof(double) * (size_t)(n * nalpha)));
+    NLG_HIP(hipMalloc(&P.sv, sizeof(double) * (size_t)(n * nalpha)));
     NLG_HIP(hipMemcpy(P.off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
     NLG_HIP(hipMemcpy(P.idx, order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     NLG_HIP(hipMemcpy(P.iden, iden.data(), sizeof(double) * (size_t)nlines, hipMemcpyHostToDevice));
@@ -2900,7 +3068,7 @@ static int proj_build(nlg_mesh *m, double alpha, int64_t n, const int64_t *lab, 
         NLG_HIP(hipMemcpy(xs.p, h_x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
         d_x = xs.p;
     }
-    NLG_LAUNCH(k_cossin, dim3(grid_for(n)), dim3(NT), 0, st, n, d_x, alpha, P.cv, P.sv);
+    for (int l = 0; l < nalpha; ++l) NLG_LAUNCH(k_cossin, dim3(grid_for(n)), dim3(NT), 0, st, n, d_x, alpha[l], P.cv + l * P.tld, P.sv + l * P.tld);
     NLG_HIP(hipGetLastError());
     NLG_HIP(hipStreamSynchronize(st));
     if (!ctx->distributed()) return 0;
@@ -2939,7 +3107,7 @@ static int proj_build(nlg_mesh *m, double alpha, int64_t n, const int64_t *lab, 
     NLG_HIP(hipMalloc(&P.gslot, sizeof(int) * gs.size()));
     NLG_HIP(hipMemcpy(P.gslot, gs.data(), sizeof(int) * gs.size(), hipMemcpyHostToDevice));
     P.nglob = (int64_t)uni.size();
-    NLG_HIP(hipMalloc(&P.glob, sizeof(double) * (size_t)(P.nglob * 2 * 3)));
+    NLG_HIP(hipMalloc(&P.glob, sizeof(double) * (size_t)(P.nglob * 2 * 3 * nalpha)));
     NLG_HIP(hipMemsetAsync(P.glob, 0, sizeof(double) * (size_t)P.nglob, st));
     const unsigned g1 = (unsigned)((nlines + NT / 64 - 1) / (NT / 64));
     if (nlines > 0)
@@ -2964,11 +3132,12 @@ int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_
     // built beside the operator's and swapped in on success: a call that fails leaves the operator as it was
     ProjLines pv, pp;
     pv.weight = m->d_bm1, pp.weight = m->d_bm2;
-    int rc = proj_build(m, alpha, m->lvn, line_label, m->d_x[idir - 1], nullptr, pv);
-    if (!rc && line_label2) rc = proj_build(m, alpha, m->lpn, line_label2, nullptr, x2, pp);
+    int rc = proj_build(m, "nlg_linop_set_projection", 1, &alpha, m->lvn, line_label, m->d_x[idir - 1], nullptr, pv);
+    if (!rc && line_label2) rc = proj_build(m, "nlg_linop_set_projection", 1, &alpha, m->lpn, line_label2, nullptr, x2, pp);
     if (!rc) {
         std::swap(op->proj_v, pv);
         std::swap(op->proj_p, pp);
+        op->proj_lanes = 0;   // one wavenumber for all lanes again
     }
     (void)hipStreamSynchronize(m->ctx->stream);   // nothing in flight may still use what is freed now
     pv.free();
@@ -2976,12 +3145,57 @@ int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_
     return rc;
 }
 
+// Wavenumber lanes: nlg_linop_set_projection with one wavenumber per lane of a block run (include/neklab_gpu.h)
+int nlg_linop_set_projection_lanes(nlg_linop *op, int nalpha, const double *alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
+                                   const double *x2) {
+    const char *who = "nlg_linop_set_projection_lanes";
+    NLG_CHECK(op && line_label, "%s: NULL argument", who);
+    NLG_CHECK(alpha, "%s: NULL alpha (one wavenumber per lane)", who);
+    NLG_CHECK(nalpha >= 1 && nalpha <= kMaxLanes, "%s: %d wavenumber lanes unsupported (1..%d)", who, nalpha, kMaxLanes);
+    NLG_NO_OTD(op, who);
+    nlg_mesh *m = op->mesh;
+    NLG_CHECK(idir >= 1 && idir <= m->dim, "%s: idir %d out of range", who, idir);
+    NLG_CHECK(op->inited, "%s: call init first", who);
+    NLG_CHECK(!op->orbit, "%s: not available in orbit mode (the base-flow lane is a full state, not one wavenumber; nlg_linop_set_orbit)", who);
+    NLG_CHECK(!op->cfg.ifheat, "%s: not available with cfg.ifheat (the projection does not touch the scalar)", who);
+    NLG_CHECK((line_label2 == nullptr) == (x2 == nullptr), "%s: pressure-mesh labels and coordinates go together", who);
+    ProjLines pv, pp;
+    pv.weight = m->d_bm1, pp.weight = m->d_bm2;
+    int rc = proj_build(m, who, nalpha, alpha, m->lvn, line_label, m->d_x[idir - 1], nullptr, pv);
+    if (!rc && line_label2) rc = proj_build(m, who, nalpha, alpha, m->lpn, line_label2, nullptr, x2, pp);
+    if (!rc) {
+        std::swap(op->proj_v, pv);
+        std::swap(op->proj_p, pp);
+        op->proj_lanes = nalpha;
+    }
+    (void)hipStreamSynchronize(m->ctx->stream);   // nothing in flight may still use what is freed now
+    pv.free();
+    pp.free();
+    return rc;
+}
+
+int nlg_linop_project_block(nlg_linop *op, int s, nlg_vec *const *v) {
+    NLG_CHECK(op && v, "nlg_linop_project_block: NULL argument");
+    NLG_CHECK(op->proj_lanes > 0, "nlg_linop_project_block: the operator has no wavenumber lanes (nlg_linop_set_projection_lanes)");
+    NLG_CHECK(s >= 1 && s <= op->proj_lanes, "nlg_linop_project_block: %d vectors on an operator with %d wavenumber lanes", s, op->proj_lanes);
+    NLG_NO_OTD(op, "nlg_linop_project_block");
+    for (int l = 0; l < s; ++l) {
+        NLG_CHECK(v[l] && v[l]->mesh == op->mesh, "nlg_linop_project_block: vector %d NULL or on a different mesh", l);
+        for (int u = 0; u < l; ++u) NLG_CHECK(v[l] != v[u], "nlg_linop_project_block: the same vector twice");
+    }
+    NLG_TRY(slab_ensure(op, s));
+    for (int l = 0; l < s; ++l) NLG_TRY(load_state(op, l, v[l], 0));
+    NLG_TRY(project_alpha_lanes(op, s, 0, (1u << s) - 1u));
+    for (int l = 0; l < s; ++l) NLG_TRY(store_state(op, l, v[l], 0));
+    return 0;
+}
+
 int nlg_linop_project(nlg_linop *op, nlg_vec *v) {
     NLG_CHECK(op && v && v->mesh == op->mesh, "nlg_linop_project: bad argument");
     NLG_CHECK(op->proj_v.nlines > 0, "nlg_linop_project: no projection set (nlg_linop_set_projection)");
     NLG_TRY(slab_ensure(op, 1));
     NLG_TRY(load_state(op, 0, v, 0));
-    NLG_TRY(project_alpha(op, 0, 0));
+    NLG_TRY(op->proj_lanes > 0 ? project_alpha_lanes(op, 1, 0, 1u) : project_alpha(op, 0, 0));   // (wavenumber lanes: alpha[0])
     NLG_TRY(store_state(op, 0, v, 0));
     return 0;
 }

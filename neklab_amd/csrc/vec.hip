@@ -513,6 +513,141 @@ __global__ __launch_bounds__(NT) void k_block_rmul(double *W, int64_t wstride, c
     }
 }
 
+// ---- lane-batched orthogonalisation (nlg_basis_cgs2_batch): s vectors, EACH against its own basis (the wavenumbers of a sweep are s
+// separate eigenproblems advanced in lock-step).  The kernels are k_block_dot, k_block_axpy, k_dot_partial and k_scal_dev with the lane
+// in the grid: the base pointers of lane l's basis and vector come by value (LaneVW), the coefficients of lane l lie l * k behind lane
+// 0's, its partial sums in the rows l * k .. l * k + k - 1 of the reduction workspace.  One launch per stage for all lanes.
+struct LaneVW {
+    const double *V[kMaxLanes];   // column 0 of lane l's basis
+    double *w[kMaxLanes];
+    int nrst[kMaxLanes];          // valid history blocks of w[l]
+};
+
+// blockIdx.y = lane * ncomp + field, blockIdx.z = tile of KB basis vectors; partial row (lane * k + j)
+template <int KB>
+__global__ __launch_bounds__(NT) void k_lane_block_dot(LaneVW P, int64_t vstride, int k, int ncomp, const double *bm1, int64_t lvs, int nblk,
+                                                       int nper, double *partial) {
+    __shared__ double sm[4 * KB];
+    const int l = blockIdx.y / ncomp, c = blockIdx.y - l * ncomp;
+    const double *V = P.V[l];
+    const double *w = P.w[l];
+    const int j0 = blockIdx.z * KB;
+    const int kc = (k - j0 < KB) ? (k - j0) : KB;
+    const int64_t n2 = lvs >> 1;
+    const int64_t per = (n2 + nblk - 1) / nblk;
+    const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
+    const double2 *w2 = reinterpret_cast<const double2 *>(w + c * lvs);
+    const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
+    const double2 *v2[KB];
+#pragma unroll
+    for (int j = 0; j < KB; ++j) {
+        const int jj = (j < kc) ? j : 0;
+        v2[j] = reinterpret_cast<const double2 *>(V + (int64_t)(j0 + jj) * vstride + c * lvs);
+    }
+    double acc[KB];
+#pragma unroll
+    for (int j = 0; j < KB; ++j) acc[j] = 0.0;
+    for (int64_t i = beg + threadIdx.x; i < end; i += NT) {
+        const double2 wv = w2[i], mv = m2[i];
+        const double x0 = wv.x * mv.x, x1 = wv.y * mv.y;
+        double2 vv[KB];
+#pragma unroll
+        for (int j = 0; j < KB; ++j) vv[j] = v2[j][i];
+#pragma unroll
+        for (int j = 0; j < KB; ++j) acc[j] += vv[j].x * x0 + vv[j].y * x1;
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < KB; ++j) {
+        const double s = wave_sum(acc[j]);
+        if (lane == 0) sm[wid * KB + j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kc) {
+        const int j = threadIdx.x;
+        const double s = sm[j] + sm[KB + j] + sm[2 * KB + j] + sm[3 * KB + j];
+        partial[((int64_t)l * k + j0 + j) * nper + c * nblk + blockIdx.x] = s;
+    }
+}
+
+// blockIdx.y = lane.  w_l += sign * V_l h_l over the main block (n2 double2 entries) and, unless main_only, over the nrst[l] valid
+// history blocks behind it, which take the coefficients hh_l where hh is given (see k_block_axpy: consistent history update)
+__global__ __launch_bounds__(NT) void k_lane_block_axpy(LaneVW P, int64_t vstride, int k, const double *h, const double *hh, int64_t n2,
+                                                        int main_only, double sign) {
+    extern __shared__ double sh0[];
+    double *sh1 = sh0 + k;
+    const int l = blockIdx.y;
+    h += (int64_t)l * k;
+    if (hh) hh += (int64_t)l * k;
+    for (int j = threadIdx.x; j < k; j += NT) {
+        sh0[j] = h[j];
+        sh1[j] = hh ? hh[j] : h[j];
+    }
+    __syncthreads();
+    const int64_t n2all = main_only ? n2 : n2 * (1 + P.nrst[l]);
+    double2 *w2 = reinterpret_cast<double2 *>(P.w[l]);
+    const double2 *V2 = reinterpret_cast<const double2 *>(P.V[l]);
+    const int64_t vs2 = vstride >> 1;
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
+        const double *sh = (hh && i >= n2) ? sh1 : sh0;
+        double s0 = 0.0, s1 = 0.0;
+        const double2 *v = V2 + i;
+        int j = 0;
+        for (; j + 8 <= k; j += 8) {
+            double2 t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t[u] = v[(int64_t)(j + u) * vs2];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                s0 += sh[j + u] * t[u].x;
+                s1 += sh[j + u] * t[u].y;
+            }
+        }
+        for (; j < k; ++j) {
+            const double2 t = v[(int64_t)j * vs2];
+            s0 += sh[j] * t.x;
+            s1 += sh[j] * t.y;
+        }
+        double2 wv = w2[i];
+        wv.x += sign * s0;
+        wv.y += sign * s1;
+        w2[i] = wv;
+    }
+}
+
+// blockIdx.y = field, blockIdx.z = lane: first stage of |w_l|^2 in the partition of k_dot_partial; partial row l
+__global__ __launch_bounds__(NT) void k_lane_dot_partial(LaneVW P, const double *bm1, int64_t lvs, int nblk, int nper, double *partial) {
+    __shared__ double sm[4];
+    const int c = blockIdx.y, l = blockIdx.z;
+    const int64_t n2 = lvs >> 1;
+    const int64_t per = (n2 + nblk - 1) / nblk;
+    const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
+    const double2 *a2 = reinterpret_cast<const double2 *>(P.w[l] + c * lvs);
+    const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
+    double acc = 0.0;
+    for (int64_t i = beg + threadIdx.x; i < end; i += NT) {
+        const double2 av = a2[i], mv = m2[i];
+        acc += av.x * av.x * mv.x + av.y * av.y * mv.y;
+    }
+    const double s = block_sum(acc, sm);
+    if (threadIdx.x == 0) partial[(int64_t)l * nper + c * nblk + blockIdx.x] = s;
+}
+
+// blockIdx.y = lane: w_l *= 1 / sqrt(q[l]) over the main block and the valid history blocks (0 where q[l] is not positive, as k_scal_dev)
+__global__ __launch_bounds__(NT) void k_lane_scal_dev(LaneVW P, const double *q, int64_t n2) {
+    const int l = blockIdx.y;
+    const double sv = q[l];
+    const double a = sv > 0.0 ? 1.0 / sqrt(sv) : 0.0;
+    const int64_t n2all = n2 * (1 + P.nrst[l]);
+    double2 *x = reinterpret_cast<double2 *>(P.w[l]);
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
+        double2 v = x[i];
+        v.x = __dmul_rn(v.x, a);
+        v.y = __dmul_rn(v.y, a);
+        x[i] = v;
+    }
+}
+
 __global__ void k_vadd(double *a, const double *b, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] += b[i];
@@ -1084,9 +1219,105 @@ int basis_cgs2_dev(nlg_basis *b, int k, nlg_vec *w) {
     return 0;
 }
 
+// The batched form of basis_cgs2_dev (consistent history update): projection, subtraction on the main block, second projection
+// (accumulated), subtraction with the second coefficients on the main block and the sum of both on the history, norm, scale -- six
+// launches plus four small reductions for all s lanes, where s calls of basis_cgs2_dev make s times as many.  The fused
+// subtraction-and-projection sweep of the single-lane path (k >= 24) has no lane form: the batched path is one variant for every k.
+// Workspace (b[0]->d_hb): coefficients [s][k] at 0, |w_l|^2 at s * k, second-pass coefficients [s][k] at 4 * nvec + 8.
+int basis_cgs2_batch_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w) {
+    nlg_basis *b0 = b[0];
+    nlg_mesh *m = b0->mesh;
+    nlg_ctx *ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    if (!b0->d_hb) NLG_HIP(hipMalloc(&b0->d_hb, sizeof(double) * ((size_t)2 * b0->nvec * 4 + 64)));
+    double *H1 = b0->d_hb, *Q = H1 + (size_t)s * k, *H2 = b0->d_hb + (size_t)b0->nvec * 4 + 8;
+    if (!g_axpby_consistent) {   // the reference's history quirk has no batched form: lane by lane, results gathered into the workspace
+        for (int l = 0; l < s; ++l) {
+            NLG_TRY(basis_cgs2_dev(b[l], k, w[l]));
+            if (k > 0) NLG_HIP(hipMemcpyAsync(H1 + (size_t)l * k, b[l]->d_h, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
+            NLG_HIP(hipMemcpyAsync(Q + l, b[l]->d_h + k, sizeof(double), hipMemcpyDeviceToDevice, st));
+        }
+        return 0;
+    }
+    LaneVW P;
+    int nrst = 0;
+    for (int l = 0; l < kMaxLanes; ++l) {
+        const int u = l < s ? l : 0;
+        P.V[l] = b[u]->d, P.w[l] = w[u]->d, P.nrst[l] = w[u]->nrst;
+        nrst = std::max(nrst, w[u]->nrst);
+    }
+    const nlg_vec *v0 = b0->views[0];
+    constexpr int KB = 8;
+    const int nblk = dot_nblk(v0), nper = nblk * v0->ncomp;
+    const int64_t n2 = v0->main_len / 2;
+    NLG_TRY(reduce_ws_reserve(ctx, s * std::max(k, 1)));
+    // rows of the reduction workspace -> out (all-reduced: ONE collective for all lanes), optionally acc += out
+    auto reduce = [&](int rows, int per, double *out, double *acc) -> int {
+        if (ctx->distributed()) {
+            NLG_LAUNCH(k_reduce_rows, dim3(rows), dim3(NT), 0, st, ctx->d_partial, per, out, 0, (double *)nullptr);
+            NLG_TRY(allreduce_sum(ctx, out, rows));
+            if (acc) NLG_LAUNCH(k_vadd, dim3((rows + 255) / 256), dim3(256), 0, st, acc, out, rows);
+        } else {
+            ++g_collectives;
+            NLG_LAUNCH(k_reduce_rows, dim3(rows), dim3(NT), 0, st, ctx->d_partial, per, out, acc ? 1 : 0, acc);
+        }
+        return 0;
+    };
+    auto dot = [&](double *out, double *acc) -> int {
+        ProfScope ps(ctx, P_BLOCKDOT);
+        NLG_LAUNCH(k_lane_block_dot<KB>, dim3(nblk, v0->ncomp * s, (k + KB - 1) / KB), dim3(NT), 0, st, P, b0->stride, k, v0->ncomp,
+                   (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
+        return reduce(s * k, nper, out, acc);
+    };
+    auto axpy = [&](const double *h, const double *hh, bool main_only) -> int {
+        ProfScope ps(ctx, P_BLOCKAXPY);
+        const int64_t n2all = main_only ? n2 : n2 * (1 + nrst);
+        NLG_LAUNCH(k_lane_block_axpy, dim3(grid_for(n2all), s), dim3(NT), sizeof(double) * 2 * k, st, P, b0->stride, k, h, hh, n2, (int)main_only, -1.0);
+        return 0;
+    };
+    if (k > 0) {
+        NLG_TRY(dot(H1, nullptr));
+        NLG_TRY(axpy(H1, nullptr, true));
+        NLG_TRY(dot(H2, H1));
+        NLG_TRY(axpy(H2, H1, false));
+    }
+    NLG_LAUNCH(k_lane_dot_partial, dim3(nblk, v0->ncomp, s), dim3(NT), 0, st, P, (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
+    NLG_TRY(reduce(s, nper, Q, nullptr));
+    NLG_LAUNCH(k_lane_scal_dev, dim3(grid_for(n2 * (1 + nrst)), s), dim3(NT), 0, st, P, (const double *)Q, n2);
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace nlg
 
 extern "C" {
+
+int nlg_basis_cgs2_batch(int s, nlg_basis *const *b, int k, nlg_vec *const *w, double *h, int ldh, double *beta) {
+    NLG_CHECK(b && w && h && beta, "nlg_basis_cgs2_batch: NULL argument");
+    NLG_CHECK(s >= 1 && s <= kMaxLanes, "nlg_basis_cgs2_batch: %d lanes unsupported (1..%d)", s, kMaxLanes);
+    for (int l = 0; l < s; ++l) NLG_CHECK(b[l] && w[l], "nlg_basis_cgs2_batch: NULL basis or vector in lane %d", l);
+    NLG_CHECK(k >= 0 && k <= b[0]->nvec, "nlg_basis_cgs2_batch: k=%d out of range [0,%d]", k, b[0]->nvec);
+    NLG_CHECK(ldh >= k, "nlg_basis_cgs2_batch: ldh=%d too small for k=%d", ldh, k);
+    for (int l = 0; l < s; ++l) {
+        NLG_CHECK(b[l]->mesh == b[0]->mesh && b[l]->nscal == b[0]->nscal && b[l]->lorder == b[0]->lorder && b[l]->nvec == b[0]->nvec,
+                  "nlg_basis_cgs2_batch: the bases differ in shape (lane %d)", l);
+        NLG_TRY(check_same(b[l]->views[0], w[l], "nlg_basis_cgs2_batch"));
+        for (int u = 0; u < l; ++u) NLG_CHECK(b[l] != b[u] && w[l] != w[u], "nlg_basis_cgs2_batch: the same basis or vector in two lanes");
+        for (int u = 0; u < s; ++u)
+            NLG_CHECK(!(w[l]->d >= b[u]->d && w[l]->d < b[u]->d + (int64_t)k * b[u]->stride),
+                      "nlg_basis_cgs2_batch: the vector of lane %d is one of the columns 0..%d it is orthogonalised against", l, k - 1);
+    }
+    NLG_TRY(nlg::basis_cgs2_batch_dev(s, b, k, w));
+    std::vector<double> tmp((size_t)s * k + s);
+    hipStream_t st = b[0]->mesh->ctx->stream;
+    NLG_HIP(hipMemcpyAsync(tmp.data(), b[0]->d_hb, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    for (int l = 0; l < s; ++l) {
+        for (int j = 0; j < k; ++j) h[(size_t)l * ldh + j] = tmp[(size_t)l * k + j];
+        beta[l] = sqrt(tmp[(size_t)s * k + l]);
+    }
+    return 0;
+}
 
 int nlg_basis_block_dot(const nlg_basis *b, int k, const nlg_vec *w, double *h) {
     NLG_CHECK(b && w && h, "nlg_basis_block_dot: NULL argument");

@@ -466,6 +466,37 @@ module neklab_gpu_capi
          type(c_ptr), value :: op, v
          integer(c_int) :: rc
       end function
+      ! wavenumber lanes (a sweep over alpha in lock-step): bindings only, the reference has no type or driver for this
+      function c_linop_set_projection_lanes(op, nalpha, alpha, idir, lab, lab2, x2) bind(C, name="nlg_linop_set_projection_lanes") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: op, lab, lab2, x2
+         integer(c_int), value :: nalpha, idir
+         real(c_double), intent(in) :: alpha(*)
+         integer(c_int) :: rc
+      end function
+      function c_linop_project_block(op, s, v) bind(C, name="nlg_linop_project_block") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: op
+         integer(c_int), value :: s
+         type(c_ptr), intent(in) :: v(*)
+         integer(c_int) :: rc
+      end function
+      function c_basis_cgs2_batch(s, b, k, w, h, ldh, beta) bind(C, name="nlg_basis_cgs2_batch") result(rc)
+         import c_int, c_ptr, c_double
+         integer(c_int), value :: s, k, ldh
+         type(c_ptr), intent(in) :: b(*), w(*)
+         real(c_double), intent(out) :: h(*), beta(*)
+         integer(c_int) :: rc
+      end function
+      function c_sweep_arnoldi_step(op, s, basis, k, H, ldh, hstride, transpose) bind(C, name="nlg_sweep_arnoldi_step") result(rc)
+         import c_int, c_int64_t, c_ptr, c_double
+         type(c_ptr), value :: op
+         integer(c_int), value :: s, k, ldh, transpose
+         integer(c_int64_t), value :: hstride
+         type(c_ptr), intent(in) :: basis(*)
+         real(c_double), intent(inout) :: H(*)
+         integer(c_int) :: rc
+      end function
       function c_linop_integrate_forced(op, ic, f_re, f_im, omega, adjoint, vout) bind(C, name="nlg_linop_integrate_forced") result(rc)
          import c_int, c_ptr, c_double
          type(c_ptr), value :: op, ic, f_re, f_im, vout

@@ -277,6 +277,19 @@ class KrylovBasis:
         check(self.lib.nlg_basis_cgs2(self.h, k, w.h, dptr(h), C.byref(beta)))
         return h[:k], beta.value
 
+    @staticmethod
+    def cgs2_batch(bases: list, k: int, ws: list):
+        """ws[l] against columns 0 .. k-1 of bases[l], all lanes in one launch per stage (nlg_basis_cgs2_batch); returns
+        (h of shape (len(bases), k), beta of shape (len(bases),))."""
+        s = len(bases)
+        assert len(ws) == s and s >= 1
+        ldh = max(int(k), 1)
+        h, beta = np.zeros((s, ldh)), np.zeros(s)
+        ab = (vp * s)(*[b.h for b in bases])
+        aw = (vp * s)(*[w.h for w in ws])
+        check(bases[0].lib.nlg_basis_cgs2_batch(s, ab, int(k), aw, dptr(h), ldh, dptr(beta)))
+        return h[:, :k], beta
+
     def block_cgs2(self, k: int, s: int) -> np.ndarray:
         """Columns k .. k+s-1 orthogonalised against 0 .. k-1 and among themselves (nlg_basis_block_cgs2); returns the
         (k+s, s) coefficient matrix: projection coefficients on top, the upper-triangular R below."""
@@ -708,6 +721,43 @@ class exptA_proj_linop(exptA_linop):
 
     def proj(self, vec: nek_dvector):
         check(self.lib.nlg_linop_project(self.h, vec.h))
+
+
+class exptA_sweep_linop(exptA_proj_linop):
+    """Wavenumber sweep in lock-step: up to four wavenumbers ride the lanes of one block propagator
+    (nlg_linop_set_projection_lanes).  Lane l of matvec_block runs at alphas[l]; matvec / rmatvec / proj are the block of
+    one and use alphas[0]."""
+
+    def __init__(self, tau: float, baseflow: nek_dvector, alphas, idir: int = 1, project_pressure: bool = True, **cfg):
+        alphas = [float(a) for a in alphas]
+        super().__init__(tau, baseflow, alphas[0] if alphas else 0.0, idir=idir, project_pressure=project_pressure, **cfg)
+        self.alphas = alphas
+        self._labels = None
+
+    def init(self):
+        exptA_linop.init(self)
+        self.set_alphas(self.alphas)
+
+    def set_alphas(self, alphas):
+        """Replace the set of wavenumbers (the driver retires converged lanes this way)."""
+        alphas = [float(a) for a in alphas]
+        if self._labels is None:
+            lab = line_labels(self.mesh, self.idir)
+            lab2, x2 = line_labels_pressure(self.mesh, self.idir) if self.project_pressure else (None, None)
+            self._labels = (lab, lab2, x2)
+        lab, lab2, x2 = self._labels
+        a = np.ascontiguousarray(alphas, dtype=np.float64)
+        check(self.lib.nlg_linop_set_projection_lanes(
+            self.h, len(alphas), dptr(a) if len(alphas) else None, self.idir, lab.ctypes.data_as(_lib.c_int64_p),
+            lab2.ctypes.data_as(_lib.c_int64_p) if lab2 is not None else None, dptr(x2) if x2 is not None else None))
+        self.alphas = alphas
+        self.alpha = alphas[0]
+
+    def proj_block(self, vecs: list):
+        """vecs[l] <- P_{alphas[l]} vecs[l] (nlg_linop_project_block)."""
+        s = len(vecs)
+        arr = (vp * s)(*[x.h for x in vecs])
+        check(self.lib.nlg_linop_project_block(self.h, s, arr))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1201,6 +1251,107 @@ def block_arnoldi_step(exptA: exptA_linop, basis: KrylovBasis, k: int, s: int, H
     """Columns k .. k+s-1 -> k+s .. k+2s-1; H (Fortran-ordered) receives H[0:k+2s, k:k+s]."""
     assert H.flags.f_contiguous
     check(exptA.lib.nlg_block_arnoldi_step(exptA.h, basis.h, int(k), int(s), dptr(H), H.shape[0], int(bool(transpose))))
+
+
+def sweep_arnoldi_step(A: "exptA_sweep_linop", bases: list, k: int, Hs: np.ndarray, transpose: bool = False):
+    """One Arnoldi step of len(bases) <= 4 separate eigenproblems in lock-step (nlg_sweep_arnoldi_step): lane l at A.alphas[l] on its
+    own basis.  Hs is C-ordered (lanes, kdim, kdim+1): Hs[l].T is lane l's Hessenberg matrix in the layout of arnoldi_step."""
+    s = len(bases)
+    assert Hs.flags.c_contiguous and Hs.ndim == 3 and Hs.shape[0] >= s
+    ab = (vp * s)(*[b.h for b in bases])
+    check(A.lib.nlg_sweep_arnoldi_step(A.h, s, ab, int(k), dptr(Hs), Hs.shape[2], Hs.shape[1] * Hs.shape[2], int(bool(transpose))))
+
+
+def _ritz_from_hessenberg(H: np.ndarray, k: int):
+    """Ritz pairs of the leading k x k block of a (>= k+1, >= k) Hessenberg matrix, by the rule of `ritz_pairs` in csrc/krylov.hip:
+    eigenpairs of H[:k, :k] (unit eigenvectors), residuals |H[k, k-1]| |y[k-1]|, sorted by decreasing modulus (stable).
+    Returns (lam[k], Y[k, k] with the eigenvectors as columns, res[k])."""
+    lam, Y = np.linalg.eig(np.asarray(H)[:k, :k])
+    Y = Y / np.linalg.norm(Y, axis=0)
+    res = abs(H[k, k - 1]) * np.abs(Y[k - 1, :])
+    order = np.argsort(-np.abs(lam), kind="stable")
+    return lam[order], Y[:, order], res[order]
+
+
+def linear_stability_analysis_wavenumbers(tau: float, baseflow: nek_dvector, alphas, kdim: int, nev: int, tol: float = 1e-6,
+                                          seed: int = 0, transpose: bool = False, outdir: str = ".", idir: int = 1,
+                                          project_pressure: bool = True, **cfg):
+    """Leading eigenvalues of the propagator restricted to each of the wavenumbers `alphas` (a dispersion relation), in lock-step: groups
+    of at most four wavenumbers ride the lanes of one exptA_sweep_linop, each lane with its own Krylov basis and Hessenberg matrix
+    (sweep_arnoldi_step).  After every step each lane's Ritz pairs are taken (_ritz_from_hessenberg); a lane is finished when nev
+    residuals are below tol, or at breakdown (beta below 1e-12 of the column norm of H); finished lanes are retired (set_alphas with
+    the remaining wavenumbers) and the run goes on with fewer lanes until all are finished or kdim steps are done.  Plain Arnoldi:
+    there are NO Krylov-Schur restarts (as for block_size > 1 in nlg_eigs), so kdim bounds the Krylov space of every wavenumber.
+    Start vector of wavenumber i: rand(True, seed=seed + i), projected.  Writes <dir|adj>_eigenspectrum_alpha<i>.npy per wavenumber.
+    Returns one tuple per alpha, as linear_stability_analysis_fixed_point does: (eigvals = log(mu) / tau, residuals, eigvecs, mu,
+    matvecs); a complex pair's eigenvectors are its real and imaginary parts, as nlg_eigs returns them."""
+    alphas = [float(a) for a in alphas]
+    mesh = baseflow.mesh
+    prefix = "adj" if transpose else "dir"
+    results = [None] * len(alphas)
+    A = None
+    for g0 in range(0, len(alphas), 4):
+        group = list(range(g0, min(g0 + 4, len(alphas))))
+        if A is None:
+            A = exptA_sweep_linop(tau, baseflow, [alphas[i] for i in group], idir=idir, project_pressure=project_pressure, **cfg)
+            A.init()
+        else:
+            A.set_alphas([alphas[i] for i in group])
+        bases = {i: KrylovBasis(mesh, kdim + 1) for i in group}
+        Hs = {i: np.zeros((kdim + 1, kdim)) for i in group}
+        for i in group:
+            bases[i][0].rand(True, seed=seed + i)
+        A.proj_block([bases[i][0] for i in group])
+        for i in group:
+            nrm = bases[i][0].norm()
+            bases[i][0].scal(1.0 / nrm)
+        active = list(group)
+        done = {}
+        k = 0
+        while active and k < kdim:
+            s = len(active)
+            Hw = np.zeros((s, kdim, kdim + 1))
+            sweep_arnoldi_step(A, [bases[i] for i in active], k, Hw, transpose=transpose)
+            k += 1
+            finished = []
+            for l, i in enumerate(active):
+                Hs[i][:k + 1, k - 1] = Hw[l, k - 1, :k + 1]
+                lam, Y, res = _ritz_from_hessenberg(Hs[i], k)
+                breakdown = Hs[i][k, k - 1] <= 1e-12 * np.linalg.norm(Hs[i][:k + 1, k - 1])
+                if breakdown or np.count_nonzero(res < tol) >= nev or k == kdim:
+                    done[i] = (k, lam, Y, res)
+                    finished.append(i)
+            if finished:
+                active = [i for i in active if i not in finished]
+                if active and k < kdim:
+                    A.set_alphas([alphas[i] for i in active])
+        tau_ = A.info()["tau"]
+        for i in group:
+            kf, lam, Y, res = done[i]
+            n = min(nev, kf)
+            eigvecs = [nek_dvector(mesh, 0, 3) for _ in range(nev)]
+            for v in eigvecs:
+                v.zero()
+            j = 0
+            while j < n:
+                bases[i].combine(kf, np.real(Y[:, j]), eigvecs[j])
+                if abs(lam[j].imag) > 0.0:
+                    if j + 1 < n:
+                        bases[i].combine(kf, (1.0 if lam[j].imag > 0.0 else -1.0) * np.imag(Y[:, j]), eigvecs[j + 1])
+                    j += 2
+                else:
+                    j += 1
+            mu = np.zeros(nev, dtype=complex)
+            residuals = np.zeros(nev)
+            mu[:n], residuals[:n] = lam[:n], res[:n]
+            with np.errstate(divide="ignore"):
+                eigvals = np.log(mu) / tau_
+            save_eigenspectrum(eigvals, residuals, os.path.join(outdir, "%s_eigenspectrum_alpha%d.npy" % (prefix, i)))
+            results[i] = (eigvals, residuals, eigvecs, mu, kf)
+            bases[i].close()
+    if A is not None:
+        A.close()
+    return results
 
 
 def eigs(exptA: exptA_linop, X: list, kdim: int = 0, tol: float = 0.0, x0: nek_dvector | None = None,
