@@ -336,7 +336,9 @@ int nlg_linop_set_tolerances(nlg_linop *op, double vtol, double ptol);
  * projects the velocity only, see DESIGN.md for why that is not enough behind an inner product that ignores the
  * pressure.  Several ranks: the labels are GLOBAL line names (the same line carries the same label on every rank
  * that holds a part of it); the weighted sums are all-reduced, as the reference's planar_avg is a global operation
- * (exponential_propagator_proj.f90:146-169).  nlg_linop_project applies the projection to the state held by a vector. */
+ * (exponential_propagator_proj.f90:146-169).  A block run (nlg_linop_matvec_block) projects all its lanes onto alpha in
+ * one launch per level, several ranks: one all-reduce for all lanes; a single run is the block of one.
+ * nlg_linop_project applies the projection to the state held by a vector. */
 int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
                              const double *x2);
 int nlg_linop_project(nlg_linop *op, nlg_vec *v);
@@ -345,9 +347,9 @@ int nlg_linop_project(nlg_linop *op, nlg_vec *v);
  * same optional pressure-mesh pair, swapped in on success only): the lines are built once and shared, the cos / sin tables
  * exist once per lane (each the table a single-alpha operator builds, bit for bit).  Afterwards lane l of
  * nlg_linop_matvec_block (s <= nalpha vectors) projects onto alpha[l] wherever a projected run projects -- initial condition,
- * replayed history states, final state with its lagged levels, pressure -- in ONE launch per level for all lanes, each lane
- * with the result the single-alpha kernel gives (same summation order per line); several ranks: one all-reduce for all
- * lanes.  nlg_linop_matvec / rmatvec / nlg_linop_project are the block of one and use alpha[0].  A later
+ * replayed history states, final state with its lagged levels, pressure -- by the kernels and the driver of
+ * nlg_linop_set_projection, which differ only in the table a lane reads: each lane has the result a single-alpha operator
+ * at alpha[l] gives, bit for bit.  nlg_linop_matvec / rmatvec / nlg_linop_project are the block of one and use alpha[0].  A later
  * nlg_linop_set_projection returns the operator to one alpha for all lanes; calling this again replaces the set (fewer
  * lanes: a sweep retires the wavenumbers that have converged).  Refused: nalpha outside 1..4, a NULL alpha, orbit mode, a
  * live nlg_otd, cfg.ifheat (the projection does not touch the scalar); on such an operator: a block run of more than nalpha

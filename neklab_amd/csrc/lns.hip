@@ -578,16 +578,30 @@ __global__ __launch_bounds__(NT) void k_proj_store(int64_t n, const double *__re
 // ---- wavenumber projection of the projected propagator (proj_alpha, src/linops/exponential_propagator_proj.f90:135-173):
 // every velocity component keeps only its cos(alpha x) / sin(alpha x) content along the homogeneous direction,
 //   u <- cv <2 u cv> + sv <2 u sv>,   <f> = sum_line bm1 f / sum_line bm1 over the points of a line along that direction
-// (Nek5000's planar_avg over the gtpp gather-scatter handle).  One wave per line.
+// (Nek5000's planar_avg over the gtpp gather-scatter handle).  One wave per line; the lane of a block run sits in gridDim.y (a
+// single vector is the block of one): lane l's fields lie l * ld behind lane 0's (the slab), its cos / sin tables l * tld behind
+// lane 0's -- tld = 0: one wavenumber for all lanes, tld = n: one per lane (wavenumber lanes) -- and the lines, the weights and the
+// denominators are shared.  Lanes whose bit in `mask` is clear are left alone (history replay: only the lanes that carry a history
+// level are reloaded and projected).  The summation order of a line is fixed (stride 64, then the butterfly), so a lane's result
+// depends on its own field and table only, not on the block it is part of.
+//
+// the line of this wave, with u, cv, sv moved to the lane; false: nothing to do (lane not in `mask`, or past the last line)
+template <typename U>
+__device__ __forceinline__ bool proj_line(int64_t nlines, const int *__restrict__ off, unsigned mask, int64_t ld, int64_t tld, U &u,
+                                          const double *__restrict__ &cv, const double *__restrict__ &sv, int64_t &g, int &b, int &e) {
+    if (!((mask >> blockIdx.y) & 1u)) return false;
+    g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (g >= nlines) return false;
+    u = lane_f3(u, lane_lo(ld));
+    cv += lane_lo(tld), sv += lane_lo(tld);
+    b = off[g], e = off[g + 1];
+    return true;
+}
+// ac[c], as[c] = sum over the points b .. e-1 of the line of 2 bm1 u_c cv and 2 bm1 u_c sv, in every lane of the wave
 template <int NF>
-__global__ __launch_bounds__(NT) void k_proj_alpha(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
-                                                   const double *__restrict__ bm1, const double *__restrict__ cv,
-                                                   const double *__restrict__ sv, const double *__restrict__ inv_den, F3 u) {
+__device__ __forceinline__ void proj_line_sums(int b, int e, const int *__restrict__ idx, const double *__restrict__ bm1, const double *cv,
+                                               const double *sv, const CF3 &u, double (&ac)[NF], double (&as)[NF]) {
     const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    if (g >= nlines) return;
-    const int b = off[g], e = off[g + 1];
-    double ac[NF], as[NF];
 #pragma unroll
     for (int c = 0; c < NF; ++c) ac[c] = as[c] = 0.0;
     for (int q = b + lane; q < e; q += 64) {
@@ -608,48 +622,45 @@ __global__ __launch_bounds__(NT) void k_proj_alpha(int64_t nlines, const int *__
             as[c] += __shfl_xor(as[c], o, 64);
         }
     }
-    const double id = inv_den[g];
-    for (int q = b + lane; q < e; q += 64) {
+}
+// u_c = cv (ac[c] / den) + sv (as[c] / den) on the points of the line, id = 1 / den
+template <int NF>
+__device__ __forceinline__ void proj_line_write(int b, int e, const int *__restrict__ idx, const double *cv, const double *sv, double id,
+                                                const double (&ac)[NF], const double (&as)[NF], const F3 &u) {
+    for (int q = b + (threadIdx.x & 63); q < e; q += 64) {
         const int i = idx[q];
 #pragma unroll
         for (int c = 0; c < NF; ++c) u.p[c][i] = cv[i] * (ac[c] * id) + sv[i] * (as[c] * id);
     }
 }
+// one rank: sums and write-back in one kernel
+template <int NF>
+__global__ __launch_bounds__(NT) void k_proj_alpha(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
+                                                   const double *__restrict__ bm1, const double *__restrict__ cv,
+                                                   const double *__restrict__ sv, int64_t tld, const double *__restrict__ inv_den,
+                                                   F3 u, int64_t ld, unsigned mask) {
+    int64_t g;
+    int b, e;
+    if (!proj_line(nlines, off, mask, ld, tld, u, cv, sv, g, b, e)) return;
+    double ac[NF], as[NF];
+    proj_line_sums<NF>(b, e, idx, bm1, cv, sv, CF3{{u.p[0], u.p[1], u.p[2]}}, ac, as);
+    proj_line_write<NF>(b, e, idx, cv, sv, inv_den[g], ac, as, u);
+}
 // Several ranks: a line along the homogeneous direction may cross rank boundaries.  The weighted sums of a rank's part of a
-// line go to the line's slot in a global array (one slot per distinct line label over all ranks), the array is all-reduced,
-// and a second kernel applies the projection with the global sums.
+// line go to the line's slots in a global array, [gslot][gridDim.y][2][NF] (one gslot per distinct line label over all ranks),
+// the array is all-reduced -- one all-reduce for all lanes -- and a second kernel applies the projection with the global sums.
 template <int NF>
 __global__ __launch_bounds__(NT) void k_proj_sums(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
                                                   const int *__restrict__ gslot, const double *__restrict__ bm1,
-                                                  const double *__restrict__ cv, const double *__restrict__ sv, CF3 u,
-                                                  double *__restrict__ glob) {
-    const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    if (g >= nlines) return;
-    const int b = off[g], e = off[g + 1];
+                                                  const double *__restrict__ cv, const double *__restrict__ sv, int64_t tld, CF3 u,
+                                                  int64_t ld, unsigned mask, double *__restrict__ glob) {
+    int64_t g;
+    int b, e;
+    if (!proj_line(nlines, off, mask, ld, tld, u, cv, sv, g, b, e)) return;
     double ac[NF], as[NF];
-#pragma unroll
-    for (int c = 0; c < NF; ++c) ac[c] = as[c] = 0.0;
-    for (int q = b + lane; q < e; q += 64) {
-        const int i = idx[q];
-        const double w = 2.0 * bm1[i], c0 = cv[i], s0 = sv[i];
-#pragma unroll
-        for (int c = 0; c < NF; ++c) {
-            const double v = u.p[c][i];
-            ac[c] += w * v * c0;
-            as[c] += w * v * s0;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NF; ++c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ac[c] += __shfl_xor(ac[c], o, 64);
-            as[c] += __shfl_xor(as[c], o, 64);
-        }
-    }
-    if (lane == 0) {
-        double *dst = glob + (int64_t)gslot[g] * (2 * NF);
+    proj_line_sums<NF>(b, e, idx, bm1, cv, sv, u, ac, as);
+    if ((threadIdx.x & 63) == 0) {
+        double *dst = glob + ((int64_t)gslot[g] * gridDim.y + blockIdx.y) * (2 * NF);
 #pragma unroll
         for (int c = 0; c < NF; ++c) {
             dst[2 * c] = ac[c];
@@ -660,127 +671,16 @@ __global__ __launch_bounds__(NT) void k_proj_sums(int64_t nlines, const int *__r
 template <int NF>
 __global__ __launch_bounds__(NT) void k_proj_apply(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
                                                    const int *__restrict__ gslot, const double *__restrict__ cv,
-                                                   const double *__restrict__ sv, const double *__restrict__ inv_den,
-                                                   const double *__restrict__ glob, F3 u) {
-    const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    if (g >= nlines) return;
-    const int b = off[g], e = off[g + 1];
-    const double *src = glob + (int64_t)gslot[g] * (2 * NF);
-    const double id = inv_den[g];
-    for (int q = b + lane; q < e; q += 64) {
-        const int i = idx[q];
-#pragma unroll
-        for (int c = 0; c < NF; ++c) u.p[c][i] = cv[i] * (src[2 * c] * id) + sv[i] * (src[2 * c + 1] * id);
-    }
-}
-// Wavenumber lanes: the same three kernels for the lanes of a block run, each with its own cos / sin table.  The lane sits in
-// gridDim.y: lane l's fields lie l * ld behind lane 0's (the slab), its tables l * tld behind lane 0's; the lines, the weights and
-// the denominators are shared.  One wave per line, and the summation order of a line is that of k_proj_alpha, so a lane's result is
-// the one the single-wavenumber kernel gives with that lane's table.  Lanes whose bit in `mask` is clear are left alone (history
-// replay: only the lanes that carry a history level are reloaded and projected).  Several ranks: slot [gslot][lane] of the
-// all-reduce buffer, one all-reduce for all lanes.
-template <int NF>
-__global__ __launch_bounds__(NT) void k_proj_alpha_lanes(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
-                                                         const double *__restrict__ bm1, const double *__restrict__ cv,
-                                                         const double *__restrict__ sv, int64_t tld, const double *__restrict__ inv_den,
-                                                         F3 u, int64_t ld, unsigned mask) {
-    if (!((mask >> blockIdx.y) & 1u)) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    if (g >= nlines) return;
-    u = lane_f3(u, lane_lo(ld));
-    cv += lane_lo(tld), sv += lane_lo(tld);
-    const int b = off[g], e = off[g + 1];
-    double ac[NF], as[NF];
-#pragma unroll
-    for (int c = 0; c < NF; ++c) ac[c] = as[c] = 0.0;
-    for (int q = b + lane; q < e; q += 64) {
-        const int i = idx[q];
-        const double w = 2.0 * bm1[i], c0 = cv[i], s0 = sv[i];
-#pragma unroll
-        for (int c = 0; c < NF; ++c) {
-            const double v = u.p[c][i];
-            ac[c] += w * v * c0;
-            as[c] += w * v * s0;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NF; ++c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ac[c] += __shfl_xor(ac[c], o, 64);
-            as[c] += __shfl_xor(as[c], o, 64);
-        }
-    }
-    const double id = inv_den[g];
-    for (int q = b + lane; q < e; q += 64) {
-        const int i = idx[q];
-#pragma unroll
-        for (int c = 0; c < NF; ++c) u.p[c][i] = cv[i] * (ac[c] * id) + sv[i] * (as[c] * id);
-    }
-}
-template <int NF>
-__global__ __launch_bounds__(NT) void k_proj_sums_lanes(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
-                                                        const int *__restrict__ gslot, const double *__restrict__ bm1,
-                                                        const double *__restrict__ cv, const double *__restrict__ sv, int64_t tld, CF3 u,
-                                                        int64_t ld, unsigned mask, double *__restrict__ glob) {
-    if (!((mask >> blockIdx.y) & 1u)) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    if (g >= nlines) return;
-    u = lane_f3(u, lane_lo(ld));
-    cv += lane_lo(tld), sv += lane_lo(tld);
-    const int b = off[g], e = off[g + 1];
-    double ac[NF], as[NF];
-#pragma unroll
-    for (int c = 0; c < NF; ++c) ac[c] = as[c] = 0.0;
-    for (int q = b + lane; q < e; q += 64) {
-        const int i = idx[q];
-        const double w = 2.0 * bm1[i], c0 = cv[i], s0 = sv[i];
-#pragma unroll
-        for (int c = 0; c < NF; ++c) {
-            const double v = u.p[c][i];
-            ac[c] += w * v * c0;
-            as[c] += w * v * s0;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NF; ++c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ac[c] += __shfl_xor(ac[c], o, 64);
-            as[c] += __shfl_xor(as[c], o, 64);
-        }
-    }
-    if (lane == 0) {
-        double *dst = glob + ((int64_t)gslot[g] * gridDim.y + blockIdx.y) * (2 * NF);
-#pragma unroll
-        for (int c = 0; c < NF; ++c) {
-            dst[2 * c] = ac[c];
-            dst[2 * c + 1] = as[c];
-        }
-    }
-}
-template <int NF>
-__global__ __launch_bounds__(NT) void k_proj_apply_lanes(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
-                                                         const int *__restrict__ gslot, const double *__restrict__ cv,
-                                                         const double *__restrict__ sv, int64_t tld, const double *__restrict__ inv_den,
-                                                         const double *__restrict__ glob, F3 u, int64_t ld, unsigned mask) {
-    if (!((mask >> blockIdx.y) & 1u)) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t g = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    if (g >= nlines) return;
-    u = lane_f3(u, lane_lo(ld));
-    cv += lane_lo(tld), sv += lane_lo(tld);
-    const int b = off[g], e = off[g + 1];
+                                                   const double *__restrict__ sv, int64_t tld, const double *__restrict__ inv_den,
+                                                   const double *__restrict__ glob, F3 u, int64_t ld, unsigned mask) {
+    int64_t g;
+    int b, e;
+    if (!proj_line(nlines, off, mask, ld, tld, u, cv, sv, g, b, e)) return;
     const double *src = glob + ((int64_t)gslot[g] * gridDim.y + blockIdx.y) * (2 * NF);
-    const double id = inv_den[g];
-    for (int q = b + lane; q < e; q += 64) {
-        const int i = idx[q];
+    double ac[NF], as[NF];
 #pragma unroll
-        for (int c = 0; c < NF; ++c) u.p[c][i] = cv[i] * (src[2 * c] * id) + sv[i] * (src[2 * c + 1] * id);
-    }
+    for (int c = 0; c < NF; ++c) ac[c] = src[2 * c], as[c] = src[2 * c + 1];
+    proj_line_write<NF>(b, e, idx, cv, sv, inv_den[g], ac, as, u);
 }
 // weights of a rank's part of every line into the global slots (set-up: the denominators)
 __global__ __launch_bounds__(NT) void k_proj_wsum(int64_t nlines, const int *__restrict__ off, const int *__restrict__ idx,
@@ -1201,13 +1101,13 @@ struct LanePred {
 
 // wavenumber projection on one mesh: lines along the homogeneous direction (groups of local dofs, off / idx), cos / sin of alpha x,
 // 1 / sum of the weights of a line; several ranks: slot of every local line in the global line list, number of global lines and
-// the all-reduce buffer ([nglob][2][nf]).  Wavenumber lanes (nlg_linop_set_projection_lanes): the lines are shared, the cos / sin
-// tables exist once per lane, lane l's at cv + l * tld and sv + l * tld, and the all-reduce buffer is [nglob][lanes][2][nf].
+// the all-reduce buffer ([nglob][lanes of the block][2][nf]).  Lane l of a block reads the tables at cv + l * tld and sv + l * tld:
+// tld = 0, one table, one wavenumber for all lanes (nlg_linop_set_projection); tld = n, nalpha tables, one wavenumber per lane
+// (nlg_linop_set_projection_lanes).  Nothing else distinguishes the two kinds of operator here.
 struct ProjLines {
     int nlines = 0;
     int *off = nullptr, *idx = nullptr, *gslot = nullptr;
     int64_t nglob = 0;
-    int nalpha = 1;
     int64_t tld = 0;
     double *cv = nullptr, *sv = nullptr, *iden = nullptr, *glob = nullptr;
     const double *weight = nullptr;   // the mesh's mass matrix (not owned)
@@ -2512,43 +2412,10 @@ int run_steps(const Lanes &L, int fdot_lane = -1) {
     return run_steps(L, fdot_lane, [](int) { return 0; });
 }
 
-// the projection of nf fields on one mesh: one kernel; several ranks: partial sums -> global slots -> all-reduce -> apply (the
+// the projection of nf fields on one mesh for the lanes 0 .. s-1 of the slab whose bit in `mask` is set (f: lane 0's fields), lane l
+// with the table at l * P.tld: one kernel; several ranks: partial sums -> global slots -> ONE all-reduce for all lanes -> apply (the
 // reference's planar_avg is a global operation, exponential_propagator_proj.f90:146-169)
-int project_lines(nlg_linop *op, const ProjLines &P, int nf, F3 f) {
-    nlg_mesh *m = op->mesh;
-    hipStream_t st = m->ctx->stream;
-    const int64_t nl = P.nlines;
-    const dim3 g((unsigned)((nl + NT / 64 - 1) / (NT / 64)));
-    const int *off = P.off, *idx = P.idx, *gs = P.gslot;
-    const double *cv = P.cv, *sv = P.sv, *iden = P.iden, *glob = P.glob;
-    if (!gs) {
-        launch_nf(nf, k_proj_alpha<1>, k_proj_alpha<2>, k_proj_alpha<3>, g, st, nl, off, idx, P.weight, cv, sv, iden, f);
-    } else {
-        const int64_t cnt = P.nglob * 2 * nf;
-        NLG_HIP(hipMemsetAsync(P.glob, 0, sizeof(double) * (size_t)cnt, st));
-        if (nl > 0) launch_nf(nf, k_proj_sums<1>, k_proj_sums<2>, k_proj_sums<3>, g, st, nl, off, idx, gs, P.weight, cv, sv, CF3{{f.p[0], f.p[1], f.p[2]}}, P.glob);
-        NLG_TRY(allreduce_sum(m->ctx, P.glob, (int)cnt));
-        if (nl > 0) launch_nf(nf, k_proj_apply<1>, k_proj_apply<2>, k_proj_apply<3>, g, st, nl, off, idx, gs, cv, sv, iden, glob, f);
-    }
-    NLG_HIP(hipGetLastError());
-    return 0;
-}
-
-// no-op unless nlg_linop_set_projection has been called: projects level `slot` of the state of lane `lane`
-int project_alpha(nlg_linop *op, int lane, int slot) {
-    if (op->proj_v.nlines == 0) return 0;
-    NLG_TRY(project_lines(op, op->proj_v, op->mesh->dim, f3(at_lane3(op, op->ubuf[slot], lane).p, op->mesh->dim)));
-    // the pressure is part of the state the integrator starts from (lagged pressure of the correction scheme) but not
-    // of the inner product: left unprojected it is a subspace the Arnoldi norm cannot see (observed: a spurious
-    // |mu| = 1.41 for plane Poiseuille flow at alpha = 2 instead of 0.945)
-    const ProjLines &Pp = op->proj_p;
-    if ((Pp.gslot || Pp.nlines > 0) && slot == 0) NLG_TRY(project_lines(op, Pp, 1, F3{{at_lane(op, op->p, lane), nullptr, nullptr}}));
-    return 0;
-}
-
-// wavenumber lanes: project_lines for the lanes 0 .. s-1 of the slab whose bit in `mask` is set, lane l with table l, in one launch
-// (f: lane 0's fields); several ranks: one all-reduce for all lanes
-int project_lines_lanes(nlg_linop *op, const ProjLines &P, int nf, F3 f, int s, unsigned mask) {
+int project_lines(nlg_linop *op, const ProjLines &P, int nf, F3 f, int s, unsigned mask) {
     nlg_mesh *m = op->mesh;
     hipStream_t st = m->ctx->stream;
     const int64_t nl = P.nlines, ld = op->slab_ld, tld = P.tld;
@@ -2556,26 +2423,30 @@ int project_lines_lanes(nlg_linop *op, const ProjLines &P, int nf, F3 f, int s, 
     const int *off = P.off, *idx = P.idx, *gs = P.gslot;
     const double *cv = P.cv, *sv = P.sv, *iden = P.iden, *glob = P.glob;
     if (!gs) {
-        launch_nf(nf, k_proj_alpha_lanes<1>, k_proj_alpha_lanes<2>, k_proj_alpha_lanes<3>, g, st, nl, off, idx, P.weight, cv, sv, tld, iden, f, ld, mask);
+        launch_nf(nf, k_proj_alpha<1>, k_proj_alpha<2>, k_proj_alpha<3>, g, st, nl, off, idx, P.weight, cv, sv, tld, iden, f, ld, mask);
     } else {
         const int64_t cnt = P.nglob * s * 2 * nf;
         NLG_HIP(hipMemsetAsync(P.glob, 0, sizeof(double) * (size_t)cnt, st));
         if (nl > 0)
-            launch_nf(nf, k_proj_sums_lanes<1>, k_proj_sums_lanes<2>, k_proj_sums_lanes<3>, g, st, nl, off, idx, gs, P.weight, cv, sv, tld,
+            launch_nf(nf, k_proj_sums<1>, k_proj_sums<2>, k_proj_sums<3>, g, st, nl, off, idx, gs, P.weight, cv, sv, tld,
                       CF3{{f.p[0], f.p[1], f.p[2]}}, ld, mask, P.glob);
         NLG_TRY(allreduce_sum(m->ctx, P.glob, (int)cnt));
-        if (nl > 0)
-            launch_nf(nf, k_proj_apply_lanes<1>, k_proj_apply_lanes<2>, k_proj_apply_lanes<3>, g, st, nl, off, idx, gs, cv, sv, tld, iden, glob, f, ld, mask);
+        if (nl > 0) launch_nf(nf, k_proj_apply<1>, k_proj_apply<2>, k_proj_apply<3>, g, st, nl, off, idx, gs, cv, sv, tld, iden, glob, f, ld, mask);
     }
     NLG_HIP(hipGetLastError());
     return 0;
 }
 
-// level `slot` of the lanes 0 .. s-1 (those in `mask`), lane l onto wavenumber l: what s calls of project_alpha do, in one launch per mesh
-int project_alpha_lanes(nlg_linop *op, int s, int slot, unsigned mask) {
-    NLG_TRY(project_lines_lanes(op, op->proj_v, op->mesh->dim, f3(op->ubuf[slot], op->mesh->dim), s, mask));
+// no-op unless a projection has been set: projects level `slot` of the state of the lanes 0 .. s-1 (those in `mask`), in one
+// launch per mesh; lane l onto wavenumber l on an operator with wavenumber lanes, every lane onto the one wavenumber otherwise
+int project_alpha(nlg_linop *op, int s, int slot, unsigned mask) {
+    if (op->proj_v.nlines == 0) return 0;
+    NLG_TRY(project_lines(op, op->proj_v, op->mesh->dim, f3(op->ubuf[slot], op->mesh->dim), s, mask));
+    // the pressure is part of the state the integrator starts from (lagged pressure of the correction scheme) but not
+    // of the inner product: left unprojected it is a subspace the Arnoldi norm cannot see (observed: a spurious
+    // |mu| = 1.41 for plane Poiseuille flow at alpha = 2 instead of 0.945)
     const ProjLines &Pp = op->proj_p;
-    if ((Pp.gslot || Pp.nlines > 0) && slot == 0) NLG_TRY(project_lines_lanes(op, Pp, 1, F3{{op->p, nullptr, nullptr}}, s, mask));
+    if ((Pp.gslot || Pp.nlines > 0) && slot == 0) NLG_TRY(project_lines(op, Pp, 1, F3{{op->p, nullptr, nullptr}}, s, mask));
     return 0;
 }
 
@@ -2613,18 +2484,12 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     // coupled (orbit) mode: lane s carries the base flow, from X0 (impulsive start, no history: periodic_orbit.f90:59-92 with
     // solve_baseflow = .true.) through the same time steps and the same launches as the s perturbation lanes before it
     const int nl = op->orbit ? s + 1 : s, lb = op->orbit ? s : -1;
-    // wavenumber lanes: lane v projects onto its own wavenumber, all lanes of a level in one launch (project_alpha_lanes); otherwise
-    // lane by lane onto the one wavenumber of the operator, or not at all (project_alpha)
-    const bool wl = op->proj_lanes > 0;
-    NLG_CHECK(!wl || s <= op->proj_lanes, "exptA block matvec: %d vectors on an operator with %d wavenumber lanes (nlg_linop_set_projection_lanes)", s,
+    NLG_CHECK(op->proj_lanes == 0 || s <= op->proj_lanes, "exptA block matvec: %d vectors on an operator with %d wavenumber lanes (nlg_linop_set_projection_lanes)", s,
               op->proj_lanes);
     const unsigned all = (1u << s) - 1u;
     NLG_TRY(begin_run(op, nl));
-    for (int v = 0; v < s; ++v) {
-        NLG_TRY(load_state(op, v, vin[v], 0));
-        if (!wl) NLG_TRY(project_alpha(op, v, 0));   // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
-    }
-    if (wl) NLG_TRY(project_alpha_lanes(op, s, 0, all));
+    for (int v = 0; v < s; ++v) NLG_TRY(load_state(op, v, vin[v], 0));
+    NLG_TRY(project_alpha(op, s, 0, all));   // exptA_proj_matvec: initial condition, exponential_propagator_proj.f90:51
     if (lb >= 0) NLG_TRY(load_state(op, lb, op->baseflow, 0));
     Lanes L{op, nl, lb};
     L.adjoint = adjoint;
@@ -2634,10 +2499,9 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
             for (int v = 0; v < s; ++v)
                 if (vin[v]->nrst > 0) {
                     NLG_TRY(load_state(op, v, vin[v], istep));   // get_rst, exponential_propagator.f90:129-142
-                    if (!wl) NLG_TRY(project_alpha(op, v, 0));   // (projected operator: replayed states are projected as well, see below)
                     replayed |= 1u << v;
                 }
-            if (wl && replayed) NLG_TRY(project_alpha_lanes(op, s, 0, replayed));
+            if (replayed) NLG_TRY(project_alpha(op, s, 0, replayed));   // (projected operator: replayed states are projected as well, see below)
         }
         return 0;
     }));
@@ -2646,11 +2510,8 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     // (state, history) that the Arnoldi process iterates has a spurious unstable mode -- observed for plane Poiseuille flow
     // at alpha = 2, Re = 7500: a "converged" |mu| = 1.41 in front of the Orr-Sommerfeld pair |mu| = 0.9448; with the
     // consistent projection the leading pair is 0.94454.
-    if (wl)
-        for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha_lanes(op, s, slot, all));
+    for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha(op, s, slot, all));
     for (int v = 0; v < s; ++v) {
-        if (!wl)
-            for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha(op, v, slot));
         // vec_out is intent(out): default-initialised (history cleared, nrst = 0), then filled
         NLG_TRY(nlg_vec_zero(vout[v]));
         NLG_TRY(store_state(op, v, vout[v], 0));
@@ -3031,7 +2892,8 @@ struct DevBuf {   // a device temporary, released on every path out of its scope
 // the lines of one mesh into P (empty on entry; the caller frees it whatever this returns): lines = groups of local dofs with the same
 // label, ordered by label then by index.  The coordinate along the homogeneous direction is on the device (d_x) or on the host (h_x).
 // nalpha wavenumbers: the lines once, one cos / sin table per wavenumber (k_cossin each: table l is the table of a single alpha[l]).
-static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *alpha, int64_t n, const int64_t *lab, const double *d_x, const double *h_x,
+// per_lane: lane l of a block reads table l (tld = n); otherwise nalpha = 1 and every lane reads the one table (tld = 0).
+static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *alpha, bool per_lane, int64_t n, const int64_t *lab, const double *d_x, const double *h_x,
                       ProjLines &P) {
     nlg_ctx *ctx = m->ctx;
     hipStream_t st = ctx->stream;
@@ -3052,8 +2914,7 @@ static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *al
         iden[g] = 1.0 / sum;
     }
     P.nlines = nlines;
-    P.nalpha = nalpha;
-    P.tld = n;
+    P.tld = per_lane ? n : 0;
     NLG_HIP(hipMalloc(&P.off, sizeof(int) * off.size()));
     NLG_HIP(hipMalloc(&P.idx, sizeof(int) * (size_t)n));
     NLG_HIP(hipMalloc(&P.iden, sizeof(double) * (size_t)nlines));
@@ -3068,7 +2929,7 @@ static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *al
         NLG_HIP(hipMemcpy(xs.p, h_x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
         d_x = xs.p;
     }
-    for (int l = 0; l < nalpha; ++l) NLG_LAUNCH(k_cossin, dim3(grid_for(n)), dim3(NT), 0, st, n, d_x, alpha[l], P.cv + l * P.tld, P.sv + l * P.tld);
+    for (int l = 0; l < nalpha; ++l) NLG_LAUNCH(k_cossin, dim3(grid_for(n)), dim3(NT), 0, st, n, d_x, alpha[l], P.cv + l * n, P.sv + l * n);
     NLG_HIP(hipGetLastError());
     NLG_HIP(hipStreamSynchronize(st));
     if (!ctx->distributed()) return 0;
@@ -3107,7 +2968,9 @@ static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *al
     NLG_HIP(hipMalloc(&P.gslot, sizeof(int) * gs.size()));
     NLG_HIP(hipMemcpy(P.gslot, gs.data(), sizeof(int) * gs.size(), hipMemcpyHostToDevice));
     P.nglob = (int64_t)uni.size();
-    NLG_HIP(hipMalloc(&P.glob, sizeof(double) * (size_t)(P.nglob * 2 * 3 * nalpha)));
+    // sized for the largest block that can be projected, kMaxLanes lanes of three fields, whatever tld: a block on a single-alpha
+    // operator shares one all-reduce as the lanes of a sweep do (a few KB either way)
+    NLG_HIP(hipMalloc(&P.glob, sizeof(double) * (size_t)(P.nglob * kMaxLanes * 2 * 3)));
     NLG_HIP(hipMemsetAsync(P.glob, 0, sizeof(double) * (size_t)P.nglob, st));
     const unsigned g1 = (unsigned)((nlines + NT / 64 - 1) / (NT / 64));
     if (nlines > 0)
@@ -3120,35 +2983,9 @@ static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *al
     return 0;
 }
 
-int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
-                             const double *x2) {
-    NLG_CHECK(op && line_label, "nlg_linop_set_projection: NULL argument");
-    NLG_NO_OTD(op, "nlg_linop_set_projection");
-    nlg_mesh *m = op->mesh;
-    NLG_CHECK(idir >= 1 && idir <= m->dim, "nlg_linop_set_projection: idir %d out of range", idir);
-    NLG_CHECK(op->inited, "nlg_linop_set_projection: call init first");
-    NLG_CHECK(!op->orbit, "nlg_linop_set_projection: not available in orbit mode (the base-flow lane is a full state, not one wavenumber; nlg_linop_set_orbit)");
-    NLG_CHECK((line_label2 == nullptr) == (x2 == nullptr), "nlg_linop_set_projection: pressure-mesh labels and coordinates go together");
-    // built beside the operator's and swapped in on success: a call that fails leaves the operator as it was
-    ProjLines pv, pp;
-    pv.weight = m->d_bm1, pp.weight = m->d_bm2;
-    int rc = proj_build(m, "nlg_linop_set_projection", 1, &alpha, m->lvn, line_label, m->d_x[idir - 1], nullptr, pv);
-    if (!rc && line_label2) rc = proj_build(m, "nlg_linop_set_projection", 1, &alpha, m->lpn, line_label2, nullptr, x2, pp);
-    if (!rc) {
-        std::swap(op->proj_v, pv);
-        std::swap(op->proj_p, pp);
-        op->proj_lanes = 0;   // one wavenumber for all lanes again
-    }
-    (void)hipStreamSynchronize(m->ctx->stream);   // nothing in flight may still use what is freed now
-    pv.free();
-    pp.free();
-    return rc;
-}
-
-// Wavenumber lanes: nlg_linop_set_projection with one wavenumber per lane of a block run (include/neklab_gpu.h)
-int nlg_linop_set_projection_lanes(nlg_linop *op, int nalpha, const double *alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
-                                   const double *x2) {
-    const char *who = "nlg_linop_set_projection_lanes";
+// nlg_linop_set_projection / nlg_linop_set_projection_lanes (include/neklab_gpu.h): one table for all lanes of a block, or one per lane
+static int set_projection(nlg_linop *op, const char *who, int nalpha, const double *alpha, bool per_lane, int idir, const int64_t *line_label,
+                          const int64_t *line_label2, const double *x2) {
     NLG_CHECK(op && line_label, "%s: NULL argument", who);
     NLG_CHECK(alpha, "%s: NULL alpha (one wavenumber per lane)", who);
     NLG_CHECK(nalpha >= 1 && nalpha <= kMaxLanes, "%s: %d wavenumber lanes unsupported (1..%d)", who, nalpha, kMaxLanes);
@@ -3157,21 +2994,41 @@ int nlg_linop_set_projection_lanes(nlg_linop *op, int nalpha, const double *alph
     NLG_CHECK(idir >= 1 && idir <= m->dim, "%s: idir %d out of range", who, idir);
     NLG_CHECK(op->inited, "%s: call init first", who);
     NLG_CHECK(!op->orbit, "%s: not available in orbit mode (the base-flow lane is a full state, not one wavenumber; nlg_linop_set_orbit)", who);
-    NLG_CHECK(!op->cfg.ifheat, "%s: not available with cfg.ifheat (the projection does not touch the scalar)", who);
+    NLG_CHECK(!per_lane || !op->cfg.ifheat, "%s: not available with cfg.ifheat (the projection does not touch the scalar)", who);
     NLG_CHECK((line_label2 == nullptr) == (x2 == nullptr), "%s: pressure-mesh labels and coordinates go together", who);
+    // built beside the operator's and swapped in on success: a call that fails leaves the operator as it was
     ProjLines pv, pp;
     pv.weight = m->d_bm1, pp.weight = m->d_bm2;
-    int rc = proj_build(m, who, nalpha, alpha, m->lvn, line_label, m->d_x[idir - 1], nullptr, pv);
-    if (!rc && line_label2) rc = proj_build(m, who, nalpha, alpha, m->lpn, line_label2, nullptr, x2, pp);
+    int rc = proj_build(m, who, nalpha, alpha, per_lane, m->lvn, line_label, m->d_x[idir - 1], nullptr, pv);
+    if (!rc && line_label2) rc = proj_build(m, who, nalpha, alpha, per_lane, m->lpn, line_label2, nullptr, x2, pp);
     if (!rc) {
         std::swap(op->proj_v, pv);
         std::swap(op->proj_p, pp);
-        op->proj_lanes = nalpha;
+        op->proj_lanes = per_lane ? nalpha : 0;
     }
     (void)hipStreamSynchronize(m->ctx->stream);   // nothing in flight may still use what is freed now
     pv.free();
     pp.free();
     return rc;
+}
+
+int nlg_linop_set_projection(nlg_linop *op, double alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
+                             const double *x2) {
+    return set_projection(op, "nlg_linop_set_projection", 1, &alpha, false, idir, line_label, line_label2, x2);
+}
+
+int nlg_linop_set_projection_lanes(nlg_linop *op, int nalpha, const double *alpha, int idir, const int64_t *line_label, const int64_t *line_label2,
+                                   const double *x2) {
+    return set_projection(op, "nlg_linop_set_projection_lanes", nalpha, alpha, true, idir, line_label, line_label2, x2);
+}
+
+// nlg_linop_project / nlg_linop_project_block after their own checks: the vectors through the lanes 0 .. s-1 of the slab
+static int project_vecs(nlg_linop *op, int s, nlg_vec *const *v) {
+    NLG_TRY(slab_ensure(op, s));
+    for (int l = 0; l < s; ++l) NLG_TRY(load_state(op, l, v[l], 0));
+    NLG_TRY(project_alpha(op, s, 0, (1u << s) - 1u));
+    for (int l = 0; l < s; ++l) NLG_TRY(store_state(op, l, v[l], 0));
+    return 0;
 }
 
 int nlg_linop_project_block(nlg_linop *op, int s, nlg_vec *const *v) {
@@ -3183,21 +3040,13 @@ int nlg_linop_project_block(nlg_linop *op, int s, nlg_vec *const *v) {
         NLG_CHECK(v[l] && v[l]->mesh == op->mesh, "nlg_linop_project_block: vector %d NULL or on a different mesh", l);
         for (int u = 0; u < l; ++u) NLG_CHECK(v[l] != v[u], "nlg_linop_project_block: the same vector twice");
     }
-    NLG_TRY(slab_ensure(op, s));
-    for (int l = 0; l < s; ++l) NLG_TRY(load_state(op, l, v[l], 0));
-    NLG_TRY(project_alpha_lanes(op, s, 0, (1u << s) - 1u));
-    for (int l = 0; l < s; ++l) NLG_TRY(store_state(op, l, v[l], 0));
-    return 0;
+    return project_vecs(op, s, v);
 }
 
 int nlg_linop_project(nlg_linop *op, nlg_vec *v) {
     NLG_CHECK(op && v && v->mesh == op->mesh, "nlg_linop_project: bad argument");
     NLG_CHECK(op->proj_v.nlines > 0, "nlg_linop_project: no projection set (nlg_linop_set_projection)");
-    NLG_TRY(slab_ensure(op, 1));
-    NLG_TRY(load_state(op, 0, v, 0));
-    NLG_TRY(op->proj_lanes > 0 ? project_alpha_lanes(op, 1, 0, 1u) : project_alpha(op, 0, 0));   // (wavenumber lanes: alpha[0])
-    NLG_TRY(store_state(op, 0, v, 0));
-    return 0;
+    return project_vecs(op, 1, &v);   // (wavenumber lanes: alpha[0])
 }
 
 int nlg_linop_set_tolerances(nlg_linop *op, double vtol, double ptol) {

@@ -1092,6 +1092,22 @@ int nlg_basis_vec(nlg_basis *b, int i, nlg_vec **out) {
 
 namespace nlg {
 
+// the tail of every reduction here: `rows` rows of `per` partial sums in the reduction workspace -> out[0:rows], all-reduced (ONE
+// collective, whatever the rows stand for), optionally acc += out.  One rank: the accumulation rides in the row reduction, and the
+// collective is counted all the same (nlg_counters)
+static int reduce_rows_all(nlg_ctx *ctx, int rows, int per, double *out, double *acc) {
+    hipStream_t st = ctx->stream;
+    if (ctx->distributed()) {
+        NLG_LAUNCH(k_reduce_rows, dim3(rows), dim3(NT), 0, st, ctx->d_partial, per, out, 0, (double *)nullptr);
+        NLG_TRY(allreduce_sum(ctx, out, rows));
+        if (acc) NLG_LAUNCH(k_vadd, dim3((rows + 255) / 256), dim3(256), 0, st, acc, out, rows);
+    } else {
+        ++g_collectives;
+        NLG_LAUNCH(k_reduce_rows, dim3(rows), dim3(NT), 0, st, ctx->d_partial, per, out, acc ? 1 : 0, acc);
+    }
+    return 0;
+}
+
 // device-resident block projection: d_out[0:k] = V^T B w (allreduced); optionally d_acc += d_out
 int basis_block_dot_dev(const nlg_basis *b, int k, const nlg_vec *w, double *d_out, double *d_acc) {
     nlg_ctx *ctx = b->mesh->ctx;
@@ -1103,16 +1119,7 @@ int basis_block_dot_dev(const nlg_basis *b, int k, const nlg_vec *w, double *d_o
     ProfScope ps(ctx, P_BLOCKDOT);
     NLG_LAUNCH(k_block_dot<KB>, dim3(nblk, v0->ncomp, (k + KB - 1) / KB), dim3(NT), 0, ctx->stream, b->d,
                        b->stride, k, w->d, b->mesh->d_bm1, b->mesh->lvs, nblk, nper, ctx->d_partial);
-    if (ctx->distributed()) {
-        NLG_LAUNCH(k_reduce_rows, dim3(k), dim3(NT), 0, ctx->stream, ctx->d_partial, nper, d_out, 0,
-                           (double *)nullptr);
-        NLG_TRY(allreduce_sum(ctx, d_out, k));
-        if (d_acc) NLG_LAUNCH(k_vadd, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, d_acc, d_out, k);
-    } else {
-        ++g_collectives;   // (counted on one rank too, nlg_counters)
-        NLG_LAUNCH(k_reduce_rows, dim3(k), dim3(NT), 0, ctx->stream, ctx->d_partial, nper, d_out,
-                           d_acc ? 1 : 0, d_acc);
-    }
+    NLG_TRY(reduce_rows_all(ctx, k, nper, d_out, d_acc));
     NLG_HIP(hipGetLastError());
     return 0;
 }
@@ -1185,14 +1192,7 @@ int basis_cgs2_dev(nlg_basis *b, int k, nlg_vec *w) {
                                            Vf + nv, b->stride, kf, (const double *)(h + k0), w->d + nv, np2, 0, np2, 0, -1.0,
                                            (const double *)nullptr);
                 }
-                if (ctx->distributed()) {
-                    NLG_LAUNCH(k_reduce_rows, dim3(kf), dim3(NT), 0, ctx->stream, ctx->d_partial, G, h2 + k0, 0, (double *)nullptr);
-                    NLG_TRY(allreduce_sum(ctx, h2 + k0, kf));
-                    NLG_LAUNCH(k_vadd, dim3((kf + 255) / 256), dim3(256), 0, ctx->stream, h + k0, h2 + k0, kf);
-                } else {
-                    ++g_collectives;
-                    NLG_LAUNCH(k_reduce_rows, dim3(kf), dim3(NT), 0, ctx->stream, ctx->d_partial, G, h2 + k0, 1, h + k0);
-                }
+                NLG_TRY(reduce_rows_all(ctx, kf, G, h2 + k0, h + k0));
                 if (k0 > 0) NLG_TRY(basis_block_dot_dev(b, k0, w, h2, h));
             } else {
                 NLG_TRY(basis_block_axpy_dev(b, k, h, w, -1.0, nullptr, true));
@@ -1209,9 +1209,7 @@ int basis_cgs2_dev(nlg_basis *b, int k, nlg_vec *w) {
     const int nblk = dot_nblk(w);
     NLG_LAUNCH(k_dot_partial, dim3(nblk, w->ncomp), dim3(NT), 0, ctx->stream, w->d, w->d, b->mesh->d_bm1,
                        b->mesh->lvs, nblk, ctx->d_partial);
-    NLG_LAUNCH(k_reduce_rows, dim3(1), dim3(NT), 0, ctx->stream, ctx->d_partial, nblk * w->ncomp, h + k, 0,
-                       (double *)nullptr);
-    NLG_TRY(allreduce_sum(ctx, h + k, 1));
+    NLG_TRY(reduce_rows_all(ctx, 1, nblk * w->ncomp, h + k, nullptr));
     const int64_t n2 = w->main_len * (1 + w->nrst) / 2;
     NLG_LAUNCH(k_scal_dev, dim3(grid_for(n2)), dim3(NT), 0, ctx->stream, reinterpret_cast<double2 *>(w->d),
                        h + k, 0, n2);
@@ -1251,23 +1249,11 @@ int basis_cgs2_batch_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w) {
     const int nblk = dot_nblk(v0), nper = nblk * v0->ncomp;
     const int64_t n2 = v0->main_len / 2;
     NLG_TRY(reduce_ws_reserve(ctx, s * std::max(k, 1)));
-    // rows of the reduction workspace -> out (all-reduced: ONE collective for all lanes), optionally acc += out
-    auto reduce = [&](int rows, int per, double *out, double *acc) -> int {
-        if (ctx->distributed()) {
-            NLG_LAUNCH(k_reduce_rows, dim3(rows), dim3(NT), 0, st, ctx->d_partial, per, out, 0, (double *)nullptr);
-            NLG_TRY(allreduce_sum(ctx, out, rows));
-            if (acc) NLG_LAUNCH(k_vadd, dim3((rows + 255) / 256), dim3(256), 0, st, acc, out, rows);
-        } else {
-            ++g_collectives;
-            NLG_LAUNCH(k_reduce_rows, dim3(rows), dim3(NT), 0, st, ctx->d_partial, per, out, acc ? 1 : 0, acc);
-        }
-        return 0;
-    };
     auto dot = [&](double *out, double *acc) -> int {
         ProfScope ps(ctx, P_BLOCKDOT);
         NLG_LAUNCH(k_lane_block_dot<KB>, dim3(nblk, v0->ncomp * s, (k + KB - 1) / KB), dim3(NT), 0, st, P, b0->stride, k, v0->ncomp,
                    (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
-        return reduce(s * k, nper, out, acc);
+        return reduce_rows_all(ctx, s * k, nper, out, acc);   // (one collective for all lanes)
     };
     auto axpy = [&](const double *h, const double *hh, bool main_only) -> int {
         ProfScope ps(ctx, P_BLOCKAXPY);
@@ -1282,7 +1268,7 @@ int basis_cgs2_batch_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w) {
         NLG_TRY(axpy(H2, H1, false));
     }
     NLG_LAUNCH(k_lane_dot_partial, dim3(nblk, v0->ncomp, s), dim3(NT), 0, st, P, (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
-    NLG_TRY(reduce(s, nper, Q, nullptr));
+    NLG_TRY(reduce_rows_all(ctx, s, nper, Q, nullptr));
     NLG_LAUNCH(k_lane_scal_dev, dim3(grid_for(n2 * (1 + nrst)), s), dim3(NT), 0, st, P, (const double *)Q, n2);
     NLG_HIP(hipGetLastError());
     return 0;
@@ -1399,15 +1385,7 @@ int nlg_basis_block_cgs2(nlg_basis *b, int k, int s, double *coef) {
         else if (s == 3) BD(3);
         else BD(4);
 #undef BD
-        if (ctx->distributed()) {
-            NLG_LAUNCH(k_reduce_rows, dim3(kk * s), dim3(NT), 0, st, ctx->d_partial, nper, out, 0, (double *)nullptr);
-            NLG_TRY(allreduce_sum(ctx, out, kk * s));
-            if (acc) NLG_LAUNCH(k_vadd, dim3((kk * s + 255) / 256), dim3(256), 0, st, acc, out, kk * s);
-        } else {
-            ++g_collectives;
-            NLG_LAUNCH(k_reduce_rows, dim3(kk * s), dim3(NT), 0, st, ctx->d_partial, nper, out, acc ? 1 : 0, acc);
-        }
-        return 0;
+        return nlg::reduce_rows_all(ctx, kk * s, nper, out, acc);
     };
     auto axpy = [&](const double *h, const double *hh, int64_t n, int64_t blk2) -> int {
         ProfScope ps(ctx, P_BLOCKAXPY);

@@ -1,6 +1,6 @@
 """One rank of tests/test_gpu_sweep_multirank.py: wavenumber lanes (nlg_linop_set_projection_lanes) with the homogeneous direction
 ACROSS the rank boundaries, as run_proj of tests/multirank_worker.py -- two lanes with different wavenumbers, projected together
-(nlg_linop_project_block) and advanced together (one block matvec); the partial line sums of both lanes travel in ONE all-reduce.
+(nlg_linop_project_block) and advanced together (one block matvec); the partial line sums of both lanes travel in ONE all-reduce.  Then the same block on the same handle after nlg_linop_set_projection: one wavenumber, one table, two lanes.
 usage: sweep_multirank_worker.py rank world segment outdir mult"""
 import os
 import sys
@@ -57,6 +57,15 @@ def run(rank, world, segment, outdir, mult):
             fields["v%d_%d" % (l, i)] = v[l].get_field(i)
         fields["outp%d" % l] = out[l].get_field(host.PR)
         fields["pvp%d" % l] = pv[l].get_field(host.PR)
+    # one wavenumber for all lanes on the same handle: the block still shares ONE all-reduce, every lane reading the one table
+    host.check(gm.lib.nlg_linop_set_projection(A.h, ALPHAS[1], 3, lab.ctypes.data_as(_lib.c_int64_p), lab2.ctypes.data_as(_lib.c_int64_p),
+                                                _lib.dptr(z2)))
+    one = [host.nek_dvector(gm) for _ in range(s)]
+    A.matvec_block(v, one)
+    for l in range(s):
+        for i in range(3):
+            fields["one%d_%d" % (l, i)] = one[l].get_field(i)
+        fields["onep%d" % l] = one[l].get_field(host.PR)
     np.savez(os.path.join(outdir, "sweep_w%d_r%d.npz" % (world, rank)), **fields)
     ctx.sync()
 

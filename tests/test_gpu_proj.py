@@ -130,3 +130,57 @@ def test_projected_matvec_block_equals_single_matvecs(gpu_ctx, dim, nel, s):
             for i in range(dim):
                 assert np.max(np.abs(blk[v].get_field(i, r) - single[v].get_field(i, r))) < 1e-11 * sc, (v, r, i)
             assert np.max(np.abs(blk[v].get_field(host.PR, r) - single[v].get_field(host.PR, r))) < 1e-9 * max(sc, np.abs(single[v].get_field(host.PR, r)).max())
+
+
+def test_single_alpha_block_takes_the_lane_path(gpu_ctx):
+    """A block of s = 3 vectors on a single-alpha operator is projected as the lanes of a sweep are: all lanes in one launch per mesh and
+    one all-reduce, every lane reading the one table.  An exptA_sweep_linop whose three wavenumbers are that alpha runs the same kernels
+    on equal tables: the same launches and collectives for the block, the same iterations per lane, and the same outputs -- to the bars
+    of test_projected_matvec_block_equals_single_matvecs, and in fact bit for bit (observed; the code is deterministic)."""
+    import ctypes as C
+    dim, s = 2, 3
+    hm, sem, gm = channel(gpu_ctx, dim, (4, 3), 6)
+    gb = host.nek_dvector(gm)
+    gb.set_field(0, 1.0 - sem.X[1] ** 2)
+    kw = dict(idir=1, re=200.0, torder=3, vtol=1e-13, ptol=1e-13, maxit_v=400, maxit_p=4000)
+    ops = {"proj": host.exptA_proj_linop(0.1, gb, 2.0, **kw), "sweep": host.exptA_sweep_linop(0.1, gb, (2.0, 2.0, 2.0), **kw)}
+    out, counts, iters = {}, {}, {}
+    for name, A in ops.items():
+        A.init()
+        vin = []
+        for v in range(s):
+            x = host.nek_dvector(gm)
+            x.rand(True, seed=20 + v)
+            x.scal(10.0 ** (-v))
+            vin.append(x)
+        y = host.nek_dvector(gm)
+        A.matvec(vin[1], y)                      # lane 1 carries a restart history
+        vin[1] = y
+        out[name] = [host.nek_dvector(gm) for _ in range(s)]
+        n0, n1, c0, c1 = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        host.check(gpu_ctx.lib.nlg_counters(C.byref(n0), C.byref(c0)))
+        A.matvec_block(vin, out[name])
+        host.check(gpu_ctx.lib.nlg_counters(C.byref(n1), C.byref(c1)))
+        counts[name] = (n1.value - n0.value, c1.value - c0.value)
+        iters[name] = [A.lane_iters(v) for v in range(s)]
+    print("block of %d: (launches, collectives) %s, iterations per lane %s" % (s, counts, iters["proj"]))
+    assert counts["proj"] == counts["sweep"]
+    assert iters["proj"] == iters["sweep"]
+    assert all(it["v_iters"] > 0 and it["p_iters"] > 0 for it in iters["proj"])
+    bitwise = True
+    for v in range(s):
+        got, want = out["proj"][v], out["sweep"][v]
+        assert got.nrst == want.nrst == 2
+        sc = max(np.abs(want.get_field(i)).max() for i in range(dim))
+        assert sc > 0.0
+        for r in range(3):
+            for i in range(dim):
+                assert np.max(np.abs(got.get_field(i, r) - want.get_field(i, r))) < 1e-11 * sc, (v, r, i)
+                bitwise = bitwise and np.array_equal(got.get_field(i, r), want.get_field(i, r))
+            pw = want.get_field(host.PR, r)
+            assert np.max(np.abs(got.get_field(host.PR, r) - pw)) < 1e-9 * max(sc, np.abs(pw).max()), (v, r)
+            bitwise = bitwise and np.array_equal(got.get_field(host.PR, r), pw)
+    print("outputs equal bit for bit:", bitwise)
+    assert bitwise
+    for A in ops.values():
+        A.close()

@@ -101,6 +101,29 @@ def test_proj_block_equals_the_single_alpha_projection_bit_for_bit(case, s):
         assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("case", [2], indirect=True)
+def test_set_projection_after_set_alphas_takes_effect(case):
+    """Both setters feed one projection path: nlg_linop_set_projection on a handle that had wavenumber lanes replaces the tables (alpha = 1
+    is not alphas[0] = 3) and the lanes -- proj is the single-alpha operator's bit for bit, and proj_block has nothing to work on."""
+    c = case
+    S = c.sweep
+    S.set_alphas(ALPHAS[:2])
+    lab = host.line_labels(c.gm, 1)
+    lab2, x2 = host.line_labels_pressure(c.gm, 1)
+    i64 = host._lib.c_int64_p
+    host.check(c.gm.lib.nlg_linop_set_projection(S.h, 1.0, 1, lab.ctypes.data_as(i64), lab2.ctypes.data_as(i64), host.dptr(x2)))
+    x = c.vec(45)
+    y = x.copy()
+    S.proj(x)
+    c.single(1.0).proj(y)
+    for a, b in zip(fields_of(c, x), fields_of(c, y)):
+        assert np.array_equal(a, b)
+    assert np.max(np.abs(x.get_field(0))) > 0.0 and np.max(np.abs(x.get_field(host.PR))) > 0.0
+    with pytest.raises(host.NlgError, match="nlg_linop_project_block: the operator has no wavenumber lanes"):
+        S.proj_block([c.vec(46), c.vec(47)])
+    S.set_alphas(ALPHAS)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. the block matvec per lane
 # ---------------------------------------------------------------------------------------------------------------------
