@@ -223,10 +223,10 @@ int nlg_basis_cgs2(const nlg_basis *b, int k, nlg_vec *w, double *h, double *bet
  * beta + l) does (restart history and pressure as in the consistent history update, a zero norm leaves a zero vector), with
  * the lane in the grid of every kernel: one launch per stage and one all-reduce per reduction (k*s, then s values) for all
  * lanes.  The bases have equal shape (mesh, nscal, lorder, nvec) and are distinct; no w[l] may be one of the columns 0 .. k-1
- * of any of them; the w[l] may differ in their number of valid history levels.  One variant for every k (the fused
- * subtraction-and-projection sweep of the single-lane path at k >= 24 has no lane form), so the coefficients agree with the
- * single-lane ones to rounding, not bit for bit.  With nlg_set_axpby_rst_consistent(0) the lanes go one by one through the
- * path of nlg_basis_cgs2. */
+ * of any of them; the w[l] may differ in their number of valid history levels.  nlg_basis_cgs2 is this call with one lane, so
+ * s = 1 equals it bit for bit at every k: one lane takes the fused subtraction-and-projection sweep from k = 24.  Several
+ * lanes take the separate kernels at every k: below k = 24 every lane equals its single call bit for bit, from there on to
+ * rounding.  nlg_set_axpby_rst_consistent(0) holds for the lanes as for a single vector (same kernels). */
 int nlg_basis_cgs2_batch(int s, nlg_basis *const *b, int k, nlg_vec *const *w, double *h, int ldh, double *beta);
 /* Block variant for s <= 4 NEW vectors held in the consecutive columns k .. k+s-1 (block Arnoldi, BASELINE.json config 5;
  * the reference advances several perturbations together through Nek5000's lpert / npert, src/neklab_nek_setup.f90:39-247,

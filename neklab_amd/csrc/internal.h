@@ -323,8 +323,16 @@ struct nlg_basis {
     int64_t stride = 0;        // doubles between consecutive vectors
     double *d = nullptr;
     std::vector<nlg_vec *> views;
-    double *d_h = nullptr;     // [2 * nvec + 8] device coefficients
-    double *d_hb = nullptr;    // block orthogonalisation: [2 * nvec * 4 + 64] coefficients of up to 4 vectors (lazy)
+    // The one coefficient workspace of every orthogonalisation on this basis, for up to kMaxLanes vectors at once (lanes of a batch,
+    // columns of a block): [ first-pass coefficients, s * k <= 4 nvec, |w_l|^2 right behind them | second pass | Gram | T ].  One
+    // vector: coefficients at 0 and |w|^2 at k, so that a step's read-back is one copy.
+    double *d_h = nullptr;
+    static size_t h_len(int nvec) { return (size_t)8 * nvec + 40; }
+    double *h1() const { return d_h; }                                // [s][k] (batch) or [k][s] (block)
+    double *hnorm(int s, int k) const { return d_h + (size_t)s * k; } // [s] squared norms before scaling
+    double *h2() const { return d_h + (size_t)4 * nvec + 8; }         // second-pass coefficients, laid out as the first
+    double *gram() const { return d_h + (size_t)8 * nvec + 8; }       // [4][4] Gram matrix of the new columns of a block
+    double *tmat() const { return gram() + 16; }                      // [4][4] its inverse Cholesky factor
     int last_block_rank = 0;   // columns kept by the last nlg_basis_block_cgs2 (< s: dependent columns were deflated)
 };
 
@@ -369,13 +377,10 @@ int shm_allgather_i64(nlg_ctx *ctx, const int64_t *d_in, int64_t *d_out, int64_t
 int shm_exchange(nlg_ctx *ctx, const nlg_halo &h, int nf, hipStream_t st);   // st: the stream the staging copies are ordered on
 void shm_close(nlg_ctx *ctx);
 
-int basis_block_dot_dev(const nlg_basis *b, int k, const nlg_vec *w, double *d_out, double *d_acc);
-int basis_block_axpy_dev(const nlg_basis *b, int k, const double *d_h, nlg_vec *w, double sign, const double *d_hh = nullptr,
-                         bool main_only = false);
-int basis_cgs2_dev(nlg_basis *b, int k, nlg_vec *w);
-// CGS2 + norm + scale of s vectors, w[l] against columns 0 .. k-1 of its own basis b[l], one launch per stage for all lanes
-// (nlg_basis_cgs2_batch).  Results on device in b[0]->d_hb: lane l's k coefficients at [l * k], its |w|^2 before scaling at [s * k + l].
-int basis_cgs2_batch_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w);
+// CGS2 + norm + scale of s vectors, w[l] against columns 0 .. k-1 of its own basis b[l], one launch per stage for all lanes; one lane
+// takes the fused subtract-and-project sweep from k = 24 (nlg_basis_cgs2, nlg_basis_cgs2_batch).  ONE read-back from b[0]'s
+// workspace: lane l's k coefficients to h[l * hstride + 0:k], its norm before scaling to beta[l * bstride]
+int basis_cgs2_host(int s, nlg_basis *const *b, int k, nlg_vec *const *w, double *h, int64_t hstride, double *beta, int64_t bstride);
 
 // ---- lns.hip ----
 int linop_proj_lanes(const nlg_linop *op);   // wavenumber lanes of the operator (nlg_linop_set_projection_lanes), 0 = none

@@ -144,6 +144,17 @@ void write_log(const char *path, int nmv, const Ritz &r, double tol) {
     fclose(f);
 }
 
+// One Arnoldi step of s lanes in lock-step, the arguments checked by the caller: lane l's column k through the (block) propagator
+// into its column k + 1, CGS2 of every lane against its OWN k + 1 columns, one read-back into column k of every lane's H.
+int arnoldi_lanes(nlg_linop *op, int s, nlg_basis *const *basis, int k, double *H, int ldh, int64_t hstride, int transpose) {
+    const nlg_vec *vi[kMaxLanes];
+    nlg_vec *vo[kMaxLanes];
+    for (int l = 0; l < s; ++l) vi[l] = basis[l]->views[k], vo[l] = basis[l]->views[k + 1];
+    NLG_TRY(nlg_linop_matvec_block(op, s, vi, vo, transpose));
+    double *col = H + (size_t)k * ldh;
+    return basis_cgs2_host(s, basis, k + 1, vo, col, hstride, col + k + 1, hstride);
+}
+
 }  // namespace
 
 extern "C" {
@@ -152,16 +163,7 @@ int nlg_arnoldi_step(nlg_linop *op, nlg_basis *basis, int k, double *H, int ldh,
     NLG_CHECK(op && basis && H, "nlg_arnoldi_step: NULL argument");
     NLG_CHECK(k >= 0 && k + 1 < basis->nvec, "nlg_arnoldi_step: k=%d needs basis columns %d, %d (nvec=%d)", k, k, k + 1, basis->nvec);
     NLG_CHECK(ldh >= k + 2, "nlg_arnoldi_step: ldh=%d too small for k=%d", ldh, k);
-    nlg_vec *vk = basis->views[k], *w = basis->views[k + 1];
-    NLG_TRY(transpose ? nlg_linop_rmatvec(op, vk, w) : nlg_linop_matvec(op, vk, w));
-    NLG_TRY(basis_cgs2_dev(basis, k + 1, w));
-    std::vector<double> tmp(k + 2);
-    hipStream_t st = basis->mesh->ctx->stream;
-    NLG_HIP(hipMemcpyAsync(tmp.data(), basis->d_h, sizeof(double) * (k + 2), hipMemcpyDeviceToHost, st));
-    NLG_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i <= k; ++i) H[(size_t)k * ldh + i] = tmp[i];
-    H[(size_t)k * ldh + k + 1] = std::sqrt(tmp[k + 1]);
-    return 0;
+    return arnoldi_lanes(op, 1, &basis, k, H, ldh, 0, transpose);
 }
 
 // One Arnoldi step of the bordered Jacobian of a periodic orbit on extended vectors (field, T): column k of the basis with period
@@ -236,25 +238,10 @@ int nlg_sweep_arnoldi_step(nlg_linop *op, int s, nlg_basis *const *basis, int k,
         for (int u = 0; u < l; ++u) NLG_CHECK(basis[l] != basis[u], "nlg_sweep_arnoldi_step: the same basis in two lanes");
     }
     NLG_CHECK(ldh >= k + 2, "nlg_sweep_arnoldi_step: ldh=%d too small for k=%d", ldh, k);
-    const nlg_vec *vi[kMaxLanes];
-    nlg_vec *vo[kMaxLanes];
-    for (int l = 0; l < s; ++l) vi[l] = basis[l]->views[k], vo[l] = basis[l]->views[k + 1];
-    const int kk = k + 1;
     for (int l = 1; l < s; ++l)
         NLG_CHECK(basis[l]->mesh == basis[0]->mesh && basis[l]->nscal == basis[0]->nscal && basis[l]->lorder == basis[0]->lorder && basis[l]->nvec == basis[0]->nvec,
                   "nlg_sweep_arnoldi_step: the bases differ in shape (lane %d)", l);
-    NLG_TRY(nlg_linop_matvec_block(op, s, vi, vo, transpose));
-    NLG_TRY(basis_cgs2_batch_dev(s, basis, kk, vo));
-    std::vector<double> tmp((size_t)s * kk + s);   // one copy for all lanes
-    hipStream_t st = basis[0]->mesh->ctx->stream;
-    NLG_HIP(hipMemcpyAsync(tmp.data(), basis[0]->d_hb, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st));
-    NLG_HIP(hipStreamSynchronize(st));
-    for (int l = 0; l < s; ++l) {
-        double *col = H + (size_t)l * hstride + (size_t)k * ldh;
-        for (int i = 0; i < kk; ++i) col[i] = tmp[(size_t)l * kk + i];
-        col[kk] = std::sqrt(tmp[(size_t)s * kk + l]);
-    }
-    return 0;
+    return arnoldi_lanes(op, s, basis, k, H, ldh, hstride, transpose);
 }
 
 int nlg_eigs_opts_default(nlg_eigs_opts *o) {

@@ -58,11 +58,28 @@ __global__ __launch_bounds__(NT) void k_scal(double2 *x, double a, int64_t n2) {
     }
 }
 
-// x *= f(s[0]) with the scalar on device: mode 0: 1/sqrt(s), mode 1: 1/s
-__global__ __launch_bounds__(NT) void k_scal_dev(double2 *x, const double *s, int mode, int64_t n2) {
-    const double sv = s[0];
-    const double a = (mode == 0) ? (sv > 0.0 ? 1.0 / sqrt(sv) : 0.0) : 1.0 / sv;
-    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2; i += (int64_t)gridDim.x * NT) {
+// ---- Lanes.  The orthogonalisation kernels below (k_scal_dev, k_dot_partial, k_block_dot, k_block_axpy) carry a lane in the grid:
+// lane l is one vector with its OWN basis (the wavenumbers of a sweep are s separate eigenproblems advanced in lock-step,
+// nlg_basis_cgs2_batch), and a single vector is the launch with one lane.  The base pointers of lane l come by value, its
+// coefficients lie l * k behind lane 0's, its partial sums in the rows l * k .. l * k + k - 1 of the reduction workspace.
+struct LaneVW {
+    const double *V[kMaxLanes];   // column 0 of lane l's basis
+    double *w[kMaxLanes];
+    int nrst[kMaxLanes];          // valid history blocks of w[l]
+};
+struct LaneAB {
+    const double *a[kMaxLanes], *b[kMaxLanes];
+};
+
+// blockIdx.y = lane: w_l *= 1 / sqrt(q[l]) over the main block (n2 double2 entries) and the valid history blocks, the scalar on
+// device (0 where q[l] is not positive)
+__global__ __launch_bounds__(NT) void k_scal_dev(LaneVW P, const double *q, int64_t n2) {
+    const int l = blockIdx.y;
+    const double sv = q[l];
+    const double a = sv > 0.0 ? 1.0 / sqrt(sv) : 0.0;
+    const int64_t n2all = n2 * (1 + P.nrst[l]);
+    double2 *x = reinterpret_cast<double2 *>(P.w[l]);
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
         double2 v = x[i];
         v.x = __dmul_rn(v.x, a);
         v.y = __dmul_rn(v.y, a);
@@ -98,16 +115,15 @@ __global__ __launch_bounds__(NT) void k_axpby(double2 *y, const double2 *x, doub
 }
 
 // first stage of glsc3-type sums over the ncomp inner-product fields:
-// partial[c*nblk + blk] = sum_{i in chunk} a_c[i] b_c[i] bm1[i]
-__global__ __launch_bounds__(NT) void k_dot_partial(const double *a, const double *b, const double *bm1, int64_t lvs,
-                                                    int nblk, double *partial) {
+// partial[l*nper + c*nblk + blk] = sum_{i in chunk} a_c[i] b_c[i] bm1[i]  of lane l = blockIdx.z (nper = ncomp*nblk)
+__global__ __launch_bounds__(NT) void k_dot_partial(LaneAB P, const double *bm1, int64_t lvs, int nblk, int nper, double *partial) {
     __shared__ double sm[4];
-    const int c = blockIdx.y;
+    const int c = blockIdx.y, l = blockIdx.z;
     const int64_t n2 = lvs >> 1;
     const int64_t per = (n2 + nblk - 1) / nblk;
     const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
-    const double2 *a2 = reinterpret_cast<const double2 *>(a + c * lvs);
-    const double2 *b2 = reinterpret_cast<const double2 *>(b + c * lvs);
+    const double2 *a2 = reinterpret_cast<const double2 *>(P.a[l] + c * lvs);
+    const double2 *b2 = reinterpret_cast<const double2 *>(P.b[l] + c * lvs);
     const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
     double acc = 0.0;
     for (int64_t i = beg + threadIdx.x; i < end; i += NT) {
@@ -115,7 +131,7 @@ __global__ __launch_bounds__(NT) void k_dot_partial(const double *a, const doubl
         acc += av.x * bv.x * mv.x + av.y * bv.y * mv.y;
     }
     const double s = block_sum(acc, sm);
-    if (threadIdx.x == 0) partial[c * nblk + blockIdx.x] = s;
+    if (threadIdx.x == 0) partial[(int64_t)l * nper + c * nblk + blockIdx.x] = s;
 }
 
 // Border of the periodic-orbit Jacobian in one pass (nlg_upo_border): over the main block of the vectors, field c = blockIdx.y of
@@ -169,12 +185,14 @@ __global__ __launch_bounds__(NT) void k_reduce_rows(const double *partial, int n
 }
 
 // h_j = V_j^T (bm1 o w) for a tile of KB basis vectors; V is read exactly once.
+// blockIdx.y = lane * ncomp + field, blockIdx.z = tile; partial row (lane * k + j)
 template <int KB>
-__global__ __launch_bounds__(NT) void k_block_dot(const double *V, int64_t vstride, int k, const double *w,
-                                                  const double *bm1, int64_t lvs, int nblk, int nper,
-                                                  double *partial) {
+__global__ __launch_bounds__(NT) void k_block_dot(LaneVW P, int64_t vstride, int k, int ncomp, const double *bm1, int64_t lvs, int nblk,
+                                                  int nper, double *partial) {
     __shared__ double sm[4 * KB];
-    const int c = blockIdx.y;
+    const int l = blockIdx.y / ncomp, c = blockIdx.y - l * ncomp;
+    const double *V = P.V[l];
+    const double *w = P.w[l];
     const int j0 = blockIdx.z * KB;
     const int kc = (k - j0 < KB) ? (k - j0) : KB;
     const int64_t n2 = lvs >> 1;
@@ -210,7 +228,7 @@ __global__ __launch_bounds__(NT) void k_block_dot(const double *V, int64_t vstri
     if (threadIdx.x < kc) {
         const int j = threadIdx.x;
         const double s = sm[j] + sm[KB + j] + sm[2 * KB + j] + sm[3 * KB + j];
-        partial[(int64_t)(j0 + j) * nper + c * nblk + blockIdx.x] = s;
+        partial[((int64_t)l * k + j0 + j) * nper + c * nblk + blockIdx.x] = s;
     }
 }
 
@@ -315,27 +333,34 @@ __global__ __launch_bounds__(NT) void k_block_axpy_dot2(const double *__restrict
     }
 }
 
-// w -= sum_j h_j V_j on the main block; history slots of w receive the same correction
-// (reference axpby quirk) or the combination of the basis history (consistent mode).
-// `hh` (may be null): a second coefficient set used for the entries at or beyond blk2 (the history blocks of a sweep
-// that covers main + history in one range): CGS2 applies the second-pass coefficients to the main block and the SUM
-// of both passes to the history, which no inner product ever reads -> the history is swept once, not twice.
-__global__ __launch_bounds__(NT) void k_block_axpy(const double *V, int64_t vstride, int k, const double *h, double *w,
-                                                   int64_t n2, int nrst, int64_t blk2, int consistent, double sign,
-                                                   const double *hh) {
+// blockIdx.y = lane.  w_l += sign * V_l h_l on the main block (n2 double2 entries); the nrst[l] valid history blocks behind it
+// follow `hist`: left alone, swept with the main block as one contiguous range (consistent mode: every entry receives the same
+// linear combination of the basis at its own place), or given the main block's correction (the reference's axpby quirk).
+// `hh` (may be null; HIST_SWEEP): a second coefficient set for the entries at or beyond n2: CGS2 applies the second-pass
+// coefficients to the main block and the SUM of both passes to the history, which no inner product ever reads -> the history is
+// swept once, not twice.
+enum { HIST_NONE = 0, HIST_SWEEP = 1, HIST_MAIN = 2 };
+__global__ __launch_bounds__(NT) void k_block_axpy(LaneVW P, int64_t vstride, int k, const double *h, const double *hh, int64_t n2,
+                                                   int hist, double sign) {
     extern __shared__ double sh0[];
     double *sh1 = sh0 + k;
+    const int l = blockIdx.y;
+    h += (int64_t)l * k;
+    if (hh) hh += (int64_t)l * k;
     for (int j = threadIdx.x; j < k; j += NT) {
         sh0[j] = h[j];
         sh1[j] = hh ? hh[j] : h[j];
     }
     __syncthreads();
-    double2 *w2 = reinterpret_cast<double2 *>(w);
-    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2; i += (int64_t)gridDim.x * NT) {
-        const double *sh = (hh && i >= blk2) ? sh1 : sh0;
+    const int64_t n2all = hist == HIST_SWEEP ? n2 * (1 + P.nrst[l]) : n2;
+    const int ncopy = hist == HIST_MAIN ? P.nrst[l] : 0;
+    double2 *w2 = reinterpret_cast<double2 *>(P.w[l]);
+    const double2 *V2 = reinterpret_cast<const double2 *>(P.V[l]);
+    const int64_t vs2 = vstride >> 1;
+    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
+        const double *sh = (hh && i >= n2) ? sh1 : sh0;
         double s0 = 0.0, s1 = 0.0;
-        const double2 *v = reinterpret_cast<const double2 *>(V) + i;
-        const int64_t vs2 = vstride >> 1;
+        const double2 *v = V2 + i;
         int j = 0;
         for (; j + 8 <= k; j += 8) {
             double2 t[8];
@@ -356,20 +381,11 @@ __global__ __launch_bounds__(NT) void k_block_axpy(const double *V, int64_t vstr
         wv.x += sign * s0;
         wv.y += sign * s1;
         w2[i] = wv;
-        for (int r = 1; r <= nrst; ++r) {
-            double c0 = s0, c1 = s1;
-            if (consistent) {
-                c0 = c1 = 0.0;
-                for (int jj = 0; jj < k; ++jj) {
-                    const double2 t = v[(int64_t)jj * vs2 + r * blk2];
-                    c0 += sh[jj] * t.x;
-                    c1 += sh[jj] * t.y;
-                }
-            }
-            double2 rv = w2[i + r * blk2];
-            rv.x += sign * c0;
-            rv.y += sign * c1;
-            w2[i + r * blk2] = rv;
+        for (int r = 1; r <= ncopy; ++r) {
+            double2 rv = w2[i + r * n2];
+            rv.x += sign * s0;
+            rv.y += sign * s1;
+            w2[i + r * n2] = rv;
         }
     }
 }
@@ -513,141 +529,6 @@ __global__ __launch_bounds__(NT) void k_block_rmul(double *W, int64_t wstride, c
     }
 }
 
-// ---- lane-batched orthogonalisation (nlg_basis_cgs2_batch): s vectors, EACH against its own basis (the wavenumbers of a sweep are s
-// separate eigenproblems advanced in lock-step).  The kernels are k_block_dot, k_block_axpy, k_dot_partial and k_scal_dev with the lane
-// in the grid: the base pointers of lane l's basis and vector come by value (LaneVW), the coefficients of lane l lie l * k behind lane
-// 0's, its partial sums in the rows l * k .. l * k + k - 1 of the reduction workspace.  One launch per stage for all lanes.
-struct LaneVW {
-    const double *V[kMaxLanes];   // column 0 of lane l's basis
-    double *w[kMaxLanes];
-    int nrst[kMaxLanes];          // valid history blocks of w[l]
-};
-
-// blockIdx.y = lane * ncomp + field, blockIdx.z = tile of KB basis vectors; partial row (lane * k + j)
-template <int KB>
-__global__ __launch_bounds__(NT) void k_lane_block_dot(LaneVW P, int64_t vstride, int k, int ncomp, const double *bm1, int64_t lvs, int nblk,
-                                                       int nper, double *partial) {
-    __shared__ double sm[4 * KB];
-    const int l = blockIdx.y / ncomp, c = blockIdx.y - l * ncomp;
-    const double *V = P.V[l];
-    const double *w = P.w[l];
-    const int j0 = blockIdx.z * KB;
-    const int kc = (k - j0 < KB) ? (k - j0) : KB;
-    const int64_t n2 = lvs >> 1;
-    const int64_t per = (n2 + nblk - 1) / nblk;
-    const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
-    const double2 *w2 = reinterpret_cast<const double2 *>(w + c * lvs);
-    const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
-    const double2 *v2[KB];
-#pragma unroll
-    for (int j = 0; j < KB; ++j) {
-        const int jj = (j < kc) ? j : 0;
-        v2[j] = reinterpret_cast<const double2 *>(V + (int64_t)(j0 + jj) * vstride + c * lvs);
-    }
-    double acc[KB];
-#pragma unroll
-    for (int j = 0; j < KB; ++j) acc[j] = 0.0;
-    for (int64_t i = beg + threadIdx.x; i < end; i += NT) {
-        const double2 wv = w2[i], mv = m2[i];
-        const double x0 = wv.x * mv.x, x1 = wv.y * mv.y;
-        double2 vv[KB];
-#pragma unroll
-        for (int j = 0; j < KB; ++j) vv[j] = v2[j][i];
-#pragma unroll
-        for (int j = 0; j < KB; ++j) acc[j] += vv[j].x * x0 + vv[j].y * x1;
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < KB; ++j) {
-        const double s = wave_sum(acc[j]);
-        if (lane == 0) sm[wid * KB + j] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kc) {
-        const int j = threadIdx.x;
-        const double s = sm[j] + sm[KB + j] + sm[2 * KB + j] + sm[3 * KB + j];
-        partial[((int64_t)l * k + j0 + j) * nper + c * nblk + blockIdx.x] = s;
-    }
-}
-
-// blockIdx.y = lane.  w_l += sign * V_l h_l over the main block (n2 double2 entries) and, unless main_only, over the nrst[l] valid
-// history blocks behind it, which take the coefficients hh_l where hh is given (see k_block_axpy: consistent history update)
-__global__ __launch_bounds__(NT) void k_lane_block_axpy(LaneVW P, int64_t vstride, int k, const double *h, const double *hh, int64_t n2,
-                                                        int main_only, double sign) {
-    extern __shared__ double sh0[];
-    double *sh1 = sh0 + k;
-    const int l = blockIdx.y;
-    h += (int64_t)l * k;
-    if (hh) hh += (int64_t)l * k;
-    for (int j = threadIdx.x; j < k; j += NT) {
-        sh0[j] = h[j];
-        sh1[j] = hh ? hh[j] : h[j];
-    }
-    __syncthreads();
-    const int64_t n2all = main_only ? n2 : n2 * (1 + P.nrst[l]);
-    double2 *w2 = reinterpret_cast<double2 *>(P.w[l]);
-    const double2 *V2 = reinterpret_cast<const double2 *>(P.V[l]);
-    const int64_t vs2 = vstride >> 1;
-    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
-        const double *sh = (hh && i >= n2) ? sh1 : sh0;
-        double s0 = 0.0, s1 = 0.0;
-        const double2 *v = V2 + i;
-        int j = 0;
-        for (; j + 8 <= k; j += 8) {
-            double2 t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = v[(int64_t)(j + u) * vs2];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                s0 += sh[j + u] * t[u].x;
-                s1 += sh[j + u] * t[u].y;
-            }
-        }
-        for (; j < k; ++j) {
-            const double2 t = v[(int64_t)j * vs2];
-            s0 += sh[j] * t.x;
-            s1 += sh[j] * t.y;
-        }
-        double2 wv = w2[i];
-        wv.x += sign * s0;
-        wv.y += sign * s1;
-        w2[i] = wv;
-    }
-}
-
-// blockIdx.y = field, blockIdx.z = lane: first stage of |w_l|^2 in the partition of k_dot_partial; partial row l
-__global__ __launch_bounds__(NT) void k_lane_dot_partial(LaneVW P, const double *bm1, int64_t lvs, int nblk, int nper, double *partial) {
-    __shared__ double sm[4];
-    const int c = blockIdx.y, l = blockIdx.z;
-    const int64_t n2 = lvs >> 1;
-    const int64_t per = (n2 + nblk - 1) / nblk;
-    const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
-    const double2 *a2 = reinterpret_cast<const double2 *>(P.w[l] + c * lvs);
-    const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
-    double acc = 0.0;
-    for (int64_t i = beg + threadIdx.x; i < end; i += NT) {
-        const double2 av = a2[i], mv = m2[i];
-        acc += av.x * av.x * mv.x + av.y * av.y * mv.y;
-    }
-    const double s = block_sum(acc, sm);
-    if (threadIdx.x == 0) partial[(int64_t)l * nper + c * nblk + blockIdx.x] = s;
-}
-
-// blockIdx.y = lane: w_l *= 1 / sqrt(q[l]) over the main block and the valid history blocks (0 where q[l] is not positive, as k_scal_dev)
-__global__ __launch_bounds__(NT) void k_lane_scal_dev(LaneVW P, const double *q, int64_t n2) {
-    const int l = blockIdx.y;
-    const double sv = q[l];
-    const double a = sv > 0.0 ? 1.0 / sqrt(sv) : 0.0;
-    const int64_t n2all = n2 * (1 + P.nrst[l]);
-    double2 *x = reinterpret_cast<double2 *>(P.w[l]);
-    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
-        double2 v = x[i];
-        v.x = __dmul_rn(v.x, a);
-        v.y = __dmul_rn(v.y, a);
-        x[i] = v;
-    }
-}
-
 __global__ void k_vadd(double *a, const double *b, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] += b[i];
@@ -682,8 +563,10 @@ namespace nlg {
 int dev_dot(const nlg_vec *a, const nlg_vec *b, int slot) {
     nlg_ctx *ctx = a->mesh->ctx;
     const int nblk = dot_nblk(a);
-    NLG_LAUNCH(k_dot_partial, dim3(nblk, a->ncomp), dim3(NT), 0, ctx->stream, a->d, b->d, a->mesh->d_bm1,
-                       a->mesh->lvs, nblk, ctx->d_partial);
+    LaneAB P = {};
+    P.a[0] = a->d, P.b[0] = b->d;
+    NLG_LAUNCH(k_dot_partial, dim3(nblk, a->ncomp), dim3(NT), 0, ctx->stream, P, (const double *)a->mesh->d_bm1, a->mesh->lvs, nblk,
+               nblk * a->ncomp, ctx->d_partial);
     NLG_LAUNCH(k_reduce_rows, dim3(1), dim3(NT), 0, ctx->stream, ctx->d_partial, nblk * a->ncomp,
                        ctx->d_scalars + slot, 0, (double *)nullptr);
     NLG_HIP(hipGetLastError());
@@ -1051,8 +934,8 @@ int nlg_basis_create(nlg_mesh *mesh, int nscal, int lorder, int nvec, nlg_basis 
         return 1;
     }
     NLG_HIP(hipMemsetAsync(b->d, 0, bytes, mesh->ctx->stream));
-    NLG_HIP(hipMalloc(&b->d_h, sizeof(double) * (size_t)(3 * nvec + 16)));
-    NLG_HIP(hipMemsetAsync(b->d_h, 0, sizeof(double) * (size_t)(3 * nvec + 16), mesh->ctx->stream));
+    NLG_HIP(hipMalloc(&b->d_h, sizeof(double) * nlg_basis::h_len(nvec)));
+    NLG_HIP(hipMemsetAsync(b->d_h, 0, sizeof(double) * nlg_basis::h_len(nvec), mesh->ctx->stream));
     NLG_TRY(reduce_ws_reserve(mesh->ctx, nvec + 8));
     b->views.resize(nvec);
     for (int i = 0; i < nvec; ++i) {
@@ -1076,7 +959,6 @@ int nlg_basis_destroy(nlg_basis *b) {
     for (auto *v : b->views) delete v;
     if (b->d) hipFree(b->d);
     if (b->d_h) hipFree(b->d_h);
-    if (b->d_hb) hipFree(b->d_hb);
     delete b;
     return 0;
 }
@@ -1108,169 +990,155 @@ static int reduce_rows_all(nlg_ctx *ctx, int rows, int per, double *out, double 
     return 0;
 }
 
-// device-resident block projection: d_out[0:k] = V^T B w (allreduced); optionally d_acc += d_out
-int basis_block_dot_dev(const nlg_basis *b, int k, const nlg_vec *w, double *d_out, double *d_acc) {
-    nlg_ctx *ctx = b->mesh->ctx;
-    const nlg_vec *v0 = b->views[0];
-    constexpr int KB = 8;
-    const int nblk = dot_nblk(v0);
-    const int nper = nblk * v0->ncomp;
-    NLG_TRY(reduce_ws_reserve(ctx, k));
-    ProfScope ps(ctx, P_BLOCKDOT);
-    NLG_LAUNCH(k_block_dot<KB>, dim3(nblk, v0->ncomp, (k + KB - 1) / KB), dim3(NT), 0, ctx->stream, b->d,
-                       b->stride, k, w->d, b->mesh->d_bm1, b->mesh->lvs, nblk, nper, ctx->d_partial);
-    NLG_TRY(reduce_rows_all(ctx, k, nper, d_out, d_acc));
-    NLG_HIP(hipGetLastError());
-    return 0;
-}
-
-int basis_block_axpy_dev(const nlg_basis *b, int k, const double *d_h, nlg_vec *w, double sign, const double *d_hh,
-                         bool main_only) {
-    nlg_ctx *ctx = b->mesh->ctx;
-    const int64_t n2 = w->main_len / 2;
-    ProfScope ps(ctx, P_BLOCKAXPY);
-    if (g_axpby_consistent) {
-        // consistent history: main block and the nrst valid history blocks are one contiguous range in which every
-        // entry receives the same linear combination -> one sweep through the unrolled path
-        const int64_t n2all = main_only ? n2 : n2 * (1 + w->nrst);
-        NLG_LAUNCH(k_block_axpy, dim3(grid_for(n2all)), dim3(NT), sizeof(double) * 2 * k, ctx->stream, b->d, b->stride,
-                           k, d_h, w->d, n2all, 0, n2, 0, sign, d_hh);
-    } else {
-        NLG_LAUNCH(k_block_axpy, dim3(grid_for(n2)), dim3(NT), sizeof(double) * 2 * k, ctx->stream, b->d, b->stride, k,
-                           d_h, w->d, n2, w->nrst, n2, 0, sign, (const double *)nullptr);
-    }
-    NLG_HIP(hipGetLastError());
-    return 0;
-}
-
-// CGS2 + norm + scale, everything stream-ordered on device. Results: d_h[0:k] coefficients,
-// d_h[k] = ||w||^2 before normalisation.
-int basis_cgs2_dev(nlg_basis *b, int k, nlg_vec *w) {
-    nlg_ctx *ctx = b->mesh->ctx;
-    double *h = b->d_h, *h2 = b->d_h + b->nvec + 8;
-    if (k > 0) {
-        NLG_TRY(basis_block_dot_dev(b, k, w, h, nullptr));
-        if (g_axpby_consistent) {
-            // first pass on the main block only; the second pass applies h2 to the main block and h + h2 (accumulated
-            // in h by the second block_dot) to the history blocks: the result is the one of two full sweeps up to
-            // rounding, at two thirds of the traffic
-            // (measured, CGS2 + norm + scale at 10^4 elements: k = 64: 6.29 -> 4.94 ms, 32: 3.28 -> 2.79, 16: 1.78 -> 1.88,
-            // 8: 1.04 -> 1.46 — the fully unrolled KMAX = 64 kernel does all 128 FMAs whatever k — hence the lower bound)
-            if (k >= 24) {
-                // first subtraction and second projection in one sweep over the LAST kf <= 128 basis vectors
-                // (k_block_axpy_dot); the k0 = k - kf vectors before them are subtracted first and projected after
-                const nlg_vec *v0 = b->views[0];
-                // k <= 64: one register tile (k_block_axpy_dot<64>); up to 128: two tiles, the second parked in LDS (k_block_axpy_dot2<64>)
-                const int kf = std::min(k, 128);
-                const int k0 = k - kf;
-                const int64_t nv = (int64_t)v0->ncomp * b->mesh->lvs;   // velocity (+ scalar) part; the pressure follows
-                const int G = 256;                                     // one block per CU (one wave per SIMD)
-                NLG_TRY(reduce_ws_reserve(ctx, k));
-                if (k0 > 0) NLG_TRY(basis_block_axpy_dev(b, k0, h, w, -1.0, nullptr, true));
-                const double *Vf = b->d + (int64_t)k0 * b->stride;
-                {
-                    ProfScope ps(ctx, P_AXPYDOT);
-                    if (kf > 64) {
-                        constexpr size_t lds2 = sizeof(double) * (2 * 64 + 64 * NT);
-                        static bool attr_set = false;
-                        if (!attr_set) {
-                            NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_block_axpy_dot2<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-                            attr_set = true;
-                        }
-                        NLG_LAUNCH(k_block_axpy_dot2<64>, dim3(G), dim3(NT), lds2, ctx->stream, Vf, b->stride, kf,
-                                           (const double *)(h + k0), w->d, (const double *)b->mesh->d_bm1, b->mesh->lvs, nv, ctx->d_partial);
-                    } else {
-                        NLG_LAUNCH(k_block_axpy_dot<64>, dim3(G), dim3(NT), 0, ctx->stream, Vf, b->stride, kf,
-                                           (const double *)(h + k0), w->d, (const double *)b->mesh->d_bm1, b->mesh->lvs, nv, ctx->d_partial);
-                    }
-                }
-                {
-                    ProfScope ps(ctx, P_BLOCKAXPY);
-                    const int64_t np2 = (w->main_len - nv) / 2;        // pressure part of the main block: subtraction only
-                    if (np2 > 0)
-                        NLG_LAUNCH(k_block_axpy, dim3(grid_for(np2)), dim3(NT), sizeof(double) * 2 * kf, ctx->stream,
-                                           Vf + nv, b->stride, kf, (const double *)(h + k0), w->d + nv, np2, 0, np2, 0, -1.0,
-                                           (const double *)nullptr);
-                }
-                NLG_TRY(reduce_rows_all(ctx, kf, G, h2 + k0, h + k0));
-                if (k0 > 0) NLG_TRY(basis_block_dot_dev(b, k0, w, h2, h));
-            } else {
-                NLG_TRY(basis_block_axpy_dev(b, k, h, w, -1.0, nullptr, true));
-                NLG_TRY(basis_block_dot_dev(b, k, w, h2, h));
-            }
-            NLG_TRY(basis_block_axpy_dev(b, k, h2, w, -1.0, h, false));
-        } else {
-            NLG_TRY(basis_block_axpy_dev(b, k, h, w, -1.0));
-            NLG_TRY(basis_block_dot_dev(b, k, w, h2, h));
-            NLG_TRY(basis_block_axpy_dev(b, k, h2, w, -1.0));
-        }
-    }
-    // norm
-    const int nblk = dot_nblk(w);
-    NLG_LAUNCH(k_dot_partial, dim3(nblk, w->ncomp), dim3(NT), 0, ctx->stream, w->d, w->d, b->mesh->d_bm1,
-                       b->mesh->lvs, nblk, ctx->d_partial);
-    NLG_TRY(reduce_rows_all(ctx, 1, nblk * w->ncomp, h + k, nullptr));
-    const int64_t n2 = w->main_len * (1 + w->nrst) / 2;
-    NLG_LAUNCH(k_scal_dev, dim3(grid_for(n2)), dim3(NT), 0, ctx->stream, reinterpret_cast<double2 *>(w->d),
-                       h + k, 0, n2);
-    NLG_HIP(hipGetLastError());
-    return 0;
-}
-
-// The batched form of basis_cgs2_dev (consistent history update): projection, subtraction on the main block, second projection
-// (accumulated), subtraction with the second coefficients on the main block and the sum of both on the history, norm, scale -- six
-// launches plus four small reductions for all s lanes, where s calls of basis_cgs2_dev make s times as many.  The fused
-// subtraction-and-projection sweep of the single-lane path (k >= 24) has no lane form: the batched path is one variant for every k.
-// Workspace (b[0]->d_hb): coefficients [s][k] at 0, |w_l|^2 at s * k, second-pass coefficients [s][k] at 4 * nvec + 8.
-int basis_cgs2_batch_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w) {
-    nlg_basis *b0 = b[0];
-    nlg_mesh *m = b0->mesh;
-    nlg_ctx *ctx = m->ctx;
-    hipStream_t st = ctx->stream;
-    if (!b0->d_hb) NLG_HIP(hipMalloc(&b0->d_hb, sizeof(double) * ((size_t)2 * b0->nvec * 4 + 64)));
-    double *H1 = b0->d_hb, *Q = H1 + (size_t)s * k, *H2 = b0->d_hb + (size_t)b0->nvec * 4 + 8;
-    if (!g_axpby_consistent) {   // the reference's history quirk has no batched form: lane by lane, results gathered into the workspace
-        for (int l = 0; l < s; ++l) {
-            NLG_TRY(basis_cgs2_dev(b[l], k, w[l]));
-            if (k > 0) NLG_HIP(hipMemcpyAsync(H1 + (size_t)l * k, b[l]->d_h, sizeof(double) * k, hipMemcpyDeviceToDevice, st));
-            NLG_HIP(hipMemcpyAsync(Q + l, b[l]->d_h + k, sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        return 0;
-    }
+// the lanes of a call: w[l] against columns of the basis b[l] (the struct travels whole: the spare entries repeat lane 0)
+static LaneVW lanes_of(int s, const nlg_basis *const *b, nlg_vec *const *w) {
     LaneVW P;
-    int nrst = 0;
     for (int l = 0; l < kMaxLanes; ++l) {
         const int u = l < s ? l : 0;
         P.V[l] = b[u]->d, P.w[l] = w[u]->d, P.nrst[l] = w[u]->nrst;
-        nrst = std::max(nrst, w[u]->nrst);
     }
+    return P;
+}
+static LaneVW one_lane(const nlg_basis *b, const nlg_vec *w) {
+    nlg_vec *wl = const_cast<nlg_vec *>(w);
+    return lanes_of(1, &b, &wl);
+}
+static int max_nrst(int s, const LaneVW &P) { return *std::max_element(P.nrst, P.nrst + s); }
+
+// device-resident block projection of s lanes: d_out[l * k + j] = V_{l,j}^T B w_l (allreduced, one collective for all lanes);
+// optionally d_acc += d_out.  b0: any of the bases (they agree in shape)
+static int lanes_block_dot(const nlg_basis *b0, int s, const LaneVW &P, int k, double *d_out, double *d_acc) {
+    nlg_mesh *m = b0->mesh;
+    nlg_ctx *ctx = m->ctx;
     const nlg_vec *v0 = b0->views[0];
     constexpr int KB = 8;
     const int nblk = dot_nblk(v0), nper = nblk * v0->ncomp;
-    const int64_t n2 = v0->main_len / 2;
-    NLG_TRY(reduce_ws_reserve(ctx, s * std::max(k, 1)));
-    auto dot = [&](double *out, double *acc) -> int {
-        ProfScope ps(ctx, P_BLOCKDOT);
-        NLG_LAUNCH(k_lane_block_dot<KB>, dim3(nblk, v0->ncomp * s, (k + KB - 1) / KB), dim3(NT), 0, st, P, b0->stride, k, v0->ncomp,
-                   (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
-        return reduce_rows_all(ctx, s * k, nper, out, acc);   // (one collective for all lanes)
-    };
-    auto axpy = [&](const double *h, const double *hh, bool main_only) -> int {
-        ProfScope ps(ctx, P_BLOCKAXPY);
-        const int64_t n2all = main_only ? n2 : n2 * (1 + nrst);
-        NLG_LAUNCH(k_lane_block_axpy, dim3(grid_for(n2all), s), dim3(NT), sizeof(double) * 2 * k, st, P, b0->stride, k, h, hh, n2, (int)main_only, -1.0);
-        return 0;
-    };
-    if (k > 0) {
-        NLG_TRY(dot(H1, nullptr));
-        NLG_TRY(axpy(H1, nullptr, true));
-        NLG_TRY(dot(H2, H1));
-        NLG_TRY(axpy(H2, H1, false));
-    }
-    NLG_LAUNCH(k_lane_dot_partial, dim3(nblk, v0->ncomp, s), dim3(NT), 0, st, P, (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
-    NLG_TRY(reduce_rows_all(ctx, s, nper, Q, nullptr));
-    NLG_LAUNCH(k_lane_scal_dev, dim3(grid_for(n2 * (1 + nrst)), s), dim3(NT), 0, st, P, (const double *)Q, n2);
+    NLG_TRY(reduce_ws_reserve(ctx, s * k));
+    ProfScope ps(ctx, P_BLOCKDOT);
+    NLG_LAUNCH(k_block_dot<KB>, dim3(nblk, v0->ncomp * s, (k + KB - 1) / KB), dim3(NT), 0, ctx->stream, P, b0->stride, k, v0->ncomp,
+               (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
+    NLG_TRY(reduce_rows_all(ctx, s * k, nper, d_out, d_acc));
     NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// w_l += sign * V_l h_l of s lanes, the history blocks as `hist` says (k_block_axpy)
+static int lanes_block_axpy(const nlg_basis *b0, int s, const LaneVW &P, int k, const double *d_h, const double *d_hh, int hist,
+                            double sign) {
+    nlg_ctx *ctx = b0->mesh->ctx;
+    const int64_t n2 = b0->views[0]->main_len / 2;
+    const int64_t n2all = hist == HIST_SWEEP ? n2 * (1 + max_nrst(s, P)) : n2;
+    ProfScope ps(ctx, P_BLOCKAXPY);
+    NLG_LAUNCH(k_block_axpy, dim3(grid_for(n2all), s), dim3(NT), sizeof(double) * 2 * k, ctx->stream, P, b0->stride, k, d_h, d_hh, n2,
+               hist, sign);
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// what a whole-vector update does to the history of w: consistent mode combines the history of the basis, literal mode repeats the
+// main block's correction (nlg_set_axpby_rst_consistent)
+static int hist_mode() { return g_axpby_consistent ? HIST_SWEEP : HIST_MAIN; }
+
+// CGS2 of ONE vector, consistent mode, k >= 24: the first subtraction and the second projection in one sweep over the LAST kf <= 128
+// basis vectors (k_block_axpy_dot); the k0 = k - kf vectors before them are subtracted first and projected after.  h holds the
+// first-pass coefficients; on return h2 the second-pass ones and h the sum.
+// (measured, CGS2 + norm + scale at 10^4 elements: k = 64: 6.29 -> 4.94 ms, 32: 3.28 -> 2.79, 16: 1.78 -> 1.88,
+// 8: 1.04 -> 1.46 — the fully unrolled KMAX = 64 kernel does all 128 FMAs whatever k — hence the lower bound)
+static int cgs2_fused_sweep(const nlg_basis *b, int k, nlg_vec *w, double *h, double *h2) {
+    nlg_ctx *ctx = b->mesh->ctx;
+    const nlg_vec *v0 = b->views[0];
+    const LaneVW P = one_lane(b, w);
+    // k <= 64: one register tile (k_block_axpy_dot<64>); up to 128: two tiles, the second parked in LDS (k_block_axpy_dot2<64>)
+    const int kf = std::min(k, 128);
+    const int k0 = k - kf;
+    const int64_t nv = (int64_t)v0->ncomp * b->mesh->lvs;   // velocity (+ scalar) part; the pressure follows
+    const int G = 256;                                     // one block per CU (one wave per SIMD)
+    NLG_TRY(reduce_ws_reserve(ctx, k));
+    if (k0 > 0) NLG_TRY(lanes_block_axpy(b, 1, P, k0, h, nullptr, HIST_NONE, -1.0));
+    const double *Vf = b->d + (int64_t)k0 * b->stride;
+    {
+        ProfScope ps(ctx, P_AXPYDOT);
+        if (kf > 64) {
+            constexpr size_t lds2 = sizeof(double) * (2 * 64 + 64 * NT);
+            static bool attr_set = false;
+            if (!attr_set) {
+                NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_block_axpy_dot2<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+                attr_set = true;
+            }
+            NLG_LAUNCH(k_block_axpy_dot2<64>, dim3(G), dim3(NT), lds2, ctx->stream, Vf, b->stride, kf, (const double *)(h + k0), w->d,
+                       (const double *)b->mesh->d_bm1, b->mesh->lvs, nv, ctx->d_partial);
+        } else {
+            NLG_LAUNCH(k_block_axpy_dot<64>, dim3(G), dim3(NT), 0, ctx->stream, Vf, b->stride, kf, (const double *)(h + k0), w->d,
+                       (const double *)b->mesh->d_bm1, b->mesh->lvs, nv, ctx->d_partial);
+        }
+    }
+    {
+        ProfScope ps(ctx, P_BLOCKAXPY);
+        const int64_t np2 = (w->main_len - nv) / 2;        // pressure part of the main block: subtraction only
+        if (np2 > 0) {
+            LaneVW Pp = {};
+            Pp.V[0] = Vf + nv, Pp.w[0] = w->d + nv;
+            NLG_LAUNCH(k_block_axpy, dim3(grid_for(np2)), dim3(NT), sizeof(double) * 2 * kf, ctx->stream, Pp, b->stride, kf,
+                       (const double *)(h + k0), (const double *)nullptr, np2, (int)HIST_NONE, -1.0);
+        }
+    }
+    NLG_TRY(reduce_rows_all(ctx, kf, G, h2 + k0, h + k0));
+    if (k0 > 0) NLG_TRY(lanes_block_dot(b, 1, P, k0, h2, h));
+    return 0;
+}
+
+// CGS2 + norm + scale of s vectors, each against its own basis, everything stream-ordered on device: four launches plus the small
+// reductions for all lanes, then norm and scale.  Results in b[0]'s workspace: h1() coefficients [s][k], hnorm(s, k) the |w_l|^2
+// before normalisation.
+static int basis_cgs2_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w) {
+    nlg_basis *b0 = b[0];
+    nlg_mesh *m = b0->mesh;
+    nlg_ctx *ctx = m->ctx;
+    double *H1 = b0->h1(), *H2 = b0->h2(), *Q = b0->hnorm(s, k);
+    const LaneVW P = lanes_of(s, b, w);
+    if (k > 0) {
+        NLG_TRY(lanes_block_dot(b0, s, P, k, H1, nullptr));
+        if (g_axpby_consistent) {
+            // first pass on the main block only; the second pass applies H2 to the main block and H1 + H2 (accumulated
+            // in H1 by the second block_dot) to the history blocks: the result is the one of two full sweeps up to
+            // rounding, at two thirds of the traffic
+            if (s == 1 && k >= 24) {
+                NLG_TRY(cgs2_fused_sweep(b0, k, w[0], H1, H2));
+            } else {
+                NLG_TRY(lanes_block_axpy(b0, s, P, k, H1, nullptr, HIST_NONE, -1.0));
+                NLG_TRY(lanes_block_dot(b0, s, P, k, H2, H1));
+            }
+            NLG_TRY(lanes_block_axpy(b0, s, P, k, H2, H1, HIST_SWEEP, -1.0));
+        } else {
+            NLG_TRY(lanes_block_axpy(b0, s, P, k, H1, nullptr, HIST_MAIN, -1.0));
+            NLG_TRY(lanes_block_dot(b0, s, P, k, H2, H1));
+            NLG_TRY(lanes_block_axpy(b0, s, P, k, H2, nullptr, HIST_MAIN, -1.0));
+        }
+    }
+    const nlg_vec *v0 = b0->views[0];
+    const int nblk = dot_nblk(v0), nper = nblk * v0->ncomp;
+    const int64_t n2 = v0->main_len / 2;
+    LaneAB A;
+    for (int l = 0; l < kMaxLanes; ++l) A.a[l] = A.b[l] = P.w[l];
+    NLG_LAUNCH(k_dot_partial, dim3(nblk, v0->ncomp, s), dim3(NT), 0, ctx->stream, A, (const double *)m->d_bm1, m->lvs, nblk, nper,
+               ctx->d_partial);
+    NLG_TRY(reduce_rows_all(ctx, s, nper, Q, nullptr));
+    NLG_LAUNCH(k_scal_dev, dim3(grid_for(n2 * (1 + max_nrst(s, P))), s), dim3(NT), 0, ctx->stream, P, (const double *)Q, n2);
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// basis_cgs2_dev and ONE read-back for all lanes: lane l's k coefficients to h[l * hstride + 0:k], its norm to beta[l * bstride]
+int basis_cgs2_host(int s, nlg_basis *const *b, int k, nlg_vec *const *w, double *h, int64_t hstride, double *beta, int64_t bstride) {
+    NLG_TRY(basis_cgs2_dev(s, b, k, w));
+    std::vector<double> tmp((size_t)s * k + s);   // (hnorm lies right behind the coefficients)
+    hipStream_t st = b[0]->mesh->ctx->stream;
+    NLG_HIP(hipMemcpyAsync(tmp.data(), b[0]->h1(), sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    for (int l = 0; l < s; ++l) {
+        for (int j = 0; j < k; ++j) h[l * hstride + j] = tmp[(size_t)l * k + j];
+        beta[l * bstride] = sqrt(tmp[(size_t)s * k + l]);
+    }
     return 0;
 }
 
@@ -1293,24 +1161,15 @@ int nlg_basis_cgs2_batch(int s, nlg_basis *const *b, int k, nlg_vec *const *w, d
             NLG_CHECK(!(w[l]->d >= b[u]->d && w[l]->d < b[u]->d + (int64_t)k * b[u]->stride),
                       "nlg_basis_cgs2_batch: the vector of lane %d is one of the columns 0..%d it is orthogonalised against", l, k - 1);
     }
-    NLG_TRY(nlg::basis_cgs2_batch_dev(s, b, k, w));
-    std::vector<double> tmp((size_t)s * k + s);
-    hipStream_t st = b[0]->mesh->ctx->stream;
-    NLG_HIP(hipMemcpyAsync(tmp.data(), b[0]->d_hb, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, st));
-    NLG_HIP(hipStreamSynchronize(st));
-    for (int l = 0; l < s; ++l) {
-        for (int j = 0; j < k; ++j) h[(size_t)l * ldh + j] = tmp[(size_t)l * k + j];
-        beta[l] = sqrt(tmp[(size_t)s * k + l]);
-    }
-    return 0;
+    return nlg::basis_cgs2_host(s, b, k, w, h, ldh, beta, 1);
 }
 
 int nlg_basis_block_dot(const nlg_basis *b, int k, const nlg_vec *w, double *h) {
     NLG_CHECK(b && w && h, "nlg_basis_block_dot: NULL argument");
     NLG_CHECK(k >= 1 && k <= b->nvec, "nlg_basis_block_dot: k=%d out of range [1,%d]", k, b->nvec);
     NLG_TRY(check_same(b->views[0], w, "nlg_basis_block_dot"));
-    NLG_TRY(nlg::basis_block_dot_dev(b, k, w, b->d_h, nullptr));
-    NLG_HIP(hipMemcpyAsync(h, b->d_h, sizeof(double) * k, hipMemcpyDeviceToHost, b->mesh->ctx->stream));
+    NLG_TRY(nlg::lanes_block_dot(b, 1, nlg::one_lane(b, w), k, b->h1(), nullptr));
+    NLG_HIP(hipMemcpyAsync(h, b->h1(), sizeof(double) * k, hipMemcpyDeviceToHost, b->mesh->ctx->stream));
     NLG_HIP(hipStreamSynchronize(b->mesh->ctx->stream));
     return 0;
 }
@@ -1319,8 +1178,8 @@ int nlg_basis_block_axpy(const nlg_basis *b, int k, const double *h, nlg_vec *w)
     NLG_CHECK(b && w && h, "nlg_basis_block_axpy: NULL argument");
     NLG_CHECK(k >= 1 && k <= b->nvec, "nlg_basis_block_axpy: k=%d out of range [1,%d]", k, b->nvec);
     NLG_TRY(check_same(b->views[0], w, "nlg_basis_block_axpy"));
-    NLG_HIP(hipMemcpyAsync(b->d_h, h, sizeof(double) * k, hipMemcpyHostToDevice, b->mesh->ctx->stream));
-    NLG_TRY(nlg::basis_block_axpy_dev(b, k, b->d_h, w, -1.0));
+    NLG_HIP(hipMemcpyAsync(b->h1(), h, sizeof(double) * k, hipMemcpyHostToDevice, b->mesh->ctx->stream));
+    NLG_TRY(nlg::lanes_block_axpy(b, 1, nlg::one_lane(b, w), k, b->h1(), nullptr, nlg::hist_mode(), -1.0));
     NLG_HIP(hipStreamSynchronize(b->mesh->ctx->stream));
     return 0;
 }
@@ -1330,13 +1189,7 @@ int nlg_basis_cgs2(const nlg_basis *bc, int k, nlg_vec *w, double *h, double *be
     NLG_CHECK(b && w && h && beta, "nlg_basis_cgs2: NULL argument");
     NLG_CHECK(k >= 0 && k <= b->nvec, "nlg_basis_cgs2: k=%d out of range [0,%d]", k, b->nvec);
     NLG_TRY(check_same(b->views[0], w, "nlg_basis_cgs2"));
-    NLG_TRY(nlg::basis_cgs2_dev(b, k, w));
-    std::vector<double> tmp(k + 1);
-    NLG_HIP(hipMemcpyAsync(tmp.data(), b->d_h, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, b->mesh->ctx->stream));
-    NLG_HIP(hipStreamSynchronize(b->mesh->ctx->stream));
-    for (int j = 0; j < k; ++j) h[j] = tmp[j];
-    *beta = sqrt(tmp[k]);
-    return 0;
+    return nlg::basis_cgs2_host(1, &b, k, &w, h, 0, beta, 0);
 }
 
 // Block classical Gram-Schmidt with re-orthogonalisation for the s consecutive columns k .. k+s-1 against the columns
@@ -1357,7 +1210,6 @@ int nlg_basis_block_cgs2(nlg_basis *b, int k, int s, double *coef) {
         coef[k] = beta;
         return 0;
     }
-    if (!b->d_hb) NLG_HIP(hipMalloc(&b->d_hb, sizeof(double) * ((size_t)2 * b->nvec * 4 + 64)));
     nlg_vec *w0 = b->views[k];
     int nrst = 0;
     for (int v = 0; v < s; ++v) nrst = std::max(nrst, b->views[k + v]->nrst);
@@ -1371,7 +1223,7 @@ int nlg_basis_block_cgs2(nlg_basis *b, int k, int s, double *coef) {
     }
     b->last_block_rank = s;
     double *W = w0->d;
-    double *H1 = b->d_hb, *H2 = b->d_hb + (size_t)b->nvec * 4, *dG = b->d_hb + (size_t)2 * b->nvec * 4, *dT = dG + 16;
+    double *H1 = b->h1(), *H2 = b->h2(), *dG = b->gram(), *dT = b->tmat();
     const int nblk = dot_nblk(w0), nper = nblk * w0->ncomp;
     const int64_t n2 = w0->main_len / 2, n2all = n2 * (1 + nrst);
     constexpr int KB = 8;
@@ -1513,8 +1365,8 @@ int nlg_basis_combine(const nlg_basis *b, int k, const double *c, nlg_vec *out) 
         for (int j = 0; j < k; ++j) nr = std::max(nr, b->views[j]->nrst);
         out->nrst = nr;
     }
-    NLG_HIP(hipMemcpyAsync(b->d_h, c, sizeof(double) * k, hipMemcpyHostToDevice, b->mesh->ctx->stream));
-    NLG_TRY(nlg::basis_block_axpy_dev(b, k, b->d_h, out, +1.0));
+    NLG_HIP(hipMemcpyAsync(b->h1(), c, sizeof(double) * k, hipMemcpyHostToDevice, b->mesh->ctx->stream));
+    NLG_TRY(nlg::lanes_block_axpy(b, 1, nlg::one_lane(b, out), k, b->h1(), nullptr, nlg::hist_mode(), +1.0));
     NLG_HIP(hipStreamSynchronize(b->mesh->ctx->stream));
     return 0;
 }

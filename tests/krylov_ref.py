@@ -113,6 +113,19 @@ def mesh_case(mid, lorder=3, seed=11, k=None):
     return make_case(_sem(mid), k or max(CGS2_K[mid]), nscal=MESHES[mid][2], lorder=lorder, eps=1e-2, seed=seed, nw=4)
 
 
+def lane_case(mid, l):
+    """Lane l of the batched tests: its own basis of 25 columns (seed 20 + l)."""
+    return mesh_case(mid, seed=20 + l, k=25)
+
+
+def lane_w(case, l):
+    """... and its vector, scaled by 10^-l so that no lane can stand in for another."""
+    return case.w[0] * 10.0 ** -l
+
+
+LITERAL_BATCH = {"mid": "C", "k": 9, "nrst": (0, 2, 1)}      # the literal-history batch of tests/test_gpu_krylov_oracle.py
+
+
 def clear_cases():
     mesh_case.cache_clear()
     _sem.cache_clear()

@@ -38,11 +38,11 @@ def oracle_columns(mid, lorder=3):
     return [kr.oracle_column(case, j) for j in range(case.k)]
 
 
-def oracle_cgs2(case, X, k, consistent, nrst):
+def oracle_cgs2(case, X, k, consistent, nrst, w=None):
     old = NekDVector.CONSISTENT_RST
     NekDVector.CONSISTENT_RST = consistent
     try:
-        w = kr.to_oracle(case, case.w[0], nrst)
+        w = kr.to_oracle(case, case.w[0] if w is None else w, nrst)
         h = cgs2_step(X[:k], w)
         beta = w.norm()
         w.scal(1.0 / beta)
@@ -73,6 +73,17 @@ def test_oracle_cgs2_literal_history_matches_reference(prec, mid, k):
     agree(case, oracle_cgs2(case, oracle_columns(mid), k, False, 2), ref, case.w[0])
     dev = kr.deviations(case, kr.cgs2_ref(case, k, consistent=True), ref)                # the two modes are different answers
     assert min(d for key, d in dev.items() if isinstance(key, tuple) and key[0] == "hist") > 1e-3
+
+
+def test_oracle_cgs2_literal_history_of_the_batch_lanes(prec):
+    """The references of the literal-history batch of tests/test_gpu_krylov_oracle.py: lanes on their own bases with 0, 2 and 1 valid
+    levels, w scaled by 10^-l.  Levels beyond nrst come back bit for bit."""
+    k = kr.LITERAL_BATCH["k"]
+    for l, nrst in enumerate(kr.LITERAL_BATCH["nrst"]):
+        case = kr.lane_case(kr.LITERAL_BATCH["mid"], l)
+        w = kr.lane_w(case, l)
+        X = [kr.oracle_column(case, j) for j in range(k)]
+        agree(case, oracle_cgs2(case, X, k, False, nrst, w), kr.cgs2_ref(case, k, consistent=False, w=w, nrst=nrst), w)
 
 
 def test_oracle_cgs2_short_history_and_lorder_1(prec):

@@ -200,6 +200,62 @@ def test_cgs2_batch_lane_by_lane(rigs, prec, mid, s, k):
         kr.check(r.case, got, kr.cgs2_ref(r.case, k, w=ws[l], nrst=nrst[l]), ws[l])
 
 
+def same_bits(a, b):
+    """Two results {h, beta, w, nrst} agree bit for bit, every level of w included, valid or not."""
+    assert a["nrst"] == b["nrst"]
+    assert np.array_equal(a["h"], b["h"]) and a["beta"] == b["beta"]
+    assert np.array_equal(a["w"], b["w"])
+
+
+def batch_lanes(rigs, mid, s, nrst):
+    """Lane l of a batch on its own rig (krylov_ref.lane_case), w scaled by 10^-l with nrst[l] valid levels, uploaded."""
+    lanes = [rigs(mid, seed=20 + l, k=25) for l in range(s)]
+    ws = [kr.lane_w(r.case, l) for l, r in enumerate(lanes)]
+    for l, r in enumerate(lanes):
+        kr.upload(r.w, r.case, ws[l], nrst[l], r.tmp)
+    return lanes, ws
+
+
+def run_batch(lanes, k):
+    h, beta = host.KrylovBasis.cgs2_batch([r.B for r in lanes], k, [r.w for r in lanes])
+    return [{"h": h[l], "beta": beta[l], "w": kr.download(r.w, r.case), "nrst": r.w.nrst} for l, r in enumerate(lanes)]
+
+
+@pytest.mark.parametrize("mid,k", [("C", 0), ("C", 9), ("C", 24), ("C", 40), ("A", 65)])
+def test_cgs2_batch_of_one_is_the_single_call(rigs, prec, mid, k):
+    """One driver: a batch of one lane is nlg_basis_cgs2 bit for bit, the separate kernels below k = 24 and the fused sweeps from
+    there (mesh A at k = 65: the two-tile kernel)."""
+    r = rigs(mid)
+    c = r.case
+    single = r.cgs2(k)
+    kr.upload(r.w, c, c.w[0], c.w_nrst[0], r.tmp)
+    same_bits(run_batch([r], k)[0], single)
+
+
+@pytest.mark.parametrize("s", [2, 4])
+@pytest.mark.parametrize("k", [1, 9, 23])
+def test_cgs2_batch_lanes_are_single_calls(rigs, prec, s, k):
+    """Below k = 24 every lane of a batch runs the operations of a single call in the same order: lane l is bit for bit
+    nlg_basis_cgs2 on a copy of its input.  Odd lanes carry two history levels, even lanes none."""
+    nrst = [2 if l % 2 else 0 for l in range(s)]
+    lanes, ws = batch_lanes(rigs, "C", s, nrst)
+    got = run_batch(lanes, k)
+    for l, r in enumerate(lanes):
+        kr.upload(r.w, r.case, ws[l], nrst[l], r.tmp)
+        h, beta = r.B.cgs2(k, r.w)
+        same_bits(got[l], {"h": h, "beta": beta, "w": kr.download(r.w, r.case), "nrst": r.w.nrst})
+
+
+def test_cgs2_batch_literal_history(rigs, literal_history, prec):
+    """nlg_set_axpby_rst_consistent(0) in a batch: every valid history level of lane l receives that lane's main-block corrections,
+    lanes with 0, 2 and 1 valid levels side by side; the levels beyond come back bit for bit (kr.check with the input).  The
+    references are checked against the oracle in tests/test_cpu_krylov_ref.py."""
+    lb = kr.LITERAL_BATCH
+    lanes, ws = batch_lanes(rigs, lb["mid"], len(lb["nrst"]), lb["nrst"])
+    for l, (r, got) in enumerate(zip(lanes, run_batch(lanes, lb["k"]))):
+        kr.check(r.case, got, kr.cgs2_ref(r.case, lb["k"], consistent=False, w=ws[l], nrst=lb["nrst"][l]), ws[l])
+
+
 # ---- nlg_basis_block_cgs2 ----
 @pytest.mark.parametrize("mid", ["C", "B"])
 @pytest.mark.parametrize("s", [2, 4])
