@@ -494,6 +494,29 @@ int nlg_op_pprec(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out, int overlap, i
 int nlg_op_opdiv(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_opgradt(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_conv(nlg_mesh *mesh, const nlg_vec *base, const nlg_vec *in, nlg_vec *out, int adjoint);
+/* The operator L itself in strong (pointwise) form, element-local: apply_L, apply_Lv, compute_LNS_conv, compute_LNS_laplacian and
+ * compute_LNS_gradp of the reference (src/linops/neklab_linops.f90:24-28, :268-426) are this one call with other coefficients:
+ *   u~_k  = mask_k in.v_k                                   (bcdirvc on read: `in` is not modified)
+ *   out.v_k = coef[0] / re * sum_i gradm1(gradm1(u~_k)_i)_i (lap_1D: no mass, no dssum)
+ *           + coef[1] * conv(base, u~, adjoint)_k / bm1     (the weak dealiased term of nlg_op_conv over the local mass = Nek convop)
+ *           + coef[2] * gradm1(P)_k,   P = in.pr interpolated from the Gauss to the GLL mesh (Nek mappr)
+ * out is neither masked nor assembled; out.pr and the scalars of out are set to zero; restart history of out is left alone.  A zero
+ * coefficient skips its term.  apply_L = (1, -1, -1), apply_Lv = (1, -1, 0), laplacian = (1, 0, 0), conv = (0, 1, 0), gradp = (0, 0, 1).
+ * adjoint: the convective term of the adjoint equations as nlg_op_conv defines it (the reference's `trans` branch also adds the saved
+ * base flow to the result, neklab_linops.f90:301-312: not reproduced).  No collective call: correct on a partitioned mesh
+ * as it stands.
+ * nlg_lns keeps the base-flow side of the convective term between calls (nothing of the time stepper: no preconditioner, no Krylov
+ * workspace) and applies to s = 1..4 vectors in one launch of the strong-form kernel: lanes that lie a constant stride apart in memory
+ * (one vector, two vectors, consecutive vectors of a basis) are read and written in place, others go through a workspace.
+ * Refused with a message: s outside 1..4, a vector on another mesh, out[v] aliasing any in[w], another out[w] or the base flow last
+ * given, all three coefficients zero, re <= 0.  A refused call leaves out untouched. */
+typedef struct nlg_lns nlg_lns;
+int nlg_lns_create(nlg_mesh *mesh, const nlg_vec *baseflow, double re, nlg_lns **out);
+int nlg_lns_set_baseflow(nlg_lns *lns, const nlg_vec *baseflow);
+int nlg_lns_set_re(nlg_lns *lns, double re);
+int nlg_lns_apply(nlg_lns *lns, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint, const double *coef);
+int nlg_lns_destroy(nlg_lns *lns);
+int nlg_op_lns(nlg_mesh *mesh, const nlg_vec *base, const nlg_vec *in, nlg_vec *out, double re, int adjoint, const double *coef);
 /* the explicit modal filter of the time stepper (nlg_exptA_config.filter_weight / filter_modes) on its own, in place on the velocity
  * fields (and scalars) of nvec <= 4 vectors, which go through the kernel together as the lanes of a block step do */
 int nlg_op_filter(nlg_mesh *mesh, int nvec, nlg_vec *const *vecs, double filter_weight, int filter_modes);

@@ -168,7 +168,13 @@ SIGNATURES = {
     "nlg_op_opdiv": (C.c_int, [vp, vp, vp]),
     "nlg_op_opgradt": (C.c_int, [vp, vp, vp]),
     "nlg_op_conv": (C.c_int, [vp, vp, vp, vp, C.c_int]),
-    "nlg_op_filter": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_double, C.c_int]),
+    "nlg_op_lns": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_int, c_double_p]),
+    "nlg_lns_create": (C.c_int, [vp, vp, C.c_double, C.POINTER(vp)]),
+    "nlg_lns_set_baseflow": (C.c_int, [vp, vp]),
+    "nlg_lns_set_re": (C.c_int, [vp, C.c_double]),
+    "nlg_lns_apply": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, c_double_p]),
+    "nlg_lns_destroy": (C.c_int, [vp]),
+    "nlg_op_filter":(C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_double, C.c_int]),
     "nlg_op_cfl": (C.c_int, [vp, vp, C.c_double, c_double_p]),
     "nlg_arnoldi_step": (C.c_int, [vp, vp, C.c_int, c_double_p, C.c_int, C.c_int]),
     "nlg_eigs_opts_default": (C.c_int, [C.POINTER(EigsOpts)]),

@@ -390,6 +390,38 @@ module neklab_gpu_capi
          type(c_ptr), value :: otd
          integer(c_int) :: rc
       end function
+      ! the operator L itself in strong form (include/neklab_gpu.h, nlg_lns_*)
+      function c_lns_create(mesh, baseflow, re, lns) bind(C, name="nlg_lns_create") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: mesh, baseflow
+         real(c_double), value :: re
+         type(c_ptr), intent(out) :: lns
+         integer(c_int) :: rc
+      end function
+      function c_lns_set_baseflow(lns, baseflow) bind(C, name="nlg_lns_set_baseflow") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: lns, baseflow
+         integer(c_int) :: rc
+      end function
+      function c_lns_set_re(lns, re) bind(C, name="nlg_lns_set_re") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: lns
+         real(c_double), value :: re
+         integer(c_int) :: rc
+      end function
+      function c_lns_apply(lns, s, vin, vout, adjoint, coef) bind(C, name="nlg_lns_apply") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: lns
+         integer(c_int), value :: s, adjoint
+         type(c_ptr), intent(in) :: vin(*), vout(*)
+         real(c_double), intent(in) :: coef(3)
+         integer(c_int) :: rc
+      end function
+      function c_lns_destroy(lns) bind(C, name="nlg_lns_destroy") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: lns
+         integer(c_int) :: rc
+      end function
       function c_linop_matvec(op, vin, vout) bind(C, name="nlg_linop_matvec") result(rc)
          import c_int, c_ptr
          type(c_ptr), value :: op, vin, vout

@@ -12,9 +12,13 @@
 !!   nek_eigs / nek_svds                  the eigs / svds calls of src/neklab_analysis.f90:80-81, :136 (nlg_eigs, nlg_svds)
 !!   nonlinear_map / set_baseflow / set_tolerances   src/systems/fixed_point.f90:4-96, neklab_systems.f90:229-335
 !!   integrate_forced                     src/linops/resolvent.f90:80-111, :133-166
+!! and the operator L itself in strong form (nlg_lns_*):
+!!   apply_exptA                          src/linops/neklab_linops.f90:224-266
+!!   compute_LNS_conv / _laplacian / _gradp, apply_L, apply_Lv   src/linops/neklab_linops.f90:268-426 (host arrays, as there)
+!!   nek_otd%matvec / rmatvec = apply_LNS / apply_adjLNS          src/neklab_otd.f90:44-45, :76-116
 module neklab_linops
    use iso_c_binding
-   use LightKrylov, only: dp, abstract_vector_rdp, abstract_exptA_linop_rdp, abstract_vector_cdp, abstract_linop_cdp, type_error
+   use LightKrylov, only: dp, abstract_vector_rdp, abstract_linop_rdp, abstract_exptA_linop_rdp, abstract_vector_cdp, abstract_linop_cdp, type_error
    use neklab_gpu_capi
    use neklab_vectors
    implicit none
@@ -22,6 +26,15 @@ module neklab_linops
    character(len=*), parameter, private :: this_module = 'neklab_linops'
 
    public :: nek_eigs, nek_svds
+   public :: apply_exptA, apply_L, apply_Lv, compute_LNS_conv, compute_LNS_laplacian, compute_LNS_gradp, set_lns_baseflow
+
+   !> state of the array routines apply_L ... compute_LNS_gradp: the reference reads the base flow from Nek5000's vx, vy, vz; here
+   !! set_lns_baseflow(bf) hands it over (Re is the case's).  Their arrays go through two scratch vectors.
+   type(c_ptr), save, private :: lns_arrays_h = c_null_ptr
+   type(nek_dvector), save, private :: lns_arrays_in, lns_arrays_out
+   real(dp), parameter, private :: coef_L(3) = [1.0_dp, -1.0_dp, -1.0_dp], coef_Lv(3) = [1.0_dp, -1.0_dp, 0.0_dp], &
+                                   coef_lap(3) = [1.0_dp, 0.0_dp, 0.0_dp], coef_conv(3) = [0.0_dp, 1.0_dp, 0.0_dp], &
+                                   coef_gradp(3) = [0.0_dp, 0.0_dp, 1.0_dp]
 
    !------------------------------------------
    !-----     EXPONENTIAL PROPAGATOR     -----
@@ -103,6 +116,24 @@ module neklab_linops
       procedure, pass(self), public :: rmatvec => resolvent_rmatvec
    end type
 
+   !---------------------------------------------
+   !-----     THE OPERATOR L ITSELF         -----
+   !---------------------------------------------
+   !> L about `baseflow` in strong form, device-resident (nlg_lns_*): matvec / rmatvec are apply_L, direct and adjoint, on
+   !! nek_dvector.  re <= 0: the case's.  init() after the base flow is set (and again after it changes).
+   type, extends(abstract_linop_rdp), public :: lns_linop
+      type(nek_dvector) :: baseflow
+      real(dp) :: re = 0.0_dp
+      type(c_ptr), private :: h = c_null_ptr
+      integer(c_intptr_t), private :: owner = 0
+   contains
+      private
+      procedure, pass(self), public :: init => init_lns
+      procedure, pass(self), public :: matvec => lns_matvec
+      procedure, pass(self), public :: rmatvec => lns_rmatvec
+      final :: finalize_lns
+   end type lns_linop
+
    !---------------------------------------------------
    !-----     OPTIMALLY TIME-DEPENDENT MODES      -----
    !---------------------------------------------------
@@ -124,16 +155,23 @@ module neklab_linops
    !! operator, the forcing (generate_forcing) and the re-orthonormalisation run inside the device time step; `basis` is filled by
    !! get_basis.  cfg as for exptA_linop (from the case unless cfg_set), cfl_limit 0.4 as in init_OTD.  User initial conditions
    !! (n_usrIC) are handed over in `basis` before init(); the reference reads them with Nek5000's load_fld.
+   !! matvec / rmatvec = apply_LNS / apply_adjLNS (src/neklab_otd.f90:44-45, :76-116): the strong-form L with vec_in's own pressure,
+   !! about `baseflow` when it is frozen and about the current base flow of the run with solve_baseflow.  The reference's type
+   !! extends abstract_linop_rdp; here nek_otd_linop (below) is that view of a nek_otd.
    type, public :: nek_otd
       integer :: r = 2
       type(nek_dvector) :: baseflow
       type(nek_dvector), allocatable :: basis(:)
       type(nlg_exptA_config) :: cfg = nlg_exptA_config()
       logical :: cfg_set = .false.
-      type(c_ptr), private :: hop = c_null_ptr, h = c_null_ptr
+      type(c_ptr), private :: hop = c_null_ptr, h = c_null_ptr, hlns = c_null_ptr
+      type(nek_dvector), private :: bf_now
+      logical, private :: moving = .false.
       integer(c_intptr_t), private :: owner = 0
    contains
       private
+      procedure, pass(self), public :: matvec => apply_LNS
+      procedure, pass(self), public :: rmatvec => apply_adjLNS
       procedure, pass(self), public :: init => init_OTD
       procedure, pass(self), public :: advance => otd_advance
       procedure, pass(self), public :: reduced => otd_reduced
@@ -144,6 +182,15 @@ module neklab_linops
       procedure, pass(self), public :: close => otd_close
       final :: finalize_otd
    end type nek_otd
+
+   !> a nek_otd where LightKrylov expects a class(abstract_linop_rdp): `A%otd => OTD`, then A%matvec / A%rmatvec are OTD's
+   type, extends(abstract_linop_rdp), public :: nek_otd_linop
+      type(nek_otd), pointer :: otd => null()
+   contains
+      private
+      procedure, pass(self), public :: matvec => otd_linop_matvec
+      procedure, pass(self), public :: rmatvec => otd_linop_rmatvec
+   end type nek_otd_linop
 
 contains
 
@@ -383,10 +430,11 @@ contains
       class(nek_otd), intent(inout) :: self
       integer(c_int) :: rc
       if (self%owner == loc(self)) then
+         if (c_associated(self%hlns)) rc = c_lns_destroy(self%hlns)
          if (c_associated(self%h)) rc = c_otd_destroy(self%h)
          if (c_associated(self%hop)) rc = c_linop_destroy(self%hop)
       end if
-      self%h = c_null_ptr; self%hop = c_null_ptr; self%owner = 0
+      self%h = c_null_ptr; self%hop = c_null_ptr; self%hlns = c_null_ptr; self%owner = 0
    end subroutine
 
    subroutine finalize_otd(self)
@@ -412,6 +460,7 @@ contains
       self%owner = loc(self)
       o%r = self%r; o%startstep = opts%startstep; o%orthostep = opts%orthostep
       o%trans = merge(1, 0, opts%trans); o%solve_baseflow = merge(1, 0, opts%solve_baseflow)
+      self%moving = opts%solve_baseflow
       if (allocated(self%basis)) then
          if (size(self%basis) /= self%r) then
             write (*, '(A,I0,A,I0)') 'ERROR in '//this_module//': init_OTD: ', size(self%basis), ' initial conditions for r = ', self%r
@@ -652,6 +701,245 @@ contains
          end do
          if (abs(g(k + 1)) <= tol) return
       end do
+   end subroutine
+
+   !---- the operator L itself -------------------------------------------------------------------------------------------
+   !> one vector through nlg_lns_apply
+   subroutine lns_apply_one(h, vec_in, vec_out, trans, coef, where)
+      type(c_ptr), intent(in) :: h
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(inout) :: vec_out
+      logical, intent(in) :: trans
+      real(dp), intent(in) :: coef(3)
+      character(len=*), intent(in) :: where
+      type(c_ptr) :: hi(1), ho(1)
+      select type (vec_in)
+      type is (nek_dvector)
+         select type (vec_out)
+         type is (nek_dvector)
+            call nek_dvector_ensure(vec_out)
+            hi(1) = nek_dvector_handle(vec_in); ho(1) = vec_out%h
+            call nlg_check(c_lns_apply(h, 1_c_int, hi, ho, merge(1_c_int, 0_c_int, trans), coef), where)
+         class default
+            call type_error('vec_out', 'nek_dvector', 'OUT', this_module, where)
+         end select
+      class default
+         call type_error('vec_in', 'nek_dvector', 'IN', this_module, where)
+      end select
+   end subroutine
+
+   subroutine init_lns(self)
+      class(lns_linop), intent(inout) :: self
+      integer(c_int) :: rc
+      if (c_associated(self%h) .and. self%owner == loc(self)) rc = c_lns_destroy(self%h)
+      self%h = c_null_ptr
+      if (self%re <= 0.0_dp) self%re = nek_case%re
+      call nlg_check(c_lns_create(nlg_mesh, nek_dvector_handle(self%baseflow), self%re, self%h), 'init_lns')
+      self%owner = loc(self)
+   end subroutine
+
+   function lns_handle(self) result(h)
+      class(lns_linop), intent(in) :: self
+      type(c_ptr) :: h
+      if (.not. c_associated(self%h) .or. self%owner /= loc(self)) then
+         write (*, '(A)') 'ERROR in '//this_module//': lns_linop%init() has not been called on this object'
+         error stop 1
+      end if
+      h = self%h
+   end function
+
+   subroutine lns_matvec(self, vec_in, vec_out)
+      class(lns_linop), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      call lns_apply_one(lns_handle(self), vec_in, vec_out, .false., coef_L, 'lns_matvec')
+   end subroutine
+
+   subroutine lns_rmatvec(self, vec_in, vec_out)
+      class(lns_linop), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      call lns_apply_one(lns_handle(self), vec_in, vec_out, .true., coef_L, 'lns_rmatvec')
+   end subroutine
+
+   subroutine finalize_lns(self)
+      type(lns_linop), intent(inout) :: self
+      integer(c_int) :: rc
+      if (c_associated(self%h) .and. self%owner == loc(self)) rc = c_lns_destroy(self%h)
+      self%h = c_null_ptr; self%owner = 0
+   end subroutine
+
+   !> nek_otd%matvec / rmatvec (apply_LNS / apply_adjLNS, src/neklab_otd.f90:76-116)
+   subroutine otd_apply_lns(self, vec_in, vec_out, trans, where)
+      class(nek_otd), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(inout) :: vec_out
+      logical, intent(in) :: trans
+      character(len=*), intent(in) :: where
+      if (self%owner /= loc(self)) then
+         if (self%owner /= 0) then
+            write (*, '(A)') 'ERROR in '//this_module//': '//where//': this nek_otd is a copy of an initialised one: call init() on it'
+            error stop 1
+         end if
+         self%owner = loc(self)      ! before init(): about the frozen base flow, with the case's Re
+         if (.not. self%cfg_set) self%cfg = nek_case
+      end if
+      if (.not. c_associated(self%hlns)) &
+         call nlg_check(c_lns_create(nlg_mesh, nek_dvector_handle(self%baseflow), self%cfg%re, self%hlns), where)
+      if (self%moving .and. c_associated(self%h)) then
+         call nek_dvector_ensure(self%bf_now)
+         call nlg_check(c_otd_get_baseflow(self%h, self%bf_now%h), where)
+         call nlg_check(c_lns_set_baseflow(self%hlns, self%bf_now%h), where)
+      end if
+      call lns_apply_one(self%hlns, vec_in, vec_out, trans, coef_L, where)
+   end subroutine
+
+   subroutine apply_LNS(self, vec_in, vec_out)
+      class(nek_otd), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      call otd_apply_lns(self, vec_in, vec_out, .false., 'apply_LNS')
+   end subroutine
+
+   subroutine apply_adjLNS(self, vec_in, vec_out)
+      class(nek_otd), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      call otd_apply_lns(self, vec_in, vec_out, .true., 'apply_adjLNS')
+   end subroutine
+
+   subroutine otd_linop_matvec(self, vec_in, vec_out)
+      class(nek_otd_linop), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      if (.not. associated(self%otd)) then
+         write (*, '(A)') 'ERROR in '//this_module//': nek_otd_linop%otd points to no nek_otd'
+         error stop 1
+      end if
+      call otd_apply_lns(self%otd, vec_in, vec_out, .false., 'apply_LNS')
+   end subroutine
+
+   subroutine otd_linop_rmatvec(self, vec_in, vec_out)
+      class(nek_otd_linop), intent(inout) :: self
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      if (.not. associated(self%otd)) then
+         write (*, '(A)') 'ERROR in '//this_module//': nek_otd_linop%otd points to no nek_otd'
+         error stop 1
+      end if
+      call otd_apply_lns(self%otd, vec_in, vec_out, .true., 'apply_adjLNS')
+   end subroutine
+
+   !> apply_exptA (src/linops/neklab_linops.f90:224-266): the interface expmlib expects, on top of matvec / rmatvec
+   subroutine apply_exptA(vec_out, A, vec_in, tau, info, trans)
+      class(abstract_vector_rdp), intent(out) :: vec_out
+      class(abstract_linop_rdp), intent(inout) :: A
+      class(abstract_vector_rdp), intent(in) :: vec_in
+      real(dp), intent(in) :: tau
+      integer, intent(out) :: info
+      logical, optional, intent(in) :: trans
+      logical :: transpose
+      transpose = .false.
+      if (present(trans)) transpose = trans
+      info = 0
+      select type (vec_in)
+      type is (nek_dvector)
+         select type (vec_out)
+         type is (nek_dvector)
+            select type (A)
+            class is (abstract_exptA_linop_rdp)
+               A%tau = tau
+               if (transpose) then
+                  call A%rmatvec(vec_in, vec_out)
+               else
+                  call A%matvec(vec_in, vec_out)
+               end if
+            class default
+               call type_error('A', 'abstract_exptA_linop', 'INOUT', this_module, 'apply_exptA')
+            end select
+         class default
+            call type_error('vec_out', 'nek_dvector', 'OUT', this_module, 'apply_exptA')
+         end select
+      class default
+         call type_error('vec_in', 'nek_dvector', 'IN', this_module, 'apply_exptA')
+      end select
+   end subroutine
+
+   !> the base flow of the array routines below (the reference reads Nek5000's vx, vy, vz); Re is the case's
+   subroutine set_lns_baseflow(bf)
+      type(nek_dvector), intent(in) :: bf
+      if (c_associated(lns_arrays_h)) then
+         call nlg_check(c_lns_set_baseflow(lns_arrays_h, nek_dvector_handle(bf)), 'set_lns_baseflow')
+         call nlg_check(c_lns_set_re(lns_arrays_h, nek_case%re), 'set_lns_baseflow')
+      else
+         call nlg_check(c_lns_create(nlg_mesh, nek_dvector_handle(bf), nek_case%re, lns_arrays_h), 'set_lns_baseflow')
+      end if
+   end subroutine
+
+   !> host arrays (Nek5000's element-major layout) -> scratch vector -> nlg_lns_apply -> host arrays.  u / p absent: zero
+   subroutine lns_arrays(who, coef, trans, ox, oy, oz, ux, uy, uz, pp)
+      character(len=*), intent(in) :: who
+      real(dp), intent(in) :: coef(3)
+      logical, intent(in) :: trans
+      real(dp), intent(inout) :: ox(*), oy(*), oz(*)
+      real(dp), optional, intent(in) :: ux(*), uy(*), uz(*), pp(*)
+      type(c_ptr) :: hi(1), ho(1)
+      if (.not. c_associated(lns_arrays_h)) then
+         write (*, '(A)') 'ERROR in '//this_module//': '//who//': no base flow: call set_lns_baseflow(bf) first'
+         error stop 1
+      end if
+      call nek_dvector_ensure(lns_arrays_in); call nek_dvector_ensure(lns_arrays_out)
+      call nlg_check(c_vec_zero(lns_arrays_in%h), who)
+      if (present(ux)) then
+         call nlg_check(c_vec_set_field(lns_arrays_in%h, 0_c_int, 0_c_int, ux, nek_lvn), who)
+         call nlg_check(c_vec_set_field(lns_arrays_in%h, 1_c_int, 0_c_int, uy, nek_lvn), who)
+         if (nek_ldim == 3) call nlg_check(c_vec_set_field(lns_arrays_in%h, 2_c_int, 0_c_int, uz, nek_lvn), who)
+      end if
+      if (present(pp)) call nlg_check(c_vec_set_field(lns_arrays_in%h, 3_c_int, 0_c_int, pp, nek_lpn), who)
+      hi(1) = lns_arrays_in%h; ho(1) = lns_arrays_out%h
+      call nlg_check(c_lns_apply(lns_arrays_h, 1_c_int, hi, ho, merge(1_c_int, 0_c_int, trans), coef), who)
+      call nlg_check(c_vec_get_field(lns_arrays_out%h, 0_c_int, 0_c_int, ox, nek_lvn), who)
+      call nlg_check(c_vec_get_field(lns_arrays_out%h, 1_c_int, 0_c_int, oy, nek_lvn), who)
+      if (nek_ldim == 3) call nlg_check(c_vec_get_field(lns_arrays_out%h, 2_c_int, 0_c_int, oz, nek_lvn), who)
+   end subroutine
+
+   logical function is_trans(trans)
+      logical, optional, intent(in) :: trans
+      is_trans = .false.
+      if (present(trans)) is_trans = trans
+   end function
+
+   subroutine compute_LNS_conv(c_x, c_y, c_z, uxp, uyp, uzp, trans)
+      real(dp), intent(inout) :: c_x(*), c_y(*), c_z(*)
+      real(dp), intent(in) :: uxp(*), uyp(*), uzp(*)
+      logical, optional :: trans
+      call lns_arrays('compute_LNS_conv', coef_conv, is_trans(trans), c_x, c_y, c_z, uxp, uyp, uzp)
+   end subroutine
+
+   subroutine compute_LNS_laplacian(d_x, d_y, d_z, uxp, uyp, uzp)
+      real(dp), intent(inout) :: d_x(*), d_y(*), d_z(*)
+      real(dp), intent(in) :: uxp(*), uyp(*), uzp(*)
+      call lns_arrays('compute_LNS_laplacian', coef_lap, .false., d_x, d_y, d_z, uxp, uyp, uzp)
+   end subroutine
+
+   subroutine compute_LNS_gradp(gp_x, gp_y, gp_z, pp)
+      real(dp), intent(inout) :: gp_x(*), gp_y(*), gp_z(*)
+      real(dp), intent(in) :: pp(*)
+      call lns_arrays('compute_LNS_gradp', coef_gradp, .false., gp_x, gp_y, gp_z, pp=pp)
+   end subroutine
+
+   subroutine apply_L(Lux, Luy, Luz, ux, uy, uz, pres, trans)
+      real(dp), intent(inout) :: Lux(*), Luy(*), Luz(*)
+      real(dp), intent(in) :: ux(*), uy(*), uz(*), pres(*)
+      logical, optional, intent(in) :: trans
+      call lns_arrays('apply_L', coef_L, is_trans(trans), Lux, Luy, Luz, ux, uy, uz, pres)
+   end subroutine
+
+   subroutine apply_Lv(Lux, Luy, Luz, ux, uy, uz, trans)
+      real(dp), intent(inout) :: Lux(*), Luy(*), Luz(*)
+      real(dp), intent(in) :: ux(*), uy(*), uz(*)
+      logical, optional, intent(in) :: trans
+      call lns_arrays('apply_Lv', coef_Lv, is_trans(trans), Lux, Luy, Luz, ux, uy, uz)
    end subroutine
 
    !---- eigs / svds on the device block path ---------------------------------------------------------------------------

@@ -1526,6 +1526,91 @@ def linear_stability_analysis_periodic_orbit(op: exptA_orbit_linop, kdim: int, n
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# The operator L itself, in strong form (nlg_lns_*; apply_L and its pieces, src/linops/neklab_linops.f90:24-28, :268-426)
+LNS_COEF = {"apply_L": (1.0, -1.0, -1.0), "apply_Lv": (1.0, -1.0, 0.0), "compute_LNS_laplacian": (1.0, 0.0, 0.0),
+            "compute_LNS_conv": (0.0, 1.0, 0.0), "compute_LNS_gradp": (0.0, 0.0, 1.0)}
+
+
+class lns_linop:
+    """L about `baseflow` at Reynolds number `re`: out = c_lap / re lap(u~) + c_conv conv(U, u~) / bm1 + c_p grad(P), element-local,
+    neither masked nor assembled (include/neklab_gpu.h: nlg_lns_apply).  matvec / rmatvec are apply_L, direct and adjoint."""
+
+    def __init__(self, baseflow: nek_dvector, re: float):
+        self.mesh, self.lib, self.baseflow, self.re = baseflow.mesh, baseflow.lib, baseflow, float(re)
+        self.h = None
+        h = vp()
+        check(self.lib.nlg_lns_create(self.mesh.h, baseflow.h, float(re), C.byref(h)))
+        self.h = h
+
+    def set_baseflow(self, baseflow: nek_dvector):
+        check(self.lib.nlg_lns_set_baseflow(self.h, baseflow.h))
+        self.baseflow = baseflow
+
+    def set_re(self, re: float):
+        check(self.lib.nlg_lns_set_re(self.h, float(re)))
+        self.re = float(re)
+
+    def apply(self, vecs, outs, trans: bool = False, coef=(1.0, -1.0, -1.0)):
+        """outs[v] = L vecs[v] for up to four vectors in one launch (a single vector may be given as such)."""
+        vecs = [vecs] if isinstance(vecs, nek_dvector) else list(vecs)
+        outs = [outs] if isinstance(outs, nek_dvector) else list(outs)
+        if len(vecs) != len(outs) or not all(isinstance(x, nek_dvector) for x in vecs + outs):
+            raise TypeError("type_error: as many nek_dvector in as out expected")
+        s = len(vecs)
+        ai = (vp * max(s, 1))(*[x.h for x in vecs])
+        ao = (vp * max(s, 1))(*[x.h for x in outs])
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.shape != (3,):
+            raise ValueError("coef = (c_lap, c_conv, c_p)")
+        check(self.lib.nlg_lns_apply(self.h, s, ai, ao, int(bool(trans)), dptr(c)))
+
+    def matvec(self, vec_in: nek_dvector, vec_out: nek_dvector):
+        self.apply([vec_in], [vec_out], False)
+
+    def rmatvec(self, vec_in: nek_dvector, vec_out: nek_dvector):
+        self.apply([vec_in], [vec_out], True)
+
+    def matvec_block(self, vecs: list, outs: list, trans: bool = False):
+        self.apply(vecs, outs, trans)
+
+    def close(self):
+        if self.h:
+            self.lib.nlg_lns_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def apply_L(lns: lns_linop, vec_in, vec_out, trans: bool = False):
+    """reference: apply_L (neklab_linops.f90:382-404): nu lap(u) - conv(u) - grad(p)"""
+    lns.apply(vec_in, vec_out, trans, LNS_COEF["apply_L"])
+
+
+def apply_Lv(lns: lns_linop, vec_in, vec_out, trans: bool = False):
+    """reference: apply_Lv (neklab_linops.f90:406-426): apply_L without the pressure gradient"""
+    lns.apply(vec_in, vec_out, trans, LNS_COEF["apply_Lv"])
+
+
+def compute_LNS_conv(lns: lns_linop, vec_in, vec_out, trans: bool = False):
+    """reference: compute_LNS_conv (neklab_linops.f90:268-313): the linearised convective term, pointwise (+ sign)"""
+    lns.apply(vec_in, vec_out, trans, LNS_COEF["compute_LNS_conv"])
+
+
+def compute_LNS_laplacian(lns: lns_linop, vec_in, vec_out):
+    """reference: compute_LNS_laplacian (neklab_linops.f90:315-330): nu lap(u)"""
+    lns.apply(vec_in, vec_out, False, LNS_COEF["compute_LNS_laplacian"])
+
+
+def compute_LNS_gradp(lns: lns_linop, vec_in, vec_out):
+    """reference: compute_LNS_gradp (neklab_linops.f90:368-380): grad of the pressure mapped to the velocity mesh"""
+    lns.apply(vec_in, vec_out, False, LNS_COEF["compute_LNS_gradp"])
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Optimally time-dependent (OTD) modes.  Reference: otd_opts / nek_otd (src/neklab_otd.f90), otd_analysis
 # (src/neklab_analysis.f90:214-344).  The time stepping, the reduced operator, the forcing and the re-orthonormalisation are
 # device work (nlg_otd_*, DESIGN.md 3.2 "OTD mode"); the r x r spectral analysis and the log files are host work, as in the
@@ -1576,6 +1661,7 @@ class nek_otd:
         self.op = exptA_linop(1.0 if tau is None else tau, baseflow, **cfg)
         self.h = None
         self.opts = None
+        self._lns, self._lns_bf = None, None   # the strong-form L of matvec / rmatvec, created by the first call
 
     def init(self, opts: "otd_opts | None" = None, basis0: "list | None" = None, icdir: str = "."):
         """init_OTD (src/neklab_otd.f90:118-204): random basis (seeds 1 .. r), the first n_usrIC modes from
@@ -1613,11 +1699,41 @@ class nek_otd:
     def advance(self, n: int = 1):
         check(self.lib.nlg_otd_advance(self.h, int(n)))
 
-    def reduced(self):
-        """(Lr, G): the basis is orthonormalised, then Lr_ij = <u_i, L u_j> on the current state; G is the Gram matrix before."""
+    def reduced(self, form: str = "weak"):
+        """(Lr, G): the basis is orthonormalised, then Lr_ij = <u_i, L u_j> on the current state; G is the Gram matrix before.
+        form = "weak": L u_j in weak form from the operators of the time step (nlg_otd_reduced).  form = "strong": the reference's
+        route (otd_analysis, src/neklab_analysis.f90:291-298), Lr_ij = <u_i, matvec(u_j)> (trans: rmatvec) with the pointwise L,
+        the same G."""
+        if form not in ("weak", "strong"):
+            raise ValueError("reduced: form is 'weak' or 'strong'")
         Lr, G = np.zeros((self.r, self.r), order="F"), np.zeros((self.r, self.r), order="F")
         check(self.lib.nlg_otd_reduced(self.h, dptr(Lr), dptr(G)))
+        if form == "strong":
+            B = [self.basis(j) for j in range(self.r)]
+            W = [nek_dvector(self.mesh) for _ in range(self.r)]
+            self._apply_lns(B, W, bool(self.opts.trans))
+            for i in range(self.r):
+                for j in range(self.r):
+                    Lr[i, j] = B[i].dot(W[j])
         return Lr, G
+
+    # ---- nek_otd as an abstract_linop_rdp (src/neklab_otd.f90:44-45, :76-116): matvec = apply_LNS, rmatvec = apply_adjLNS
+    def _apply_lns(self, vecs, outs, trans: bool):
+        """apply_L with the vectors' own pressure, about the operator's base flow when it is frozen and about current_baseflow()
+        when solve_baseflow is on (the base-flow side of the convective term is rebuilt before every such call)"""
+        moving = self.h is not None and self.opts is not None and self.opts.solve_baseflow
+        if self._lns is None:
+            self._lns = lns_linop(self.baseflow, self.op.cfg.re)
+        if moving:
+            self._lns_bf = self.current_baseflow(self._lns_bf)
+            self._lns.set_baseflow(self._lns_bf)
+        self._lns.apply(vecs, outs, trans)
+
+    def matvec(self, vec_in: nek_dvector, vec_out: nek_dvector):
+        self._apply_lns([vec_in], [vec_out], False)
+
+    def rmatvec(self, vec_in: nek_dvector, vec_out: nek_dvector):
+        self._apply_lns([vec_in], [vec_out], True)
 
     def basis(self, i: int, out: "nek_dvector | None" = None) -> nek_dvector:
         out = out if out is not None else nek_dvector(self.mesh)
@@ -1662,6 +1778,9 @@ class nek_otd:
         return paths
 
     def close(self):
+        if getattr(self, "_lns", None) is not None:
+            self._lns.close()
+            self._lns = None
         if self.h:
             self.lib.nlg_otd_destroy(self.h)
             self.h = None
