@@ -1567,14 +1567,56 @@ struct Lanes {
     int64_t ld() const { return nl > 1 ? op->slab_ld : 0; }   // the lane stride the kernels receive
 };
 
-// The velocity solve in three pieces: problem set-up, one operator application, bookkeeping afterwards.
+// One Helmholtz solve w = QQ^T (h1 A + h2 B) p by Jacobi-PCG -- the velocity's (helm_problem) and the temperature's (heat_problem) -- in
+// pieces: problem set-up, one operator application, the run; the iteration bookkeeping stays with the two callers.  The solve carries
+// all that an application needs: the operator is not consulted again.
 struct HelmSolve {
     CGProblem P;
-    bool xp = false;
-    double nu = 0.0, h2 = 0.0;
+    double *x[1], *r[1], *z[1], *p[1], *w[1], *pc[1], *sd[1];   // the pointer arrays of a one-field solve (the velocity's are the operator's)
+    bool xp = false;      // every vector of the iteration in the x-planes-first layout
+    double h1 = 0.0, h2 = 0.0;
     double *pw_part = nullptr;
+    double *ring = nullptr;   // direction ring (deferred solution update): slot 0 of field 0; field q is q * ring_field doubles behind
+    int64_t ring_field = 0;
     mutable int it = 0;   // operator applications so far (= the slot of the direction ring the next one writes, modulo its depth)
 };
+
+// the settings common to the two solves; the vectors, the preconditioner and the prediction are the caller's
+void helm_common(const Lanes &L, int nf, double h1, double h2, HelmSolve &H) {
+    nlg_linop *op = L.op;
+    nlg_mesh *m = op->mesh;
+    const auto &c = op->cfg;
+    CGProblem &P = H.P;
+    H.h1 = h1;
+    H.h2 = h2;
+    P.nf = nf;
+    P.n = m->lvn;
+    P.tol2 = c.vtol * c.vtol;
+    P.use_tol = c.fixed_iters_v > 0 ? 0 : 1;
+    P.maxit = c.fixed_iters_v > 0 ? c.fixed_iters_v : c.maxit_v;
+    P.s = op->d_s;
+    P.inv_n = 0.0;
+    P.nl = L.nl;
+    P.ld = L.ld();
+    // The Dirichlet mask is not applied to w: p is masked (z = pc r with pc = mask/diag), so (p, w) does not see the masked
+    // entries, and k_cg_update zeroes the residual where pc == 0.
+    // (p, w) = sum over the local dofs of p . w_local (p is continuous), summed inside the operator kernel, which also
+    // performs p <- z + beta p while it loads p.
+    H.pw_part = op->d_part;
+    P.pw_part = H.pw_part;
+    P.pw_n = sem_axhelm_blocks(m, P.nf);
+    P.pw_sum = false;
+    P.fused_pupdate = true;
+    // deferred solution update: one ring serves both solves, the scalar's directions one field wide (the two solves never overlap:
+    // each ring is consumed right after its solve).  The single-reduction variant keeps p itself: it runs without a ring (ph = 0)
+    if (op->ph > 0) {
+        H.ring = op->phist;
+        H.ring_field = m->lvs;
+        for (int q = 0; q < P.nf; ++q) P.hist.p0[q] = H.ring + q * H.ring_field;
+        P.hist.stride = P.nf * H.ring_field;
+        P.hist.ph = op->ph;
+    }
+}
 
 int helm_problem(const Lanes &L, int order, double h2, HelmSolve &H) {
     nlg_linop *op = L.op;
@@ -1586,12 +1628,10 @@ int helm_problem(const Lanes &L, int order, double h2, HelmSolve &H) {
     // free at this point), the solution on the way out (into rhs, which the caller reads as the increment)
     const bool xp = op->use_xp > 0;
     H.xp = xp;
-    H.h2 = h2;
     const bool born_xp = xp && op->rhs_in_xp;   // adv_a wrote the right-hand side masked and slab-permuted already
     op->rhs_in_xp = false;
     if (xp && !born_xp) NLG_TRY(sem_to_xp(m, op->rhs, op->gp, dim, L.nl, L.ld(), m->d_mask));   // ... and masked on the way
-    P.nf = dim;
-    P.n = m->lvn;
+    helm_common(L, dim, 1.0 / c.re, h2, H);
     P.x = op->x;
     P.r = (xp && !born_xp) ? op->gp : op->rhs;
     P.z = op->z;
@@ -1604,76 +1644,75 @@ int helm_problem(const Lanes &L, int order, double h2, HelmSolve &H) {
     }
     P.ipw = xp ? m->d_vmult_xp : m->d_vmult;
     P.nw = xp ? op->nwv_xp : op->nwv;
-    P.tol2 = c.vtol * c.vtol;
-    P.use_tol = c.fixed_iters_v > 0 ? 0 : 1;
-    P.maxit = c.fixed_iters_v > 0 ? c.fixed_iters_v : c.maxit_v;
-    P.s = op->d_s;
-    P.inv_n = 0.0;
-    P.nl = L.nl;
-    P.ld = L.ld();
+    if (op->use_sr) P.sd = op->cgs;
     // the iteration count barely changes from one time step to the next: launch exactly the previous count, then look at
     // the flags every second iteration; launches issued after convergence are gated on the device but still cost a launch
     P.chunk = 2;
     for (int v = 0; v < L.nl; ++v) P.chunk = std::max(P.chunk, std::min(op->pred[v].v.predict(op->istep), 64));
-    H.nu = 1.0 / c.re;
-    // w = QQ^T (nu A + h2 B) p.  The Dirichlet mask is not applied to w: p is masked (z = pc r with pc = mask/diag), so
-    // (p, w) does not see the masked entries, and k_cg_update zeroes the residual where pc == 0.
-    // (p, w) = sum over the local dofs of p . w_local (p is continuous), summed inside the operator kernel, which also
-    // performs p <- z + beta p while it loads p.
-    H.pw_part = op->d_part;
-    P.pw_part = H.pw_part;
-    P.pw_n = sem_axhelm_blocks(m, dim);
-    P.pw_sum = false;
-    P.fused_pupdate = true;
     // z = pc r is a pointwise product of what the operator kernel can read itself: it is not stored (NLG_PCG_STORE_Z=1 keeps it)
     P.z_free = op->z_free;
-    if (op->ph > 0) {
-        for (int q = 0; q < dim; ++q) P.hist.p0[q] = op->phist + (int64_t)q * m->lvs;
-        P.hist.stride = (int64_t)dim * m->lvs;
-        P.hist.ph = op->ph;
-    }
     return 0;
 }
 
-int helm_apply(const Lanes &L, const HelmSolve &H) {
+// The temperature's solve at BDF order k: one field, natural layout, z stored, the masked Jacobi array pct[k]; the right-hand side is in
+// trhs, the increment goes to tx.  The compact preconditioner (one 1 / diag and a mask byte in place of three masked arrays: nothing to
+// save with one field), z-free (which builds on it) and the slab-permuted layout (pct and tmask exist in the natural one only) are the
+// velocity's alone.
+void heat_problem(const Lanes &L, int k, double h1, double h2, HelmSolve &H) {
     nlg_linop *op = L.op;
-    nlg_mesh *m = op->mesh;
-    const int dim = m->dim;
-    // z-free: the kernel reads the residual where it read z, and 1 / diag and the mask bytes of the solve (H.P.pc, H.P.pc_mb)
-    double *const *zf = H.P.z_free ? H.P.r : op->z;
-    const double *pcinv = H.P.z_free ? H.P.pc[0] : nullptr;
-    const unsigned char *pcmb = H.P.z_free ? H.P.pc_mb : nullptr;
-    if (H.P.hist.ph > 0) {
+    CGProblem &P = H.P;
+    helm_common(L, 1, h1, h2, H);
+    H.x[0] = op->tx, H.r[0] = op->trhs, H.z[0] = op->tz, H.p[0] = op->tpv, H.w[0] = op->tw, H.pc[0] = op->pct[k], H.sd[0] = op->tcgs;
+    P.x = H.x, P.r = H.r, P.z = H.z, P.p = H.p, P.w = H.w, P.pc = H.pc;
+    if (op->use_sr) P.sd = H.sd;
+    P.ipw = op->mesh->d_vmult;
+    P.nw = op->nwv;
+    P.chunk = 2;
+    for (int v = 0; v < L.nl; ++v) P.chunk = std::max(P.chunk, std::min(op->pred[v].last_titers, 64));
+}
+
+int helm_apply(const Lanes &L, const HelmSolve &H) {
+    nlg_mesh *m = L.op->mesh;
+    const CGProblem &P = H.P;
+    // z-free: the kernel reads the residual where it read z, and 1 / diag and the mask bytes of the solve (P.pc, P.pc_mb)
+    double *const *zf = P.z_free ? P.r : P.z;
+    const double *pcinv = P.z_free ? P.pc[0] : nullptr;
+    const unsigned char *pcmb = P.z_free ? P.pc_mb : nullptr;
+    if (P.hist.ph > 0) {
         // direction ring: read direction it - 1, store direction it one slot further (the first application multiplies slot ph - 1 by
         // beta = 0: the ring is zeroed with the slab and holds finite values ever after)
-        const int ph = H.P.hist.ph, so = H.it % ph, si = (H.it + ph - 1) % ph;
+        const int ph = P.hist.ph, so = H.it % ph, si = (H.it + ph - 1) % ph;
         ++H.it;
         double *pin[3] = {nullptr, nullptr, nullptr};
-        for (int q = 0; q < dim; ++q) pin[q] = op->phist + si * H.P.hist.stride + (int64_t)q * m->lvs;
-        NLG_TRY(sem_axhelm(m, pin, op->w, dim, H.nu, H.h2, H.pw_part, zf, op->d_s + S_BETA, op->d_s + S_DONE, H.xp, L.nl, L.ld(),
-                           (so - si) * H.P.hist.stride, pcinv, pcmb));
+        for (int q = 0; q < P.nf; ++q) pin[q] = H.ring + si * P.hist.stride + q * H.ring_field;
+        NLG_TRY(sem_axhelm(m, pin, P.w, P.nf, H.h1, H.h2, H.pw_part, zf, P.s + S_BETA, P.s + S_DONE, H.xp, P.nl, P.ld, (so - si) * P.hist.stride, pcinv, pcmb));
     } else {
-        NLG_TRY(sem_axhelm(m, op->pv, op->w, dim, H.nu, H.h2, H.pw_part, zf, op->d_s + S_BETA, op->d_s + S_DONE, H.xp, L.nl, L.ld(), 0, pcinv, pcmb));
+        NLG_TRY(sem_axhelm(m, P.p, P.w, P.nf, H.h1, H.h2, H.pw_part, zf, P.s + S_BETA, P.s + S_DONE, H.xp, P.nl, P.ld, 0, pcinv, pcmb));
     }
-    NLG_TRY(sem_gs(m, op->w, dim, op->d_s + S_DONE, H.xp ? LAYOUT_XP : LAYOUT_NAT, L.nl, L.ld(), L.ld()));
+    NLG_TRY(sem_gs(m, P.w, P.nf, P.s + S_DONE, H.xp ? LAYOUT_XP : LAYOUT_NAT, P.nl, P.ld, P.ld));
     return 0;
+}
+
+// the PCG of a filled solve; iters[v]: the iterations of lane v
+int helm_run(const Lanes &L, HelmSolve &H, int *iters) {
+    nlg_mesh *m = L.op->mesh;
+    if (H.P.sd) {   // single-reduction variant
+        H.P.apply_plain = [&H, m]() -> int {   // w = QQ^T (h1 A + h2 B) z and the first-stage sums of (z, w): no direction update inside
+            const CGProblem &P = H.P;
+            NLG_TRY(sem_axhelm(m, P.z, P.w, P.nf, H.h1, H.h2, H.pw_part, nullptr, nullptr, P.s + S_DONE, H.xp, P.nl, P.ld));
+            return sem_gs(m, P.w, P.nf, P.s + S_DONE, H.xp ? LAYOUT_XP : LAYOUT_NAT, P.nl, P.ld, P.ld);
+        };
+    }
+    auto apply = [&](double *) -> int { return helm_apply(L, H); };
+    return run_pcg(L.op, H.P, apply, iters);
 }
 
 int helm_solve(const Lanes &L, int order, double h2) {
     nlg_linop *op = L.op;
     HelmSolve H;
     NLG_TRY(helm_problem(L, order, h2, H));
-    if (op->use_sr) {
-        nlg_mesh *m = op->mesh;
-        H.P.sd = op->cgs;
-        H.P.apply_plain = [&, op, m]() -> int {   // w = QQ^T (nu A + h2 B) z and the first-stage sums of (z, w): no direction update inside
-            NLG_TRY(sem_axhelm(m, op->z, op->w, m->dim, H.nu, H.h2, H.pw_part, nullptr, nullptr, op->d_s + S_DONE, H.xp, L.nl, L.ld()));
-            return sem_gs(m, op->w, m->dim, op->d_s + S_DONE, H.xp ? LAYOUT_XP : LAYOUT_NAT, L.nl, L.ld(), L.ld());
-        };
-    }
-    auto apply = [&](double *) -> int { return helm_apply(L, H); };
     int iters[kMaxLanes] = {};
-    NLG_TRY(run_pcg(op, H.P, apply, iters));
+    NLG_TRY(helm_run(L, H, iters));
     // (slab-permuted solve: the increment stays in that layout, adv_b reads it through the slot table)
     for (int v = 0; v < L.nl; ++v) {
         op->st_viters += iters[v];
@@ -1685,7 +1724,7 @@ int helm_solve(const Lanes &L, int order, double h2) {
 
 // One scalar (temperature) step of the Boussinesq coupling, see oracle/lns.py advance (ifheat branch):
 //   rhocp (b0 theta^{n+1} - sum bd_j theta^{n-j}) / dt = -rhocp EXT[(U.grad) theta + (u.grad) Theta] + conductivity lap theta^{n+1}
-// in residual form, Jacobi-PCG; the new level ends in tbuf[0].
+// in residual form; the solve is an instance of the velocity's Helmholtz PCG (HelmSolve, heat_problem); the new level ends in tbuf[0].
 int heat_step(const Lanes &L, int k, double b0) {
     nlg_linop *op = L.op;
     nlg_mesh *m = op->mesh;
@@ -1732,63 +1771,10 @@ int heat_step(const Lanes &L, int k, double b0) {
         CF3 mk = {{m->d_tmask, nullptr, nullptr}};
         NLG_LAUNCH(k_colmul_gated<1>, lgrid(grid_for(m->lvn), nl), dim3(NT), 0, st, (const double *)nullptr, rhs, mk, m->lvn, ld);
     }
-    // Jacobi-PCG, one field; the operator kernel sums (p, w) and updates p itself
-    double *x[1] = {op->tx}, *z[1] = {op->tz}, *p[1] = {op->tpv}, *pc[1] = {op->pct[k]};
-    CGProblem P;
-    P.nf = 1;
-    P.n = m->lvn;
-    P.x = x;
-    P.r = trhs;
-    P.z = z;
-    P.p = p;
-    P.w = tw;
-    P.pc = pc;
-    P.ipw = m->d_vmult;
-    P.nw = op->nwv;
-    P.tol2 = c.vtol * c.vtol;
-    P.use_tol = c.fixed_iters_v > 0 ? 0 : 1;
-    P.maxit = c.fixed_iters_v > 0 ? c.fixed_iters_v : c.maxit_v;
-    P.s = op->d_s;
-    P.inv_n = 0.0;
-    P.nl = nl;
-    P.ld = ld;
-    P.chunk = 2;
-    for (int v = 0; v < nl; ++v) P.chunk = std::max(P.chunk, std::min(op->pred[v].last_titers, 64));
-    P.pw_part = op->d_part;
-    P.pw_n = sem_axhelm_blocks(m, 1);
-    P.pw_sum = false;
-    P.fused_pupdate = true;
-    // deferred solution update as in the velocity solve (helm_apply): the scalar's directions use the velocity solve's ring, one field wide
-    // (the two solves never overlap: each ring is consumed right after its solve)
-    const bool defer = op->ph > 0 && !op->use_sr;
-    if (defer) {
-        P.hist.p0[0] = op->phist;
-        P.hist.stride = m->lvs;
-        P.hist.ph = op->ph;
-    }
-    int napp = 0;
-    auto apply = [&](double *) -> int {
-        if (defer) {
-            const int ph = op->ph, so = napp % ph, si = (napp + ph - 1) % ph;
-            ++napp;
-            double *pin[1] = {op->phist + (int64_t)si * m->lvs};
-            NLG_TRY(sem_axhelm(m, pin, tw, 1, h1, h2, op->d_part, z, op->d_s + S_BETA, op->d_s + S_DONE, false, nl, ld, (so - si) * (int64_t)m->lvs));
-        } else {
-            NLG_TRY(sem_axhelm(m, p, tw, 1, h1, h2, op->d_part, z, op->d_s + S_BETA, op->d_s + S_DONE, false, nl, ld));
-        }
-        NLG_TRY(sem_gs(m, tw, 1, op->d_s + S_DONE, LAYOUT_NAT, nl, ld, ld));
-        return 0;
-    };
-    double *sdt[1] = {op->tcgs};
-    if (op->use_sr) {
-        P.sd = sdt;
-        P.apply_plain = [&]() -> int {
-            NLG_TRY(sem_axhelm(m, z, tw, 1, h1, h2, op->d_part, nullptr, nullptr, op->d_s + S_DONE, false, nl, ld));
-            return sem_gs(m, tw, 1, op->d_s + S_DONE, LAYOUT_NAT, nl, ld, ld);
-        };
-    }
+    HelmSolve H;
+    heat_problem(L, k, h1, h2, H);
     int iters[kMaxLanes] = {};
-    NLG_TRY(run_pcg(op, P, apply, iters));
+    NLG_TRY(helm_run(L, H, iters));
     for (int v = 0; v < nl; ++v) {
         op->st_titers += iters[v];
         op->pred[v].last_titers = iters[v];
@@ -1797,8 +1783,8 @@ int heat_step(const Lanes &L, int k, double b0) {
     {
         F3 y = {{op->tbuf[2], nullptr, nullptr}};
         CF3 a = {{op->tbuf[0], nullptr, nullptr}}, b = {{op->tx, nullptr, nullptr}}, none = {{nullptr, nullptr, nullptr}};
-        if (defer)
-            NLG_LAUNCH(k_add_hist<1>, lgrid(grid_for(m->lvn), nl), dim3(NT), 0, st, (const double *)op->d_s, m->lvn, 1, (const int *)nullptr, y, a, b, P.hist, ld);
+        if (H.P.hist.ph > 0)   // the directions are still in the ring (deferred solution update)
+            NLG_LAUNCH(k_add_hist<1>, lgrid(grid_for(m->lvn), nl), dim3(NT), 0, st, (const double *)op->d_s, m->lvn, 1, (const int *)nullptr, y, a, b, H.P.hist, ld);
         else
             NLG_LAUNCH(k_lin3<1>, lgrid(grid_for(m->lvn), nl), dim3(NT), 0, st, m->lvn, y, a, b, 1.0, none, 0.0, ld);
         rotate3(op->tbuf);

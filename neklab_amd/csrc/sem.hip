@@ -2847,77 +2847,64 @@ __global__ __launch_bounds__(256) void k_interp4_mfma(int64_t E, const double *_
 // the form buys is issue slots -- one instruction per 1024 multiply-adds instead of one per 64 plus its operand traffic -- in a kernel
 // that ran at 33 % of the HBM peak with the vector pipe as the bound.  Lanes of a block step: blockIdx.y.
 // =================================================================================================
-template <int N, int ND, bool DYN>
-__global__ __launch_bounds__(256, (ND > 16) ? 1 : 2) void k_conv3m(int64_t E, const double *__restrict__ Jg, const double *__restrict__ DJg, CF3 Ur, CF9 GU,
-                                                   CF3L ul, F3L outl, int adjoint) {
-    static_assert(ND <= 32 && N <= 16 && ND > N, "fine rows in one or two 16-row tiles: lx1 = 8 (lxd 12), 10 (15), 12 (18: rows 16, 17 in a second tile)");
-    constexpr int NP = N * N * N, NPD = ND * ND * ND, NDQ = ND + 1, NQ = N + 1;
-    constexpr int CX = N * N, CY = ND * N, CZ = ND * ND;     // columns of the x, y and z passes
-    constexpr int KF = (N + 3) / 4, KB = (ND + 3) / 4;       // k-steps of a forward (contraction over a coarse index) / backward pass
-    constexpr int RF = KB, RB = KF;                          // D registers that hold real rows: fine rows forward, coarse rows backward
-    constexpr int RT = (ND + 15) / 16;                       // 16-row tiles of a forward result; register r = 4 rt + r' holds fine row lg + 4 r
-    constexpr int NTZ = (CZ + 63) / 64;                      // z-pass column tiles per wave (lx1 = 8: 9 tiles on 4 waves: 3, 2, 2, 2)
-    constexpr bool XF = CX % 16 == 0, YF = CY % 16 == 0, ZF = CZ % 16 == 0;   // full column tiles (lx1 = 8): no column guards
-    constexpr bool RFF = ND % 4 == 0, RBF = N % 4 == 0;                       // full register rows: no row guards
+// The velocity kernel k_conv3m and the temperature kernel k_conv3m_scalar are two instances of the pieces of Conv3m below: geometry and
+// LDS carve-up, the matrix fragments, the chained GEMM, one field through the three forward passes, one accumulator tile set through the
+// three backward passes.  What a kernel adds is which of {value, three derivatives} each of its fields needs and how the z pass folds them.
+// One 16-row tile per matrix: lx1 = 8 (lxd 12) and 10 (15).  lx1 = 12 (lxd 18) needs a SECOND row tile for fine rows 16, 17 in every
+// forward pass; that form was built and measured a tie with the plane-sweep kernel (sem_conv_apply), so the row-tile dimension is gone.
+template <int N, int ND>
+struct Conv3m {
+    static_assert(ND <= 16 && N <= 12 && ND > N, "one 16-row tile per matrix: lx1 = 8 (lxd 12), 10 (15)");
+    static constexpr int NP = N * N * N, NPD = ND * ND * ND, NDQ = ND + 1, NQ = N + 1;
+    static constexpr int CX = N * N, CY = ND * N, CZ = ND * ND;     // columns of the x, y and z passes
+    static constexpr int KF = (N + 3) / 4, KB = (ND + 3) / 4;       // k-steps of a forward (contraction over a coarse index) / backward pass
+    static constexpr int RF = KB, RB = KF;                          // D registers that hold real rows: fine rows forward, coarse rows backward
+    static constexpr int NTZ = (CZ + 63) / 64;                      // z-pass column tiles per wave (lx1 = 8: 9 tiles on 4 waves: 3, 2, 2, 2)
+    static constexpr bool XF = CX % 16 == 0, YF = CY % 16 == 0, ZF = CZ % 16 == 0;   // full column tiles (lx1 = 8): no column guards
+    static constexpr bool RFF = ND % 4 == 0, RBF = N % 4 == 0;                       // full register rows: no row guards
     // forward x pass: (a | j, k) in sA, sB; y pass: (a, b | k) in sAA, sAD, sBA.  Backward: sAA = after the z pass, sA = after the y
     // pass, sB = the result (i | j, k).  lx1 = 10: 80 KB, more than a kernel may declare statically -> dynamic LDS, two blocks per CU still
-    constexpr int LA = NDQ * CX, LY = CZ * N;
-    extern __shared__ double conv3m_dyn[];
-    __shared__ double st_lds[DYN ? 1 : 2 * LA + 3 * LY];
-    double *sA = DYN ? conv3m_dyn : st_lds, *sB = sA + LA, *sAA = sB + LA, *sAD = sAA + LY, *sBA = sAD + LY;
-    const int lane = threadIdx.x & 63, l15 = lane & 15, lg = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t e = blockIdx.x;
-    const int lv = blockIdx.y;
-    if (e >= E) return;
-    double ja[RT][KF], da[RT][KF], jt[KB];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+    static constexpr int LA = NDQ * CX, LY = CZ * N, LDS = 2 * LA + 3 * LY;   // doubles
+    double *sA, *sB, *sAA, *sAD, *sBA;
+    int l15, lg, wave;
+    double ja[KF], da[KF], jt[KB];   // matrix fragments: J and DJ as A[row = fine index][k = coarse index], J^T as A[row = coarse][k = fine]
+
+    __device__ __forceinline__ Conv3m(double *lds, const double *__restrict__ Jg, const double *__restrict__ DJg)
+        : sA(lds), sB(sA + LA), sAA(sB + LA), sAD(sAA + LY), sBA(sAD + LY) {
+        const int lane = threadIdx.x & 63;
+        l15 = lane & 15, lg = lane >> 4;
+        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #pragma unroll
         for (int ks = 0; ks < KF; ++ks) {
-            const bool ok = 16 * rt + l15 < ND && (RBF || lg + 4 * ks < N);
-            ja[rt][ks] = ok ? Jg[(16 * rt + l15) * N + lg + 4 * ks] : 0.0;       // A[row = fine index][k = coarse index]
-            da[rt][ks] = ok ? DJg[(16 * rt + l15) * N + lg + 4 * ks] : 0.0;
+            const bool ok = l15 < ND && (RBF || lg + 4 * ks < N);
+            ja[ks] = ok ? Jg[l15 * N + lg + 4 * ks] : 0.0;
+            da[ks] = ok ? DJg[l15 * N + lg + 4 * ks] : 0.0;
         }
 #pragma unroll
-    for (int ks = 0; ks < KB; ++ks) jt[ks] = (l15 < N && (RFF || lg + 4 * ks < ND)) ? Jg[(lg + 4 * ks) * N + l15] : 0.0;   // A[row = coarse][k = fine] = J^T
-    const v4f64 zero = {0.0, 0.0, 0.0, 0.0};
-    const double sgn = adjoint ? -1.0 : 1.0;
+        for (int ks = 0; ks < KB; ++ks) jt[ks] = (l15 < N && (RFF || lg + 4 * ks < ND)) ? Jg[(lg + 4 * ks) * N + l15] : 0.0;
+    }
+    // is register r of a forward D tile / of a z-pass operand a real fine row; its point in a fine-mesh field (qb: the tile's first row)
+    __device__ __forceinline__ bool fine_row(int r) const { return RFF || lg + 4 * r < ND; }
+    __device__ __forceinline__ int64_t fine_q(int64_t qb, int r) const { return qb + (int64_t)CZ * (lg + 4 * r); }
+
     // one small GEMM: D = sum_ks A[ks] B[ks]
-    auto mm = [&](const auto &A, const auto &B, auto nks) {
+    template <int K>
+    static __device__ __forceinline__ v4f64 mm(const double (&A)[K], const double (&B)[K]) {
+        const v4f64 zero = {0.0, 0.0, 0.0, 0.0};
         v4f64 d = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0], B[0], zero, 0, 0, 0);
 #pragma unroll
-        for (int ks = 1; ks < decltype(nks)::value; ++ks) d = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], B[ks], d, 0, 0, 0);
+        for (int ks = 1; ks < K; ++ks) d = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], B[ks], d, 0, 0, 0);
         return d;
-    };
-    constexpr std::integral_constant<int, KF> kf{};
-    constexpr std::integral_constant<int, KB> kb{};
-    // forward GEMM: all fine rows of the result, out[r] = row lg + 4 r
-    auto fw = [&](const double (&A)[RT][KF], const double (&B)[KF], double (&out)[RF]) {
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            const v4f64 d = mm(A[rt], B, kf);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (4 * rt + q < RF) out[4 * rt + q] = d[q];
-        }
-    };
-    // KEEPU: keep the transporting base flow Ur_j of this wave's column tiles in registers across the three velocity components m instead of
-    // re-reading it for every m (the PMC traffic of this kernel is 1.40 x its algorithmic bytes, and those re-reads are the difference).
-    // Measured at lx1 = 8 (194 registers, no spills): 420 - 432 -> 443 us -- the re-reads come from the Infinity Cache at no cost worth 54
-    // registers; at lxd = 15 it spills (78 registers).  Off.
-    constexpr bool KEEPU = false;
-    double buk[KEEPU ? NTZ : 1][3][RF];
-    double acc[NTZ][3][RF];   // [column tile of this wave][output component][D register = fine level (lane >> 4) + 4 r]
-#pragma unroll
-    for (int ti = 0; ti < NTZ; ++ti)
-#pragma unroll
-        for (int ic = 0; ic < 3; ++ic)
-#pragma unroll
-            for (int r = 0; r < RF; ++r) acc[ti][ic][r] = 0.0;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        const double *__restrict__ u = ul.p[lv][m] + e * NP;
+    }
+
+    // One field u of element e through the three forward passes.  VAL: its value on the fine mesh is wanted (r0), DER: its three
+    // derivatives (r1 = d/dr_2, r2 = d/dr_1, r3 = d/dr_0); a pass without DER issues no DJ GEMM and touches none of sB, sAD, sBA.
+    // Per z-pass column tile ti of this wave: b = pre(okc, qb) lets the caller request its base-flow values of the tile's points
+    // (qb: point (col, row 0) of element e) BEFORE the matrix work; fold(ti, b, r0, r1, r2, r3) then receives the D registers -- row
+    // lg + 4 r in register r -- of what was wanted (the others are zero).  No barrier after the z pass: the caller places it.
+    template <bool VAL, bool DER, typename Pre, typename Fold>
+    __device__ __forceinline__ void forward(const double *__restrict__ u, int64_t e, Pre pre, Fold fold) const {
+        const v4f64 zero = {0.0, 0.0, 0.0, 0.0};
         // ---- x pass: columns (j, k)
         for (int t = wave; t * 16 < CX; t += 4) {
             const int col = 16 * t + l15;
@@ -2925,17 +2912,17 @@ __global__ __launch_bounds__(256, (ND > 16) ? 1 : 2) void k_conv3m(int64_t E, co
             double bv[KF];
 #pragma unroll
             for (int ks = 0; ks < KF; ++ks) bv[ks] = (okc && (RBF || lg + 4 * ks < N)) ? u[lg + 4 * ks + N * col] : 0.0;
-            double aj[RF], ad[RF];
-            fw(ja, bv, aj);
-            fw(da, bv, ad);
+            const v4f64 aj = mm(ja, bv);
+            v4f64 ad = zero;
+            if constexpr (DER) ad = mm(da, bv);
 #pragma unroll
             for (int r = 0; r < RF; ++r)
-                if (okc && (RFF || lg + 4 * r < ND)) {
+                if (okc && fine_row(r)) {
                     sA[lg + 4 * r + NDQ * col] = aj[r];
-                    sB[lg + 4 * r + NDQ * col] = ad[r];
+                    if constexpr (DER) sB[lg + 4 * r + NDQ * col] = ad[r];
                 }
         }
-        lds_barrier();   // (also: every wave has left the z pass of the previous component, whose operands the y pass overwrites)
+        lds_barrier();   // (also: every wave has left the z pass of the previous field, whose operands the y pass overwrites)
         // ---- y pass: columns (a, k)
         for (int t = wave; t * 16 < CY; t += 4) {
             const int col = 16 * t + l15;
@@ -2947,19 +2934,23 @@ __global__ __launch_bounds__(256, (ND > 16) ? 1 : 2) void k_conv3m(int64_t E, co
                 const int j = lg + 4 * ks;
                 const bool ok = okc && (RBF || j < N);
                 va[ks] = ok ? sA[a + NDQ * (j + N * kz)] : 0.0;
-                vb[ks] = ok ? sB[a + NDQ * (j + N * kz)] : 0.0;
+                vb[ks] = (DER && ok) ? sB[a + NDQ * (j + N * kz)] : 0.0;
             }
-            double aa[RF], ad[RF], ba[RF];
-            fw(ja, va, aa);
-            fw(da, va, ad);
-            fw(ja, vb, ba);
+            const v4f64 aa = mm(ja, va);
+            v4f64 ad = zero, ba = zero;
+            if constexpr (DER) {
+                ad = mm(da, va);
+                ba = mm(ja, vb);
+            }
 #pragma unroll
             for (int r = 0; r < RF; ++r)
-                if (okc && (RFF || lg + 4 * r < ND)) {
+                if (okc && fine_row(r)) {
                     const int q = a + ND * (lg + 4 * r + ND * kz);
                     sAA[q] = aa[r];
-                    sAD[q] = ad[r];
-                    sBA[q] = ba[r];
+                    if constexpr (DER) {
+                        sAD[q] = ad[r];
+                        sBA[q] = ba[r];
+                    }
                 }
         }
         lds_barrier();
@@ -2970,53 +2961,43 @@ __global__ __launch_bounds__(256, (ND > 16) ? 1 : 2) void k_conv3m(int64_t E, co
             if (t * 16 < CZ) {   // wave-uniform
                 const int col = 16 * t + l15;
                 const bool okc = ZF || col < CZ;
-                // base-flow values of the tile's points, requested before the matrix work: Ur_j and the three G of this component
-                const int64_t qb = e * NPD + col;
-                double bg[3][RF];
-#pragma unroll
-                for (int r = 0; r < RF; ++r) {
-                    const bool ok = okc && (RFF || lg + 4 * r < ND);
-                    const int64_t q = qb + (int64_t)CZ * (lg + 4 * r);
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        if (KEEPU ? m == 0 : true) buk[KEEPU ? ti : 0][j][r] = ok ? Ur.p[j][q] : 0.0;   // KEEPU: the same for every component m, loaded once and kept
-                        bg[j][r] = ok ? (adjoint ? GU.p[m * 3 + j][q] : GU.p[j * 3 + m][q]) : 0.0;   // multiplies uf_m in output component j
-                    }
-                }
-                const double (&bu)[3][RF] = buk[KEEPU ? ti : 0];
+                // pin the element's offset: otherwise the compiler forms the addresses of the caller's base-flow points once for all fields
+                // and keeps them (54 registers in k_conv3m: one wave per SIMD less at lx1 = 8, spills at lx1 = 10)
+                int64_t eb = e * NPD;
+                asm volatile("" : "+s"(eb));
+                const auto b = pre(okc, eb + col);
                 double v0[KF], v1[KF], v2[KF];
 #pragma unroll
                 for (int ks = 0; ks < KF; ++ks) {
                     const int k = lg + 4 * ks;
                     const bool ok = okc && (RBF || k < N);
                     v0[ks] = ok ? sAA[col + CZ * k] : 0.0;
-                    v1[ks] = ok ? sAD[col + CZ * k] : 0.0;
-                    v2[ks] = ok ? sBA[col + CZ * k] : 0.0;
+                    v1[ks] = (DER && ok) ? sAD[col + CZ * k] : 0.0;
+                    v2[ks] = (DER && ok) ? sBA[col + CZ * k] : 0.0;
                 }
-                double r0[RF], r1[RF], r2[RF], r3[RF];
-                fw(ja, v0, r0);   // uf_m
-                fw(da, v0, r1);   // d/dr_2 (z)
-                fw(ja, v1, r2);   // d/dr_1 (y)
-                fw(ja, v2, r3);   // d/dr_0 (x)
-#pragma unroll
-                for (int r = 0; r < RF; ++r) {
-                    acc[ti][m][r] += sgn * (bu[0][r] * r3[r] + bu[1][r] * r2[r] + bu[2][r] * r1[r]);
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) acc[ti][j][r] += r0[r] * bg[j][r];
+                v4f64 r0 = zero, r1 = zero, r2 = zero, r3 = zero;
+                if constexpr (VAL) r0 = mm(ja, v0);   // the value
+                if constexpr (DER) {
+                    r1 = mm(da, v0);   // d/dr_2 (z)
+                    r2 = mm(ja, v1);   // d/dr_1 (y)
+                    r3 = mm(ja, v2);   // d/dr_0 (x)
                 }
+                fold(ti, b, r0, r1, r2, r3);
             }
         }
     }
-    // ---- backward: J_z^T from registers, J_y^T and J_x^T through LDS, one output component at a time
-#pragma unroll
-    for (int ic = 0; ic < 3; ++ic) {
-        lds_barrier();   // sAA: the last z pass / the y pass of the previous component has read it; sB: the previous store has read it
+
+    // The backward projection of one accumulator tile set to one coarse field of NP doubles at op: J_z^T from registers -- register r
+    // of the D layout IS the B operand of k-step r -- then J_y^T and J_x^T through LDS and a coalesced store.  The caller's barrier
+    // comes first: sAA must have been read by whoever used it last (a z pass, or the y stage of the previous projection), sB by the
+    // previous store.
+    __device__ __forceinline__ void backward(const double (&acc)[NTZ][RF], double *__restrict__ op) const {
 #pragma unroll
         for (int ti = 0; ti < NTZ; ++ti) {
             const int t = wave + 4 * ti;
             if (t * 16 < CZ) {
                 const int col = 16 * t + l15;
-                const v4f64 tt = mm(jt, acc[ti][ic], kb);      // (rows beyond the fine mesh and columns beyond (a, b) carry zeros)
+                const v4f64 tt = mm(jt, acc[ti]);      // (rows beyond the fine mesh and columns beyond (a, b) carry zeros)
 #pragma unroll
                 for (int r = 0; r < RB; ++r)
                     if ((ZF || col < CZ) && (RBF || lg + 4 * r < N)) sAA[col + CZ * (lg + 4 * r)] = tt[r];   // T(a, b | k)
@@ -3029,8 +3010,8 @@ __global__ __launch_bounds__(256, (ND > 16) ? 1 : 2) void k_conv3m(int64_t E, co
             const int a = col % ND, kz = col / ND;
             double vb[KB];
 #pragma unroll
-            for (int ks = 0; ks < KB; ++ks) vb[ks] = (okc && (RFF || lg + 4 * ks < ND)) ? sAA[a + ND * (lg + 4 * ks) + CZ * kz] : 0.0;
-            const v4f64 ss = mm(jt, vb, kb);
+            for (int ks = 0; ks < KB; ++ks) vb[ks] = (okc && fine_row(ks)) ? sAA[a + ND * (lg + 4 * ks) + CZ * kz] : 0.0;
+            const v4f64 ss = mm(jt, vb);
 #pragma unroll
             for (int r = 0; r < RB; ++r)
                 if (okc && (RBF || lg + 4 * r < N)) sA[a + NDQ * (lg + 4 * r + N * kz)] = ss[r];
@@ -3041,203 +3022,142 @@ __global__ __launch_bounds__(256, (ND > 16) ? 1 : 2) void k_conv3m(int64_t E, co
             const bool okc = XF || col < CX;
             double va[KB];
 #pragma unroll
-            for (int ks = 0; ks < KB; ++ks) va[ks] = (okc && (RFF || lg + 4 * ks < ND)) ? sA[lg + 4 * ks + NDQ * col] : 0.0;
-            const v4f64 oo = mm(jt, va, kb);
+            for (int ks = 0; ks < KB; ++ks) va[ks] = (okc && fine_row(ks)) ? sA[lg + 4 * ks + NDQ * col] : 0.0;
+            const v4f64 oo = mm(jt, va);
 #pragma unroll
             for (int r = 0; r < RB; ++r)
                 if (okc && (RBF || lg + 4 * r < N)) sB[lg + 4 * r + NQ * col] = oo[r];
         }
         lds_barrier();
-        {
-            double *__restrict__ op = outl.p[lv][ic] + e * NP;
-            for (int q = threadIdx.x; q < NP; q += 256) op[q] = sB[(q % N) + NQ * (q / N)];
-        }
+        for (int q = threadIdx.x; q < NP; q += 256) op[q] = sB[(q % N) + NQ * (q / N)];
+    }
+};
+
+// The velocity instance.  All three components go through the forward passes for value AND derivatives; component m folds
+// sgn (Ur . grad u_m) into acc[m] and u_m G_jm into every acc[j]; three fields are projected back.
+// Keeping the transporting base flow Ur_j of a wave's column tiles in registers across the three components instead of re-reading it for
+// every m was tried (the PMC traffic of this kernel is 1.40 x its algorithmic bytes, and those re-reads are the difference).  Measured at
+// lx1 = 8 (194 registers, no spills): 420 - 432 -> 443 us -- the re-reads come from the Infinity Cache at no cost worth 54 registers; at
+// lxd = 15 it spills (78 registers).  Not kept.
+template <int N, int ND, bool DYN>
+__global__ __launch_bounds__(256, 2) void k_conv3m(int64_t E, const double *__restrict__ Jg, const double *__restrict__ DJg, CF3 Ur, CF9 GU,
+                                                   CF3L ul, F3L outl, int adjoint) {
+    using C3 = Conv3m<N, ND>;
+    constexpr int RF = C3::RF, NTZ = C3::NTZ, NP = C3::NP;
+    extern __shared__ double conv3m_dyn[];
+    __shared__ double st_lds[DYN ? 1 : C3::LDS];
+    const int64_t e = blockIdx.x;
+    const int lv = blockIdx.y;
+    if (e >= E) return;
+    const C3 c(DYN ? conv3m_dyn : st_lds, Jg, DJg);
+    const double sgn = adjoint ? -1.0 : 1.0;
+    struct Base {
+        double u[3][RF], g[3][RF];
+    };
+    double acc[3][NTZ][RF];   // [output component][column tile of this wave][D register = fine level (lane >> 4) + 4 r]
+#pragma unroll
+    for (int ic = 0; ic < 3; ++ic)
+#pragma unroll
+        for (int ti = 0; ti < NTZ; ++ti)
+#pragma unroll
+            for (int r = 0; r < RF; ++r) acc[ic][ti][r] = 0.0;
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+        c.template forward<true, true>(
+            ul.p[lv][m] + e * NP, e,
+            [&](bool okc, int64_t qb) {   // Ur_j and the three G of this component
+                Base b;
+#pragma unroll
+                for (int r = 0; r < RF; ++r) {
+                    const bool ok = okc && c.fine_row(r);
+                    const int64_t q = c.fine_q(qb, r);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        b.u[j][r] = ok ? Ur.p[j][q] : 0.0;
+                        b.g[j][r] = ok ? (adjoint ? GU.p[m * 3 + j][q] : GU.p[j * 3 + m][q]) : 0.0;   // multiplies uf_m in output component j
+                    }
+                }
+                return b;
+            },
+            [&](int ti, const Base &b, v4f64 r0, v4f64 r1, v4f64 r2, v4f64 r3) {
+#pragma unroll
+                for (int r = 0; r < RF; ++r) {
+                    acc[m][ti][r] += sgn * (b.u[0][r] * r3[r] + b.u[1][r] * r2[r] + b.u[2][r] * r1[r]);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) acc[j][ti][r] += r0[r] * b.g[j][r];
+                }
+            });
+    // ---- backward, one output component at a time
+#pragma unroll
+    for (int ic = 0; ic < 3; ++ic) {
+        lds_barrier();   // sAA: the last z pass / the y pass of the previous component has read it; sB: the previous store has read it
+        c.backward(acc[ic], outl.p[lv][ic] + e * NP);
     }
 }
 
-// The scalar (temperature) transport term of the Boussinesq coupling in the same matrix-pipe form (see k_conv3s_scalar for the term):
+// The temperature instance: the scalar transport term of the Boussinesq coupling (see k_conv3s_scalar for the term),
 //   out = J^T [ sgn sum_j Ur_j (d theta / d r_j)_fine + gsel sum_m uf_m GT_m ]       direct: sgn = gsel = 1; adjoint: sgn = -1, gsel = 0
 // Four fields go through the forward passes -- the velocity components for their VALUE only (one matrix per pass; skipped in the adjoint),
 // theta for its three derivatives -- into ONE running sum per column tile; one field is projected back.
 template <int N, int ND, bool DYN>
 __global__ __launch_bounds__(256, 2) void k_conv3m_scalar(int64_t E, const double *__restrict__ Jg, const double *__restrict__ DJg, CF3 Ur, CF3 GT, CF3 uv,
                                                           const double *__restrict__ theta, double *__restrict__ out, int adjoint) {
-    static_assert(ND <= 16 && N <= 12 && ND > N, "one 16-row tile per matrix: lx1 = 8 (lxd 12), 10 (15)");
-    constexpr int NP = N * N * N, NPD = ND * ND * ND, NDQ = ND + 1, NQ = N + 1;
-    constexpr int CX = N * N, CY = ND * N, CZ = ND * ND;
-    constexpr int KF = (N + 3) / 4, KB = (ND + 3) / 4, RF = KB, RB = KF;
-    constexpr int NTZ = (CZ + 63) / 64;
-    constexpr bool XF = CX % 16 == 0, YF = CY % 16 == 0, ZF = CZ % 16 == 0, RFF = ND % 4 == 0, RBF = N % 4 == 0;
-    constexpr int LA = NDQ * CX, LY = CZ * N;
+    using C3 = Conv3m<N, ND>;
+    constexpr int RF = C3::RF, NTZ = C3::NTZ, NP = C3::NP;
     extern __shared__ double conv3ms_dyn[];
-    __shared__ double st_lds[DYN ? 1 : 2 * LA + 3 * LY];
-    double *sA = DYN ? conv3ms_dyn : st_lds, *sB = sA + LA, *sAA = sB + LA, *sAD = sAA + LY, *sBA = sAD + LY;
-    const int lane = threadIdx.x & 63, l15 = lane & 15, lg = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    __shared__ double st_lds[DYN ? 1 : C3::LDS];
     const int64_t e = blockIdx.x;
     if (e >= E) return;
-    double ja[KF], da[KF], jt[KB];
-#pragma unroll
-    for (int ks = 0; ks < KF; ++ks) {
-        const bool ok = l15 < ND && (RBF || lg + 4 * ks < N);
-        ja[ks] = ok ? Jg[l15 * N + lg + 4 * ks] : 0.0;
-        da[ks] = ok ? DJg[l15 * N + lg + 4 * ks] : 0.0;
-    }
-#pragma unroll
-    for (int ks = 0; ks < KB; ++ks) jt[ks] = (l15 < N && (RFF || lg + 4 * ks < ND)) ? Jg[(lg + 4 * ks) * N + l15] : 0.0;
-    const v4f64 zero = {0.0, 0.0, 0.0, 0.0};
+    const C3 c(DYN ? conv3ms_dyn : st_lds, Jg, DJg);
     const double sgn = adjoint ? -1.0 : 1.0;
-    auto mm = [&](const auto &A, const auto &B, auto nks) {
-        v4f64 d = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0], B[0], zero, 0, 0, 0);
-#pragma unroll
-        for (int ks = 1; ks < decltype(nks)::value; ++ks) d = __builtin_amdgcn_mfma_f64_16x16x4f64(A[ks], B[ks], d, 0, 0, 0);
-        return d;
+    struct Base {
+        double v[3][RF];
     };
-    constexpr std::integral_constant<int, KF> kf{};
-    constexpr std::integral_constant<int, KB> kb{};
     double acc[NTZ][RF];
 #pragma unroll
     for (int ti = 0; ti < NTZ; ++ti)
 #pragma unroll
         for (int r = 0; r < RF; ++r) acc[ti][r] = 0.0;
-    // one field through the three forward passes; TH: theta (derivatives), else a velocity component (value, times GT_f)
-    auto field = [&](auto th, const double *__restrict__ u, const double *__restrict__ gt) {
-        constexpr bool TH = decltype(th)::value;
-        for (int t = wave; t * 16 < CX; t += 4) {
-            const int col = 16 * t + l15;
-            const bool okc = XF || col < CX;
-            double bv[KF];
+    // a velocity component: its value times GT_f
+    auto value = [&](const double *__restrict__ u, const double *__restrict__ gt) {
+        c.template forward<true, false>(
+            u, e,
+            [&](bool okc, int64_t qb) {
+                Base b;
 #pragma unroll
-            for (int ks = 0; ks < KF; ++ks) bv[ks] = (okc && (RBF || lg + 4 * ks < N)) ? u[lg + 4 * ks + N * col] : 0.0;
-            const v4f64 aj = mm(ja, bv, kf);
-            v4f64 ad = zero;
-            if constexpr (TH) ad = mm(da, bv, kf);
+                for (int r = 0; r < RF; ++r) b.v[0][r] = (okc && c.fine_row(r)) ? gt[c.fine_q(qb, r)] : 0.0;
+                return b;
+            },
+            [&](int ti, const Base &b, v4f64 r0, v4f64, v4f64, v4f64) {
 #pragma unroll
-            for (int r = 0; r < RF; ++r)
-                if (okc && (RFF || lg + 4 * r < ND)) {
-                    sA[lg + 4 * r + NDQ * col] = aj[r];
-                    if constexpr (TH) sB[lg + 4 * r + NDQ * col] = ad[r];
-                }
-        }
-        lds_barrier();
-        for (int t = wave; t * 16 < CY; t += 4) {
-            const int col = 16 * t + l15;
-            const bool okc = YF || col < CY;
-            const int a = col % ND, kz = col / ND;
-            double va[KF], vb[KF];
-#pragma unroll
-            for (int ks = 0; ks < KF; ++ks) {
-                const int j = lg + 4 * ks;
-                const bool ok = okc && (RBF || j < N);
-                va[ks] = ok ? sA[a + NDQ * (j + N * kz)] : 0.0;
-                vb[ks] = (TH && ok) ? sB[a + NDQ * (j + N * kz)] : 0.0;
-            }
-            const v4f64 aa = mm(ja, va, kf);
-            v4f64 ad = zero, ba = zero;
-            if constexpr (TH) {
-                ad = mm(da, va, kf);
-                ba = mm(ja, vb, kf);
-            }
-#pragma unroll
-            for (int r = 0; r < RF; ++r)
-                if (okc && (RFF || lg + 4 * r < ND)) {
-                    const int q = a + ND * (lg + 4 * r + ND * kz);
-                    sAA[q] = aa[r];
-                    if constexpr (TH) {
-                        sAD[q] = ad[r];
-                        sBA[q] = ba[r];
-                    }
-                }
-        }
-        lds_barrier();
-#pragma unroll
-        for (int ti = 0; ti < NTZ; ++ti) {
-            const int t = wave + 4 * ti;
-            if (t * 16 < CZ) {
-                const int col = 16 * t + l15;
-                const bool okc = ZF || col < CZ;
-                const int64_t qb = e * NPD + col;
-                double b0[RF], b1[RF], b2[RF];
-#pragma unroll
-                for (int r = 0; r < RF; ++r) {
-                    const bool ok = okc && (RFF || lg + 4 * r < ND);
-                    const int64_t q = qb + (int64_t)CZ * (lg + 4 * r);
-                    if constexpr (TH) {
-                        b0[r] = ok ? Ur.p[0][q] : 0.0, b1[r] = ok ? Ur.p[1][q] : 0.0, b2[r] = ok ? Ur.p[2][q] : 0.0;
-                    } else {
-                        b0[r] = ok ? gt[q] : 0.0;
-                    }
-                }
-                double v0[KF], v1[KF], v2[KF];
-#pragma unroll
-                for (int ks = 0; ks < KF; ++ks) {
-                    const int k = lg + 4 * ks;
-                    const bool ok = okc && (RBF || k < N);
-                    v0[ks] = ok ? sAA[col + CZ * k] : 0.0;
-                    v1[ks] = (TH && ok) ? sAD[col + CZ * k] : 0.0;
-                    v2[ks] = (TH && ok) ? sBA[col + CZ * k] : 0.0;
-                }
-                if constexpr (TH) {
-                    const v4f64 r1 = mm(da, v0, kf), r2 = mm(ja, v1, kf), r3 = mm(ja, v2, kf);   // d/dr_2, d/dr_1, d/dr_0
-#pragma unroll
-                    for (int r = 0; r < RF; ++r) acc[ti][r] += sgn * (b0[r] * r3[r] + b1[r] * r2[r] + b2[r] * r1[r]);
-                } else {
-                    const v4f64 r0 = mm(ja, v0, kf);
-#pragma unroll
-                    for (int r = 0; r < RF; ++r) acc[ti][r] += r0[r] * b0[r];
-                }
-            }
-        }
+                for (int r = 0; r < RF; ++r) acc[ti][r] += r0[r] * b.v[0][r];
+            });
         lds_barrier();   // the next field's passes overwrite the stage arrays
     };
     if (!adjoint) {
-        field(std::false_type{}, uv.p[0] + e * NP, GT.p[0]);
-        field(std::false_type{}, uv.p[1] + e * NP, GT.p[1]);
-        field(std::false_type{}, uv.p[2] + e * NP, GT.p[2]);
+        value(uv.p[0] + e * NP, GT.p[0]);
+        value(uv.p[1] + e * NP, GT.p[1]);
+        value(uv.p[2] + e * NP, GT.p[2]);
     }
-    field(std::true_type{}, theta + e * NP, nullptr);
-    // ---- backward
+    // theta: its derivatives along the transporting base flow
+    c.template forward<false, true>(
+        theta + e * NP, e,
+        [&](bool okc, int64_t qb) {
+            Base b;
 #pragma unroll
-    for (int ti = 0; ti < NTZ; ++ti) {
-        const int t = wave + 4 * ti;
-        if (t * 16 < CZ) {
-            const int col = 16 * t + l15;
-            const v4f64 tt = mm(jt, acc[ti], kb);
+            for (int r = 0; r < RF; ++r) {
+                const bool ok = okc && c.fine_row(r);
+                const int64_t q = c.fine_q(qb, r);
+                b.v[0][r] = ok ? Ur.p[0][q] : 0.0, b.v[1][r] = ok ? Ur.p[1][q] : 0.0, b.v[2][r] = ok ? Ur.p[2][q] : 0.0;
+            }
+            return b;
+        },
+        [&](int ti, const Base &b, v4f64, v4f64 r1, v4f64 r2, v4f64 r3) {
 #pragma unroll
-            for (int r = 0; r < RB; ++r)
-                if ((ZF || col < CZ) && (RBF || lg + 4 * r < N)) sAA[col + CZ * (lg + 4 * r)] = tt[r];
-        }
-    }
-    lds_barrier();
-    for (int t = wave; t * 16 < CY; t += 4) {
-        const int col = 16 * t + l15;
-        const bool okc = YF || col < CY;
-        const int a = col % ND, kz = col / ND;
-        double vb[KB];
-#pragma unroll
-        for (int ks = 0; ks < KB; ++ks) vb[ks] = (okc && (RFF || lg + 4 * ks < ND)) ? sAA[a + ND * (lg + 4 * ks) + CZ * kz] : 0.0;
-        const v4f64 ss = mm(jt, vb, kb);
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-            if (okc && (RBF || lg + 4 * r < N)) sA[a + NDQ * (lg + 4 * r + N * kz)] = ss[r];
-    }
-    lds_barrier();
-    for (int t = wave; t * 16 < CX; t += 4) {
-        const int col = 16 * t + l15;
-        const bool okc = XF || col < CX;
-        double va[KB];
-#pragma unroll
-        for (int ks = 0; ks < KB; ++ks) va[ks] = (okc && (RFF || lg + 4 * ks < ND)) ? sA[lg + 4 * ks + NDQ * col] : 0.0;
-        const v4f64 oo = mm(jt, va, kb);
-#pragma unroll
-        for (int r = 0; r < RB; ++r)
-            if (okc && (RBF || lg + 4 * r < N)) sB[lg + 4 * r + NQ * col] = oo[r];
-    }
-    lds_barrier();
-    {
-        double *__restrict__ op = out + e * NP;
-        for (int q = threadIdx.x; q < NP; q += 256) op[q] = sB[(q % N) + NQ * (q / N)];
-    }
+            for (int r = 0; r < RF; ++r) acc[ti][r] += sgn * (b.v[0][r] * r3[r] + b.v[1][r] * r2[r] + b.v[2][r] * r1[r]);
+        });
+    lds_barrier();   // sAA: the z pass has read it
+    c.backward(acc, out + e * NP);
 }
 
 // CFL (Nek compute_cfl): max over points of dt * sum_j |u_rj| * rdr
@@ -4348,6 +4268,17 @@ int sem_scalar_grad_apply(nlg_mesh *m, double *const *GT, const double *theta, d
     return 0;
 }
 
+// a kernel with more dynamic LDS than the default limit has to be told so once
+template <auto KERNEL>
+static int allow_dyn_lds(size_t bytes) {
+    static bool done = false;
+    if (!done) {
+        NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        done = true;
+    }
+    return 0;
+}
+
 // adjoint != 0: out = - J^T [ Ur . grad theta ]  (the transport term of the adjoint temperature equation; no u . grad Theta)
 int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, double *const *u, const double *theta, double *out, int adjoint, int nl,
                           int64_t ld) {
@@ -4364,11 +4295,7 @@ int sem_conv_scalar_apply(nlg_mesh *m, double *const *Ur, double *const *GT, dou
                        cur, cgt, cu, theta, out, adjoint);
         } else if (m->n == 10) {
             constexpr size_t lds = sizeof(double) * (2 * 16 * 100 + 3 * 225 * 10);
-            static bool attr_set = false;
-            if (!attr_set) {
-                NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3m_scalar<10, 15, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                attr_set = true;
-            }
+            NLG_TRY((allow_dyn_lds<&k_conv3m_scalar<10, 15, true>>(lds)));
             NLG_LAUNCH((k_conv3m_scalar<10, 15, true>), dim3((unsigned)m->E), dim3(256), lds, m->ctx->stream, m->E, (const double *)m->d_Jd, (const double *)m->d_DJd,
                        cur, cgt, cu, theta, out, adjoint);
         } else {
@@ -4438,21 +4365,13 @@ int sem_conv_apply(nlg_mesh *m, double *const *Ur, double *const *GU, double *co
                 break;
             case 9: {
                 constexpr size_t lds = sizeof(double) * (2 * 13 * 81 + 3 * 169 * 9 + 3 * 9 * 81);   // x-stage, y-stage and u arrays: 69 KB
-                static bool attr_set = false;
-                if (!attr_set) {
-                    NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3<9, 13, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    attr_set = true;
-                }
+                NLG_TRY((allow_dyn_lds<&k_conv3<9, 13, 256, true>>(lds)));
                 NLG_LAUNCH((k_conv3<9, 13, 256, true>), dim3((unsigned)m->E), dim3(256), lds, m->ctx->stream, m->E, (const double *)m->d_Jd,
                            (const double *)m->d_DJd, cur, cg, cu, co, nl, adjoint);
             } break;
             case 10: {
                 constexpr size_t lds = sizeof(double) * (2 * 16 * 100 + 3 * 225 * 10);   // 79.6 KB: two blocks per CU
-                static bool attr_set = false;
-                if (!attr_set) {
-                    NLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3m<10, 15, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    attr_set = true;
-                }
+                NLG_TRY((allow_dyn_lds<&k_conv3m<10, 15, true>>(lds)));
                 NLG_LAUNCH((k_conv3m<10, 15, true>), dim3((unsigned)m->E, (unsigned)nl), dim3(256), lds, m->ctx->stream, m->E, (const double *)m->d_Jd,
                            (const double *)m->d_DJd, cur, cg, cu, co, adjoint);
             } break;

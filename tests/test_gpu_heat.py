@@ -133,7 +133,7 @@ def test_nonlinear_map_with_temperature_matches_oracle(gpu_ctx):
     assert np.max(np.abs(gF.get_field(host.THETA).reshape(sem.shape1) * (1 - sem.tmask))) == 0.0
 
 
-@pytest.mark.parametrize("dim,n,s", [(2, 6, 2), (3, 8, 3), (3, 10, 2)])
+@pytest.mark.parametrize("dim,n,s", [(2, 6, 2), (3, 8, 3), (3, 10, 2), (3, 8, 4)])
 @pytest.mark.parametrize("adjoint", [False, True])
 def test_boussinesq_matvec_block_equals_single_matvecs(gpu_ctx, dim, n, s, adjoint):
     """Lane-batched propagator with the temperature coupling (the reference's coupled operator
