@@ -517,6 +517,35 @@ int nlg_lns_set_re(nlg_lns *lns, double re);
 int nlg_lns_apply(nlg_lns *lns, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint, const double *coef);
 int nlg_lns_destroy(nlg_lns *lns);
 int nlg_op_lns(nlg_mesh *mesh, const nlg_vec *base, const nlg_vec *in, nlg_vec *out, double re, int adjoint, const double *coef);
+/* Eigenvalue sensitivity from a direct / adjoint pair: the wavemaker and the gradient of the eigenvalue with respect to the base flow.
+ * For real velocity fields u, a on mesh 1, with u~ = mask (.) u and a~ = mask (.) a (the velocity Dirichlet masks are applied on read,
+ * as nlg_lns_apply does; d_j is the pointwise physical derivative gradm1 of an element: no mass matrix, no gather-scatter):
+ *   T(u, a)_j = - sum_i a~_i d_j u~_i          (transport part)
+ *   P(u, a)_j = + sum_i u~_i d_i a~_j          (production part)
+ *   S(u, a)   = T + P
+ * Then <a, [L(U + dU) - L(U)] u> = <S(u, a), dU> in the nek_ddot inner product, where L is the operator of nlg_lns_apply, u is
+ * solenoidal and the boundary term of one integration by parts vanishes.  The term (div u) a_j is left out on purpose.
+ * For a complex pair, direct u^ = u_r + i u_i with L u^ = lambda u^, adjoint u^+ = a_r + i a_i with L+ u^+ = conj(lambda) u^+:
+ *   d       = <u^+, u^> = (a_r.u_r + a_i.u_i) + i (a_r.u_i - a_i.u_r)          (nek_ddot)
+ *   S_re    = S(u_r, a_r) + S(u_i, a_i)        S_im = S(u_i, a_r) - S(u_r, a_i)
+ *   grad_U lambda = (S_re + i S_im) / d        (same split for T and P)
+ *   W(x)    = |u^(x)| |u^+(x)| / |d|           (wavemaker; |u^(x)|^2 = sum_i (u_r,i^2 + u_i,i^2), of the masked fields)
+ *   dlambda ~ <Re grad_U lambda, dU> + i <Im grad_U lambda, dU>
+ * A real eigenpair has no imaginary parts: pass them as NULL.
+ * nlg_sens_apply: s = 1..4 pairs in one launch of k_lns_sens.  dir_im, adj_im: NULL, or arrays whose entries are NULL for the real
+ *   pairs.  scale: the complex factor 1 / d of pair v at scale[2 v], scale[2 v + 1] (NULL: 1).  grad_re[v] receives Re(S scale),
+ *   grad_im[v] Im(S scale), transp_re / transp_im the same of T alone, wavemaker[v] carries W |scale| in its first velocity component.
+ *   grad_im, transp_re, transp_im, wavemaker: NULL, or arrays with NULL entries, for what is not asked for: neither computed nor stored.
+ *   Of every output vector the velocity carries the field; its pressure, scalars and restart history are zeroed, so that nlg_vec_dot
+ *   against a dU and the field writers work on it.  Element-local and without a collective call: correct on a partitioned mesh.
+ *   Refused with a message: NULL dir_re / adj_re / grad_re (or entries), s outside 1..4, a vector on another mesh, an output that
+ *   aliases an input or another output, dir_im[v] without adj_im[v] or the reverse, lx1 outside 4..10, 12.  A refused call leaves
+ *   nothing changed.
+ * nlg_sens_pairing: d[0] + i d[1] = <u^+, u^>, four dots in one reduction with one all-reduce (dir_im = adj_im = NULL: one dot). */
+int nlg_sens_apply(nlg_mesh *mesh, int s, const nlg_vec *const *dir_re, const nlg_vec *const *dir_im, const nlg_vec *const *adj_re,
+                   const nlg_vec *const *adj_im, const double *scale, nlg_vec *const *grad_re, nlg_vec *const *grad_im,
+                   nlg_vec *const *transp_re, nlg_vec *const *transp_im, nlg_vec *const *wavemaker);
+int nlg_sens_pairing(const nlg_vec *dir_re, const nlg_vec *dir_im, const nlg_vec *adj_re, const nlg_vec *adj_im, double *d);
 /* the explicit modal filter of the time stepper (nlg_exptA_config.filter_weight / filter_modes) on its own, in place on the velocity
  * fields (and scalars) of nvec <= 4 vectors, which go through the kernel together as the lanes of a block step do */
 int nlg_op_filter(nlg_mesh *mesh, int nvec, nlg_vec *const *vecs, double filter_weight, int filter_modes);

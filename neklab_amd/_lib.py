@@ -174,6 +174,8 @@ SIGNATURES = {
     "nlg_lns_set_re": (C.c_int, [vp, C.c_double]),
     "nlg_lns_apply": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, c_double_p]),
     "nlg_lns_destroy": (C.c_int, [vp]),
+    "nlg_sens_apply": (C.c_int, [vp, C.c_int] + [C.POINTER(vp)] * 4 + [c_double_p] + [C.POINTER(vp)] * 5),
+    "nlg_sens_pairing": (C.c_int, [vp, vp, vp, vp, c_double_p]),
     "nlg_op_filter":(C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_double, C.c_int]),
     "nlg_op_cfl": (C.c_int, [vp, vp, C.c_double, c_double_p]),
     "nlg_arnoldi_step": (C.c_int, [vp, vp, C.c_int, c_double_p, C.c_int, C.c_int]),

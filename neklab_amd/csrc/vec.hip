@@ -1164,6 +1164,39 @@ int nlg_basis_cgs2_batch(int s, nlg_basis *const *b, int k, nlg_vec *const *w, d
     return nlg::basis_cgs2_host(s, b, k, w, h, ldh, beta, 1);
 }
 
+// d = <u^+, u^> = (a_r . u_r + a_i . u_i) + i (a_r . u_i - a_i . u_r): the four dots as four lanes of the first stage, one row
+// reduction, ONE all-reduce and one read-back (a real pair: one dot)
+int nlg_sens_pairing(const nlg_vec *dir_re, const nlg_vec *dir_im, const nlg_vec *adj_re, const nlg_vec *adj_im, double *d) {
+    NLG_CHECK(dir_re && adj_re && d, "nlg_sens_pairing: NULL argument");
+    NLG_CHECK((dir_im != nullptr) == (adj_im != nullptr), "nlg_sens_pairing: %s given without %s", dir_im ? "dir_im" : "adj_im",
+              dir_im ? "adj_im" : "dir_im");
+    NLG_TRY(check_same(dir_re, adj_re, "nlg_sens_pairing"));
+    if (dir_im) {
+        NLG_TRY(check_same(dir_re, dir_im, "nlg_sens_pairing"));
+        NLG_TRY(check_same(dir_re, adj_im, "nlg_sens_pairing"));
+    }
+    nlg_mesh *m = dir_re->mesh;
+    nlg_ctx *ctx = m->ctx;
+    const int rows = dir_im ? 4 : 1;
+    const int nblk = dot_nblk(dir_re), nper = nblk * dir_re->ncomp;
+    LaneAB P = {};
+    P.a[0] = adj_re->d, P.b[0] = dir_re->d;
+    if (dir_im) {
+        P.a[1] = adj_im->d, P.b[1] = dir_im->d;
+        P.a[2] = adj_re->d, P.b[2] = dir_im->d;
+        P.a[3] = adj_im->d, P.b[3] = dir_re->d;
+    }
+    NLG_TRY(reduce_ws_reserve(ctx, rows));
+    NLG_LAUNCH(k_dot_partial, dim3(nblk, dir_re->ncomp, rows), dim3(NT), 0, ctx->stream, P, (const double *)m->d_bm1, m->lvs, nblk, nper,
+               ctx->d_partial);
+    NLG_TRY(reduce_rows_all(ctx, rows, nper, ctx->d_scalars, nullptr));
+    NLG_HIP(hipGetLastError());
+    double q[4] = {0.0, 0.0, 0.0, 0.0};
+    NLG_TRY(scalars_to_host(ctx, 0, rows, q));
+    d[0] = q[0] + q[1], d[1] = q[2] - q[3];
+    return 0;
+}
+
 int nlg_basis_block_dot(const nlg_basis *b, int k, const nlg_vec *w, double *h) {
     NLG_CHECK(b && w && h, "nlg_basis_block_dot: NULL argument");
     NLG_CHECK(k >= 1 && k <= b->nvec, "nlg_basis_block_dot: k=%d out of range [1,%d]", k, b->nvec);

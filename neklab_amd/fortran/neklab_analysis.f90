@@ -13,8 +13,8 @@ module neklab_analysis
    use LightKrylov, only: dp, eigs, svds, save_eigenspectrum, zero_basis, initialize_krylov_subspace, newton, gmres_rdp, &
                           newton_dp_opts, newton_dp_metadata
    use LightKrylov, only: abstract_vector_rdp, abstract_exptA_linop_rdp, abstract_system_rdp
-   use iso_c_binding, only: c_int
-   use neklab_gpu_capi, only: nlg_check, c_vec_get_field, c_vec_set_field, nek_lpn
+   use iso_c_binding, only: c_int, c_ptr, c_null_ptr, c_loc, c_double
+   use neklab_gpu_capi, only: nlg_check, c_vec_get_field, c_vec_set_field, nek_lpn, nlg_mesh, c_sens_apply, c_sens_pairing
    use neklab_vectors
    use neklab_linops
    use neklab_utils
@@ -23,7 +23,7 @@ module neklab_analysis
    private
 
    public :: linear_stability_analysis_fixed_point, transient_growth_analysis_fixed_point, newton_fixed_point_iteration
-   public :: otd_analysis
+   public :: otd_analysis, eigenvalue_sensitivity
    !> .true.: Arnoldi / Lanczos on the device; .false.: LightKrylov's loops over the type-bound procedures
    logical, save, public :: device_eigs = .false.
 
@@ -128,6 +128,63 @@ contains
       call sys%finalize_timer()
       call sys%jacobian%finalize_timer()
    end subroutine newton_fixed_point_iteration
+
+   !> Structural sensitivity and base-flow gradient of an eigenvalue from its direct mode u^ = dir_re + i dir_im and its adjoint mode
+   !! u^+ = adj_re + i adj_im (a real eigenpair: no imaginary parts), on the device (nlg_sens_pairing, nlg_sens_apply; the definitions
+   !! stand in include/neklab_gpu.h):  d = <u^+, u^>,  grad_re + i grad_im = grad_U lambda = [S(u_r, a_r) + S(u_i, a_i) + i (S(u_i, a_r)
+   !! - S(u_r, a_i))] / d  with  S(u, a)_j = - sum_i a_i d_j u_i + sum_i u_i d_i a_j  of the masked fields (element-local; the term
+   !! (div u) a_j is left out on purpose),  transp_re + i transp_im the same of the first sum alone,  wavemaker: |u^| |u^+| / |d| in its
+   !! first velocity component.  The first-order shift of the eigenvalue under a base-flow change dU is
+   !! cmplx(grad_re%dot(dU), grad_im%dot(dU)).
+   subroutine eigenvalue_sensitivity(dir_re, adj_re, d, grad_re, grad_im, dir_im, adj_im, wavemaker, transp_re, transp_im)
+      type(nek_dvector), intent(in) :: dir_re, adj_re
+      complex(dp), intent(out) :: d
+      type(nek_dvector), intent(inout) :: grad_re, grad_im
+      type(nek_dvector), optional, intent(in) :: dir_im, adj_im
+      type(nek_dvector), optional, intent(inout) :: wavemaker, transp_re, transp_im
+      type(c_ptr), target :: h(9)
+      type(c_ptr) :: a(9)
+      real(c_double), target :: fac(2)
+      real(c_double) :: dd(2)
+      complex(dp) :: inv
+      integer :: i
+
+      if (present(dir_im) .neqv. present(adj_im)) then
+         write (*, '(A)') 'ERROR in eigenvalue_sensitivity: dir_im and adj_im come together or not at all'
+         error stop 1
+      end if
+      h = c_null_ptr
+      h(1) = nek_dvector_handle(dir_re)
+      h(3) = nek_dvector_handle(adj_re)
+      if (present(dir_im)) then
+         h(2) = nek_dvector_handle(dir_im)
+         h(4) = nek_dvector_handle(adj_im)
+      end if
+      call nlg_check(c_sens_pairing(h(1), h(2), h(3), h(4), dd), 'eigenvalue_sensitivity')
+      d = cmplx(dd(1), dd(2), kind=dp)
+      if (abs(d) == 0.0_dp) then
+         write (*, '(A)') 'ERROR in eigenvalue_sensitivity: <adjoint, direct> vanishes: the pair cannot be normalised'
+         error stop 1
+      end if
+      inv = 1.0_dp/d
+      fac = [real(inv, dp), aimag(inv)]
+      call nek_dvector_ensure(grad_re); h(5) = grad_re%h
+      call nek_dvector_ensure(grad_im); h(6) = grad_im%h
+      if (present(transp_re)) then
+         call nek_dvector_ensure(transp_re); h(7) = transp_re%h
+      end if
+      if (present(transp_im)) then
+         call nek_dvector_ensure(transp_im); h(8) = transp_im%h
+      end if
+      if (present(wavemaker)) then
+         call nek_dvector_ensure(wavemaker); h(9) = wavemaker%h
+      end if
+      ! one pair: every array of the call has one entry, h(i) itself
+      do i = 1, 9
+         a(i) = c_loc(h(i))
+      end do
+      call nlg_check(c_sens_apply(nlg_mesh, 1_c_int, a(1), a(2), a(3), a(4), c_loc(fac), a(5), a(6), a(7), a(8), a(9)), 'eigenvalue_sensitivity')
+   end subroutine eigenvalue_sensitivity
 
    !> otd_analysis (src/neklab_analysis.f90:214-344): nsteps device time steps of the OTD modes in chunks that end at the next print /
    !! io / restart step; there the basis is orthonormalised and Lr read out, Ls.dat / Lr.dat are appended in the reference's formats,

@@ -417,6 +417,21 @@ module neklab_gpu_capi
          real(c_double), intent(in) :: coef(3)
          integer(c_int) :: rc
       end function
+      !> the array arguments are C arrays of vector handles (c_loc of a type(c_ptr) array), c_null_ptr for what is absent
+      function c_sens_apply(mesh, s, dir_re, dir_im, adj_re, adj_im, scale, grad_re, grad_im, transp_re, transp_im, wavemaker) &
+         bind(C, name="nlg_sens_apply") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: mesh
+         integer(c_int), value :: s
+         type(c_ptr), value :: dir_re, dir_im, adj_re, adj_im, scale, grad_re, grad_im, transp_re, transp_im, wavemaker
+         integer(c_int) :: rc
+      end function
+      function c_sens_pairing(dir_re, dir_im, adj_re, adj_im, d) bind(C, name="nlg_sens_pairing") result(rc)
+         import c_int, c_ptr, c_double
+         type(c_ptr), value :: dir_re, dir_im, adj_re, adj_im
+         real(c_double), intent(out) :: d(2)
+         integer(c_int) :: rc
+      end function
       function c_lns_destroy(lns) bind(C, name="nlg_lns_destroy") result(rc)
          import c_int, c_ptr
          type(c_ptr), value :: lns

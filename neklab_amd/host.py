@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 
 import numpy as np
 
@@ -1608,6 +1609,207 @@ def compute_LNS_laplacian(lns: lns_linop, vec_in, vec_out):
 def compute_LNS_gradp(lns: lns_linop, vec_in, vec_out):
     """reference: compute_LNS_gradp (neklab_linops.f90:368-380): grad of the pressure mapped to the velocity mesh"""
     lns.apply(vec_in, vec_out, False, LNS_COEF["compute_LNS_gradp"])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Eigenvalue sensitivity: wavemaker and base-flow gradient of an eigenvalue from a direct / adjoint pair (nlg_sens_apply,
+# nlg_sens_pairing; the definitions stand in include/neklab_gpu.h)
+def _sens_pairs(x, what: str):
+    """(re, im | None) or a list of up to four such pairs -> (list of pairs, was a single pair)"""
+    single = len(x) == 2 and isinstance(x[0], nek_dvector) and (x[1] is None or isinstance(x[1], nek_dvector))
+    pairs = [tuple(x)] if single else [tuple(p) for p in x]
+    for p in pairs:
+        if len(p) != 2 or not isinstance(p[0], nek_dvector) or not (p[1] is None or isinstance(p[1], nek_dvector)):
+            raise TypeError("type_error: %s is a pair (re, im | None) of nek_dvector or a list of such pairs" % what)
+    return pairs, single
+
+
+def sens_pairing(direct, adjoint) -> complex:
+    """d = <u^+, u^> = (a_r.u_r + a_i.u_i) + i (a_r.u_i - a_i.u_r) of one pair, in the nek_ddot inner product (nlg_sens_pairing)."""
+    (ur, ui), (ar, ai) = direct, adjoint
+    d = np.zeros(2)
+    check(ur.lib.nlg_sens_pairing(ur.h, ui.h if ui is not None else None, ar.h, ai.h if ai is not None else None, dptr(d)))
+    return complex(d[0], d[1])
+
+
+def eigenvalue_sensitivity(direct, adjoint, parts: bool = False, wavemaker: bool = True, average: bool = False, scale=None):
+    """Structural sensitivity and base-flow gradient of an eigenvalue.  For real velocity fields u, a on mesh 1, with u~ = mask (.) u and
+    a~ = mask (.) a (the velocity Dirichlet masks are applied on read, as apply_L does; d_j is the pointwise physical derivative gradm1
+    of an element: no mass matrix, no gather-scatter):
+
+        T(u, a)_j = - sum_i a~_i d_j u~_i          (transport part)
+        P(u, a)_j = + sum_i u~_i d_i a~_j          (production part)
+        S(u, a)   = T + P
+
+    Then <a, [L(U + dU) - L(U)] u> = <S(u, a), dU> in the nek_ddot inner product, where L is the operator of apply_L, u is solenoidal
+    and the boundary term of one integration by parts vanishes.  The term (div u) a_j is left out on purpose.  For a complex pair,
+    direct u^ = u_r + i u_i with L u^ = lambda u^, adjoint u^+ = a_r + i a_i with L+ u^+ = conj(lambda) u^+:
+
+        d       = <u^+, u^> = (a_r.u_r + a_i.u_i) + i (a_r.u_i - a_i.u_r)          (nek_ddot)
+        S_re    = S(u_r, a_r) + S(u_i, a_i)        S_im = S(u_i, a_r) - S(u_r, a_i)
+        grad_U lambda = (S_re + i S_im) / d        (same split for T and P)
+        W(x)    = |u^(x)| |u^+(x)| / |d|           (wavemaker; |u^(x)|^2 = sum_i (u_r,i^2 + u_i,i^2))
+        dlambda ~ <Re grad_U lambda, dU> + i <Im grad_U lambda, dU>
+
+    `direct`, `adjoint`: (re, im | None) pairs of nek_dvector -- a real eigenpair has no imaginary parts -- or lists of up to four such
+    pairs, which go through the kernel in one launch.  Returns (d, grad, transport, W): d complex; grad = (re, im) of nek_dvector, the
+    gradient of the eigenvalue; transport the same of T alone (parts=True, else None); W a nek_dvector whose first velocity component
+    carries the wavemaker (wavemaker=True, else None); lists of these when lists were given.  The fields are element-local, the form
+    whose `dot` with a dU is the quadrature of the integrand; average=True replaces them by their multiplicity-weighted gather-scatter
+    average (what `rand` applies), for plotting.  scale: the complex factor(s) used instead of 1 / d."""
+    dpairs, single = _sens_pairs(direct, "direct")
+    apairs, single_a = _sens_pairs(adjoint, "adjoint")
+    if single != single_a or len(dpairs) != len(apairs):
+        raise TypeError("type_error: as many direct as adjoint pairs expected")
+    s = len(dpairs)
+    mesh = dpairs[0][0].mesh
+    lib = mesh.lib
+    d = [sens_pairing(dp, ap) for dp, ap in zip(dpairs, apairs)] if s <= 4 else []
+    if scale is None:
+        if any(x == 0.0 for x in d):
+            raise NlgError("eigenvalue_sensitivity: <adjoint, direct> vanishes: the pair cannot be normalised")
+        fac = [1.0 / x for x in d]
+    else:
+        fac = [complex(x) for x in (np.atleast_1d(scale))]
+        if len(fac) != s:
+            raise ValueError("scale: one complex factor per pair")
+    sc = np.array([[f.real, f.imag] for f in fac], dtype=np.float64).reshape(-1)
+    new = lambda: nek_dvector(mesh, dpairs[0][0].nscal, dpairs[0][0].lorder)
+    grad = [(new(), new()) for _ in range(s)]
+    transport = [(new(), new()) for _ in range(s)] if parts else None
+    W = [new() for _ in range(s)] if wavemaker else None
+    n = max(s, 1)
+
+    def arr(vs):
+        if vs is None:
+            return None
+        return (vp * n)(*[(x.h if x is not None else None) for x in vs])
+
+    check(lib.nlg_sens_apply(mesh.h, s, arr([p[0] for p in dpairs]), arr([p[1] for p in dpairs]), arr([p[0] for p in apairs]),
+                             arr([p[1] for p in apairs]), dptr(sc), arr([g[0] for g in grad]), arr([g[1] for g in grad]),
+                             arr([t[0] for t in transport]) if parts else None, arr([t[1] for t in transport]) if parts else None,
+                             arr(W)))
+    if average:
+        vmult = mesh.get("vmult")
+        for v in [x for g in grad for x in g] + ([x for t in transport for x in t] if parts else []) + (W or []):
+            check(lib.nlg_op_dssum(mesh.h, v.h))
+            for k in range(mesh.dim):
+                v.set_field(k, v.get_field(k) * vmult)
+    if single:
+        return d[0], grad[0], transport[0] if parts else None, W[0] if wavemaker else None
+    return d, grad, transport, W
+
+
+def predict_eigenvalue_shift(grad, dU: nek_dvector) -> complex:
+    """First-order shift of the eigenvalue under the base-flow change dU: <Re grad_U lambda, dU> + i <Im grad_U lambda, dU> with
+    grad = (re, im) as eigenvalue_sensitivity returns it (element-local form)."""
+    gre, gim = (grad.re, grad.im) if isinstance(grad, nek_zvector) else grad
+    return complex(gre.dot(dU), gim.dot(dU))
+
+
+def _match_adjoint_modes(lam_d, res_d, lam_a, res_a, match_tol):
+    """For every direct eigenvalue the index of the adjoint eigenvalue closest to it; raises where they differ by more than the bound."""
+    idx = []
+    for k, lam in enumerate(lam_d):
+        j = int(np.argmin(np.abs(lam_a - lam)))
+        bound = match_tol if match_tol is not None else 10.0 * (abs(res_d[k]) + abs(res_a[j])) + 1e-10 * abs(lam)
+        if abs(lam_a[j] - lam) > bound:
+            raise NlgError("sensitivity_analysis: direct eigenvalue %d (%.12g%+.12gj) has no adjoint partner: the closest adjoint "
+                           "eigenvalue is %.12g%+.12gj, %.3e away (bound %.3e)" % (k, lam.real, lam.imag, lam_a[j].real, lam_a[j].imag,
+                                                                                   abs(lam_a[j] - lam), bound))
+        idx.append(j)
+    return idx
+
+
+def sensitivity_analysis(exptA: exptA_linop, kdim: int, nev: int, tol: float = 0.0, outdir: str = ".", seed: int = 0,
+                         outpost: bool = False, session: str = "neklab", parts: bool = False, average: bool = False,
+                         match_tol: "float | None" = None, X0: "nek_dvector | None" = None):
+    """Direct and adjoint stability analysis of the fixed point `exptA` was built about (linear_stability_analysis_fixed_point twice),
+    the modes paired by eigenvalue, and eigenvalue_sensitivity of every pair.
+
+    Pairing.  Both runs return their eigenvectors in the real LAPACK pair convention: for a complex pair at (k, k + 1), X[k] + i X[k+1]
+    belongs to the eigenvalue of positive imaginary part, mu+.  The direct mode of lambda = log(mu+) / tau is u^ = X[k] + i X[k+1].
+    The adjoint run's Y[j] + i Y[j+1] belongs to mu+ of the (real) adjoint propagator too, while the adjoint partner of lambda is the
+    adjoint eigenvector of conj(lambda): u^+ = Y[j] - i Y[j+1].  (With Y[j] + i Y[j+1] instead, <u^+, u^> is the pairing with the mode of
+    conj(lambda) and vanishes to rounding.)  One sensitivity per real eigenvalue and one per complex pair (for its mu+ member; that of
+    the conjugate eigenvalue is the conjugate field).
+
+    Raises if a direct eigenvalue has no adjoint eigenvalue within 10 x the sum of the two Ritz residuals of the multipliers (match_tol:
+    another absolute bound on |mu_direct - mu_adjoint|; the adjoint is the discretised continuous one, so on a coarse mesh or with a
+    large time step the two spectra differ by more than their residuals), or if |d| / (|u^| |u^+|) <= 1e-10: that level means the wrong
+    partner.
+
+    Writes sensitivity.npy, rows [Re lambda, Im lambda, Re d, Im d], and with outpost=True the field files sgr (Re grad), sgi (Im grad)
+    and wmk (wavemaker).  Returns a dict: eigvals, d, grad, transport, W (lists, one entry per sensitivity), modes = the (direct, adjoint)
+    pairs used, direct / adjoint = what the two stability runs returned, and seconds = the wall time of the three stages."""
+    clock = [time.perf_counter()]
+    run_d = linear_stability_analysis_fixed_point(exptA, kdim, nev, adjoint=False, X0=X0, tol=tol, outdir=outdir, seed=seed,
+                                                  outpost=outpost, session=session)
+    clock.append(time.perf_counter())
+    run_a = linear_stability_analysis_fixed_point(exptA, kdim, nev, adjoint=True, X0=X0, tol=tol, outdir=outdir, seed=seed,
+                                                  outpost=outpost, session=session)
+    clock.append(time.perf_counter())
+    lam_d, res_d, Xd, mu_d, _ = run_d
+    lam_a, res_a, Xa, mu_a, _ = run_a
+    match = _match_adjoint_modes(mu_d, res_d, mu_a, res_a, match_tol)
+    # pairs of the adjoint run, as nlg_eigs forms them: a complex eigenvalue and its successor
+    ahead, j = [-1] * nev, 0
+    while j < nev:
+        if mu_a[j].imag != 0.0:
+            if j + 1 < nev:
+                ahead[j] = ahead[j + 1] = j
+            j += 2
+        else:
+            ahead[j] = j
+            j += 1
+    heads, lams, direct, adjoint = [], [], [], []
+    k = 0
+    while k < nev:
+        j = match[k]
+        lams.append(lam_d[k])
+        if mu_d[k].imag == 0.0:
+            heads.append(k)
+            direct.append((Xd[k], None))
+            adjoint.append((Xa[j], None))
+            k += 1
+            continue
+        if k + 1 >= nev:
+            lams.pop()
+            break                                                    # the second member of the pair was not asked for
+        jh = ahead[j]                                                # the adjoint run's pair that holds eigenvalue j
+        if jh < 0:
+            raise NlgError("sensitivity_analysis: the adjoint run returned one member only of the pair of eigenvalue %d" % k)
+        # X[k] + i X[k+1] belongs to mu+ whichever member came first; lambda = the eigenvalue of positive imaginary part
+        lams[-1] = lam_d[k] if mu_d[k].imag > 0.0 else lam_d[k + 1]
+        aim = Xa[jh + 1].copy()
+        aim.scal(-1.0)                                               # u^+ = Y[j] - i Y[j+1]
+        heads.append(k)
+        direct.append((Xd[k], Xd[k + 1]))
+        adjoint.append((Xa[jh], aim))
+        k += 2
+    d, grad, transport, W = [], [], [], []
+    for b in range(0, len(heads), 4):
+        db, gb, tb, wb = eigenvalue_sensitivity(direct[b:b + 4], adjoint[b:b + 4], parts=parts, wavemaker=True, average=average)
+        for q, (dp, ap) in enumerate(zip(direct[b:b + 4], adjoint[b:b + 4])):
+            nd = np.sqrt(sum(x.dot(x) for x in dp if x is not None))
+            na = np.sqrt(sum(x.dot(x) for x in ap if x is not None))
+            if abs(db[q]) <= 1e-10 * nd * na:
+                raise NlgError("sensitivity_analysis: |<u^+, u^>| = %.3e of |u^| |u^+| for eigenvalue %d: the adjoint mode is not its "
+                               "partner" % (abs(db[q]) / (nd * na), heads[b + q]))
+        d += db
+        grad += gb
+        transport += tb if parts else []
+        W += wb
+    exptA.mesh.ctx.sync()
+    clock.append(time.perf_counter())
+    lam = np.array(lams)
+    np.save(os.path.join(outdir, "sensitivity.npy"), np.column_stack([lam.real, lam.imag, np.real(d), np.imag(d)]))
+    if outpost:
+        outpost_dnek([g[0] for g in grad], "sgr", session, outdir)
+        outpost_dnek([g[1] for g in grad], "sgi", session, outdir)
+        outpost_dnek(W, "wmk", session, outdir)
+    return dict(eigvals=lam, d=d, grad=grad, transport=transport if parts else None, W=W, modes=list(zip(direct, adjoint)),
+                direct=run_d, adjoint=run_a, seconds=dict(direct=clock[1] - clock[0], adjoint=clock[2] - clock[1], sensitivity=clock[3] - clock[2]))
 
 
 # ------------------------------------------------------------------------------------------------------------------
