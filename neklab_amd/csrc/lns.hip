@@ -2330,6 +2330,18 @@ int store_state(nlg_linop *op, int lane, nlg_vec *v, int irst) {
     return 0;
 }
 
+// An intent(out) vector, default-initialised (history cleared, nrst = 0), whose blocks 0 .. nfill are about to be filled by
+// store_state: zero only the blocks behind them.  store_state writes every field the operator carries (the callers check that the
+// vector carries the same ones) and leaves the padding behind a field alone, which is zero in every vector from its creation on
+// (vec.hip), so a fill of the blocks 0 .. nfill would be overwritten to the last byte that matters.
+int clear_for_store(nlg_vec *v, int nfill) {
+    const int ntail = v->lorder - 1 - nfill;
+    if (ntail > 0)
+        NLG_HIP(hipMemsetAsync(v->d + (int64_t)(1 + nfill) * v->main_len, 0, sizeof(double) * (size_t)(ntail * v->main_len), v->mesh->ctx->stream));
+    v->nrst = 0;
+    return 0;
+}
+
 // out (velocity and pressure of its main block) = c (state of lane `lane` - X0), X0 = the operator's base flow, in one pass
 int state_minus_x0(nlg_linop *op, int lane, double c, nlg_vec *out) {
     nlg_mesh *m = op->mesh;
@@ -2498,12 +2510,13 @@ int do_matvec_block(nlg_linop *op, int s, const nlg_vec *const *vin, nlg_vec *co
     // consistent projection the leading pair is 0.94454.
     for (int slot = 0; slot < 3; ++slot) NLG_TRY(project_alpha(op, s, slot, all));
     for (int v = 0; v < s; ++v) {
-        // vec_out is intent(out): default-initialised (history cleared, nrst = 0), then filled
-        NLG_TRY(nlg_vec_zero(vout[v]));
+        // vec_out is intent(out): default-initialised (history cleared, nrst = 0), then filled -- the main block here, the
+        // history blocks 1 .. nrst below
+        NLG_TRY(clear_for_store(vout[v], nrst));
         NLG_TRY(store_state(op, v, vout[v], 0));
     }
     if (lb >= 0) {   // Phi_T(X0), before the history steps (which advance the base flow as well, periodic_orbit.f90:185-213)
-        NLG_TRY(nlg_vec_zero(op->orbit_end));
+        NLG_TRY(clear_for_store(op->orbit_end, 0));
         NLG_TRY(store_state(op, lb, op->orbit_end, 0));
         op->orbit_end_valid = true;
     }
@@ -2571,7 +2584,7 @@ int do_integrate_forced_block(nlg_linop *op, int s, const nlg_vec *const *ic, co
     L.omega = omega, L.sign = adjoint ? -1.0 : 1.0;
     NLG_TRY(run_steps(L));
     for (int v = 0; v < s; ++v) {
-        NLG_TRY(nlg_vec_zero(vout[v]));
+        NLG_TRY(clear_for_store(vout[v], 0));
         NLG_TRY(store_state(op, v, vout[v], 0));
     }
     return 0;
@@ -2601,7 +2614,7 @@ int do_nonlinear_map(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout) {
     Lanes L{op, 1};
     L.nonlinear = 1;
     NLG_TRY(run_steps(L));
-    NLG_TRY(nlg_vec_zero(vout));
+    NLG_TRY(clear_for_store(vout, 0));
     NLG_TRY(store_state(op, 0, vout, 0));
     NLG_TRY(nlg_vec_axpby(-1.0, vin, 1.0, vout));   // vec_out%sub(vec_in), fixed_point.f90:29
     // the base-flow dependent set-up now belongs to vec_in: a later linear matvec needs nlg_linop_set_baseflow

@@ -40,6 +40,23 @@ __device__ __forceinline__ double block_sum(double v, double *sm) {
     return r;
 }
 
+// A load of the basis in a kernel that passes over it once: non-temporal, so that the 8 - 27 GB of a sweep do not push the arrays
+// that ARE re-used (w, bm1, the coefficients) out of L2 and the Infinity Cache.  NTL = false: a plain load, for the few columns of a
+// small k that DO survive in the Infinity Cache from one pass of CGS2 to the next (stream_basis below).  The two fused sweeps
+// (k_block_axpy_dot, k_block_axpy_dot2: one wave per SIMD, 64 loads in flight per wave) keep plain loads: non-temporal ones were
+// 0.05 ms faster on one grade of MI355X box and 0.04 ms slower on the other (profiles/arnoldi_tail_ab_same_box.txt)
+template <bool NTL = true>
+__device__ __forceinline__ double2 ld_once(const double2 *p) {
+    if (!NTL) return *p;
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    const v2d t = __builtin_nontemporal_load(reinterpret_cast<const v2d *>(p));
+    return make_double2(t.x, t.y);
+}
+// k columns of `len` doubles each, read by every pass of an orthogonalisation: streamed past the caches from four times the
+// Infinity Cache (256 MB) on.  Below that part of the basis is still there when the next pass comes (measured at 140 MB per column:
+// CGS2 at k = 1, 2 loses 0.09 / 0.06 ms with non-temporal loads, k = 4 is even, k = 8 gains 0.08 ms)
+inline bool stream_basis(int k, int64_t len) { return (int64_t)k * len * (int64_t)sizeof(double) >= ((int64_t)1 << 30); }
+
 __global__ __launch_bounds__(NT) void k_fill(double2 *x, double v, int64_t n2) {
     for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2; i += (int64_t)gridDim.x * NT) x[i] = make_double2(v, v);
 }
@@ -71,13 +88,16 @@ struct LaneAB {
     const double *a[kMaxLanes], *b[kMaxLanes];
 };
 
-// blockIdx.y = lane: w_l *= 1 / sqrt(q[l]) over the main block (n2 double2 entries) and the valid history blocks, the scalar on
-// device (0 where q[l] is not positive)
-__global__ __launch_bounds__(NT) void k_scal_dev(LaneVW P, const double *q, int64_t n2) {
+// the normalisation factor of a vector whose squared norm is sv (0 where sv is not positive): ONE expression for every kernel that
+// scales by it, so that they all multiply by the same bits
+__device__ __forceinline__ double inv_norm(double sv) { return sv > 0.0 ? 1.0 / sqrt(sv) : 0.0; }
+
+// blockIdx.y = lane: w_l *= inv_norm(q[l]) over the main block (n2 double2 entries) and, with `hist`, the valid history blocks, the
+// scalar on device
+__global__ __launch_bounds__(NT) void k_scal_dev(LaneVW P, const double *q, int64_t n2, int hist) {
     const int l = blockIdx.y;
-    const double sv = q[l];
-    const double a = sv > 0.0 ? 1.0 / sqrt(sv) : 0.0;
-    const int64_t n2all = n2 * (1 + P.nrst[l]);
+    const double a = inv_norm(q[l]);
+    const int64_t n2all = hist ? n2 * (1 + P.nrst[l]) : n2;
     double2 *x = reinterpret_cast<double2 *>(P.w[l]);
     for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
         double2 v = x[i];
@@ -184,20 +204,36 @@ __global__ __launch_bounds__(NT) void k_reduce_rows(const double *partial, int n
     }
 }
 
+// The block projections cut the work into reduction chunks (points) x tiles (KB basis vectors); every tile of a chunk reads the same
+// w and bm1.  blockIdx.x carries both so that the tiles of a chunk are dispatched next to each other AND onto the same XCD, where the
+// first of them leaves w and bm1 in L2 for the others: workgroups go round the 8 XCDs in the order of blockIdx.x, so within a group
+// of 8 chunks the chunk is blockIdx.x mod 8 and the tile the quotient.  Placement is only observed, not promised: it decides where
+// the re-reads are served from, never a result.  (k = 64, 10^4 elements: k_block_dot 1.455 -> 1.396 ms beside tiles in blockIdx.z.)
+constexpr int kXcd = 8;
+inline unsigned chunk_tile_grid(int nblk, int ntile) { return (unsigned)((nblk + kXcd - 1) / kXcd * kXcd * ntile); }
+__device__ __forceinline__ void chunk_tile(int ntile, int &chunk, int &tile) {
+    const int grp = blockIdx.x / (kXcd * ntile), rem = blockIdx.x - grp * kXcd * ntile;
+    chunk = grp * kXcd + rem % kXcd;      // may lie beyond nblk in the last group: such a block has nothing to do
+    tile = rem / kXcd;
+}
+
 // h_j = V_j^T (bm1 o w) for a tile of KB basis vectors; V is read exactly once.
-// blockIdx.y = lane * ncomp + field, blockIdx.z = tile; partial row (lane * k + j)
-template <int KB>
+// blockIdx.x = chunk and tile (chunk_tile), blockIdx.y = lane * ncomp + field; partial row (lane * k + j)
+template <int KB, bool NTL>
 __global__ __launch_bounds__(NT) void k_block_dot(LaneVW P, int64_t vstride, int k, int ncomp, const double *bm1, int64_t lvs, int nblk,
                                                   int nper, double *partial) {
     __shared__ double sm[4 * KB];
     const int l = blockIdx.y / ncomp, c = blockIdx.y - l * ncomp;
     const double *V = P.V[l];
     const double *w = P.w[l];
-    const int j0 = blockIdx.z * KB;
+    int chunk, tile;
+    chunk_tile((k + KB - 1) / KB, chunk, tile);
+    if (chunk >= nblk) return;
+    const int j0 = tile * KB;
     const int kc = (k - j0 < KB) ? (k - j0) : KB;
     const int64_t n2 = lvs >> 1;
     const int64_t per = (n2 + nblk - 1) / nblk;
-    const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
+    const int64_t beg = chunk * per, end = (beg + per < n2) ? beg + per : n2;
     const double2 *w2 = reinterpret_cast<const double2 *>(w + c * lvs);
     const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
     const double2 *v2[KB];
@@ -214,7 +250,7 @@ __global__ __launch_bounds__(NT) void k_block_dot(LaneVW P, int64_t vstride, int
         const double x0 = wv.x * mv.x, x1 = wv.y * mv.y;
         double2 vv[KB];
 #pragma unroll
-        for (int j = 0; j < KB; ++j) vv[j] = v2[j][i];
+        for (int j = 0; j < KB; ++j) vv[j] = ld_once<NTL>(v2[j] + i);
 #pragma unroll
         for (int j = 0; j < KB; ++j) acc[j] += vv[j].x * x0 + vv[j].y * x1;
     }
@@ -228,7 +264,7 @@ __global__ __launch_bounds__(NT) void k_block_dot(LaneVW P, int64_t vstride, int
     if (threadIdx.x < kc) {
         const int j = threadIdx.x;
         const double s = sm[j] + sm[KB + j] + sm[2 * KB + j] + sm[3 * KB + j];
-        partial[((int64_t)l * k + j0 + j) * nper + c * nblk + blockIdx.x] = s;
+        partial[((int64_t)l * k + j0 + j) * nper + c * nblk + chunk] = s;
     }
 }
 
@@ -339,12 +375,17 @@ __global__ __launch_bounds__(NT) void k_block_axpy_dot2(const double *__restrict
 // `hh` (may be null; HIST_SWEEP): a second coefficient set for the entries at or beyond n2: CGS2 applies the second-pass
 // coefficients to the main block and the SUM of both passes to the history, which no inner product ever reads -> the history is
 // swept once, not twice.
-enum { HIST_NONE = 0, HIST_SWEEP = 1, HIST_MAIN = 2 };
+// TAIL (the end of CGS2, `hist` = HIST_ONLY): the history blocks alone (a lane without any: nothing), every updated entry then
+// multiplied by inv_norm(q[l]) -- the update rounded first, the product after, as k_scal_dev would do to the stored value in a pass
+// of its own.  A template parameter, so that the plain sweep compiles as if the tail did not exist.
+enum { HIST_NONE = 0, HIST_SWEEP = 1, HIST_MAIN = 2, HIST_ONLY = 3 };
+template <bool TAIL, bool NTL>
 __global__ __launch_bounds__(NT) void k_block_axpy(LaneVW P, int64_t vstride, int k, const double *h, const double *hh, int64_t n2,
-                                                   int hist, double sign) {
+                                                   int hist, double sign, const double *q) {
     extern __shared__ double sh0[];
     double *sh1 = sh0 + k;
     const int l = blockIdx.y;
+    if (TAIL && P.nrst[l] == 0) return;
     h += (int64_t)l * k;
     if (hh) hh += (int64_t)l * k;
     for (int j = threadIdx.x; j < k; j += NT) {
@@ -352,12 +393,14 @@ __global__ __launch_bounds__(NT) void k_block_axpy(LaneVW P, int64_t vstride, in
         sh1[j] = hh ? hh[j] : h[j];
     }
     __syncthreads();
-    const int64_t n2all = hist == HIST_SWEEP ? n2 * (1 + P.nrst[l]) : n2;
-    const int ncopy = hist == HIST_MAIN ? P.nrst[l] : 0;
+    const int64_t n2all = (TAIL || hist == HIST_SWEEP) ? n2 * (1 + P.nrst[l]) : n2;
+    const int64_t ibeg = TAIL ? n2 : 0;
+    const int ncopy = (!TAIL && hist == HIST_MAIN) ? P.nrst[l] : 0;
+    const double a = TAIL ? inv_norm(q[l]) : 1.0;
     double2 *w2 = reinterpret_cast<double2 *>(P.w[l]);
     const double2 *V2 = reinterpret_cast<const double2 *>(P.V[l]);
     const int64_t vs2 = vstride >> 1;
-    for (int64_t i = blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
+    for (int64_t i = ibeg + blockIdx.x * (int64_t)NT + threadIdx.x; i < n2all; i += (int64_t)gridDim.x * NT) {
         const double *sh = (hh && i >= n2) ? sh1 : sh0;
         double s0 = 0.0, s1 = 0.0;
         const double2 *v = V2 + i;
@@ -365,7 +408,7 @@ __global__ __launch_bounds__(NT) void k_block_axpy(LaneVW P, int64_t vstride, in
         for (; j + 8 <= k; j += 8) {
             double2 t[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = v[(int64_t)(j + u) * vs2];
+            for (int u = 0; u < 8; ++u) t[u] = ld_once<NTL>(v + (int64_t)(j + u) * vs2);
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 s0 += sh[j + u] * t[u].x;
@@ -373,13 +416,17 @@ __global__ __launch_bounds__(NT) void k_block_axpy(LaneVW P, int64_t vstride, in
             }
         }
         for (; j < k; ++j) {
-            const double2 t = v[(int64_t)j * vs2];
+            const double2 t = ld_once<NTL>(v + (int64_t)j * vs2);
             s0 += sh[j] * t.x;
             s1 += sh[j] * t.y;
         }
         double2 wv = w2[i];
         wv.x += sign * s0;
         wv.y += sign * s1;
+        if (TAIL) {
+            wv.x = __dmul_rn(wv.x, a);
+            wv.y = __dmul_rn(wv.y, a);
+        }
         w2[i] = wv;
         for (int r = 1; r <= ncopy; ++r) {
             double2 rv = w2[i + r * n2];
@@ -398,11 +445,14 @@ __global__ __launch_bounds__(NT) void k_block_dot_s(const double *V, int64_t vst
                                                     const double *bm1, int64_t lvs, int nblk, int nper, double *partial) {
     __shared__ double sm[4 * KB * S];
     const int c = blockIdx.y;
-    const int j0 = blockIdx.z * KB;
+    int chunk, tile;
+    chunk_tile((k + KB - 1) / KB, chunk, tile);
+    if (chunk >= nblk) return;
+    const int j0 = tile * KB;
     const int kc = (k - j0 < KB) ? (k - j0) : KB;
     const int64_t n2 = lvs >> 1;
     const int64_t per = (n2 + nblk - 1) / nblk;
-    const int64_t beg = blockIdx.x * per, end = (beg + per < n2) ? beg + per : n2;
+    const int64_t beg = chunk * per, end = (beg + per < n2) ? beg + per : n2;
     const double2 *m2 = reinterpret_cast<const double2 *>(bm1);
     const double2 *v2[KB];
 #pragma unroll
@@ -426,7 +476,7 @@ __global__ __launch_bounds__(NT) void k_block_dot_s(const double *V, int64_t vst
         }
         double2 vv[KB];
 #pragma unroll
-        for (int j = 0; j < KB; ++j) vv[j] = v2[j][i];
+        for (int j = 0; j < KB; ++j) vv[j] = ld_once(v2[j] + i);
 #pragma unroll
         for (int j = 0; j < KB; ++j)
 #pragma unroll
@@ -444,7 +494,7 @@ __global__ __launch_bounds__(NT) void k_block_dot_s(const double *V, int64_t vst
     if (threadIdx.x < kc * S) {
         const int q = threadIdx.x;   // j * S + v
         const double t = (sm[q] + sm[KB * S + q]) + (sm[2 * KB * S + q] + sm[3 * KB * S + q]);
-        partial[((int64_t)j0 * S + q) * nper + c * nblk + blockIdx.x] = t;
+        partial[((int64_t)j0 * S + q) * nper + c * nblk + chunk] = t;
     }
 }
 
@@ -473,7 +523,7 @@ __global__ __launch_bounds__(NT) void k_block_axpy_s(const double *V, int64_t vs
         for (; j + 8 <= k; j += 8) {
             double2 t[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = v[(int64_t)(j + u) * vs2];
+            for (int u = 0; u < 8; ++u) t[u] = ld_once(v + (int64_t)(j + u) * vs2);
 #pragma unroll
             for (int u = 0; u < 8; ++u)
 #pragma unroll
@@ -483,7 +533,7 @@ __global__ __launch_bounds__(NT) void k_block_axpy_s(const double *V, int64_t vs
                 }
         }
         for (; j < k; ++j) {
-            const double2 t = v[(int64_t)j * vs2];
+            const double2 t = ld_once(v + (int64_t)j * vs2);
 #pragma unroll
             for (int q = 0; q < S; ++q) {
                 s0[q] += sh[j * S + q] * t.x;
@@ -1015,22 +1065,39 @@ static int lanes_block_dot(const nlg_basis *b0, int s, const LaneVW &P, int k, d
     const int nblk = dot_nblk(v0), nper = nblk * v0->ncomp;
     NLG_TRY(reduce_ws_reserve(ctx, s * k));
     ProfScope ps(ctx, P_BLOCKDOT);
-    NLG_LAUNCH(k_block_dot<KB>, dim3(nblk, v0->ncomp * s, (k + KB - 1) / KB), dim3(NT), 0, ctx->stream, P, b0->stride, k, v0->ncomp,
-               (const double *)m->d_bm1, m->lvs, nblk, nper, ctx->d_partial);
+    const dim3 g(chunk_tile_grid(nblk, (k + KB - 1) / KB), v0->ncomp * s);
+    if (stream_basis(k, v0->main_len))
+        NLG_LAUNCH((k_block_dot<KB, true>), g, dim3(NT), 0, ctx->stream, P, b0->stride, k, v0->ncomp, (const double *)m->d_bm1, m->lvs, nblk,
+                   nper, ctx->d_partial);
+    else
+        NLG_LAUNCH((k_block_dot<KB, false>), g, dim3(NT), 0, ctx->stream, P, b0->stride, k, v0->ncomp, (const double *)m->d_bm1, m->lvs, nblk,
+                   nper, ctx->d_partial);
     NLG_TRY(reduce_rows_all(ctx, s * k, nper, d_out, d_acc));
     NLG_HIP(hipGetLastError());
     return 0;
 }
 
-// w_l += sign * V_l h_l of s lanes, the history blocks as `hist` says (k_block_axpy)
+// w_l += sign * V_l h_l of s lanes, the history blocks as `hist` says (k_block_axpy); d_q (may be null): the squared norms by
+// whose inv_norm the updated entries are scaled.  HIST_ONLY without a history block in any lane: no launch
 static int lanes_block_axpy(const nlg_basis *b0, int s, const LaneVW &P, int k, const double *d_h, const double *d_hh, int hist,
-                            double sign) {
+                            double sign, const double *d_q = nullptr) {
     nlg_ctx *ctx = b0->mesh->ctx;
     const int64_t n2 = b0->views[0]->main_len / 2;
-    const int64_t n2all = hist == HIST_SWEEP ? n2 * (1 + max_nrst(s, P)) : n2;
+    const int mr = max_nrst(s, P);
+    if (hist == HIST_ONLY && mr == 0) return 0;
+    const int64_t n2all = hist == HIST_SWEEP ? n2 * (1 + mr) : hist == HIST_ONLY ? n2 * mr : n2;
     ProfScope ps(ctx, P_BLOCKAXPY);
-    NLG_LAUNCH(k_block_axpy, dim3(grid_for(n2all), s), dim3(NT), sizeof(double) * 2 * k, ctx->stream, P, b0->stride, k, d_h, d_hh, n2,
-               hist, sign);
+    const bool ntl = stream_basis(k, 2 * n2);
+#define BAX(T_, N_) NLG_LAUNCH((k_block_axpy<T_, N_>), dim3(grid_for(n2all), s), dim3(NT), sizeof(double) * 2 * k, ctx->stream, P, b0->stride, k, \
+                               d_h, d_hh, n2, hist, sign, d_q)
+    if (hist == HIST_ONLY) {
+        if (ntl) BAX(true, true);
+        else BAX(true, false);
+    } else {
+        if (ntl) BAX(false, true);
+        else BAX(false, false);
+    }
+#undef BAX
     NLG_HIP(hipGetLastError());
     return 0;
 }
@@ -1078,8 +1145,12 @@ static int cgs2_fused_sweep(const nlg_basis *b, int k, nlg_vec *w, double *h, do
         if (np2 > 0) {
             LaneVW Pp = {};
             Pp.V[0] = Vf + nv, Pp.w[0] = w->d + nv;
-            NLG_LAUNCH(k_block_axpy, dim3(grid_for(np2)), dim3(NT), sizeof(double) * 2 * kf, ctx->stream, Pp, b->stride, kf,
-                       (const double *)(h + k0), (const double *)nullptr, np2, (int)HIST_NONE, -1.0);
+            if (stream_basis(kf, w->main_len))
+                NLG_LAUNCH((k_block_axpy<false, true>), dim3(grid_for(np2)), dim3(NT), sizeof(double) * 2 * kf, ctx->stream, Pp, b->stride, kf,
+                           (const double *)(h + k0), (const double *)nullptr, np2, (int)HIST_NONE, -1.0, (const double *)nullptr);
+            else
+                NLG_LAUNCH((k_block_axpy<false, false>), dim3(grid_for(np2)), dim3(NT), sizeof(double) * 2 * kf, ctx->stream, Pp, b->stride, kf,
+                           (const double *)(h + k0), (const double *)nullptr, np2, (int)HIST_NONE, -1.0, (const double *)nullptr);
         }
     }
     NLG_TRY(reduce_rows_all(ctx, kf, G, h2 + k0, h + k0));
@@ -1087,28 +1158,37 @@ static int cgs2_fused_sweep(const nlg_basis *b, int k, nlg_vec *w, double *h, do
     return 0;
 }
 
-// CGS2 + norm + scale of s vectors, each against its own basis, everything stream-ordered on device: four launches plus the small
-// reductions for all lanes, then norm and scale.  Results in b[0]'s workspace: h1() coefficients [s][k], hnorm(s, k) the |w_l|^2
-// before normalisation.
+// CGS2 + norm + scale of s vectors, each against its own basis, everything stream-ordered on device.  Results in b[0]'s workspace:
+// h1() coefficients [s][k], hnorm(s, k) the |w_l|^2 before normalisation.
+// Consistent mode touches the history blocks of w ONCE.  No inner product reads them, so both subtractions and the scale can wait
+// until the norm is known:
+//   1. projection, first subtraction, second projection on the main block (three launches, or the fused sweep of one vector at
+//      k >= 24), then the second subtraction on the main block alone (H2);
+//   2. |w|^2 of the main block (k_dot_partial + row reduction);
+//   3. ONE launch over the history blocks: w_hist <- fl(w_hist - V_hist (H1 + H2)) * inv_norm(|w|^2), lane by lane with its own
+//      number of blocks and its own norm (nothing for a lane, or a call, without history);
+//   4. the scale of the main block.
+// Every stored value is what a sweep over all blocks followed by a scale of all blocks gives, bit for bit (the subtraction is
+// rounded before the product either way); the history is read and written once instead of twice.
+// Literal mode repeats the main block's correction in the history, which ties the two together: sweep, sweep, norm, scale of all.
 static int basis_cgs2_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w) {
     nlg_basis *b0 = b[0];
     nlg_mesh *m = b0->mesh;
     nlg_ctx *ctx = m->ctx;
     double *H1 = b0->h1(), *H2 = b0->h2(), *Q = b0->hnorm(s, k);
     const LaneVW P = lanes_of(s, b, w);
+    const bool split = k > 0 && g_axpby_consistent;   // the history waits for the norm (step 3)
     if (k > 0) {
         NLG_TRY(lanes_block_dot(b0, s, P, k, H1, nullptr));
         if (g_axpby_consistent) {
-            // first pass on the main block only; the second pass applies H2 to the main block and H1 + H2 (accumulated
-            // in H1 by the second block_dot) to the history blocks: the result is the one of two full sweeps up to
-            // rounding, at two thirds of the traffic
+            // the second block_dot accumulates H2 into H1: H1 = the sum of both passes, what the history receives
             if (s == 1 && k >= 24) {
                 NLG_TRY(cgs2_fused_sweep(b0, k, w[0], H1, H2));
             } else {
                 NLG_TRY(lanes_block_axpy(b0, s, P, k, H1, nullptr, HIST_NONE, -1.0));
                 NLG_TRY(lanes_block_dot(b0, s, P, k, H2, H1));
             }
-            NLG_TRY(lanes_block_axpy(b0, s, P, k, H2, H1, HIST_SWEEP, -1.0));
+            NLG_TRY(lanes_block_axpy(b0, s, P, k, H2, nullptr, HIST_NONE, -1.0));
         } else {
             NLG_TRY(lanes_block_axpy(b0, s, P, k, H1, nullptr, HIST_MAIN, -1.0));
             NLG_TRY(lanes_block_dot(b0, s, P, k, H2, H1));
@@ -1123,7 +1203,9 @@ static int basis_cgs2_dev(int s, nlg_basis *const *b, int k, nlg_vec *const *w) 
     NLG_LAUNCH(k_dot_partial, dim3(nblk, v0->ncomp, s), dim3(NT), 0, ctx->stream, A, (const double *)m->d_bm1, m->lvs, nblk, nper,
                ctx->d_partial);
     NLG_TRY(reduce_rows_all(ctx, s, nper, Q, nullptr));
-    NLG_LAUNCH(k_scal_dev, dim3(grid_for(n2 * (1 + max_nrst(s, P))), s), dim3(NT), 0, ctx->stream, P, (const double *)Q, n2);
+    if (split) NLG_TRY(lanes_block_axpy(b0, s, P, k, H1, nullptr, HIST_ONLY, -1.0, Q));
+    NLG_LAUNCH(k_scal_dev, dim3(grid_for(split ? n2 : n2 * (1 + max_nrst(s, P))), s), dim3(NT), 0, ctx->stream, P, (const double *)Q, n2,
+               split ? 0 : 1);
     NLG_HIP(hipGetLastError());
     return 0;
 }
@@ -1263,7 +1345,7 @@ int nlg_basis_block_cgs2(nlg_basis *b, int k, int s, double *coef) {
     NLG_TRY(reduce_ws_reserve(ctx, std::max(k, s) * s));
     auto dots = [&](const double *V, int kk, double *out, double *acc) -> int {
         ProfScope ps(ctx, P_BLOCKDOT);
-        const dim3 g(nblk, w0->ncomp, (kk + KB - 1) / KB);
+        const dim3 g(chunk_tile_grid(nblk, (kk + KB - 1) / KB), w0->ncomp);
 #define BD(S_) NLG_LAUNCH((k_block_dot_s<KB, S_>), g, dim3(NT), 0, st, V, b->stride, kk, (const double *)W, b->stride, \
                                   (const double *)b->mesh->d_bm1, b->mesh->lvs, nblk, nper, ctx->d_partial)
         if (s == 2) BD(2);
