@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "fg_slot.h"
 #include "neklab_gpu.h"
 
 namespace nlg {
@@ -62,6 +63,15 @@ constexpr int kAlign = 32;              // field starts aligned to 32 doubles (2
 
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
+template <typename T = double>
+struct DevBuf {   // a device temporary, released on every path out of its scope
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+};
+
 }  // namespace nlg
 
 // kernel classes that can be timed with HIP events on the launch stream (bench.py roofline leg)
@@ -110,30 +120,6 @@ struct nlg_ops1d {
     std::vector<double> DJd;   // nd x n
     std::vector<double> rdr;   // n  inverse reference spacing (CFL)
 };
-
-// Face-grouped slot of point (a, j, k) inside an element: the 8 corners, the 12 edges (interior points of an edge
-// contiguous), the 6 face interiors (contiguous (N-2)^2 blocks), then the element interior.  The copies of a shared
-// face or edge are then contiguous runs in every element that shares it, so the gather-scatter moves whole runs
-// instead of one 8-byte word per 64-byte line.  FG = false gives the natural ix-fastest index.
-__host__ __device__ inline int fg_slot(int N, int a, int j, int k) {
-    const int M = N - 2;
-    const int ba = (a == 0 || a == N - 1), bj = (j == 0 || j == N - 1), bk = (k == 0 || k == N - 1);
-    const int sa = a == N - 1, sj = j == N - 1, sk = k == N - 1;
-    const int nb = ba + bj + bk;
-    if (nb == 3) return sa + 2 * sj + 4 * sk;
-    if (nb == 2) {
-        if (!ba) return 8 + (0 + sj + 2 * sk) * M + (a - 1);
-        if (!bj) return 8 + (4 + sa + 2 * sk) * M + (j - 1);
-        return 8 + (8 + sa + 2 * sj) * M + (k - 1);
-    }
-    const int fbase = 8 + 12 * M;
-    if (nb == 1) {
-        if (ba) return fbase + (0 + sa) * M * M + (j - 1) + M * (k - 1);
-        if (bj) return fbase + (2 + sj) * M * M + (a - 1) + M * (k - 1);
-        return fbase + (4 + sk) * M * M + (a - 1) + M * (j - 1);
-    }
-    return fbase + 6 * M * M + (a - 1) + M * ((j - 1) + M * (k - 1));
-}
 
 // "Slab-permuted" slot of point (a, j, k) (historically "xp", x-planes first): every k-slab of an element stays one dense run
 // of N N doubles, but inside the slab the points are permuted so that the element-boundary points are contiguous:

@@ -2883,11 +2883,6 @@ int nlg_linop_set_baseflow(nlg_linop *op, const nlg_vec *baseflow) {
     return nlg_linop_init(op);
 }
 
-struct DevBuf {   // a device temporary, released on every path out of its scope
-    double *p = nullptr;
-    ~DevBuf() { (void)hipFree(p); }
-};
-
 // the lines of one mesh into P (empty on entry; the caller frees it whatever this returns): lines = groups of local dofs with the same
 // label, ordered by label then by index.  The coordinate along the homogeneous direction is on the device (d_x) or on the host (h_x).
 // nalpha wavenumbers: the lines once, one cos / sin table per wavenumber (k_cossin each: table l is the table of a single alpha[l]).
@@ -2922,7 +2917,7 @@ static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *al
     NLG_HIP(hipMemcpy(P.off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
     NLG_HIP(hipMemcpy(P.idx, order.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
     NLG_HIP(hipMemcpy(P.iden, iden.data(), sizeof(double) * (size_t)nlines, hipMemcpyHostToDevice));
-    DevBuf xs;
+    DevBuf<double> xs;
     if (h_x) {   // (pressure mesh)
         NLG_HIP(hipMalloc(&xs.p, sizeof(double) * (size_t)n));
         NLG_HIP(hipMemcpy(xs.p, h_x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
@@ -2939,7 +2934,7 @@ static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *al
     std::vector<double> cnts(nr);
     int64_t maxc = 1;
     {
-        DevBuf cnt;
+        DevBuf<double> cnt;
         NLG_HIP(hipMalloc(&cnt.p, sizeof(double) * (nr + 1)));
         NLG_HIP(hipMemcpy(cnt.p + nr, &mine, sizeof(double), hipMemcpyHostToDevice));
         NLG_TRY(allgather_f64(ctx, cnt.p + nr, cnt.p, 1));
@@ -2950,7 +2945,7 @@ static int proj_build(nlg_mesh *m, const char *who, int nalpha, const double *al
     std::vector<int64_t> mylab((size_t)maxc, -1), all((size_t)maxc * nr);
     for (int g = 0; g < nlines; ++g) mylab[g] = lab[order[off[g]]];
     {
-        DevBuf labs;   // (labels travel as 8-byte words)
+        DevBuf<double> labs;   // (labels travel as 8-byte words)
         NLG_HIP(hipMalloc(&labs.p, sizeof(int64_t) * (size_t)maxc * (nr + 1)));
         NLG_HIP(hipMemcpy(labs.p + (size_t)maxc * nr, mylab.data(), sizeof(int64_t) * (size_t)maxc, hipMemcpyHostToDevice));
         NLG_TRY(allgather_f64(ctx, labs.p + (size_t)maxc * nr, labs.p, maxc));

@@ -28,12 +28,14 @@
 // M is a fixed symmetric positive (semi-)definite operator, so plain PCG stays valid.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <numeric>
-#include <unordered_map>
+#include <string>
 
 #include <rocsolver/rocsolver.h>
 
 #include "internal.h"
+#include "pprec_host.h"
 
 using namespace nlg;
 
@@ -1135,128 +1137,7 @@ __global__ __launch_bounds__(NT) void k_gj_update(int n, int k, double *__restri
     A[(size_t)i * n + j] = v;
 }
 
-// ---- host helpers -------------------------------------------------------------------------------------
-// symmetric eigen-decomposition by cyclic Jacobi rotations (n <= 16): A = V diag(w) V^T
-void jacobi_eig(int n, std::vector<double> &A, std::vector<double> &V, std::vector<double> &w) {
-    V.assign((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        double off = 0.0;
-        for (int i = 0; i < n; ++i)
-            for (int j = i + 1; j < n; ++j) off += A[(size_t)i * n + j] * A[(size_t)i * n + j];
-        if (off < 1e-300) break;
-        for (int p = 0; p < n; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = A[(size_t)p * n + q];
-                if (std::fabs(apq) < 1e-300) continue;
-                const double theta = (A[(size_t)q * n + q] - A[(size_t)p * n + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
-                    A[(size_t)k * n + p] = c * akp - s * akq;
-                    A[(size_t)k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
-                    A[(size_t)p * n + k] = c * apk - s * aqk;
-                    A[(size_t)q * n + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double vkp = V[(size_t)k * n + p], vkq = V[(size_t)k * n + q];
-                    V[(size_t)k * n + p] = c * vkp - s * vkq;
-                    V[(size_t)k * n + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    w.resize(n);
-    for (int i = 0; i < n; ++i) w[i] = A[(size_t)i * n + i];
-}
-
-// generalised symmetric problem A s = lam B s, B SPD: S^T B S = I, S^T A S = diag(lam). S row-major [point][mode].
-int gen_eig(int n, const std::vector<double> &A, const std::vector<double> &B, std::vector<double> &S,
-            std::vector<double> &lam) {
-    std::vector<double> L((size_t)n * n, 0.0);
-    for (int j = 0; j < n; ++j) {
-        double d = B[(size_t)j * n + j];
-        for (int k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
-        if (!(d > 0.0)) return 1;
-        L[(size_t)j * n + j] = std::sqrt(d);
-        for (int i = j + 1; i < n; ++i) {
-            double s = B[(size_t)i * n + j];
-            for (int k = 0; k < j; ++k) s -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
-            L[(size_t)i * n + j] = s / L[(size_t)j * n + j];
-        }
-    }
-    // Linv (lower)
-    std::vector<double> Li((size_t)n * n, 0.0);
-    for (int c = 0; c < n; ++c) {
-        Li[(size_t)c * n + c] = 1.0 / L[(size_t)c * n + c];
-        for (int i = c + 1; i < n; ++i) {
-            double s = 0.0;
-            for (int k = c; k < i; ++k) s += L[(size_t)i * n + k] * Li[(size_t)k * n + c];
-            Li[(size_t)i * n + c] = -s / L[(size_t)i * n + i];
-        }
-    }
-    std::vector<double> T((size_t)n * n, 0.0), Cm((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < n; ++k) s += Li[(size_t)i * n + k] * A[(size_t)k * n + j];
-            T[(size_t)i * n + j] = s;
-        }
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < n; ++k) s += T[(size_t)i * n + k] * Li[(size_t)j * n + k];
-            Cm[(size_t)i * n + j] = s;
-        }
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j) Cm[(size_t)i * n + j] = Cm[(size_t)j * n + i] = 0.5 * (Cm[(size_t)i * n + j] + Cm[(size_t)j * n + i]);
-    std::vector<double> V;
-    jacobi_eig(n, Cm, V, lam);
-    S.assign((size_t)n * n, 0.0);   // S = Li^T V
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < n; ++k) s += Li[(size_t)k * n + i] * V[(size_t)k * n + j];
-            S[(size_t)i * n + j] = s;
-        }
-    return 0;
-}
-
-// dense SPD inverse by Cholesky (in place, row-major); returns non-zero if not positive definite
-int spd_inverse(int n, std::vector<double> &A) {
-    std::vector<double> L((size_t)n * n, 0.0);
-    for (int j = 0; j < n; ++j) {
-        double d = A[(size_t)j * n + j];
-        for (int k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
-        if (!(d > 0.0)) return 1;
-        L[(size_t)j * n + j] = std::sqrt(d);
-        for (int i = j + 1; i < n; ++i) {
-            double s = A[(size_t)i * n + j];
-            for (int k = 0; k < j; ++k) s -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
-            L[(size_t)i * n + j] = s / L[(size_t)j * n + j];
-        }
-    }
-    std::vector<double> Li((size_t)n * n, 0.0);
-    for (int c = 0; c < n; ++c) {
-        Li[(size_t)c * n + c] = 1.0 / L[(size_t)c * n + c];
-        for (int i = c + 1; i < n; ++i) {
-            double s = 0.0;
-            for (int k = c; k < i; ++k) s += L[(size_t)i * n + k] * Li[(size_t)k * n + c];
-            Li[(size_t)i * n + c] = -s / L[(size_t)i * n + i];
-        }
-    }
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j <= i; ++j) {
-            double s = 0.0;
-            for (int k = i; k < n; ++k) s += Li[(size_t)k * n + i] * Li[(size_t)k * n + j];
-            A[(size_t)i * n + j] = A[(size_t)j * n + i] = s;
-        }
-    return 0;
-}
-
+// ---- set-up: the device parts (the host arithmetic of the stages is in pprec_host.cpp) ---------------------------------
 template <typename T>
 int up(const std::vector<T> &v, T **d) {
     NLG_HIP(hipMalloc(d, sizeof(T) * std::max<size_t>(v.size(), 1)));
@@ -1264,707 +1145,369 @@ int up(const std::vector<T> &v, T **d) {
     return 0;
 }
 
+struct HaloOff {   // the operator without the halo exchange for the life of the guard
+    nlg_halo &h;
+    const bool was;
+    explicit HaloOff(nlg_halo &halo) : h(halo), was(halo.active) { h.active = false; }
+    ~HaloOff() { h.active = was; }
+};
+struct BlasHandle {
+    rocblas_handle h = nullptr;
+    ~BlasHandle() { if (h) rocblas_destroy_handle(h); }
+};
+
+int env_int(const char *name, int dflt) {
+    const char *ev = getenv(name);
+    return ev ? atoi(ev) : dflt;
+}
+// a host stage's failure becomes the library's error
+int stage(int rc, const std::string &err) {
+    if (rc) set_error("%s", err.c_str());
+    return rc;
+}
+
+Hat hat_of(const nlg_mesh *m) {
+    Hat hat;
+    for (int k = 0; k < 12; ++k) hat.h1[k] = k < m->n2 ? m->pprec.hat1[k] : 0.0;
+    return hat;
+}
+// pp = the hat of corner c of every element of colour `col`
+void probe_vertex(nlg_mesh *m, const int *d_colour, int col, int c, double *pp) {
+    const dim3 gp((unsigned)((m->lpn + NT - 1) / NT));
+    if (m->dim == 3)
+        NLG_LAUNCH(k_q1_probe<3>, gp, dim3(NT), 0, m->ctx->stream, m->E, m->n2, hat_of(m), d_colour, col, c, pp);
+    else
+        NLG_LAUNCH(k_q1_probe<2>, gp, dim3(NT), 0, m->ctx->stream, m->E, m->n2, hat_of(m), d_colour, col, c, pp);
+}
+// pp = the indicator of aggregate a prolonged to the pressure points (a < 0: zero)
+void probe_aggregate(nlg_mesh *m, int a, double *pp) {
+    const nlg_pprec &P = m->pprec;
+    const dim3 gp((unsigned)((m->lpn + NT - 1) / NT));
+    if (m->dim == 3)
+        NLG_LAUNCH(k_agg_probe<3>, gp, dim3(NT), 0, m->ctx->stream, m->E, m->n2, hat_of(m), (const int *)P.d_vg, (const int *)P.d_agg, a, pp);
+    else
+        NLG_LAUNCH(k_agg_probe<2>, gp, dim3(NT), 0, m->ctx->stream, m->E, m->n2, hat_of(m), (const int *)P.d_vg, (const int *)P.d_agg, a, pp);
+}
+// out[e][corner] = R_1^T ep per element, the plain restriction (no extended grids, no PCG update)
+void restrict_corners(nlg_mesh *m, double *ep, double *out) {
+    const dim3 ge((unsigned)((m->E + 3) / 4));
+    if (m->dim == 3)
+        NLG_LAUNCH(k_q1_restrict_local<3>, ge, dim3(NT), 0, m->ctx->stream, (const double *)nullptr, m->E, m->n2, hat_of(m), ep, out, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
+    else
+        NLG_LAUNCH(k_q1_restrict_local<2>, ge, dim3(NT), 0, m->ctx->stream, (const double *)nullptr, m->E, m->n2, hat_of(m), ep, out, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
+}
+
+// hw <- QQ^T hw through the device.  Halo on: a face neighbour on another rank counts like a local one (its ghost layer
+// travels with the halo exchange of the array W, pprec_apply)
+int sum_face_lengths(nlg_mesh *m, std::vector<double> &hw) {
+    hipStream_t st = m->ctx->stream;
+    double *dw = sem_scratch1(m, 0);
+    NLG_CHECK(dw, "pprec_setup: scratch allocation failed");
+    NLG_HIP(hipMemcpyAsync(dw, hw.data(), sizeof(double) * hw.size(), hipMemcpyHostToDevice, st));
+    double *f1[1] = {dw};
+    NLG_TRY(sem_gs(m, f1, 1));
+    NLG_HIP(hipMemcpyAsync(hw.data(), dw, sizeof(double) * hw.size(), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// The overlapping variant: extended 1-D operators from the line left neighbour | element | right neighbour, the overlap
+// destinations and the exchange arrays (return array Wr in the face-grouped layout in 3-D, in the natural layout in 2-D)
+int setup_overlap(nlg_mesh *m, const pph::Shape &s, const pph::Ops &o, const pph::Lengths &L) {
+    nlg_pprec &P = m->pprec;
+    hipStream_t st = m->ctx->stream;
+    std::string err;
+    std::vector<double> hw;
+    pph::face_lengths(s, L, hw);
+    NLG_TRY(sum_face_lengths(m, hw));
+    pph::ExtLines X;
+    NLG_TRY(stage(pph::extended_lines(s, o, L, hw, X, err), err));
+    NLG_TRY(up(X.wq, &P.d_wq));
+    P.thrx = X.thrx;
+    NLG_TRY(up(X.Sx, &P.d_Sx));
+    std::vector<int> pidx((size_t)2 * m->gs.npairs);   // the two-copy groups of the gather-scatter in the layout of Wr
+    NLG_HIP(hipMemcpy(pidx.data(), s.dim == 3 ? m->gs.d_indices_fg : m->gs.d_indices, sizeof(int) * pidx.size(), hipMemcpyDeviceToHost));
+    pph::OverlapDest D;
+    NLG_TRY(stage(pph::overlap_destinations(s, pidx, X.hasnb, m->halo.active, D, err), err));
+    NLG_TRY(up(D.pin, &P.d_pin));
+    NLG_TRY(up(D.pret, &P.d_pret));
+    NLG_HIP(hipMalloc(&P.d_Wr, sizeof(double) * (size_t)m->lvs));
+    NLG_HIP(hipMemsetAsync(P.d_Wr, 0, sizeof(double) * (size_t)m->lvs, st));
+    NLG_TRY(up(X.lamx, &P.d_lamx));
+    NLG_HIP(hipMalloc(&P.d_W, sizeof(double) * (size_t)m->lvs));
+    NLG_HIP(hipMemsetAsync(P.d_W, 0, sizeof(double) * (size_t)m->lvs, st));
+    P.overlap = true;
+    return 0;
+}
+
+// A_c = R_1^T E R_1 by probing E on the device (rank-local: without the halo exchange): one E application per
+// (colour, corner) gives the 2^dim x 2^dim blocks of every neighbouring pair of elements
+int probe_coarse_operator(nlg_mesh *m, const pph::CoarseTopo &T, pph::ProbedRows &rows) {
+    hipStream_t st = m->ctx->stream;
+    const int NC = 1 << m->dim;
+    const int64_t E = m->E;
+    DevBuf<int> d_colour;
+    DevBuf<double> d_t8;
+    NLG_TRY(up(T.colour, &d_colour.p));
+    NLG_HIP(hipMalloc(&d_t8.p, sizeof(double) * (size_t)E * NC));
+    double *pp = sem_scratch2(m, 0), *ep = sem_scratch2(m, 1);
+    NLG_CHECK(pp && ep, "pprec_setup: scratch allocation failed");
+    HaloOff halo_off(m->halo);
+    rows.assign((size_t)T.nvert, std::unordered_map<int, double>());
+    std::vector<double> t8((size_t)E * NC);
+    std::vector<int> owner((size_t)E);
+    for (int col = 0; col < T.ncol; ++col) {
+        std::fill(owner.begin(), owner.end(), -1);
+        for (int64_t e = 0; e < E; ++e)
+            if (T.colour[e] == col)
+                for (int e1 : T.adj[e]) owner[e1] = (int)e;
+        for (int c = 0; c < NC; ++c) {
+            probe_vertex(m, d_colour.p, col, c, pp);
+            NLG_TRY(sem_cdabdtp(m, pp, ep));
+            restrict_corners(m, ep, d_t8.p);
+            if (hipMemcpyAsync(t8.data(), d_t8.p, sizeof(double) * t8.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) {
+                set_error("pprec_setup: device error while probing the coarse operator");
+                return 1;
+            }
+            for (int64_t e1 = 0; e1 < E; ++e1) {
+                const int e0 = owner[e1];
+                if (e0 < 0) continue;
+                const int vcol = T.vg[(size_t)e0 * NC + c];
+                for (int c1 = 0; c1 < NC; ++c1) {
+                    const double val = t8[(size_t)e1 * NC + c1];
+                    if (val != 0.0) rows[T.vg[(size_t)e1 * NC + c1]][vcol] += val;
+                }
+            }
+        }
+    }
+    return 0;
+}
+
+// dense SPD inverse in place (row-major): Gauss-Jordan without pivoting, two launches per pivot
+int gj_inverse(hipStream_t st, double *dA, int nn) {
+    DevBuf<double> rk, ck;
+    DevBuf<int> bad;
+    int hbad = 0;
+    NLG_HIP(hipMalloc(&rk.p, sizeof(double) * (size_t)nn));
+    NLG_HIP(hipMalloc(&ck.p, sizeof(double) * (size_t)nn));
+    NLG_HIP(hipMalloc(&bad.p, sizeof(int)));
+    NLG_HIP(hipMemsetAsync(bad.p, 0, sizeof(int), st));
+    const unsigned gx = (unsigned)((nn + NT - 1) / NT);
+    for (int k = 0; k < nn; ++k) {
+        NLG_LAUNCH(k_gj_prep, dim3(gx), dim3(NT), 0, st, nn, k, (const double *)dA, rk.p, ck.p, bad.p);
+        NLG_LAUNCH(k_gj_update, dim3(gx, (unsigned)nn), dim3(NT), 0, st, nn, k, dA, (const double *)rk.p, (const double *)ck.p);
+    }
+    NLG_HIP(hipGetLastError());
+    NLG_HIP(hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    NLG_CHECK(hbad == 0, "pprec_setup: aggregate operator is not positive definite");
+    return 0;
+}
+
+// The dense inverse of the aggregate level.  From lib_min unknowns (NLG_LIB_INVERSE_MIN; several ranks): Cholesky
+// factorisation and inverse from rocSOLVER — set-up only, a plain dense library call; the two-launches-per-pivot
+// Gauss-Jordan above streams the matrix once per pivot (18k unknowns: 25 s)
+int spd_inverse_dev(hipStream_t st, double *dA, int nn, int lib_min) {
+    if (nn < lib_min) return gj_inverse(st, dA, nn);
+    BlasHandle hb;
+    NLG_CHECK(rocblas_create_handle(&hb.h) == rocblas_status_success, "pprec_setup: rocblas_create_handle failed");
+    rocblas_set_stream(hb.h, st);
+    DevBuf<int> dinfo;
+    int hinfo[2] = {0, 0};
+    NLG_HIP(hipMalloc(&dinfo.p, 2 * sizeof(int)));
+    const rocblas_status s1 = rocsolver_dpotrf(hb.h, rocblas_fill_lower, nn, dA, nn, dinfo.p);
+    const rocblas_status s2 = s1 == rocblas_status_success ? rocsolver_dpotri(hb.h, rocblas_fill_lower, nn, dA, nn, dinfo.p + 1) : s1;
+    NLG_HIP(hipMemcpyAsync(hinfo, dinfo.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    NLG_CHECK(s1 == rocblas_status_success && s2 == rocblas_status_success, "pprec_setup: rocSOLVER potrf/potri failed (%d, %d)", (int)s1, (int)s2);
+    NLG_CHECK(hinfo[0] == 0 && hinfo[1] == 0, "pprec_setup: aggregate operator is not positive definite (potrf info %d)", hinfo[0]);
+    // column-major lower triangle = row-major upper triangle: mirror it
+    NLG_LAUNCH(k_mirror_upper, dim3((unsigned)((nn + 255) / 256), (unsigned)nn), dim3(256), 0, st, nn, dA);
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+
+// out = the vectors `in` (one length on every rank) of all ranks, one after the other
+int gather_host(nlg_ctx *ctx, const std::vector<double> &in, std::vector<double> &out) {
+    hipStream_t st = ctx->stream;
+    const size_t c = in.size(), nr = (size_t)ctx->nranks;
+    DevBuf<double> di, d_o;
+    NLG_HIP(hipMalloc(&di.p, sizeof(double) * c));
+    NLG_HIP(hipMalloc(&d_o.p, sizeof(double) * c * nr));
+    NLG_HIP(hipMemcpyAsync(di.p, in.data(), sizeof(double) * c, hipMemcpyHostToDevice, st));
+    NLG_TRY(allgather_f64(ctx, di.p, d_o.p, (int64_t)c));
+    out.resize(c * nr);
+    NLG_HIP(hipMemcpyAsync(out.data(), d_o.p, sizeof(double) * c * nr, hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Several ranks: ONE aggregate level over all ranks.  The vertex hats are cut at the rank boundaries (the
+// pressure space is discontinuous, so the cut functions are admissible), hence the diagonal block of a rank is the
+// halo-free operator assembled before and only the aggregates that touch an element with a shared node couple to
+// other ranks.  Those columns are probed with the global operator (halo on), one aggregate of one rank at a time;
+// the rows are gathered, the (12k x 12k at 8 x 10^4 elements) operator is inverted redundantly on every rank
+// and each rank keeps its own rows of the inverse.  Per application: one all-gather of na_max doubles.
+// (Rank-local coarse solves — the first version — took 45 pressure iterations on 2 x 512 elements against 14
+// on one rank: the block-Jacobi coarse solve over-corrects the nearly constant-per-rank modes.)
+int global_aggregate_level(nlg_mesh *m, const pph::CoarseTopo &T, const std::vector<int> &agg, const pph::AggLevel &G, int lib_min) {
+    nlg_pprec &P = m->pprec;
+    nlg_ctx *ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const int nr = ctx->nranks, me = ctx->rank, na = G.na, nvert = T.nvert, NC = 1 << m->dim;
+    const int64_t E = m->E;
+    const std::vector<double> &Acc = G.Acc;
+    // aggregates whose support holds an element with a node shared with another rank
+    std::vector<char> velem((size_t)E, 0), aflag((size_t)na, 0);
+    for (int idx : m->halo.h_cidx) velem[idx / m->np1] = 1;
+    for (int64_t e = 0; e < E; ++e)
+        if (velem[e])
+            for (int c = 0; c < NC; ++c) aflag[agg[T.vg[(size_t)e * NC + c]]] = 1;
+    std::vector<int> ifa;
+    for (int a = 0; a < na; ++a)
+        if (aflag[a]) ifa.push_back(a);
+    double tr = 0.0;
+    for (int i = 0; i < na; ++i) tr += Acc[(size_t)i * na + i];
+    std::vector<double> info;
+    NLG_TRY(gather_host(ctx, {(double)na, (double)ifa.size(), tr}, info));
+    std::vector<int> na_all(nr), ni_all(nr);
+    int na_max = 0, ni_max = 0;
+    double tr_all = 0.0, nreal = 0.0;
+    for (int q = 0; q < nr; ++q) {
+        na_all[q] = (int)info[3 * q];
+        ni_all[q] = (int)info[3 * q + 1];
+        tr_all += info[3 * q + 2];
+        nreal += na_all[q];
+        na_max = std::max(na_max, na_all[q]);
+        ni_max = std::max(ni_max, ni_all[q]);
+    }
+    const int64_t ntot = (int64_t)nr * na_max;
+    NLG_CHECK(ntot <= 60000, "pprec_setup: global aggregate level of %lld unknowns is too large for the dense inverse", (long long)ntot);
+    std::vector<double> ifa_pad((size_t)std::max(ni_max, 1), -1.0), ifa_all;
+    for (size_t i = 0; i < ifa.size(); ++i) ifa_pad[i] = ifa[i];
+    NLG_TRY(gather_host(ctx, ifa_pad, ifa_all));
+    // this rank's rows: diagonal block from the halo-free assembly, the rest by probing
+    DevBuf<double> d_rows, d_full;
+    {
+        std::vector<double> rowsH((size_t)na_max * ntot, 0.0);
+        for (int i = 0; i < na; ++i)
+            for (int j = 0; j < na; ++j) rowsH[(size_t)i * ntot + (size_t)me * na_max + j] = Acc[(size_t)i * na + j];
+        NLG_TRY(up(rowsH, &d_rows.p));
+    }
+    NLG_HIP(hipMalloc(&P.d_ra, sizeof(double) * (size_t)na_max));
+    NLG_HIP(hipMemsetAsync(P.d_ra, 0, sizeof(double) * (size_t)na_max, st));
+    NLG_HIP(hipMalloc(&P.d_rag, sizeof(double) * (size_t)ntot));
+    double *pp = sem_scratch2(m, 0), *ep = sem_scratch2(m, 1);
+    NLG_CHECK(pp && ep, "pprec_setup: scratch allocation failed");
+    const size_t stride_i = (size_t)std::max(ni_max, 1);
+    for (int r = 0; r < nr; ++r)
+        for (int i = 0; i < ni_all[r]; ++i) {
+            const int a_src = (int)ifa_all[(size_t)r * stride_i + i];
+            probe_aggregate(m, me == r ? a_src : -1, pp);
+            NLG_TRY(sem_cdabdtp(m, pp, ep));
+            if (me == r) continue;   // own block: already there
+            restrict_corners(m, ep, P.d_tq);
+            NLG_LAUNCH(k_q1_gather, dim3((nvert + NT - 1) / NT), dim3(NT), 0, st, (const double *)nullptr, nvert, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, 0.0, P.d_x);
+            NLG_LAUNCH(k_agg_restrict, dim3((na + 3) / 4), dim3(NT), 0, st, (const double *)nullptr, na, P.d_ap, P.d_am, P.d_rc, P.d_ra);
+            NLG_LAUNCH(k_store_col, dim3((na + 255) / 256), dim3(256), 0, st, na, (const double *)P.d_ra, d_rows.p, ntot, (int64_t)r * na_max + a_src);
+        }
+    NLG_HIP(hipGetLastError());
+    NLG_HIP(hipMalloc(&d_full.p, sizeof(double) * (size_t)ntot * ntot));
+    NLG_TRY(allgather_f64(ctx, d_rows.p, d_full.p, (int64_t)na_max * ntot));
+    DevBuf<int> d_na_of;
+    NLG_TRY(up(na_all, &d_na_of.p));
+    const double alpha = m->has_outflow ? 0.0 : tr_all / nreal / nreal;
+    NLG_LAUNCH(k_glob_fix, dim3((unsigned)((ntot + 255) / 256), (unsigned)ntot), dim3(256), 0, st, ntot, na_max, (const int *)d_na_of.p, alpha, d_full.p);
+    NLG_TRY(spd_inverse_dev(st, d_full.p, (int)ntot, lib_min));
+    const int64_t nrow_el = (int64_t)std::max(na, 1) * ntot;
+    NLG_HIP(hipMalloc(&P.d_Ainv32, sizeof(float) * (size_t)nrow_el));
+    NLG_LAUNCH(k_to_float, dim3((unsigned)((nrow_el + 255) / 256)), dim3(256), 0, st, (int64_t)na * ntot,
+               (const double *)(d_full.p + (size_t)me * na_max * ntot), P.d_Ainv32);
+    NLG_HIP(hipGetLastError());
+    NLG_HIP(hipStreamSynchronize(st));
+    P.na_max = na_max;
+    P.ncols = (int)ntot;
+    return 0;
+}
+
+struct FreeUnlessReady {   // a set-up that fails leaves nlg_pprec empty, never half filled
+    nlg_mesh *m;
+    ~FreeUnlessReady() { if (!m->pprec.ready) pprec_free(m); }
+};
+
 }  // namespace
 
 namespace nlg {
 
+// The stages of the set-up in order: the host arithmetic of pprec_host.cpp with the device work in between.
 int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d) {
+    FreeUnlessReady guard{m};
     nlg_pprec &P = m->pprec;
     nlg_ctx *ctx = m->ctx;
     hipStream_t st = ctx->stream;
-    const int dim = m->dim, n = m->n, n2 = m->n2, np1 = m->np1, np2 = m->np2;
-    const int64_t E = m->E;
-    const nlg_ops1d &o = m->ops;
-    // ---- host copies of what the set-up needs
-    std::vector<double> vmult((size_t)m->lvn), binv((size_t)m->lvn);
+    const int exact_max = env_int("NLG_COARSE_EXACT_MAX", 2048);   // more vertices than this: aggregates
+    const int lib_min = env_int("NLG_LIB_INVERSE_MIN", 4096);      // from this many unknowns: rocSOLVER
+    const bool multi = ctx->distributed() && ctx->nranks > 1;
+    const int dim = m->dim, n = m->n, NC = 1 << dim;
+    pph::Shape s;
+    s.dim = dim, s.n = n, s.n2 = m->n2, s.E = m->E;
+    const pph::Ops o = {m->ops.w1.data(), m->ops.w2.data(), m->ops.D12.data(), m->ops.I12.data()};
+    std::string err;
+    std::vector<double> vmult((size_t)m->lvn);
     NLG_HIP(hipMemcpyAsync(vmult.data(), m->d_vmult, sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToHost, st));
-    NLG_HIP(hipMemcpyAsync(binv.data(), m->d_binvm1, sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToHost, st));
     NLG_HIP(hipStreamSynchronize(st));
     const double *X[3] = {d->xm1, d->ym1, d->zm1};
     const double *msk[3] = {d->v1mask, d->v2mask, d->v3mask};
-    // ---- 1. element-wise fast diagonalisation
-    std::vector<double> Dh((size_t)n2 * n), Ih((size_t)n2 * n);
-    for (int k = 0; k < n2; ++k)
-        for (int j = 0; j < n; ++j) {
-            Dh[(size_t)k * n + j] = o.w2[k] * o.D12[(size_t)k * n + j];
-            Ih[(size_t)k * n + j] = o.w2[k] * o.I12[(size_t)k * n + j];
-        }
-    std::vector<double> hS((size_t)E * 3 * n2 * n2, 0.0), hden((size_t)E * np2, 0.0);
-    std::vector<double> lam3((size_t)3 * n2);
-    std::vector<double> Lall((size_t)E * 3, 0.0), endfac((size_t)E * 6, 0.0);   // edge lengths; end-point factors [e][d][side]
-    const int mid = n / 2;
-    double denmax = 0.0;
-    for (int64_t e = 0; e < E; ++e) {
-        for (int dd = 0; dd < dim; ++dd) {
-            // face centres in direction dd
-            double c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
-            int cnt = 0;
-            for (int p = 0; p < np1; ++p) {
-                const int ijk[3] = {p % n, (p / n) % n, p / (n * n)};
-                if (ijk[dd] == 0) {
-                    for (int c = 0; c < dim; ++c) c0[c] += X[c][e * np1 + p];
-                    ++cnt;
-                } else if (ijk[dd] == n - 1) {
-                    for (int c = 0; c < dim; ++c) c1[c] += X[c][e * np1 + p];
-                }
-            }
-            double l = 0.0;
-            for (int c = 0; c < dim; ++c) l += (c1[c] - c0[c]) * (c1[c] - c0[c]) / ((double)cnt * cnt);
-            l = std::sqrt(l);
-            std::vector<double> bi(n);
-            for (int i = 0; i < n; ++i) bi[i] = 1.0 / (0.5 * l * o.w1[i]);
-            for (int side = 0; side < 2; ++side) {
-                int ijk[3] = {mid, mid, dim == 3 ? mid : 0};
-                ijk[dd] = side == 0 ? 0 : n - 1;
-                const int64_t q = e * np1 + ijk[0] + n * (ijk[1] + n * ijk[2]);
-                const int k = side == 0 ? 0 : n - 1;
-                bi[k] = (msk[dd][q] == 0.0) ? 0.0 : bi[k] * vmult[q];
-                endfac[(size_t)e * 6 + dd * 2 + side] = (msk[dd][q] == 0.0) ? 0.0 : vmult[q];
-            }
-            Lall[(size_t)e * 3 + dd] = l;
-            std::vector<double> A((size_t)n2 * n2), B((size_t)n2 * n2), S, lam;
-            for (int a = 0; a < n2; ++a)
-                for (int b = 0; b < n2; ++b) {
-                    double sa = 0.0, sb = 0.0;
-                    for (int j = 0; j < n; ++j) {
-                        sa += Dh[(size_t)a * n + j] * bi[j] * Dh[(size_t)b * n + j];
-                        sb += Ih[(size_t)a * n + j] * bi[j] * Ih[(size_t)b * n + j];
-                    }
-                    A[(size_t)a * n2 + b] = sa;
-                    B[(size_t)a * n2 + b] = 0.25 * l * l * sb;
-                }
-            NLG_CHECK(gen_eig(n2, A, B, S, lam) == 0, "pprec_setup: 1-D mass matrix not positive definite (element %lld)", (long long)e);
-            for (int q = 0; q < n2 * n2; ++q) hS[((size_t)e * 3 + dd) * n2 * n2 + q] = S[q];
-            for (int a = 0; a < n2; ++a) lam3[(size_t)dd * n2 + a] = std::max(lam[a], 0.0);
-        }
-        for (int q = 0; q < np2; ++q) {
-            const int a = q % n2, b = (q / n2) % n2, c = q / (n2 * n2);
-            double den = lam3[a] + lam3[n2 + b] + (dim == 3 ? lam3[2 * n2 + c] : 0.0);
-            hden[(size_t)e * np2 + q] = den;
-            denmax = std::max(denmax, den);
-        }
-    }
-    for (auto &v : hden) v = (v > 1e-12 * denmax) ? 1.0 / v : 0.0;
-    NLG_TRY(up(hS, &P.d_S));
-    NLG_TRY(up(hden, &P.d_invden));
 
-    // ---- 1b. overlapping variant: extended 1-D operators from the line left neighbour | element | right neighbour
-    // (return array Wr in the face-grouped layout in 3-D, in the natural layout in 2-D)
-    if (((dim == 3 && m->gs.d_indices_fg && n <= 12 && n != 11) || (dim == 2 && n <= 8)) && m->gs.npairs > 0) {
-        // normal edge length of the face neighbours, through the gather-scatter: every element puts its own
-        // normal length on the interior points of its faces, the sum minus the own value is the neighbour's
-        std::vector<double> hw((size_t)m->lvn, 0.0);
-        auto face_node = [&](int dd, int side, int u, int v) {
-            int ijk[3] = {0, 0, 0};
-            ijk[dd] = side == 0 ? 0 : n - 1;
-            ijk[(dd + 1) % dim] = u;
-            if (dim == 3) ijk[(dd + 2) % 3] = v;
-            return ijk[0] + n * (ijk[1] + n * ijk[2]);
-        };
-        for (int64_t e = 0; e < E; ++e)
-            for (int dd = 0; dd < dim; ++dd)
-                for (int side = 0; side < 2; ++side)
-                    for (int v = 1; v < (dim == 3 ? n - 1 : 2); ++v)
-                        for (int u = 1; u < n - 1; ++u) hw[(size_t)e * np1 + face_node(dd, side, u, v)] = Lall[(size_t)e * 3 + dd];
-        double *dw = sem_scratch1(m, 0);
-        NLG_CHECK(dw, "pprec_setup: scratch allocation failed");
-        NLG_HIP(hipMemcpyAsync(dw, hw.data(), sizeof(double) * (size_t)m->lvn, hipMemcpyHostToDevice, st));
-        {
-            // halo on: a face neighbour on another rank counts like a local one (its ghost layer travels with the
-            // halo exchange of the array W, pprec_apply)
-            double *f1[1] = {dw};
-            NLG_TRY(sem_gs(m, f1, 1));
-        }
-        NLG_HIP(hipMemcpyAsync(hw.data(), dw, sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToHost, st));
-        NLG_HIP(hipStreamSynchronize(st));
-        const int mx = n;   // extended 1-D size
-        std::vector<double> hSx((size_t)E * 3 * mx * mx, 0.0), hlx((size_t)E * 3 * mx, 0.0);
-        std::vector<double> Bl((size_t)3 * n), bq((size_t)3 * n), Ae((size_t)mx * mx), Be((size_t)mx * mx), Sx, lx;
-        std::vector<double> Dl((size_t)mx * 3 * n), Il((size_t)mx * 3 * n);   // rows: the mx extended pressure points
-        // symmetric weighting D M D, D = diag(count^-1/2), count = number of extended subdomains that contain the point
-        // (1 + one per face neighbour whose ghost layer it is).  Prototype (docs/prototypes/precond_proto5.py, 6^3 elements,
-        // lx1 = 6): unweighted 21 / 29 iterations with the exact / approximate coarse solve, weighted 14 / 18;
-        // without overlap 29.
-        std::vector<double> hwq((size_t)E * np2, 1.0);
-        std::vector<char> hasnb((size_t)E * 6, 0);   // [e][2 dd + side]: the face has a neighbour (on this rank or another)
-        double dmax = 0.0;
-        for (int64_t e = 0; e < E; ++e) {
-            for (int dd = 0; dd < dim; ++dd) {
-                const double lm = Lall[(size_t)e * 3 + dd];
-                double ln[2];
-                for (int side = 0; side < 2; ++side) {
-                    const double sum = hw[(size_t)e * np1 + face_node(dd, side, mid, dim == 3 ? mid : 0)];
-                    ln[side] = sum - lm > 1e-10 * lm ? sum - lm : 0.0;
-                    hasnb[(size_t)e * 6 + dd * 2 + side] = ln[side] > 0.0;
-                }
-                const double len[3] = {ln[0], lm, ln[1]};
-                for (int side = 0; side < 2; ++side)
-                    if (ln[side] > 0.0)
-                        for (int q = 0; q < np2; ++q) {
-                            const int idx3[3] = {q % n2, (q / n2) % n2, q / (n2 * n2)};
-                            if (idx3[dd] == (side == 0 ? 0 : n2 - 1)) hwq[(size_t)e * np2 + q] += 1.0;
-                        }
-                const int nvl = 3 * n - 2;
-                std::fill(Bl.begin(), Bl.end(), 0.0);
-                std::fill(Dl.begin(), Dl.end(), 0.0);
-                std::fill(Il.begin(), Il.end(), 0.0);
-                for (int q = 0; q < 3; ++q) {
-                    if (len[q] == 0.0) continue;
-                    const int ov = q * (n - 1);
-                    for (int i = 0; i < n; ++i) Bl[ov + i] += 0.5 * len[q] * o.w1[i];
-                    // extended rows owned by element q of the line: left -> row 0 (its last pressure point),
-                    // middle -> rows 1..n2, right -> row mx-1 (its first pressure point)
-                    const int r0 = q == 0 ? 0 : (q == 1 ? 1 : mx - 1);
-                    const int k0 = q == 0 ? n2 - 1 : 0, nk = q == 1 ? n2 : 1;
-                    for (int k = 0; k < nk; ++k)
-                        for (int i = 0; i < n; ++i) {
-                            Dl[(size_t)(r0 + k) * 3 * n + ov + i] = Dh[(size_t)(k0 + k) * n + i];
-                            Il[(size_t)(r0 + k) * 3 * n + ov + i] = 0.5 * len[q] * Ih[(size_t)(k0 + k) * n + i];
-                        }
-                }
-                for (int i = 0; i < nvl; ++i) bq[i] = Bl[i] > 0.0 ? 1.0 / Bl[i] : 0.0;
-                // end points: with a neighbour, the far end of the neighbour is lumped as an interior interface (1/2);
-                // without one, the own end point follows the rule of the non-overlapping operator (wall -> 0)
-                if (len[0] > 0.0) bq[0] *= 0.5; else bq[n - 1] *= endfac[(size_t)e * 6 + dd * 2 + 0];
-                if (len[2] > 0.0) bq[nvl - 1] *= 0.5; else bq[2 * (n - 1)] *= endfac[(size_t)e * 6 + dd * 2 + 1];
-                for (int a = 0; a < mx; ++a)
-                    for (int b = 0; b < mx; ++b) {
-                        double sa = 0.0, sb = 0.0;
-                        for (int i = 0; i < nvl; ++i) {
-                            sa += Dl[(size_t)a * 3 * n + i] * bq[i] * Dl[(size_t)b * 3 * n + i];
-                            sb += Il[(size_t)a * 3 * n + i] * bq[i] * Il[(size_t)b * 3 * n + i];
-                        }
-                        Ae[(size_t)a * mx + b] = sa;
-                        Be[(size_t)a * mx + b] = sb;
-                    }
-                for (int side = 0; side < 2; ++side)
-                    if (ln[side] == 0.0) {   // no neighbour: the ghost point is decoupled (its right-hand side is zero)
-                        const int g = side == 0 ? 0 : mx - 1;
-                        for (int b = 0; b < mx; ++b) Ae[(size_t)g * mx + b] = Ae[(size_t)b * mx + g] = Be[(size_t)g * mx + b] = Be[(size_t)b * mx + g] = 0.0;
-                        Ae[(size_t)g * mx + g] = 1.0;
-                        Be[(size_t)g * mx + g] = 1.0;
-                    }
-                NLG_CHECK(gen_eig(mx, Ae, Be, Sx, lx) == 0, "pprec_setup: extended 1-D mass matrix not positive definite (element %lld)", (long long)e);
-                for (int q = 0; q < mx * mx; ++q) hSx[((size_t)e * 3 + dd) * mx * mx + q] = Sx[q];
-                for (int a = 0; a < mx; ++a) hlx[((size_t)e * 3 + dd) * mx + a] = std::max(lx[a], 0.0);
-            }
-            double mxl = 0.0;
-            for (int dd = 0; dd < dim; ++dd) {
-                double mm = 0.0;
-                for (int a = 0; a < mx; ++a) mm = std::max(mm, hlx[((size_t)e * 3 + dd) * mx + a]);
-                mxl += mm;
-            }
-            dmax = std::max(dmax, mxl);
-        }
-        for (auto &v : hwq) v = 1.0 / std::sqrt(v);
-        NLG_TRY(up(hwq, &P.d_wq));
-        P.thrx = 1e-12 * dmax;
-        NLG_TRY(up(hSx, &P.d_Sx));
-        {
-            // destinations of the overlap values per element face point k (compact, the order of face_pt / fg_slot's face blocks):
-            //   pin[e][k]  = index in Win (natural layout) of the ghost point that the pressure layer of e next to k is for;
-            //   pret[e][k] = index in Wret of the face slot that the solve of e at ghost point k is for (3-D: face-grouped
-            //                layout, 2-D: natural layout, so pret = pin);
-            // the neighbour's face point for a face inside this rank, the own one for a face on a rank boundary (copy-mode halo
-            // exchange), -1 without a neighbour.  The local partners are the two-copy groups of the gather-scatter in the
-            // layout of Wret.
-            const int M = n2, F = dim == 3 ? n2 * n2 : n2, NF = 2 * dim * F, NP = dim == 3 ? n * n * n : n * n, FB = 8 + 12 * M;
-            std::vector<int> fnat(NF), fret(NF), kof(NP, -1);   // face point -> slot in Win, in Wret; slot in Wret -> face point
-            for (int f = 0; f < 2 * dim; ++f)
-                for (int v = 0; v < (dim == 3 ? M : 1); ++v)
-                    for (int u = 0; u < M; ++u) {
-                        const int dd = f >> 1, x = (f & 1) ? n - 1 : 0;
-                        const int a = dd == 0 ? x : u + 1, b = dd == 0 ? u + 1 : (dd == 1 ? x : v + 1);
-                        const int c = dim == 3 ? (dd == 2 ? x : v + 1) : 0;
-                        const int k = f * F + u + M * v;
-                        fnat[k] = a + n * (b + n * c);
-                        NLG_CHECK(dim == 2 || fg_slot(n, a, b, c) == FB + k, "pprec_setup: internal (face point order)");
-                        fret[k] = dim == 3 ? FB + k : fnat[k];
-                        kof[fret[k]] = k;
-                    }
-            NLG_CHECK((int64_t)E * NP < INT32_MAX, "pprec_setup: %lld elements are too many for 32-bit overlap indices", (long long)E);
-            std::vector<int> pidx((size_t)2 * m->gs.npairs), mate((size_t)E * NP, -1);
-            NLG_HIP(hipMemcpy(pidx.data(), dim == 3 ? m->gs.d_indices_fg : m->gs.d_indices, sizeof(int) * pidx.size(), hipMemcpyDeviceToHost));
-            for (int64_t g = 0; g < m->gs.npairs; ++g) {
-                const int i0 = pidx[2 * g], i1 = pidx[2 * g + 1];
-                NLG_CHECK(i0 >= 0 && i1 >= 0 && i0 < E * NP && i1 < E * NP, "pprec_setup: pair index out of range");
-                if (kof[i0 % NP] >= 0 && kof[i1 % NP] >= 0) mate[i0] = i1, mate[i1] = i0;
-            }
-            std::vector<int> pin((size_t)E * NF, -1), pret((size_t)E * NF, -1);
-            for (int64_t e = 0; e < E; ++e)
-                for (int k = 0; k < NF; ++k) {
-                    const int own = (int)(e * NP + fret[k]), mt = mate[own];
-                    const bool nb = hasnb[(size_t)e * 6 + k / F];
-                    int di = -1, dr = -1;
-                    if (mt >= 0) {
-                        NLG_CHECK(nb, "pprec_setup: element %lld face %d has a partner but no neighbour length", (long long)e, k / F);
-                        di = (mt / NP) * NP + fnat[kof[mt % NP]];
-                        dr = mt;
-                    } else if (nb) {
-                        NLG_CHECK(m->halo.active, "pprec_setup: element %lld face %d: neighbour without a partner point", (long long)e, k / F);
-                        di = (int)(e * NP + fnat[k]);
-                        dr = own;
-                    }
-                    pin[(size_t)e * NF + k] = di;
-                    pret[(size_t)e * NF + k] = dr;
-                }
-            // every ghost slot of a face with a neighbour has exactly one producer, every other slot none (a wrong index in the
-            // scatter stores of the kernels would be a fault on the device, not a wrong number)
-            {
-                std::vector<unsigned char> cin((size_t)E * NP, 0), cret((size_t)E * NP, 0);
-                int64_t nw = 0;
-                for (size_t i = 0; i < pin.size(); ++i) {
-                    if (pin[i] < 0) continue;
-                    NLG_CHECK(pin[i] < E * NP && pret[i] >= 0 && pret[i] < E * NP, "pprec_setup: overlap destination out of range");
-                    NLG_CHECK(++cin[pin[i]] == 1 && ++cret[pret[i]] == 1, "pprec_setup: overlap slot with two producers");
-                    ++nw;
-                }
-                int64_t nexp = 0;
-                for (int64_t e = 0; e < E; ++e)
-                    for (int k = 0; k < NF; ++k) {
-                        const int want = pin[(size_t)e * NF + k] >= 0;
-                        NLG_CHECK(cin[(size_t)e * NP + fnat[k]] == want && cret[(size_t)e * NP + fret[k]] == want,
-                                  "pprec_setup: ghost slot of element %lld face %d without its producer", (long long)e, k / F);
-                        nexp += want;
-                    }
-                NLG_CHECK(nexp == nw, "pprec_setup: overlap values written outside the ghost slots");
-            }
-            NLG_TRY(up(pin, &P.d_pin));
-            NLG_TRY(up(pret, &P.d_pret));
-            NLG_HIP(hipMalloc(&P.d_Wr, sizeof(double) * (size_t)m->lvs));
-            NLG_HIP(hipMemsetAsync(P.d_Wr, 0, sizeof(double) * (size_t)m->lvs, st));
-        }
-        NLG_TRY(up(hlx, &P.d_lamx));
-        NLG_HIP(hipMalloc(&P.d_W, sizeof(double) * (size_t)m->lvs));
-        NLG_HIP(hipMemsetAsync(P.d_W, 0, sizeof(double) * (size_t)m->lvs, st));
-        P.overlap = true;
-    }
-    // ---- 2. coarse space: element vertices, trilinear hats at the GL points
-    const int NC = 1 << dim;
+    // local solves: edge lengths, element-wise fast diagonalisation and, where the mesh has shared faces, the overlap
+    pph::Lengths L;
+    pph::LocalFdm F;
+    pph::edge_lengths(s, X, msk, vmult.data(), L);
+    NLG_TRY(stage(pph::local_fdm(s, o, L, F, err), err));
+    NLG_TRY(up(F.S, &P.d_S));
+    NLG_TRY(up(F.invden, &P.d_invden));
+    if (((dim == 3 && m->gs.d_indices_fg && n <= 12 && n != 11) || (dim == 2 && n <= 8)) && m->gs.npairs > 0)
+        NLG_TRY(setup_overlap(m, s, o, L));
+
+    // coarse space: element vertices, trilinear hats at the GL points; A_c probed colour by colour
     P.ncorner = NC;
-    for (int k = 0; k < n2; ++k) P.hat1[k] = 0.5 * (1.0 + o.z2[k]);
-    Hat hat;
-    for (int k = 0; k < 12; ++k) hat.h1[k] = k < n2 ? P.hat1[k] : 0.0;
-    std::vector<int> vg((size_t)E * NC);
-    int nvert = 0;
-    {
-        const int64_t *glo = d->glo_num;
-        std::vector<int64_t> lab((size_t)E * NC);
-        for (int64_t e = 0; e < E; ++e)
-            for (int c = 0; c < NC; ++c) {
-                const int i = (c & 1) ? n - 1 : 0, j = (c & 2) ? n - 1 : 0, k = (c & 4) ? n - 1 : 0;
-                lab[(size_t)e * NC + c] = glo[e * np1 + i + n * (j + n * k)];
-            }
-        std::vector<int64_t> u(lab);
-        std::sort(u.begin(), u.end());
-        u.erase(std::unique(u.begin(), u.end()), u.end());
-        nvert = (int)u.size();
-        for (size_t q = 0; q < lab.size(); ++q) vg[q] = (int)(std::lower_bound(u.begin(), u.end(), lab[q]) - u.begin());
-    }
-    P.nvert = nvert;
-    // vertex -> incident (element, corner) entries
-    std::vector<int> vp((size_t)nvert + 1, 0), vi((size_t)E * NC);
-    for (size_t q = 0; q < vg.size(); ++q) vp[vg[q] + 1]++;
-    for (int v = 0; v < nvert; ++v) vp[v + 1] += vp[v];
-    {
-        std::vector<int> pos(vp.begin(), vp.end() - 1);
-        for (size_t q = 0; q < vg.size(); ++q) vi[pos[vg[q]]++] = (int)q;
-    }
-    // element adjacency (conforming hexahedra that share any node share a vertex)
-    std::vector<std::vector<int>> adj((size_t)E);
-    for (int64_t e = 0; e < E; ++e) {
-        auto &a = adj[e];
-        for (int c = 0; c < NC; ++c) {
-            const int v = vg[(size_t)e * NC + c];
-            for (int q = vp[v]; q < vp[v + 1]; ++q) a.push_back(vi[q] / NC);
-        }
-        std::sort(a.begin(), a.end());
-        a.erase(std::unique(a.begin(), a.end()), a.end());
-    }
-    // greedy colouring: two elements of one colour have no common neighbour
-    std::vector<int> colour((size_t)E, -1);
-    int ncol = 0;
-    {
-        std::vector<int> mark;
-        for (int64_t e = 0; e < E; ++e) {
-            mark.assign((size_t)ncol + 1, 0);
-            for (int e1 : adj[e])
-                for (int e2 : adj[e1])
-                    if (colour[e2] >= 0) mark[colour[e2]] = 1;
-            int cidx = 0;
-            while (cidx < ncol && mark[cidx]) ++cidx;
-            colour[e] = cidx;
-            if (cidx == ncol) ++ncol;
-        }
-    }
-    // ---- 3. A_c = R_1^T E R_1 by probing E on the device (rank-local: without the halo exchange)
-    std::vector<std::unordered_map<int, double>> rows((size_t)nvert);
-    {
-        int *d_colour = nullptr;
-        double *d_t8 = nullptr;
-        NLG_TRY(up(colour, &d_colour));
-        NLG_HIP(hipMalloc(&d_t8, sizeof(double) * (size_t)E * NC));
-        double *pp = sem_scratch2(m, 0), *ep = sem_scratch2(m, 1);
-        NLG_CHECK(pp && ep, "pprec_setup: scratch allocation failed");
-        const bool halo_was = m->halo.active;
-        m->halo.active = false;
-        std::vector<double> t8((size_t)E * NC);
-        std::vector<int> owner((size_t)E);
-        const unsigned gp = (unsigned)((m->lpn + NT - 1) / NT), ge = (unsigned)((E + 3) / 4);
-        int rc = 0;
-        for (int col = 0; col < ncol && rc == 0; ++col) {
-            std::fill(owner.begin(), owner.end(), -1);
-            for (int64_t e = 0; e < E; ++e)
-                if (colour[e] == col)
-                    for (int e1 : adj[e]) owner[e1] = (int)e;
-            for (int c = 0; c < NC && rc == 0; ++c) {
-                if (dim == 3) {
-                    NLG_LAUNCH(k_q1_probe<3>, dim3(gp), dim3(NT), 0, st, E, n2, hat, d_colour, col, c, pp);
-                } else {
-                    NLG_LAUNCH(k_q1_probe<2>, dim3(gp), dim3(NT), 0, st, E, n2, hat, d_colour, col, c, pp);
-                }
-                rc = sem_cdabdtp(m, pp, ep);
-                if (rc) break;
-                if (dim == 3) {
-                    NLG_LAUNCH(k_q1_restrict_local<3>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, d_t8, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
-                } else {
-                    NLG_LAUNCH(k_q1_restrict_local<2>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, d_t8, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
-                }
-                if (hipMemcpyAsync(t8.data(), d_t8, sizeof(double) * t8.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) {
-                    set_error("pprec_setup: device error while probing the coarse operator");
-                    rc = 1;
-                    break;
-                }
-                for (int64_t e1 = 0; e1 < E; ++e1) {
-                    const int e0 = owner[e1];
-                    if (e0 < 0) continue;
-                    const int vcol = vg[(size_t)e0 * NC + c];
-                    for (int c1 = 0; c1 < NC; ++c1) {
-                        const double val = t8[(size_t)e1 * NC + c1];
-                        if (val != 0.0) rows[vg[(size_t)e1 * NC + c1]][vcol] += val;
-                    }
-                }
-            }
-        }
-        m->halo.active = halo_was;
-        hipFree(d_colour);
-        hipFree(d_t8);
-        if (rc) return rc;
-    }
-    // symmetrise (the probing is symmetric up to rounding) and build the CSR
-    for (int u = 0; u < nvert; ++u)
-        for (auto &kv : rows[u])
-            if (kv.first > u) {
-                auto it = rows[kv.first].find(u);
-                const double other = it == rows[kv.first].end() ? kv.second : it->second;
-                const double avg = 0.5 * (kv.second + other);
-                kv.second = avg;
-                rows[kv.first][u] = avg;
-            }
-    std::vector<int> rp((size_t)nvert + 1, 0), ci;
-    std::vector<double> av, dinv((size_t)nvert, 0.0);
-    for (int u = 0; u < nvert; ++u) {
-        std::vector<std::pair<int, double>> r(rows[u].begin(), rows[u].end());
-        std::sort(r.begin(), r.end());
-        for (auto &kv : r) {
-            ci.push_back(kv.first);
-            av.push_back(kv.second);
-            if (kv.first == u) dinv[u] = kv.second > 0 ? 1.0 / kv.second : 0.0;
-        }
-        rp[u + 1] = (int)ci.size();
-    }
-    // ---- 4. aggregates of vertices (greedy over the vertices that share an element) and the dense inverse on them
-    std::vector<int> agg((size_t)nvert, -1);
-    std::vector<char> viface((size_t)nvert, 0);   // vertex on a rank boundary
-    int na = 0;
-    int exact_max = 2048;
-    if (const char *ev = getenv("NLG_COARSE_EXACT_MAX")) exact_max = atoi(ev);
-    if (nvert <= exact_max) {
-        for (int v = 0; v < nvert; ++v) agg[v] = v;
-        na = nvert;
-    } else {
-        auto near = [&](int v, std::vector<int> &out) {
-            out.clear();
-            for (int q = vp[v]; q < vp[v + 1]; ++q) {
-                const int e = vi[q] / NC;
-                for (int c = 0; c < NC; ++c) out.push_back(vg[(size_t)e * NC + c]);
-            }
-            std::sort(out.begin(), out.end());
-            out.erase(std::unique(out.begin(), out.end()), out.end());
-        };
-        std::vector<int> nb;
-        // several ranks: the hats of the vertices on a rank boundary are cut there, and the two halves of one hat are
-        // coupled as strongly as the operator penalises a jump, which inflates the diagonal the vertex-level Jacobi term
-        // divides by.  Such vertices therefore become aggregates of their own: the aggregate level is global,
-        // knows the coupling between the halves and solves them exactly; their Jacobi term is dropped.
-        // 3 x 16^3 elements, pressure iterations per time step: plain 2x2x2 aggregates 41.75, planar 2x2 patches of
-        // boundary vertices 21, the same without their Jacobi term 16.5, singletons 12.75 (the two patch variants were
-        // removed); one rank 12.5.
-        const bool iface = ctx->distributed() && ctx->nranks > 1;
-        if (iface) {
-            for (int idx : m->halo.h_cidx) {
-                const int64_t e = idx / np1;
-                const int pt = idx % np1;
-                for (int c = 0; c < NC; ++c) {
-                    const int i = (c & 1) ? n - 1 : 0, j = (c & 2) ? n - 1 : 0, k = (c & 4) ? n - 1 : 0;
-                    if (pt == i + n * (j + n * k)) viface[vg[(size_t)e * NC + c]] = 1;
-                }
-            }
-            for (int64_t e = 0; e < E; ++e) {
-                int cnt = 0;
-                for (int c = 0; c < NC; ++c) {
-                    const int v = vg[(size_t)e * NC + c];
-                    if (viface[v] && agg[v] < 0) ++cnt;
-                }
-                if (cnt < 1) continue;
-                for (int c = 0; c < NC; ++c) {
-                    const int v = vg[(size_t)e * NC + c];
-                    if (viface[v] && agg[v] < 0) agg[v] = na++;
-                }
-            }
-        }
-        // an element whose corners are all free becomes an aggregate (2 x 2 x 2 vertices on structured meshes): the
-        // aggregate-level operator stays small enough for a dense inverse (nvert / 8 rows) and, unlike the
-        // vertex-plus-all-neighbours aggregates used first (27 vertices), accurate enough for the overlapping local
-        // solves (12^3 elements: 30.5 iterations with the 27-vertex aggregates, 21.75 with the exact coarse solve)
-        for (int64_t e = 0; e < E; ++e) {
-            bool free_all = true;
-            for (int c = 0; c < NC; ++c)
-                if (agg[vg[(size_t)e * NC + c]] >= 0) free_all = false;
-            if (!free_all) continue;
-            for (int c = 0; c < NC; ++c) agg[vg[(size_t)e * NC + c]] = na;
-            ++na;
-        }
-        if (iface)   // the far-side corners of the boundary elements
-            for (int64_t e = 0; e < E; ++e) {
-                int cnt = 0;
-                for (int c = 0; c < NC; ++c)
-                    if (agg[vg[(size_t)e * NC + c]] < 0) ++cnt;
-                if (cnt < NC / 2) continue;
-                for (int c = 0; c < NC; ++c)
-                    if (agg[vg[(size_t)e * NC + c]] < 0) agg[vg[(size_t)e * NC + c]] = na;
-                ++na;
-            }
-        for (int v = 0; v < nvert; ++v) {
-            if (agg[v] >= 0) continue;
-            near(v, nb);
-            int best = -1;
-            double bv = -1.0;
-            for (int pass = 0; pass < 2 && best < 0; ++pass)   // first among the vertices of the same kind
-                for (int w : nb) {
-                    if (w == v || agg[w] < 0 || (pass == 0 && viface[w] != viface[v])) continue;
-                    auto it = rows[v].find(w);
-                    const double cv = it == rows[v].end() ? 0.0 : std::fabs(it->second);
-                    if (cv > bv) {
-                        bv = cv;
-                        best = agg[w];
-                    }
-                }
-            agg[v] = best >= 0 ? best : na++;
-        }
-        if (iface)
-            for (int v = 0; v < nvert; ++v)
-                if (viface[v]) dinv[v] = 0.0;
-    }
-    std::vector<double> Acc((size_t)na * na, 0.0);
-    for (int u = 0; u < nvert; ++u)
-        for (int q = rp[u]; q < rp[u + 1]; ++q) Acc[(size_t)agg[u] * na + agg[ci[q]]] += av[q];
-    for (int i = 0; i < na; ++i)
-        for (int j = i + 1; j < na; ++j) Acc[(size_t)i * na + j] = Acc[(size_t)j * na + i] = 0.5 * (Acc[(size_t)i * na + j] + Acc[(size_t)j * na + i]);
-    const bool multi = ctx->distributed() && ctx->nranks > 1;
-    if (!m->has_outflow && !multi) {
-        // constant null space (the hats sum to one): shift it so that the inverse acts as the pseudo-inverse on
-        // mean-free data.  (Several ranks: the shift is applied to the gathered global operator below.)
-        double tr = 0.0;
-        for (int i = 0; i < na; ++i) tr += Acc[(size_t)i * na + i];
-        const double alpha = tr / na / na;   // the null vector of the aggregated operator is the vector of ones
-        for (int i = 0; i < na; ++i)
-            for (int j = 0; j < na; ++j) Acc[(size_t)i * na + j] += alpha;
-    }
-    std::vector<int> ap((size_t)na + 1, 0), am((size_t)nvert);
-    for (int v = 0; v < nvert; ++v) ap[agg[v] + 1]++;
-    for (int a = 0; a < na; ++a) ap[a + 1] += ap[a];
-    {
-        std::vector<int> pos(ap.begin(), ap.end() - 1);
-        for (int v = 0; v < nvert; ++v) am[pos[agg[v]]++] = v;
-    }
+    for (int k = 0; k < m->n2; ++k) P.hat1[k] = 0.5 * (1.0 + m->ops.z2[k]);
+    pph::CoarseTopo T;
+    pph::coarse_topology(s, d->glo_num, T);
+    P.nvert = T.nvert;
+    pph::ProbedRows rows;
+    NLG_TRY(probe_coarse_operator(m, T, rows));
+    pph::CoarseCsr A;
+    pph::coarse_rows(rows, A);
+
+    // aggregates of vertices and the operator on them
+    std::vector<char> viface;   // vertex on a rank boundary
+    pph::boundary_vertices(s, T, multi ? m->halo.h_cidx : std::vector<int>(), viface);
+    std::vector<int> agg;
+    const int na = pph::aggregate(s, T, A, exact_max, multi, viface, agg);
+    pph::AggLevel G;
+    pph::assemble_acc(A, agg, na, !m->has_outflow && !multi, G);
     P.na = na;
-    NLG_TRY(up(vg, &P.d_vg));
-    NLG_TRY(up(vp, &P.d_v2e_p));
-    NLG_TRY(up(vi, &P.d_v2e_i));
-    NLG_TRY(up(dinv, &P.d_dinv));
+    NLG_TRY(up(T.vg, &P.d_vg));
+    NLG_TRY(up(T.vp, &P.d_v2e_p));
+    NLG_TRY(up(T.vi, &P.d_v2e_i));
+    NLG_TRY(up(A.dinv, &P.d_dinv));
     NLG_TRY(up(agg, &P.d_agg));
-    NLG_TRY(up(ap, &P.d_ap));
-    NLG_TRY(up(am, &P.d_am));
-    NLG_HIP(hipMalloc(&P.d_tq, sizeof(double) * (size_t)E * NC));
-    for (double **v : {&P.d_rc, &P.d_x}) NLG_HIP(hipMalloc(v, sizeof(double) * (size_t)std::max(nvert, 1)));
+    NLG_TRY(up(G.ap, &P.d_ap));
+    NLG_TRY(up(G.am, &P.d_am));
+    NLG_HIP(hipMalloc(&P.d_tq, sizeof(double) * (size_t)m->E * NC));
+    for (double **v : {&P.d_rc, &P.d_x}) NLG_HIP(hipMalloc(v, sizeof(double) * (size_t)std::max(T.nvert, 1)));
     NLG_HIP(hipMalloc(&P.d_xa, sizeof(double) * (size_t)std::max(na, 1)));
 
-    auto gj_inverse = [&](double *dA, int nn) -> int {
-        double *rk = nullptr, *ck = nullptr;
-        int *bad = nullptr, hbad = 0;
-        NLG_HIP(hipMalloc(&rk, sizeof(double) * (size_t)nn));
-        NLG_HIP(hipMalloc(&ck, sizeof(double) * (size_t)nn));
-        NLG_HIP(hipMalloc(&bad, sizeof(int)));
-        NLG_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
-        const unsigned gx = (unsigned)((nn + NT - 1) / NT);
-        for (int k = 0; k < nn; ++k) {
-            NLG_LAUNCH(k_gj_prep, dim3(gx), dim3(NT), 0, st, nn, k, (const double *)dA, rk, ck, bad);
-            NLG_LAUNCH(k_gj_update, dim3(gx, (unsigned)nn), dim3(NT), 0, st, nn, k, dA, (const double *)rk, (const double *)ck);
-        }
-        NLG_HIP(hipGetLastError());
-        NLG_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-        NLG_HIP(hipStreamSynchronize(st));
-        hipFree(rk);
-        hipFree(ck);
-        hipFree(bad);
-        NLG_CHECK(hbad == 0, "pprec_setup: aggregate operator is not positive definite");
-        return 0;
-    };
-
-    // large operators (several ranks): Cholesky factorisation and inverse from rocSOLVER — set-up only, a plain dense
-    // library call; the two-launches-per-pivot Gauss-Jordan above streams the matrix once per pivot (18k unknowns: 25 s)
-    auto spd_inverse_dev = [&](double *dA, int nn) -> int {
-        int lib_min = 4096;
-        if (const char *ev = getenv("NLG_LIB_INVERSE_MIN")) lib_min = atoi(ev);
-        if (nn < lib_min) return gj_inverse(dA, nn);
-        rocblas_handle hb = nullptr;
-        NLG_CHECK(rocblas_create_handle(&hb) == rocblas_status_success, "pprec_setup: rocblas_create_handle failed");
-        rocblas_set_stream(hb, st);
-        int *dinfo = nullptr, hinfo[2] = {0, 0};
-        NLG_HIP(hipMalloc(&dinfo, 2 * sizeof(int)));
-        const rocblas_status s1 = rocsolver_dpotrf(hb, rocblas_fill_lower, nn, dA, nn, dinfo);
-        const rocblas_status s2 = s1 == rocblas_status_success ? rocsolver_dpotri(hb, rocblas_fill_lower, nn, dA, nn, dinfo + 1) : s1;
-        NLG_HIP(hipMemcpyAsync(hinfo, dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        NLG_HIP(hipStreamSynchronize(st));
-        hipFree(dinfo);
-        rocblas_destroy_handle(hb);
-        NLG_CHECK(s1 == rocblas_status_success && s2 == rocblas_status_success, "pprec_setup: rocSOLVER potrf/potri failed (%d, %d)", (int)s1, (int)s2);
-        NLG_CHECK(hinfo[0] == 0 && hinfo[1] == 0, "pprec_setup: aggregate operator is not positive definite (potrf info %d)", hinfo[0]);
-        // column-major lower triangle = row-major upper triangle: mirror it
-        NLG_LAUNCH(k_mirror_upper, dim3((unsigned)((nn + 255) / 256), (unsigned)nn), dim3(256), 0, st, nn, dA);
-        NLG_HIP(hipGetLastError());
-        return 0;
-    };
-
-    if (!multi) {
-        NLG_TRY(up(Acc, &P.d_Ainv));
-        NLG_TRY(spd_inverse_dev(P.d_Ainv, na));   // (library Cholesky above NLG_LIB_INVERSE_MIN unknowns, else Gauss-Jordan)
+    // the dense inverse: of this rank's aggregates, or of the global aggregate level
+    if (multi) {
+        NLG_TRY(global_aggregate_level(m, T, agg, G, lib_min));
+    } else {
+        NLG_TRY(up(G.Acc, &P.d_Ainv));
+        NLG_TRY(spd_inverse_dev(st, P.d_Ainv, na, lib_min));
         P.na_max = P.ncols = na;
         NLG_HIP(hipMalloc(&P.d_ra, sizeof(double) * (size_t)std::max(na, 1)));
-        P.ready = true;
-        return 0;
-    }
-
-    // ---- 5. several ranks: ONE aggregate level over all ranks.  The vertex hats are cut at the rank boundaries (the
-    // pressure space is discontinuous, so the cut functions are admissible), hence the diagonal block of a rank is the
-    // halo-free operator assembled above and only the aggregates that touch an element with a shared node couple to
-    // other ranks.  Those columns are probed with the global operator (halo on), one aggregate of one rank at a time;
-    // the rows are gathered, the (12k x 12k at 8 x 10^4 elements) operator is inverted redundantly on every rank
-    // and each rank keeps its own rows of the inverse.  Per application: one all-gather of na_max doubles.
-    // (Rank-local coarse solves — the first version — took 45 pressure iterations on 2 x 512 elements against 14
-    // on one rank: the block-Jacobi coarse solve over-corrects the nearly constant-per-rank modes.)
-    {
-        const int nr = ctx->nranks, me = ctx->rank;
-        NLG_CHECK(st == ctx->stream, "pprec_setup: internal (stream)");
-        auto gather_host = [&](const std::vector<double> &in, std::vector<double> &out) -> int {
-            double *di = nullptr, *d_o = nullptr;
-            const size_t c = in.size();
-            NLG_HIP(hipMalloc(&di, sizeof(double) * c));
-            NLG_HIP(hipMalloc(&d_o, sizeof(double) * c * nr));
-            NLG_HIP(hipMemcpyAsync(di, in.data(), sizeof(double) * c, hipMemcpyHostToDevice, st));
-            NLG_TRY(allgather_f64(ctx, di, d_o, (int64_t)c));
-            out.resize(c * nr);
-            NLG_HIP(hipMemcpyAsync(out.data(), d_o, sizeof(double) * c * nr, hipMemcpyDeviceToHost, st));
-            NLG_HIP(hipStreamSynchronize(st));
-            hipFree(di);
-            hipFree(d_o);
-            return 0;
-        };
-        // aggregates whose support holds an element with a node shared with another rank
-        std::vector<char> velem((size_t)E, 0), aflag((size_t)na, 0);
-        for (int idx : m->halo.h_cidx) velem[idx / np1] = 1;
-        for (int64_t e = 0; e < E; ++e)
-            if (velem[e])
-                for (int c = 0; c < NC; ++c) aflag[agg[vg[(size_t)e * NC + c]]] = 1;
-        std::vector<int> ifa;
-        for (int a = 0; a < na; ++a)
-            if (aflag[a]) ifa.push_back(a);
-        double tr = 0.0;
-        for (int i = 0; i < na; ++i) tr += Acc[(size_t)i * na + i];
-        std::vector<double> info;
-        NLG_TRY(gather_host({(double)na, (double)ifa.size(), tr}, info));
-        std::vector<int> na_all(nr), ni_all(nr);
-        int na_max = 0, ni_max = 0;
-        double tr_all = 0.0, nreal = 0.0;
-        for (int q = 0; q < nr; ++q) {
-            na_all[q] = (int)info[3 * q];
-            ni_all[q] = (int)info[3 * q + 1];
-            tr_all += info[3 * q + 2];
-            nreal += na_all[q];
-            na_max = std::max(na_max, na_all[q]);
-            ni_max = std::max(ni_max, ni_all[q]);
-        }
-        const int64_t ntot = (int64_t)nr * na_max;
-        NLG_CHECK(ntot <= 60000, "pprec_setup: global aggregate level of %lld unknowns is too large for the dense inverse", (long long)ntot);
-        std::vector<double> ifa_pad((size_t)std::max(ni_max, 1), -1.0), ifa_all;
-        for (size_t i = 0; i < ifa.size(); ++i) ifa_pad[i] = ifa[i];
-        NLG_TRY(gather_host(ifa_pad, ifa_all));
-        // this rank's rows: diagonal block from the halo-free assembly, the rest by probing
-        double *d_rows = nullptr, *d_full = nullptr;
-        {
-            std::vector<double> rowsH((size_t)na_max * ntot, 0.0);
-            for (int i = 0; i < na; ++i)
-                for (int j = 0; j < na; ++j) rowsH[(size_t)i * ntot + (size_t)me * na_max + j] = Acc[(size_t)i * na + j];
-            NLG_TRY(up(rowsH, &d_rows));
-        }
-        NLG_HIP(hipMalloc(&P.d_ra, sizeof(double) * (size_t)na_max));
-        NLG_HIP(hipMemsetAsync(P.d_ra, 0, sizeof(double) * (size_t)na_max, st));
-        NLG_HIP(hipMalloc(&P.d_rag, sizeof(double) * (size_t)ntot));
-        double *pp = sem_scratch2(m, 0), *ep = sem_scratch2(m, 1);
-        NLG_CHECK(pp && ep, "pprec_setup: scratch allocation failed");
-        const unsigned gp = (unsigned)((m->lpn + NT - 1) / NT), ge = (unsigned)((E + 3) / 4);
-        const size_t stride_i = (size_t)std::max(ni_max, 1);
-        for (int r = 0; r < nr; ++r)
-            for (int i = 0; i < ni_all[r]; ++i) {
-                const int a_src = (int)ifa_all[(size_t)r * stride_i + i];
-                const int a = me == r ? a_src : -1;
-                if (dim == 3) {
-                    NLG_LAUNCH(k_agg_probe<3>, dim3(gp), dim3(NT), 0, st, E, n2, hat, (const int *)P.d_vg, (const int *)P.d_agg, a, pp);
-                } else {
-                    NLG_LAUNCH(k_agg_probe<2>, dim3(gp), dim3(NT), 0, st, E, n2, hat, (const int *)P.d_vg, (const int *)P.d_agg, a, pp);
-                }
-                NLG_TRY(sem_cdabdtp(m, pp, ep));
-                if (me == r) continue;   // own block: already there
-                if (dim == 3) {
-                    NLG_LAUNCH(k_q1_restrict_local<3>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, P.d_tq, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
-                } else {
-                    NLG_LAUNCH(k_q1_restrict_local<2>, dim3(ge), dim3(NT), 0, st, (const double *)nullptr, E, n2, hat, ep, P.d_tq, (double *)nullptr, (const double *)nullptr, (const int *)nullptr, nlg_pcg_upd{});
-                }
-                NLG_LAUNCH(k_q1_gather, dim3((nvert + NT - 1) / NT), dim3(NT), 0, st, (const double *)nullptr, nvert, P.d_v2e_p, P.d_v2e_i, P.d_tq, P.d_rc, P.d_dinv, 0.0, P.d_x);
-                NLG_LAUNCH(k_agg_restrict, dim3((na + 3) / 4), dim3(NT), 0, st, (const double *)nullptr, na, P.d_ap, P.d_am, P.d_rc, P.d_ra);
-                NLG_LAUNCH(k_store_col, dim3((na + 255) / 256), dim3(256), 0, st, na, (const double *)P.d_ra, d_rows, ntot, (int64_t)r * na_max + a_src);
-            }
-        NLG_HIP(hipGetLastError());
-        NLG_HIP(hipMalloc(&d_full, sizeof(double) * (size_t)ntot * ntot));
-        NLG_TRY(allgather_f64(ctx, d_rows, d_full, (int64_t)na_max * ntot));
-        int *d_na_of = nullptr;
-        NLG_TRY(up(na_all, &d_na_of));
-        const double alpha = m->has_outflow ? 0.0 : tr_all / nreal / nreal;
-        NLG_LAUNCH(k_glob_fix, dim3((unsigned)((ntot + 255) / 256), (unsigned)ntot), dim3(256), 0, st, ntot, na_max, (const int *)d_na_of, alpha, d_full);
-        NLG_TRY(spd_inverse_dev(d_full, (int)ntot));
-        const int64_t nrow_el = (int64_t)std::max(na, 1) * ntot;
-        NLG_HIP(hipMalloc(&P.d_Ainv32, sizeof(float) * (size_t)nrow_el));
-        NLG_LAUNCH(k_to_float, dim3((unsigned)((nrow_el + 255) / 256)), dim3(256), 0, st, (int64_t)na * ntot,
-                           (const double *)(d_full + (size_t)me * na_max * ntot), P.d_Ainv32);
-        NLG_HIP(hipGetLastError());
-        NLG_HIP(hipStreamSynchronize(st));
-        hipFree(d_full);
-        hipFree(d_rows);
-        hipFree(d_na_of);
-        P.na_max = na_max;
-        P.ncols = (int)ntot;
     }
     P.ready = true;
     return 0;

@@ -1,6 +1,8 @@
 """ORACLE (test infrastructure only) -- the two-level Schwarz preconditioner of the consistent Poisson operator
 E = D (mask B^-1 QQ^T) D^T, restated in float64 numpy from its definition (header of neklab_amd/csrc/pprec.hip and the
-set-up in pprec_setup):
+stages of the set-up in neklab_amd/csrc/pprec_host.cpp, which tests/test_cpu_pprec_setup.py compares with the methods here:
+edge_lengths ~ _lengths, local_fdm ~ _setup_local, extended_lines ~ ext_line / _setup_overlap, overlap_destinations ~
+_neighbours, coarse_topology / coarse_rows / assemble_acc ~ _setup_coarse, aggregate ~ _aggregate):
 
     M^-1 r = sum_e R_e^T W A~_e^-1 W R_e r  +  R_1 V(A_c) R_1^T r
 
@@ -16,7 +18,7 @@ set-up in pprec_setup):
 * R_1: the trilinear (bilinear) hats of the element vertices at the GL points; A_c = R_1^T E R_1 from SEM.cdabdtp
   applied to the hat columns.  Exact mode (nvert <= exact_max): A_c^-1, shifted by alpha 1 1^T, alpha = tr / na^2,
   without outflow.  Aggregated mode: omega diag(A_c)^-1 + P (P^T A_c P)^-1 P^T with the greedy vertex aggregates of
-  pprec_setup step 4 (one rank).
+  the stage `aggregate` of pprec_host.cpp (one rank).
 
 Imports nothing from neklab_amd: the oracle shares no table with the device.
 """
@@ -26,7 +28,7 @@ import numpy as np
 
 
 def overlap_available(dim, n):
-    """The layer of face overlap exists in 3-D for lx1 <= 12 except 11 and in 2-D for lx1 <= 8 (pprec_setup)."""
+    """The layer of face overlap exists in 3-D for lx1 <= 12 except 11 and in 2-D for lx1 <= 8 (pprec_setup in pprec.hip)."""
     return (dim == 3 and n <= 12 and n != 11) or (dim == 2 and n <= 8)
 
 
@@ -290,7 +292,7 @@ class SchwarzPrec:
         self.dinv = np.where(d > 0, 1.0 / np.where(d > 0, d, 1.0), 0.0)
 
     def _aggregate(self, Ac):
-        """pprec_setup step 4, one rank: elements whose corners are all free become aggregates (element order); every
+        """The stage `aggregate` of pprec_host.cpp, one rank: elements whose corners are all free become aggregates (element order); every
         other vertex (vertex order) joins the aggregate of its most strongly coupled, already aggregated vertex among the
         vertices of its elements (the first one on ties), else starts one.  Also reports whether a choice was a near-tie
         (the device could then resolve it differently by rounding)."""
