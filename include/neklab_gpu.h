@@ -494,6 +494,33 @@ int nlg_op_pprec(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out, int overlap, i
 int nlg_op_opdiv(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_opgradt(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_conv(nlg_mesh *mesh, const nlg_vec *base, const nlg_vec *in, nlg_vec *out, int adjoint);
+/* ONE application of the operator of a PCG loop in the form that only the solver calls, for tests against a reference (nothing is
+ * iterated, so nothing is amplified).  Host arrays, natural element layout, lane-major: a per-lane field argument is [nl][nf][points],
+ * a per-lane scalar [nl].  On the device the lanes sit a padded stride apart, as in the solver's slab.  Every output buffer holds
+ * `sentinel` (finite) before the launch: what a kernel does not write comes back as the sentinel.
+ *
+ * helmholtz_pcg = the velocity / temperature solve's application (helm_apply): the Helmholtz kernel with the first-stage sums and the
+ * done flags, then the gather-scatter gated by the same flags; no mask is applied to w.
+ *   fused = 0 : w = QQ^T (h1 A + h2 B) u                       (the single-reduction PCG's plain application; zf, beta, pcinv unused)
+ *   fused = 1 : u <- zf + beta[lane] u, then the same           (direction update inside the kernel)
+ *   zfree = 1 : u <- pc zf + beta[lane] u with pc = mask_c ? pcinv : 0, the product rounded on its own; pcinv [points] is shared by the
+ *               fields and lanes, the mask bytes are built from the mesh's Dirichlet masks as nlg_linop_init builds them
+ *   ring  = 1 : the updated direction goes to the next slot of a direction ring instead of over u
+ *   xp    = 1 : every vector in the slab-permuted layout of the 3-D velocity solve (inputs permuted on the way in, outputs on the way out)
+ *   nf: 1 or dim.  Refused: zfree or xp in 2-D, zfree or ring without fused, xp on a mesh without the tables.
+ *   u_out = the direction after the call (ring = 0: the buffer u was read from), u_src = the buffer u was read from, w_out = w,
+ *   part [nl][part_cap] = the sums of u . w_local per block (w before the gather-scatter), *npart of them per lane.
+ * cdabdtp_pcg = the pressure solve's application (pres_apply): out = E p with the done flags as gates, part [nl][part_cap] with
+ *   part[b] = sum p out and part[*npart + b] = sum out over block b (3-D: one element per block).
+ *   fused = 1 : p <- (z - zmean[lane]) + beta[lane] p inside the gradient kernel (3-D, lx1 = 8..10; refused elsewhere), the sums with
+ *               the updated p;  ring = 1 (fused only): the updated p goes to another buffer, ring = 0: over p
+ *   p_out = the direction after the call, p_src = the buffer p was read from.
+ * A lane with done != 0 is skipped by every kernel. */
+int nlg_op_helmholtz_pcg(nlg_mesh *mesh, int nf, int nl, double h1, double h2, const double *u, const double *zf, const double *beta,
+                         const double *done, const double *pcinv, int xp, int zfree, int ring, int fused, double sentinel, double *u_out,
+                         double *u_src, double *w_out, double *part, int part_cap, int *npart);
+int nlg_op_cdabdtp_pcg(nlg_mesh *mesh, int nl, const double *p, const double *z, const double *beta, const double *zmean, const double *done,
+                       int fused, int ring, double sentinel, double *p_out, double *p_src, double *out, double *part, int part_cap, int *npart);
 /* The operator L itself in strong (pointwise) form, element-local: apply_L, apply_Lv, compute_LNS_conv, compute_LNS_laplacian and
  * compute_LNS_gradp of the reference (src/linops/neklab_linops.f90:24-28, :268-426) are this one call with other coefficients:
  *   u~_k  = mask_k in.v_k                                   (bcdirvc on read: `in` is not modified)

@@ -370,6 +370,7 @@ int basis_cgs2_host(int s, nlg_basis *const *b, int k, nlg_vec *const *w, double
 
 // ---- lns.hip ----
 int linop_proj_lanes(const nlg_linop *op);   // wavenumber lanes of the operator (nlg_linop_set_projection_lanes), 0 = none
+int vel_mask_bytes(nlg_mesh *m, bool xp, unsigned char *out);   // the mask bytes of the velocity PCG (pcmb of sem_axhelm): bit c = mask_c != 0; xp: slab-permuted
 
 // ---- pprec.hip ----
 int pprec_setup(nlg_mesh *m, const nlg_mesh_desc *d);

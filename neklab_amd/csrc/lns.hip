@@ -2625,6 +2625,23 @@ int do_nonlinear_map(nlg_linop *op, const nlg_vec *vin, nlg_vec *vout) {
 
 namespace nlg {
 int linop_proj_lanes(const nlg_linop *op) { return op->proj_lanes; }
+
+// one byte per velocity point, bit c = mask_c != 0, in the natural or (xp) the slab-permuted layout: the compact Dirichlet mask of the
+// velocity PCG (out: m->lvs bytes; scratch fields 3 and 4 are overwritten)
+int vel_mask_bytes(nlg_mesh *m, bool xp, unsigned char *out) {
+    hipStream_t st = m->ctx->stream;
+    double *t0 = sem_scratch1(m, 3), *t1 = xp ? sem_scratch1(m, 4) : nullptr;
+    NLG_CHECK(t0 && (t1 || !xp), "vel_mask_bytes: scratch allocation failed");
+    NLG_LAUNCH(k_maskbits, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, t0, (const double *)m->d_mask[0], (const double *)m->d_mask[1],
+                       (const double *)m->d_mask[2]);
+    if (xp) {
+        double *a[1] = {t0}, *b[1] = {t1};
+        NLG_TRY(sem_to_xp(m, a, b, 1));
+    }
+    NLG_LAUNCH(k_to_bytes, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, out, (const double *)(xp ? t1 : t0));
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
 }  // namespace nlg
 
 extern "C" {
@@ -2814,17 +2831,11 @@ int nlg_linop_init(nlg_linop *op) {
         }
     }
     if (compact) {
-        NLG_LAUNCH(k_maskbits, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, t0, (const double *)m->d_mask[0], (const double *)m->d_mask[1],
-                           (const double *)m->d_mask[2]);
-        if (xp) {
-            double *a[1] = {t0}, *b[1] = {t1};
-            NLG_TRY(sem_to_xp(m, a, b, 1));
-        }
         if (!op->maskb_v) {
             NLG_HIP(hipMalloc(&op->maskb_v, (size_t)m->lvs));
             NLG_HIP(hipMemsetAsync(op->maskb_v, 0, (size_t)m->lvs, st));
         }
-        NLG_LAUNCH(k_to_bytes, dim3(grid_for(m->lvn)), dim3(NT), 0, st, m->lvn, op->maskb_v, (const double *)(xp ? t1 : t0));
+        NLG_TRY(vel_mask_bytes(m, xp, op->maskb_v));
     }
     // (the velocity solve always runs the direction update inside the operator kernel, helm_problem)
     op->z_free = dim == 3 && op->maskb_v && !op->use_sr && !op->store_z && sem_axhelm_forms_z(m);

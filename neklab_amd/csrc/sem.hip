@@ -5392,6 +5392,147 @@ int nlg_op_opgradt(nlg_mesh *m, const nlg_vec *in, nlg_vec *out) {
     return sem_opgradt(m, in->pr(), w);
 }
 
+// ---- one application of the operator of a PCG loop in the form only the solver calls (lns.hip helm_apply / pres_apply) ----
+// The lanes of every per-lane argument sit ld doubles apart in slabs of their own, as in the solver's slab; host arrays are lane-major
+// [nl][nf][len] in the natural element layout.
+static int slab_new(nlg_mesh *m, DevBuf<> &b, int64_t n, double fill) {
+    NLG_HIP(hipMalloc(&b.p, sizeof(double) * (size_t)n));
+    NLG_LAUNCH(k_set, dim3(grid_for(n)), dim3(NT), 0, m->ctx->stream, b.p, fill, n);
+    NLG_HIP(hipGetLastError());
+    return 0;
+}
+// lane v, field q: device d + v * ld + q * fs  <->  host h + (v * nf + q) * len
+static int slab_put(nlg_mesh *m, double *d, const double *h, int nl, int nf, int64_t len, int64_t ld, int64_t fs) {
+    for (int v = 0; v < nl; ++v)
+        for (int q = 0; q < nf; ++q)
+            NLG_HIP(hipMemcpyAsync(d + v * ld + q * fs, h + ((int64_t)v * nf + q) * len, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, m->ctx->stream));
+    return 0;
+}
+static int slab_get(nlg_mesh *m, double *h, const double *d, int nl, int nf, int64_t len, int64_t ld, int64_t fs) {
+    for (int v = 0; v < nl; ++v)
+        for (int q = 0; q < nf; ++q)
+            NLG_HIP(hipMemcpyAsync(h + ((int64_t)v * nf + q) * len, d + v * ld + q * fs, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, m->ctx->stream));
+    return 0;
+}
+enum { PS_BETA = 0, PS_DONE = 1, PS_ZMEAN = 2 };   // the scalars of a lane inside its slab
+
+int nlg_op_helmholtz_pcg(nlg_mesh *m, int nf, int nl, double h1, double h2, const double *u, const double *zf, const double *beta, const double *done,
+                         const double *pcinv, int xp, int zfree, int ring, int fused, double sentinel, double *u_out, double *u_src, double *w_out,
+                         double *part, int part_cap, int *npart) {
+    NLG_CHECK(m && u && done && u_out && u_src && w_out && part && npart, "nlg_op_helmholtz_pcg: bad arguments");
+    const int dim = m->dim;
+    NLG_CHECK((nf == 1 || nf == dim) && nl >= 1 && nl <= kMaxLanes, "nlg_op_helmholtz_pcg: nf = %d (1 or %d), nl = %d (1 to %d)", nf, dim, nl, kMaxLanes);
+    NLG_CHECK(!fused || (zf && beta), "nlg_op_helmholtz_pcg: the fused direction update needs zf and beta");
+    NLG_CHECK(!zfree || (fused && pcinv), "nlg_op_helmholtz_pcg: the z-free form is a form of the fused direction update and needs pcinv");
+    NLG_CHECK(!ring || fused, "nlg_op_helmholtz_pcg: the direction ring exists with the fused direction update only");
+    NLG_CHECK(!zfree || dim == 3, "nlg_op_helmholtz_pcg: the z-free form exists in 3-D only");
+    NLG_CHECK(!xp || dim == 3, "nlg_op_helmholtz_pcg: the slab-permuted layout exists in 3-D only");
+    NLG_CHECK(!xp || (m->d_slot_xp && (m->gs.d_indices_xp || m->gs.ngroups == 0)), "nlg_op_helmholtz_pcg: this mesh has no slab-permuted tables");
+    NLG_CHECK(std::isfinite(sentinel), "nlg_op_helmholtz_pcg: the sentinel must be finite");
+    const int nb = sem_axhelm_blocks(m, nf);
+    NLG_CHECK(part_cap >= nb, "nlg_op_helmholtz_pcg: %d partial sums per lane, room for %d", nb, part_cap);
+    *npart = nb;
+    hipStream_t st = m->ctx->stream;
+    const int64_t fs = m->lvs, n = m->lvn, slot = (int64_t)nf * fs;   // slot: one direction of the ring (PHist::stride of the velocity solve)
+    const int64_t ld = round_up(std::max<int64_t>(2 * slot, part_cap), kAlign);
+    DevBuf<> U, Z, W, T, S, Pt, pci, pcn;
+    DevBuf<unsigned char> mb;
+    NLG_TRY(slab_new(m, U, nl * ld, sentinel));    // [lane][ring slot 0 = source, 1][field]
+    NLG_TRY(slab_new(m, W, nl * ld, sentinel));
+    NLG_TRY(slab_new(m, Pt, nl * ld, sentinel));
+    NLG_TRY(slab_new(m, Z, nl * ld, 0.0));
+    NLG_TRY(slab_new(m, T, nl * ld, 0.0));         // staging in the natural layout
+    NLG_TRY(slab_new(m, S, nl * ld, 0.0));
+    std::vector<double> hs((size_t)(nl * ld), 0.0);
+    for (int v = 0; v < nl; ++v) hs[v * ld + PS_BETA] = beta ? beta[v] : 0.0, hs[v * ld + PS_DONE] = done[v];
+    NLG_HIP(hipMemcpyAsync(S.p, hs.data(), sizeof(double) * hs.size(), hipMemcpyHostToDevice, st));
+    double *pu[3], *pz[3], *pw[3], *pt[3];
+    for (int q = 0; q < 3; ++q) pu[q] = q < nf ? U.p + q * fs : nullptr, pz[q] = q < nf ? Z.p + q * fs : nullptr, pw[q] = q < nf ? W.p + q * fs : nullptr, pt[q] = q < nf ? T.p + q * fs : nullptr;
+    // inputs: natural layout, or through sem_to_xp as the solver's right-hand side arrives
+    auto put = [&](double *const *dst, const double *h) -> int {
+        NLG_TRY(slab_put(m, xp ? T.p : dst[0], h, nl, nf, n, ld, fs));
+        if (xp) NLG_TRY(sem_to_xp(m, pt, dst, nf, nl, ld));
+        return 0;
+    };
+    NLG_TRY(put(pu, u));
+    if (fused) NLG_TRY(put(pz, zf));
+    if (zfree) {   // 1 / diag in the layout of the solve and the mask bytes as nlg_linop_init builds them
+        NLG_TRY(slab_new(m, pci, fs, 0.0));
+        NLG_TRY(slab_new(m, pcn, fs, 0.0));
+        NLG_HIP(hipMalloc(&mb.p, (size_t)fs));
+        NLG_HIP(hipMemsetAsync(mb.p, 0, (size_t)fs, st));
+        NLG_HIP(hipMemcpyAsync(xp ? pcn.p : pci.p, pcinv, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+        if (xp) {
+            double *a[1] = {pcn.p}, *b[1] = {pci.p};
+            NLG_TRY(sem_to_xp(m, a, b, 1));
+        }
+        NLG_TRY(vel_mask_bytes(m, xp != 0, mb.p));
+    }
+    // ---- the calls of helm_apply (fused) / helm_run's apply_plain
+    const double *beta_p = S.p + PS_BETA, *done_p = S.p + PS_DONE;
+    if (fused)
+        NLG_TRY(sem_axhelm(m, pu, pw, nf, h1, h2, Pt.p, pz, beta_p, done_p, xp != 0, nl, ld, ring ? slot : 0, zfree ? pci.p : nullptr, zfree ? mb.p : nullptr));
+    else
+        NLG_TRY(sem_axhelm(m, pu, pw, nf, h1, h2, Pt.p, nullptr, nullptr, done_p, xp != 0, nl, ld));
+    NLG_TRY(sem_gs(m, pw, nf, done_p, xp ? LAYOUT_XP : LAYOUT_NAT, nl, ld, ld));
+    // ---- outputs
+    auto get = [&](double *h, double *const *src) -> int {
+        if (xp) NLG_TRY(sem_from_xp(m, src, pt, nf, nl, ld));
+        return slab_get(m, h, xp ? T.p : src[0], nl, nf, n, ld, fs);
+    };
+    double *po[3];
+    for (int q = 0; q < 3; ++q) po[q] = q < nf ? pu[q] + (ring ? slot : 0) : nullptr;
+    NLG_TRY(get(u_src, pu));   // (the staging slab is reused: kernels and copies are ordered on the one stream)
+    NLG_TRY(get(u_out, po));
+    NLG_TRY(get(w_out, pw));
+    NLG_TRY(slab_get(m, part, Pt.p, nl, 1, part_cap, ld, 0));
+    NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int nlg_op_cdabdtp_pcg(nlg_mesh *m, int nl, const double *p, const double *z, const double *beta, const double *zmean, const double *done, int fused,
+                       int ring, double sentinel, double *p_out, double *p_src, double *out, double *part, int part_cap, int *npart) {
+    NLG_CHECK(m && p && done && p_out && p_src && out && part && npart, "nlg_op_cdabdtp_pcg: bad arguments");
+    NLG_CHECK(nl >= 1 && nl <= kMaxLanes, "nlg_op_cdabdtp_pcg: nl = %d (1 to %d)", nl, kMaxLanes);
+    NLG_CHECK(!fused || (z && beta && zmean), "nlg_op_cdabdtp_pcg: the fused direction update needs z, beta and zmean");
+    NLG_CHECK(!fused || sem_opgradt_fuses_pupdate(m), "nlg_op_cdabdtp_pcg: the gradient kernel of this size does not perform the direction update");
+    NLG_CHECK(!ring || fused, "nlg_op_cdabdtp_pcg: the direction ring exists with the fused direction update only");
+    NLG_CHECK(std::isfinite(sentinel), "nlg_op_cdabdtp_pcg: the sentinel must be finite");
+    const int nb = sem_opdiv_blocks(m);
+    NLG_CHECK(part_cap >= 2 * nb, "nlg_op_cdabdtp_pcg: %d partial sums per lane, room for %d", 2 * nb, part_cap);
+    *npart = nb;
+    hipStream_t st = m->ctx->stream;
+    const int64_t fs = m->lps, n = m->lpn;   // fs: one direction of the ring (PHist::stride of the pressure solve)
+    const int64_t ld = round_up(std::max<int64_t>(2 * fs, part_cap), kAlign);
+    DevBuf<> Pd, Z, W, S, Pt;
+    NLG_TRY(slab_new(m, Pd, nl * ld, sentinel));   // [lane][ring slot 0 = source, 1]
+    NLG_TRY(slab_new(m, W, nl * ld, sentinel));
+    NLG_TRY(slab_new(m, Pt, nl * ld, sentinel));
+    NLG_TRY(slab_new(m, Z, nl * ld, 0.0));
+    NLG_TRY(slab_new(m, S, nl * ld, 0.0));
+    std::vector<double> hs((size_t)(nl * ld), 0.0);
+    for (int v = 0; v < nl; ++v) {
+        hs[v * ld + PS_BETA] = beta ? beta[v] : 0.0;
+        hs[v * ld + PS_ZMEAN] = zmean ? zmean[v] : 0.0;
+        hs[v * ld + PS_DONE] = done[v];
+    }
+    NLG_HIP(hipMemcpyAsync(S.p, hs.data(), sizeof(double) * hs.size(), hipMemcpyHostToDevice, st));
+    NLG_TRY(slab_put(m, Pd.p, p, nl, 1, n, ld, 0));
+    if (fused) NLG_TRY(slab_put(m, Z.p, z, nl, 1, n, ld, 0));
+    // ---- the call of pres_apply
+    double *p_in = Pd.p, *p_upd = Pd.p + (ring ? fs : 0);
+    nlg_pupd upd;
+    upd.z = Z.p, upd.beta = S.p + PS_BETA, upd.zmean = S.p + PS_ZMEAN, upd.p = p_upd;
+    NLG_TRY(sem_cdabdtp(m, p_in, W.p, Pt.p, S.p + PS_DONE, fused ? &upd : nullptr, nl, ld));
+    // ---- outputs
+    NLG_TRY(slab_get(m, p_src, p_in, nl, 1, n, ld, 0));
+    NLG_TRY(slab_get(m, p_out, p_upd, nl, 1, n, ld, 0));
+    NLG_TRY(slab_get(m, out, W.p, nl, 1, n, ld, 0));
+    NLG_TRY(slab_get(m, part, Pt.p, nl, 1, part_cap, ld, 0));
+    NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 int nlg_op_cfl(nlg_mesh *m, const nlg_vec *base, double dt, double *cfl) {
     NLG_CHECK(m && base && cfl && base->mesh == m, "nlg_op_cfl: bad arguments");
     double *u[3];

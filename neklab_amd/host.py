@@ -110,6 +110,42 @@ class Mesh:
         check(self.lib.nlg_mesh_pop_mfma(self.h, C.byref(out)))
         return out.value
 
+    # ---- one application of a PCG loop's operator in the solver-only form (include/neklab_gpu.h: nlg_op_helmholtz_pcg, nlg_op_cdabdtp_pcg)
+    def helmholtz_pcg(self, u, h1, h2, zf=None, beta=None, done=None, pcinv=None, xp=0, zfree=0, ring=0, fused=0, sentinel=-7.25):
+        """u, zf: [nl][nf][lvn]; beta, done: [nl]; pcinv: [lvn].  Returns dict(u_out, u_src, w: [nl][nf][lvn], part: [nl][cap], npart)."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        nl, nf = u.shape[:2]
+        assert u.shape[2:] == (self.lvn,)
+        f = lambda a, shape: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))
+        zf, beta, pcinv = f(zf, u.shape), f(beta, (nl,)), f(pcinv, (self.lvn,))
+        done = f(np.zeros(nl) if done is None else done, (nl,))
+        cap = self.E * nf
+        out = dict(u_out=np.empty_like(u), u_src=np.empty_like(u), w=np.empty_like(u), part=np.empty((nl, cap)))
+        npart = C.c_int()
+        p = lambda a: None if a is None else dptr(a)
+        check(self.lib.nlg_op_helmholtz_pcg(self.h, nf, nl, float(h1), float(h2), p(u), p(zf), p(beta), p(done), p(pcinv), int(xp), int(zfree),
+                                            int(ring), int(fused), float(sentinel), p(out["u_out"]), p(out["u_src"]), p(out["w"]), p(out["part"]),
+                                            cap, C.byref(npart)))
+        out["npart"] = npart.value
+        return out
+
+    def cdabdtp_pcg(self, p, z=None, beta=None, zmean=None, done=None, fused=0, ring=0, sentinel=-7.25):
+        """p, z: [nl][lpn]; beta, zmean, done: [nl].  Returns dict(p_out, p_src, out: [nl][lpn], part: [nl][cap], npart)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        nl = p.shape[0]
+        assert p.shape[1:] == (self.lpn,)
+        f = lambda a, shape: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))
+        z, beta, zmean = f(z, p.shape), f(beta, (nl,)), f(zmean, (nl,))
+        done = f(np.zeros(nl) if done is None else done, (nl,))
+        cap = 2 * self.E
+        out = dict(p_out=np.empty_like(p), p_src=np.empty_like(p), out=np.empty_like(p), part=np.empty((nl, cap)))
+        npart = C.c_int()
+        q = lambda a: None if a is None else dptr(a)
+        check(self.lib.nlg_op_cdabdtp_pcg(self.h, nl, q(p), q(z), q(beta), q(zmean), q(done), int(fused), int(ring), float(sentinel),
+                                          q(out["p_out"]), q(out["p_src"]), q(out["out"]), q(out["part"]), cap, C.byref(npart)))
+        out["npart"] = npart.value
+        return out
+
     def close(self):
         if self.h:
             self.lib.nlg_mesh_destroy(self.h)
