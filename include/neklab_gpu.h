@@ -466,6 +466,59 @@ int nlg_otd_get_basis(nlg_otd *otd, int i, nlg_vec *out);   /* i 0-based */
 int nlg_otd_get_baseflow(nlg_otd *otd, nlg_vec *out);       /* its current state (the operator's base flow when it is frozen) */
 int nlg_otd_info(const nlg_otd *otd, int64_t *istep, double *time, double *dt);
 int nlg_otd_destroy(nlg_otd *otd);
+/* History points (Nek5000's `hpts` with a .his file; examples/cylinder/dns/Re180/1cyl.his, 1cyl.usr: userchk).
+ * nlg_probe_locate: pure host code, no GPU needed.  For every point x* = xyz[p] find the element e and the reference coordinates
+ *   r in [-1, 1]^dim with x_e(r) = x*, x_e the Lagrange interpolant of xm1, ym1, zm1 on the GLL nodes.  Candidates: the elements whose
+ *   GLL-node bounding box, grown by 10 % of its extent, holds the point.  Newton from the nearest GLL node of each candidate, every
+ *   iterate clamped to [-1.5, 1.5], stopped at |dr|_inf <= 1e-13, given up after 50 iterations; a component of r within the stop of a
+ *   face is set onto it.  status: 0 = found with |r|_inf <= 1; 1 = found with 1 < |r|_inf <= 1 + tol_r (points meant to lie on a curved
+ *   wall, whose polynomial side is not the true curve): r is then clamped to the element; 2 = not found, elem = -1.  dist (may be NULL)
+ *   = |x_e(r) - x*| of what is returned.  Several holders (a face, an edge, a vertex, a periodic seam): the smallest global element id
+ *   lglel (NULL: 0 .. E-1) among the holders with status 0 wins, among those with status 1 if there is none: independent of the
+ *   partition.  elem is the local index.  Returns non-zero for a bad argument (dim, n outside 2..16, NULL arrays, negative tol_r).
+ * nlg_probes: the located points on the device -- per point the local element and the 1-D Lagrange weights at r (barycentric form,
+ *   exact at a node) on the GLL nodes and on the Gauss nodes of the pressure mesh.  Several ranks: create is collective with the same
+ *   points on every rank; the rank that holds the winning element owns the point (one all-reduce at creation), so that a point on a
+ *   partition interface is sampled exactly once.  A point that no rank holds (status 2) is refused with a message that names it.
+ *   status: the winner's status, global element id, r and dist, the same on every rank (any array may be NULL).
+ *   sample: fields of s = 1..4 vectors at every point in ONE launch of k_probe_sample (one wave per point and vector, fixed summation
+ *   order: bitwise reproducible, a vector in a call of several equals its single call, a point at a GLL node returns the nodal value):
+ *   out[s][npts][nf], nf = dim + 1 (+ 1 with a scalar): velocity components, pressure (interpolated on the Gauss nodes), temperature.
+ *   Several ranks: one all-reduce; every rank receives all values.
+ * nlg_dns: a nonlinear run of the operator's time stepper as ONE continuous run (impulsive start from X0, BDF / EXT order min(istep,
+ *   torder), cfg.filter_* as in every run), with two monitors evaluated on the device after every step: the fields at the history points
+ *   and the recurrence norm d(t) = |u(t) - u_ref| in the nek_ddot inner product (velocity, temperature if carried; no pressure).
+ *   create: X0 becomes the operator's base flow and the operator is initialised: dt = cfg.dt, or from the CFL rule at X0 (cfg.cfl_limit),
+ *     as nlg_linop_nonlinear_map does, and fixed from then on.  Refused with a message: an operator in orbit mode, with a live nlg_otd or
+ *     nlg_dns, with a wavenumber projection; X0 on another mesh or with the wrong number of scalars.  While the nlg_dns lives, every
+ *     matvec, set_*, init, integrate_forced, nonlinear_map and nlg_otd_create on op is refused, and so is nlg_linop_destroy.
+ *   set_probes / set_reference (ref NULL: the state as it stands; never called: no recurrence, dist = 0): the series starts again, with
+ *     the state as it stands as its sample 0.  The points must outlive their use: nlg_probes_destroy refuses while they are attached.
+ *   advance: sample 0 is the state the series starts from (X0 at t = 0 unless the monitors were changed later); every step appends one
+ *     sample.  The monitors cost at most three launches per step and neither a host synchronisation nor a collective: samples go to a
+ *     ring of `chunk` slots on the device, which is copied to the host series when it fills and by nlg_dns_series (several ranks: one
+ *     all-reduce per copy).  The series does not depend on chunk.
+ *   series: time[count], probe[count][npts][nf], dist[count] of the samples first .. first + count - 1 (any array may be NULL).
+ *   destroy: the operator's base-flow set-up is rebuilt from X0: matvecs on op are the propagator about X0. */
+int nlg_probe_locate(int dim, int n, int64_t E, const double *x, const double *y, const double *z, const int64_t *lglel, int64_t npts,
+                     const double *xyz, double tol_r, int64_t *elem, double *rst, int *status, double *dist);
+typedef struct nlg_probes nlg_probes;
+int nlg_probes_create(nlg_mesh *mesh, int64_t npts, const double *xyz, double tol_r, nlg_probes **out);
+int nlg_probes_status(const nlg_probes *p, int *status, int64_t *elem_global, double *rst, double *dist);
+int nlg_probes_sample(nlg_probes *p, int s, const nlg_vec *const *vecs, double *out);
+int nlg_probes_destroy(nlg_probes *p);
+typedef struct nlg_dns nlg_dns;
+typedef struct nlg_dns_opts { int chunk; /* ring length in steps, default 256 */ } nlg_dns_opts;
+int nlg_dns_opts_default(nlg_dns_opts *o);
+int nlg_dns_create(nlg_linop *op, const nlg_vec *X0, const nlg_dns_opts *o, nlg_dns **out);
+int nlg_dns_set_probes(nlg_dns *d, nlg_probes *p);
+int nlg_dns_set_reference(nlg_dns *d, const nlg_vec *ref);
+int nlg_dns_advance(nlg_dns *d, int nsteps);
+int nlg_dns_series(nlg_dns *d, int64_t first, int64_t count, double *time, double *probe, double *dist);
+int nlg_dns_count(const nlg_dns *d, int64_t *nsamples);
+int nlg_dns_get_state(nlg_dns *d, nlg_vec *out);
+int nlg_dns_info(const nlg_dns *d, int64_t *istep, double *time, double *dt);
+int nlg_dns_destroy(nlg_dns *d);
 /* %tau read/written by the driver (src/neklab_analysis.f90:84; apply_exptA neklab_linops.f90:252) */
 int nlg_linop_set_tau(nlg_linop *op, double tau);
 int nlg_linop_get_info(const nlg_linop *op, double *tau, double *dt, int *nsteps, double *cfl);

@@ -53,6 +53,10 @@ class OtdOpts(C.Structure):
     _fields_ = [("r", C.c_int), ("startstep", C.c_int), ("orthostep", C.c_int), ("trans", C.c_int), ("solve_baseflow", C.c_int)]
 
 
+class DnsOpts(C.Structure):
+    _fields_ = [("chunk", C.c_int)]
+
+
 # every symbol include/neklab_gpu.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "nlg_last_error": (C.c_char_p, []),
@@ -159,6 +163,22 @@ SIGNATURES = {
     "nlg_otd_get_baseflow": (C.c_int, [vp, vp]),
     "nlg_otd_info": (C.c_int, [vp, c_int64_p, c_double_p, c_double_p]),
     "nlg_otd_destroy": (C.c_int, [vp]),
+    "nlg_probe_locate": (C.c_int, [C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p, c_int64_p, C.c_int64, c_double_p, C.c_double,
+                                   c_int64_p, c_double_p, c_int_p, c_double_p]),
+    "nlg_probes_create": (C.c_int, [vp, C.c_int64, c_double_p, C.c_double, C.POINTER(vp)]),
+    "nlg_probes_status": (C.c_int, [vp, c_int_p, c_int64_p, c_double_p, c_double_p]),
+    "nlg_probes_sample": (C.c_int, [vp, C.c_int, C.POINTER(vp), c_double_p]),
+    "nlg_probes_destroy": (C.c_int, [vp]),
+    "nlg_dns_opts_default": (C.c_int, [C.POINTER(DnsOpts)]),
+    "nlg_dns_create": (C.c_int, [vp, vp, C.POINTER(DnsOpts), C.POINTER(vp)]),
+    "nlg_dns_set_probes": (C.c_int, [vp, vp]),
+    "nlg_dns_set_reference": (C.c_int, [vp, vp]),
+    "nlg_dns_advance": (C.c_int, [vp, C.c_int]),
+    "nlg_dns_series": (C.c_int, [vp, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p]),
+    "nlg_dns_count": (C.c_int, [vp, c_int64_p]),
+    "nlg_dns_get_state": (C.c_int, [vp, vp]),
+    "nlg_dns_info": (C.c_int, [vp, c_int64_p, c_double_p, c_double_p]),
+    "nlg_dns_destroy": (C.c_int, [vp]),
     "nlg_linop_get_info": (C.c_int, [vp, c_double_p, c_double_p, c_int_p, c_double_p]),
     "nlg_linop_get_stats": (C.c_int, [vp, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "nlg_op_helmholtz": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int]),

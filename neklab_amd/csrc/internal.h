@@ -322,7 +322,35 @@ struct nlg_basis {
     int last_block_rank = 0;   // columns kept by the last nlg_basis_block_cgs2 (< s: dependent columns were deflated)
 };
 
+// History points (probe.hip): per located point the local element and the 1-D Lagrange weights at its reference coordinates, on the
+// GLL nodes (velocity mesh) and on the Gauss nodes (pressure mesh).  A point another rank owns has elem -1 and is skipped.
+struct nlg_probes {
+    nlg_mesh *mesh = nullptr;
+    int64_t npts = 0;
+    int attached = 0;                     // nlg_dns objects that sample these points (nlg_probes_destroy refuses while > 0)
+    std::vector<int> status;              // global: of the winning element, the same on every rank
+    std::vector<int64_t> elem_global;
+    std::vector<double> rst, dist;        // [npts][dim], [npts]
+    std::vector<char> owned;
+    int *d_elem = nullptr;                // [npts] local element, -1 = not this rank's
+    double *d_w1 = nullptr, *d_w2 = nullptr;   // [npts][dim][n], [npts][dim][n2]
+    double *d_out = nullptr;              // [kMaxLanes][npts][kMaxProbeFields]: the result of nlg_probes_sample before it goes to the host
+};
+
 namespace nlg {
+
+// ---- probe.hip ----
+constexpr int kMaxProbeFields = 5;   // velocity (dim), pressure, temperature
+constexpr int kRecurBlocks = 512;    // fixed first-stage grid of the recurrence norm
+// the fields of s lanes, lane 0's pointers and every other lane's: f[v][q], q < nf; field `mesh2` (-1: none) lives on the pressure mesh
+struct ProbeFields {
+    const double *f[kMaxLanes][kMaxProbeFields];
+    int nf, mesh2;
+};
+// out[v][point][field] for the lanes v < s, one launch; points of other ranks are not written
+int probes_sample(const nlg_probes *p, int s, const ProbeFields &F, double *out);
+// *out = sum_c sum_i bm1_i (u_c,i - ref_c,i)^2 over nf <= 4 velocity-mesh fields of this rank, two launches; part: [kRecurBlocks]
+int recur_dist2(nlg_mesh *m, int nf, const double *const *u, const double *const *ref, double *part, double *out);
 
 // ---- ctx.hip: optional per-kernel-class event timing ----
 void prof_begin(nlg_ctx *ctx, int id);

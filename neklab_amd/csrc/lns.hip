@@ -1121,10 +1121,12 @@ struct ProjLines {
 }  // namespace
 
 struct nlg_otd;
+struct nlg_dns;
 
 struct nlg_linop {
     nlg_mesh *mesh = nullptr;
     nlg_otd *otd = nullptr;    // an OTD run lives on this operator: the lanes of the slab hold its state (nlg_otd_create)
+    nlg_dns *dns = nullptr;    // a DNS run lives on this operator: lane 0 holds its state (nlg_dns_create)
     nlg_exptA_config cfg;
     nlg_vec *baseflow = nullptr;
     bool inited = false;
@@ -1214,8 +1216,27 @@ struct nlg_otd {
     double *d = nullptr, *part = nullptr;
     double time = 0.0;
 };
-// every entry point that would overwrite the lanes refuses while an OTD run lives on the operator
-#define NLG_NO_OTD(op, who) NLG_CHECK(!(op)->otd, "%s: an nlg_otd lives on this operator and its lanes hold the OTD state; nlg_otd_destroy it first", who)
+// A DNS run: lane 0 of the operator's slab advanced by the nonlinear step as ONE continuous run, sampled after every step into a ring
+// on the device -- slot k = [npts][nf] history-point values, then dist2 = |u - u_ref|^2 -- that is copied to the host series when it
+// fills and when the series is read.
+struct nlg_dns {
+    nlg_linop *op = nullptr;
+    nlg_dns_opts o;
+    nlg_probes *probes = nullptr;
+    nlg_vec *ref = nullptr;
+    int nf = 0;               // fields per point: velocity, pressure, temperature if carried
+    int64_t slot_len = 1;     // npts * nf + 1
+    int fill = 0;             // slots of the ring in use
+    bool started = false;     // sample 0 of the series is taken
+    double *ring = nullptr, *part = nullptr;
+    std::vector<double> time, probe, dist2;   // the series on the host
+};
+// every entry point that would overwrite the lanes refuses while an OTD or a DNS run lives on the operator
+#define NLG_NO_OTD(op, who)                                                                                                                           \
+    do {                                                                                                                                              \
+        NLG_CHECK(!(op)->otd, "%s: an nlg_otd lives on this operator and its lanes hold the OTD state; nlg_otd_destroy it first", who);              \
+        NLG_CHECK(!(op)->dns, "%s: an nlg_dns lives on this operator and lane 0 holds its state; nlg_dns_destroy it first", who);                     \
+    } while (0)
 
 namespace {
 
@@ -3259,6 +3280,7 @@ int nlg_otd_create(nlg_linop *op, const nlg_otd_opts *o, const nlg_vec *const *b
     NLG_CHECK(op->proj_v.nlines == 0, "nlg_otd_create: OTD modes and the wavenumber projection exclude each other");
     NLG_CHECK(!op->orbit, "nlg_otd_create: the operator is in orbit mode (nlg_linop_set_orbit); use solve_baseflow on a frozen operator");
     NLG_CHECK(!op->otd, "nlg_otd_create: an nlg_otd already lives on this operator");
+    NLG_CHECK(!op->dns, "nlg_otd_create: an nlg_dns lives on this operator; nlg_dns_destroy it first");
     NLG_CHECK(o->startstep >= 1 && o->orthostep >= 1, "nlg_otd_create: startstep and orthostep must be positive");
     nlg_mesh *m = op->mesh;
     if (basis0)
@@ -3372,6 +3394,206 @@ int nlg_otd_info(const nlg_otd *ot, int64_t *istep, double *time, double *dt) {
     if (istep) *istep = ot->op->istep;
     if (time) *time = ot->time;
     if (dt) *dt = ot->op->dt;
+    return 0;
+}
+
+// ---- DNS runs with history points and a recurrence monitor (include/neklab_gpu.h; examples/cylinder/dns of the reference) ----------
+int nlg_dns_opts_default(nlg_dns_opts *o) {
+    NLG_CHECK(o, "nlg_dns_opts_default: NULL");
+    o->chunk = 256;
+    return 0;
+}
+
+// the ring goes to the host series: one all-reduce over its filled part (history points and dist2 together), one copy
+static int dns_flush(nlg_dns *d) {
+    if (d->fill == 0) return 0;
+    nlg_mesh *m = d->op->mesh;
+    hipStream_t st = m->ctx->stream;
+    const int64_t cnt = d->fill * d->slot_len, np = d->slot_len - 1;
+    NLG_CHECK(cnt < ((int64_t)1 << 31), "nlg_dns: a ring of %lld values is too long for one all-reduce; use a smaller chunk", (long long)cnt);
+    NLG_TRY(allreduce_sum(m->ctx, d->ring, (int)cnt));
+    std::vector<double> h((size_t)cnt);
+    NLG_HIP(hipMemcpyAsync(h.data(), d->ring, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipMemsetAsync(d->ring, 0, sizeof(double) * (size_t)cnt, st));   // slots of points another rank owns are never written
+    NLG_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < d->fill; ++k) {
+        const double *s = h.data() + k * d->slot_len;
+        d->probe.insert(d->probe.end(), s, s + np);
+        d->dist2.push_back(s[np]);
+    }
+    d->fill = 0;
+    return 0;
+}
+
+// one sample of the state as it stands: at most three launches, nothing waits for the device
+static int dns_sample(nlg_dns *d) {
+    nlg_linop *op = d->op;
+    nlg_mesh *m = op->mesh;
+    const int dim = m->dim;
+    if (d->fill == d->o.chunk) NLG_TRY(dns_flush(d));
+    double *slot = d->ring + d->fill * d->slot_len;
+    if (d->probes) {
+        ProbeFields F;
+        memset(&F, 0, sizeof(F));
+        F.nf = d->nf;
+        F.mesh2 = dim;
+        for (int c = 0; c < dim; ++c) F.f[0][c] = op->ubuf[0][c];
+        F.f[0][dim] = op->p;
+        if (op->cfg.ifheat) F.f[0][dim + 1] = op->tbuf[0];
+        NLG_TRY(probes_sample(d->probes, 1, F, slot));
+    }
+    if (d->ref) {
+        const double *u[4] = {}, *r[4] = {};
+        for (int c = 0; c < dim; ++c) u[c] = op->ubuf[0][c], r[c] = d->ref->vel(c);
+        if (op->cfg.ifheat) u[dim] = op->tbuf[0], r[dim] = d->ref->theta(0);
+        NLG_TRY(recur_dist2(m, dim + (op->cfg.ifheat ? 1 : 0), u, r, d->part, slot + d->slot_len - 1));
+    }
+    d->time.push_back(op->istep * op->dt);
+    d->fill += 1;
+    return 0;
+}
+
+// the monitors changed: the series starts again, with the state as it stands as its sample 0
+static int dns_restart_series(nlg_dns *d) {
+    hipStream_t st = d->op->mesh->ctx->stream;
+    NLG_HIP(hipStreamSynchronize(st));
+    (void)hipFree(d->ring);
+    d->ring = nullptr;
+    d->slot_len = (d->probes ? d->probes->npts * d->nf : 0) + 1;
+    NLG_HIP(hipMalloc(&d->ring, sizeof(double) * (size_t)(d->o.chunk * d->slot_len)));
+    NLG_HIP(hipMemsetAsync(d->ring, 0, sizeof(double) * (size_t)(d->o.chunk * d->slot_len), st));
+    d->fill = 0;
+    d->started = false;
+    d->time.clear(), d->probe.clear(), d->dist2.clear();
+    return 0;
+}
+
+int nlg_dns_destroy(nlg_dns *d) {
+    if (!d) return 0;
+    hipDeviceSynchronize();
+    nlg_linop *op = d->op;
+    const bool live = op && op->dns == d;
+    if (live) op->dns = nullptr;
+    if (d->probes) d->probes->attached -= 1;
+    if (d->ref) nlg_vec_destroy(d->ref);
+    (void)hipFree(d->ring);
+    (void)hipFree(d->part);
+    delete d;
+    if (live) {
+        // the run rebuilt the fine-mesh factors of the convective term in every step: they belong to the operator's base flow (X0)
+        // again, so that a later matvec is the propagator about X0
+        nlg_mesh *m = op->mesh;
+        double *U[3] = {op->baseflow->vel(0), op->baseflow->vel(1), m->dim == 3 ? op->baseflow->vel(2) : nullptr};
+        NLG_TRY(sem_conv_setup(m, U, op->Ur, op->GU));
+        if (op->cfg.ifheat) NLG_TRY(sem_conv_scalar_setup(m, op->baseflow->theta(0), op->GT));
+    }
+    return 0;
+}
+
+int nlg_dns_create(nlg_linop *op, const nlg_vec *X0, const nlg_dns_opts *o, nlg_dns **out) {
+    NLG_CHECK(op && X0 && o && out, "nlg_dns_create: NULL argument");
+    NLG_CHECK(o->chunk >= 1, "nlg_dns_create: chunk = %d must be positive", o->chunk);
+    NLG_CHECK(!op->orbit, "nlg_dns_create: the operator is in orbit mode (nlg_linop_set_orbit) and holds X0 as its base flow; use a second operator");
+    NLG_CHECK(!op->otd, "nlg_dns_create: an nlg_otd lives on this operator");
+    NLG_CHECK(!op->dns, "nlg_dns_create: an nlg_dns already lives on this operator");
+    NLG_CHECK(op->proj_v.nlines == 0, "nlg_dns_create: a DNS run and the wavenumber projection exclude each other");
+    nlg_mesh *m = op->mesh;
+    NLG_CHECK(X0->mesh == m, "nlg_dns_create: X0 lives on a different mesh");
+    NLG_CHECK(X0->nscal == (op->cfg.ifheat ? 1 : 0), "nlg_dns_create: X0 carries %d scalar(s), the operator expects %d (cfg.ifheat)", X0->nscal,
+              op->cfg.ifheat ? 1 : 0);
+    // the time step follows X0 (cfg.dt, or the CFL rule at X0), as in nonlinear_map, and then stays
+    NLG_TRY(nlg_vec_copy(op->baseflow, X0));
+    NLG_TRY(nlg_linop_init(op));
+    nlg_dns *d = new nlg_dns();
+    d->op = op;
+    d->o = *o;
+    d->nf = m->dim + 1 + (op->cfg.ifheat ? 1 : 0);
+    int rc = hipMalloc(&d->part, sizeof(double) * kRecurBlocks) == hipSuccess ? 0 : 1;
+    if (rc) set_error("nlg_dns_create: out of device memory");
+    if (!rc) rc = dns_restart_series(d);
+    if (!rc) rc = begin_run(op, 1);   // the run goes on across the calls of nlg_dns_advance: op->istep is its time-step index
+    if (!rc) rc = load_state(op, 0, X0, 0);
+    if (rc) {
+        nlg_dns_destroy(d);
+        return rc;
+    }
+    op->dns = d;
+    *out = d;
+    return 0;
+}
+
+int nlg_dns_set_probes(nlg_dns *d, nlg_probes *p) {
+    NLG_CHECK(d, "nlg_dns_set_probes: NULL");
+    NLG_CHECK(!p || p->mesh == d->op->mesh, "nlg_dns_set_probes: the history points were located on a different mesh");
+    if (d->probes) d->probes->attached -= 1;
+    d->probes = p;
+    if (p) p->attached += 1;
+    return dns_restart_series(d);
+}
+
+int nlg_dns_set_reference(nlg_dns *d, const nlg_vec *ref) {
+    NLG_CHECK(d, "nlg_dns_set_reference: NULL");
+    nlg_linop *op = d->op;
+    NLG_CHECK(!ref || (ref->mesh == op->mesh && ref->nscal == (op->cfg.ifheat ? 1 : 0)), "nlg_dns_set_reference: the reference lives on another mesh or carries other scalars");
+    if (!d->ref) NLG_TRY(nlg_vec_create(op->mesh, op->cfg.ifheat ? 1 : 0, 1, &d->ref));
+    if (ref) {
+        NLG_TRY(vec_copy_main(d->ref, ref));
+        if (op->cfg.ifheat)
+            NLG_HIP(hipMemcpyAsync(d->ref->theta(0), ref->theta(0), sizeof(double) * (size_t)op->mesh->lvn, hipMemcpyDeviceToDevice, op->mesh->ctx->stream));
+    } else {
+        NLG_TRY(store_state(op, 0, d->ref, 0));
+    }
+    return dns_restart_series(d);
+}
+
+int nlg_dns_advance(nlg_dns *d, int nsteps) {
+    NLG_CHECK(d && nsteps >= 0, "nlg_dns_advance: bad argument");
+    nlg_linop *op = d->op;
+    Lanes L{op, 1};
+    L.nonlinear = 1;
+    if (!d->started) {
+        NLG_TRY(dns_sample(d));
+        d->started = true;
+    }
+    for (int s = 0; s < nsteps; ++s) {
+        NLG_TRY(advance(L));
+        NLG_TRY(dns_sample(d));
+    }
+    return 0;
+}
+
+int nlg_dns_count(const nlg_dns *d, int64_t *nsamples) {
+    NLG_CHECK(d && nsamples, "nlg_dns_count: NULL argument");
+    *nsamples = (int64_t)d->time.size();
+    return 0;
+}
+
+int nlg_dns_series(nlg_dns *d, int64_t first, int64_t count, double *time, double *probe, double *dist) {
+    NLG_CHECK(d, "nlg_dns_series: NULL");
+    NLG_TRY(nlg_dns_advance(d, 0));   // sample 0, if nothing has been taken yet
+    NLG_TRY(dns_flush(d));
+    NLG_CHECK(first >= 0 && count >= 0 && first + count <= (int64_t)d->time.size(), "nlg_dns_series: samples %lld .. %lld out of range (%lld taken)",
+              (long long)first, (long long)(first + count), (long long)d->time.size());
+    const int64_t np = d->slot_len - 1;
+    for (int64_t k = 0; k < count; ++k) {
+        if (time) time[k] = d->time[first + k];
+        if (dist) dist[k] = d->ref ? std::sqrt(std::max(d->dist2[first + k], 0.0)) : 0.0;
+    }
+    if (probe && np > 0) memcpy(probe, d->probe.data() + first * np, sizeof(double) * (size_t)(count * np));
+    return 0;
+}
+
+int nlg_dns_get_state(nlg_dns *d, nlg_vec *out) {
+    NLG_CHECK(d && out && out->mesh == d->op->mesh && out->nscal == (d->op->cfg.ifheat ? 1 : 0), "nlg_dns_get_state: bad argument");
+    NLG_TRY(clear_for_store(out, 0));
+    return store_state(d->op, 0, out, 0);
+}
+
+int nlg_dns_info(const nlg_dns *d, int64_t *istep, double *time, double *dt) {
+    NLG_CHECK(d, "nlg_dns_info: NULL");
+    if (istep) *istep = d->op->istep;
+    if (time) *time = d->op->istep * d->op->dt;
+    if (dt) *dt = d->op->dt;
     return 0;
 }
 

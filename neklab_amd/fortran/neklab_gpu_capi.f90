@@ -49,6 +49,11 @@ module neklab_gpu_capi
       integer(c_int) :: r = 2, startstep = 1, orthostep = 10, trans = 0, solve_baseflow = 0
    end type
 
+   !> nlg_dns_opts with the default of nlg_dns_opts_default
+   type, bind(C), public :: nlg_dns_opts
+      integer(c_int) :: chunk = 256
+   end type
+
    !> what the reference reads from Nek5000's `param(.)` / logical flags: the template every exptA_linop starts from,
    !! the number of active scalars (ifto / ifpsco) and `lorder` of SIZE for every nek_dvector
    type(nlg_exptA_config), save, public :: nek_case
@@ -388,6 +393,107 @@ module neklab_gpu_capi
       function c_otd_destroy(otd) bind(C, name="nlg_otd_destroy") result(rc)
          import c_int, c_ptr
          type(c_ptr), value :: otd
+         integer(c_int) :: rc
+      end function
+      ! history points and DNS runs (include/neklab_gpu.h, nlg_probes_*, nlg_dns_*)
+      function c_probe_locate(dim, n, E, x, y, z, lglel, npts, xyz, tol_r, elem, rst, status, dist) bind(C, name="nlg_probe_locate") result(rc)
+         import c_int, c_int64_t, c_double, c_ptr
+         integer(c_int), value :: dim, n
+         integer(c_int64_t), value :: E, npts
+         real(c_double), intent(in) :: x(*), y(*), z(*), xyz(*)
+         type(c_ptr), value :: lglel          ! address of E global element ids, or c_null_ptr
+         real(c_double), value :: tol_r
+         integer(c_int64_t), intent(out) :: elem(*)
+         real(c_double), intent(out) :: rst(*), dist(*)
+         integer(c_int), intent(out) :: status(*)
+         integer(c_int) :: rc
+      end function
+      function c_probes_create(mesh, npts, xyz, tol_r, p) bind(C, name="nlg_probes_create") result(rc)
+         import c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: mesh
+         integer(c_int64_t), value :: npts
+         real(c_double), intent(in) :: xyz(*)
+         real(c_double), value :: tol_r
+         type(c_ptr), intent(out) :: p
+         integer(c_int) :: rc
+      end function
+      function c_probes_status(p, status, elem_global, rst, dist) bind(C, name="nlg_probes_status") result(rc)
+         import c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: p
+         integer(c_int), intent(out) :: status(*)
+         integer(c_int64_t), intent(out) :: elem_global(*)
+         real(c_double), intent(out) :: rst(*), dist(*)
+         integer(c_int) :: rc
+      end function
+      function c_probes_sample(p, s, vecs, out) bind(C, name="nlg_probes_sample") result(rc)
+         import c_int, c_double, c_ptr
+         type(c_ptr), value :: p
+         integer(c_int), value :: s
+         type(c_ptr), value :: vecs           ! address of an array of s vector handles
+         real(c_double), intent(out) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function c_probes_destroy(p) bind(C, name="nlg_probes_destroy") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: p
+         integer(c_int) :: rc
+      end function
+      function c_dns_opts_default(o) bind(C, name="nlg_dns_opts_default") result(rc)
+         import c_int, nlg_dns_opts
+         type(nlg_dns_opts), intent(out) :: o
+         integer(c_int) :: rc
+      end function
+      function c_dns_create(op, X0, o, dns) bind(C, name="nlg_dns_create") result(rc)
+         import c_int, c_ptr, nlg_dns_opts
+         type(c_ptr), value :: op, X0
+         type(nlg_dns_opts), intent(in) :: o
+         type(c_ptr), intent(out) :: dns
+         integer(c_int) :: rc
+      end function
+      function c_dns_set_probes(dns, p) bind(C, name="nlg_dns_set_probes") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: dns, p
+         integer(c_int) :: rc
+      end function
+      function c_dns_set_reference(dns, ref) bind(C, name="nlg_dns_set_reference") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: dns, ref       ! ref c_null_ptr: the state as it stands
+         integer(c_int) :: rc
+      end function
+      function c_dns_advance(dns, nsteps) bind(C, name="nlg_dns_advance") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: dns
+         integer(c_int), value :: nsteps
+         integer(c_int) :: rc
+      end function
+      function c_dns_series(dns, first, count, time, probe, dist) bind(C, name="nlg_dns_series") result(rc)
+         import c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: dns
+         integer(c_int64_t), value :: first, count
+         real(c_double), intent(out) :: time(*), probe(*), dist(*)
+         integer(c_int) :: rc
+      end function
+      function c_dns_count(dns, nsamples) bind(C, name="nlg_dns_count") result(rc)
+         import c_int, c_int64_t, c_ptr
+         type(c_ptr), value :: dns
+         integer(c_int64_t), intent(out) :: nsamples
+         integer(c_int) :: rc
+      end function
+      function c_dns_get_state(dns, vout) bind(C, name="nlg_dns_get_state") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: dns, vout
+         integer(c_int) :: rc
+      end function
+      function c_dns_info(dns, istep, time, dt) bind(C, name="nlg_dns_info") result(rc)
+         import c_int, c_ptr, c_double, c_int64_t
+         type(c_ptr), value :: dns
+         integer(c_int64_t), intent(out) :: istep
+         real(c_double), intent(out) :: time, dt
+         integer(c_int) :: rc
+      end function
+      function c_dns_destroy(dns) bind(C, name="nlg_dns_destroy") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: dns
          integer(c_int) :: rc
       end function
       ! the operator L itself in strong form (include/neklab_gpu.h, nlg_lns_*)

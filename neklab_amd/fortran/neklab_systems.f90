@@ -88,6 +88,29 @@ module neklab_systems
    integer, save, public :: upo_fixed_nsteps = 0, upo_gmres_kdim = 30
    public :: gmres_upo
 
+   !> A nonlinear run with history points and a recurrence monitor (include/neklab_gpu.h, nlg_dns_*): what the reference's case
+   !! examples/cylinder/dns/Re180 does in its userchk with `call hpts()` and rnorm = |u(t) - u_ref|.  A plain type, not a LightKrylov
+   !! object.  init(X0): the options of nek_case (dt > 0: that step; else the CFL rule at X0 with cfl_limit = 0.4), the step is then fixed.
+   type, public :: nek_dns
+      integer :: chunk = 256                                 ! ring length in steps
+      type(c_ptr), private :: h = c_null_ptr, hop = c_null_ptr, hp = c_null_ptr
+      integer(c_intptr_t), private :: owner = 0              ! the object that created the handles (a bitwise copy does not own them)
+      integer, private :: npts = 0, nf = 0
+      real(dp), allocatable, private :: xyz(:, :)
+   contains
+      procedure, pass(self), public :: init => dns_init
+      procedure, pass(self), public :: advance => dns_advance
+      procedure, pass(self), public :: set_history_points => dns_set_history_points
+      procedure, pass(self), public :: set_reference => dns_set_reference
+      procedure, pass(self), public :: series => dns_series
+      procedure, pass(self), public :: nsamples => dns_nsamples
+      procedure, pass(self), public :: state => dns_state
+      procedure, pass(self), public :: info => dns_info
+      procedure, pass(self), public :: hpts => dns_hpts
+      procedure, pass(self), public :: finalize => dns_close
+      final :: finalize_dns
+   end type
+
    !> the solver tolerance the schedulers last chose = what Nek5000 keeps in param(21) / param(22) (neklab_systems.f90:261-264)
    !> the reference's param(22) (Nek5000's velocity tolerance), which its schedulers, nonlinear_map and the Jacobian products read and
    !! write in turn (neklab_systems.f90:259-260, fixed_point.f90:14-17, :49-62, :87): ONE variable here too, so that the tolerance of
@@ -434,6 +457,148 @@ contains
       tol = min(tol, loosest)
       solver_tol = tol
       info = 0
+   end subroutine
+
+   !---- nek_dns ------------------------------------------------------------------------------------------------------
+   function dns_handle(self) result(h)
+      class(nek_dns), intent(in) :: self
+      type(c_ptr) :: h
+      if (.not. c_associated(self%h) .or. self%owner /= loc(self)) then
+         write (*, '(A)') 'ERROR in '//this_module//': DNS%init() has not been called on this object'
+         error stop 1
+      end if
+      h = self%h
+   end function
+
+   subroutine dns_close(self)
+      class(nek_dns), intent(inout) :: self
+      integer(c_int) :: rc
+      if (self%owner == loc(self)) then
+         if (c_associated(self%h)) rc = c_dns_destroy(self%h)
+         if (c_associated(self%hp)) rc = c_probes_destroy(self%hp)
+         if (c_associated(self%hop)) rc = c_linop_destroy(self%hop)
+      end if
+      self%h = c_null_ptr; self%hop = c_null_ptr; self%hp = c_null_ptr; self%owner = 0; self%npts = 0
+   end subroutine
+
+   subroutine finalize_dns(self)
+      type(nek_dns), intent(inout) :: self
+      call dns_close(self)
+   end subroutine
+
+   subroutine dns_init(self, X0)
+      class(nek_dns), intent(inout) :: self
+      type(nek_dvector), intent(in) :: X0
+      type(nlg_exptA_config) :: cfg
+      type(nlg_dns_opts) :: o
+      call dns_close(self)
+      cfg = nek_case
+      cfg%cfl_limit = 0.4_dp
+      if (cfg%dt > 0.0_dp) cfg%tau = cfg%dt       ! a run has no tau: the step is the given one, not tau / ceil(tau / dt)
+      call nlg_check(c_linop_create(nlg_mesh, cfg, nek_dvector_handle(X0), self%hop), 'nek_dns init')
+      self%owner = loc(self)
+      o%chunk = int(self%chunk, c_int)
+      call nlg_check(c_dns_create(self%hop, nek_dvector_handle(X0), o, self%h), 'nek_dns init')
+      self%nf = nek_ldim + 1 + merge(1, 0, cfg%ifheat /= 0)
+   end subroutine
+
+   subroutine dns_advance(self, nsteps)
+      class(nek_dns), intent(inout) :: self
+      integer, intent(in) :: nsteps
+      call nlg_check(c_dns_advance(dns_handle(self), int(nsteps, c_int)), 'nek_dns advance')
+   end subroutine
+
+   !> xyz(ldim, npts); tol_r (default 1e-10) as in nlg_probe_locate.  The series starts again from the state as it stands.
+   subroutine dns_set_history_points(self, xyz, tol_r)
+      class(nek_dns), intent(inout) :: self
+      real(dp), intent(in) :: xyz(:, :)
+      real(dp), intent(in), optional :: tol_r
+      real(dp) :: tol
+      type(c_ptr) :: hnew
+      integer(c_int) :: rc
+      tol = 1.0e-10_dp
+      if (present(tol_r)) tol = tol_r
+      if (size(xyz, 1) /= nek_ldim) then
+         write (*, '(A)') 'ERROR in '//this_module//': set_history_points: xyz must be (ldim, npts)'
+         error stop 1
+      end if
+      call nlg_check(c_probes_create(nlg_mesh, int(size(xyz, 2), c_int64_t), xyz, tol, hnew), 'nek_dns set_history_points')
+      call nlg_check(c_dns_set_probes(dns_handle(self), hnew), 'nek_dns set_history_points')
+      if (c_associated(self%hp)) rc = c_probes_destroy(self%hp)
+      self%hp = hnew
+      self%npts = size(xyz, 2)
+      self%xyz = xyz
+   end subroutine
+
+   !> u_ref of the recurrence norm: vec, or the state as it stands.  The series starts again from the state as it stands.
+   subroutine dns_set_reference(self, vec)
+      class(nek_dns), intent(inout) :: self
+      type(nek_dvector), intent(in), optional :: vec
+      if (present(vec)) then
+         call nlg_check(c_dns_set_reference(dns_handle(self), nek_dvector_handle(vec)), 'nek_dns set_reference')
+      else
+         call nlg_check(c_dns_set_reference(dns_handle(self), c_null_ptr), 'nek_dns set_reference')
+      end if
+   end subroutine
+
+   function dns_nsamples(self) result(n)
+      class(nek_dns), intent(inout) :: self
+      integer :: n
+      integer(c_int64_t) :: cnt
+      call nlg_check(c_dns_advance(dns_handle(self), 0_c_int), 'nek_dns nsamples')      ! sample 0, if nothing has been taken yet
+      call nlg_check(c_dns_count(dns_handle(self), cnt), 'nek_dns nsamples')
+      n = int(cnt)
+   end function
+
+   !> time(nsamples), probe(nf, npts, nsamples), dist(nsamples): (re)allocated; sample 1 is the state the series started from
+   subroutine dns_series(self, time, probe, dist)
+      class(nek_dns), intent(inout) :: self
+      real(dp), allocatable, intent(out) :: time(:), probe(:, :, :), dist(:)
+      integer :: n
+      n = dns_nsamples(self)
+      allocate (time(n), dist(n), probe(self%nf, max(self%npts, 1), n))
+      probe = 0.0_dp
+      call nlg_check(c_dns_series(dns_handle(self), 0_c_int64_t, int(n, c_int64_t), time, probe, dist), 'nek_dns series')
+      if (self%npts == 0) then
+         deallocate (probe); allocate (probe(self%nf, 0, n))
+      end if
+   end subroutine
+
+   subroutine dns_state(self, vec_out)
+      class(nek_dns), intent(in) :: self
+      type(nek_dvector), intent(inout) :: vec_out
+      call nek_dvector_ensure(vec_out)
+      call nlg_check(c_dns_get_state(dns_handle(self), vec_out%h), 'nek_dns state')
+   end subroutine
+
+   subroutine dns_info(self, istep, time, dt)
+      class(nek_dns), intent(in) :: self
+      integer, intent(out) :: istep
+      real(dp), intent(out) :: time, dt
+      integer(c_int64_t) :: is
+      call nlg_check(c_dns_info(dns_handle(self), is, time, dt), 'nek_dns info')
+      istep = int(is)
+   end subroutine
+
+   !> the series as text: the number of points and their coordinates, then per sample and point one line `time, fields...` in
+   !! 1pE15.7 (Nek5000's hpts layout restated from memory, unverified; the layout of nekio.write_his)
+   subroutine dns_hpts(self, filename)
+      class(nek_dns), intent(inout) :: self
+      character(len=*), intent(in) :: filename
+      real(dp), allocatable :: time(:), probe(:, :, :), dist(:)
+      integer :: u, k, q
+      call dns_series(self, time, probe, dist)
+      open (newunit=u, file=filename, status='replace', action='write')
+      write (u, '(I0)') self%npts
+      do q = 1, self%npts
+         write (u, '(1p,3E15.7)') self%xyz(:, q)
+      end do
+      do k = 1, size(time)
+         do q = 1, self%npts
+            write (u, '(1p,6E15.7)') time(k), probe(:, q, k)
+         end do
+      end do
+      close (u)
    end subroutine
 
 end module neklab_systems

@@ -2070,3 +2070,184 @@ def otd_analysis(OTD: nek_otd, opts: "otd_opts | None" = None, nsteps: int = 100
             outpost_dnek([OTD.basis(j) for j in range(OTD.r)], "rst", session, outdir, first_index=nrst * OTD.r + 1, time=time)
             nrst += 1
     return rows
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# DNS runs with history points and a recurrence monitor: the first stage of the reference's periodic-orbit workflow
+# (examples/cylinder/dns/Re180: a nonlinear run whose userchk calls hpts() and prints rnorm = |u(t) - u_ref|; the period guess of
+# examples/cylinder/newton/Re180_periodic_orbit was read off those two signals).
+def locate_points(mesh, xyz, tol_r: float = 1e-10):
+    """nlg_probe_locate on a host mesh (neklab_amd.mesh.BoxMesh or anything with dim, n, x, y, z, elem_gid): pure host code.
+    -> dict(elem [local, -1], rst, status, dist)"""
+    lib = _lib.load()
+    xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, mesh.dim))
+    npts = xyz.shape[0]
+    x, y = np.ascontiguousarray(mesh.x, dtype=np.float64), np.ascontiguousarray(mesh.y, dtype=np.float64)
+    z = np.ascontiguousarray(mesh.z, dtype=np.float64) if mesh.dim == 3 else None
+    gid = None if mesh.elem_gid is None else np.ascontiguousarray(mesh.elem_gid, dtype=np.int64)
+    elem, rst = np.zeros(npts, dtype=np.int64), np.zeros((npts, mesh.dim))
+    status, dist = np.zeros(npts, dtype=np.int32), np.zeros(npts)
+    rc = lib.nlg_probe_locate(mesh.dim, mesh.n, x.shape[0], dptr(x), dptr(y), None if z is None else dptr(z),
+                              None if gid is None else gid.ctypes.data_as(_lib.c_int64_p), npts, dptr(xyz), float(tol_r),
+                              elem.ctypes.data_as(_lib.c_int64_p), dptr(rst), status.ctypes.data_as(_lib.c_int_p), dptr(dist))
+    if rc != 0:
+        raise NlgError("nlg_probe_locate: bad argument")
+    return {"elem": elem, "rst": rst, "status": status, "dist": dist}
+
+
+class history_points:
+    """Points at which fields are evaluated by their Lagrange interpolant (Nek5000's hpts with a .his file).  `status`, `elem`
+    (global element id), `rst` and `dist` describe the location (nlg_probe_locate); a point in no element raises."""
+
+    def __init__(self, mesh: Mesh, xyz, tol_r: float = 1e-10):
+        self.mesh, self.lib = mesh, mesh.lib
+        self.xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, mesh.dim))
+        self.npts = self.xyz.shape[0]
+        h = vp()
+        check(self.lib.nlg_probes_create(mesh.h, self.npts, dptr(self.xyz), float(tol_r), C.byref(h)))
+        self.h = h
+        self.status, self.elem = np.zeros(self.npts, dtype=np.int32), np.zeros(self.npts, dtype=np.int64)
+        self.rst, self.dist = np.zeros((self.npts, mesh.dim)), np.zeros(self.npts)
+        check(self.lib.nlg_probes_status(h, self.status.ctypes.data_as(_lib.c_int_p), self.elem.ctypes.data_as(_lib.c_int64_p), dptr(self.rst),
+                                         dptr(self.dist)))
+
+    def sample(self, vecs) -> np.ndarray:
+        """Fields of 1 to 4 nek_dvector at every point in one launch: [len(vecs)][npts][nf] (a single vector: [npts][nf]), fields =
+        velocity components, pressure, temperature if the vectors carry one."""
+        single = isinstance(vecs, nek_dvector)
+        vecs = [vecs] if single else list(vecs)
+        nf = self.mesh.dim + 1 + (1 if vecs[0].nscal >= 1 else 0)
+        out = np.zeros((len(vecs), self.npts, nf))
+        arr = (vp * len(vecs))(*[v.h for v in vecs])
+        check(self.lib.nlg_probes_sample(self.h, len(vecs), arr, dptr(out)))
+        return out[0] if single else out
+
+    def close(self):
+        if self.h:
+            check(self.lib.nlg_probes_destroy(self.h))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class nek_dns:
+    """A nonlinear run from X0 with a fixed time step (`dt`, or the CFL rule at X0 with cfl_limit, 0.4 by default), sampled after every
+    step: the fields at the history points and d(t) = |u(t) - u_ref|.  Keyword arguments are the options of exptA_linop.  While the run
+    lives its operator refuses every other run; after close() a borrowed operator (`op=`) is the propagator about X0."""
+
+    def __init__(self, X0: nek_dvector, re: float = 0.0, torder: int = 3, dt: float = 0.0, chunk: int = 256, op: "exptA_linop | None" = None, **cfg):
+        self.mesh, self.lib, self.X0 = X0.mesh, X0.lib, X0
+        self._own_op = op is None
+        if op is None:
+            cfg.setdefault("cfl_limit", 0.4)
+            # a run has no tau, but the operator's rule snaps dt to tau / ceil(tau / dt): tau = dt keeps a given step as given (see nek_otd)
+            tau = cfg.pop("tau", None)
+            if dt > 0.0:
+                tau = dt
+            op = exptA_linop(1.0 if tau is None else tau, X0, re=re, torder=torder, dt=dt, **cfg)
+        elif cfg or re or dt:
+            raise TypeError("nek_dns: an existing operator brings its own options")
+        self.op = op   # `op=`: the run borrows an existing operator (its dt rule, tolerances, filter); X0 becomes its base flow
+        self.hp = None
+        o = _lib.DnsOpts()
+        check(self.lib.nlg_dns_opts_default(C.byref(o)))
+        o.chunk = int(chunk)
+        h = vp()
+        self.h = None
+        check(self.lib.nlg_dns_create(self.op.h, X0.h, C.byref(o), C.byref(h)))
+        self.h = h
+
+    def set_history_points(self, hp: "history_points | None"):
+        """The series starts again from the state as it stands."""
+        check(self.lib.nlg_dns_set_probes(self.h, None if hp is None else hp.h))
+        self.hp = hp
+
+    def set_reference(self, vec: "nek_dvector | None" = None):
+        """u_ref of the recurrence norm: `vec`, or the state as it stands.  The series starts again from the state as it stands."""
+        check(self.lib.nlg_dns_set_reference(self.h, None if vec is None else vec.h))
+
+    def advance(self, nsteps: int = 1):
+        check(self.lib.nlg_dns_advance(self.h, int(nsteps)))
+
+    def series(self) -> dict:
+        """time[nsamples], probe[nsamples, npts, nf], dist[nsamples]; sample 0 is the state the series started from."""
+        check(self.lib.nlg_dns_advance(self.h, 0))
+        n = C.c_int64()
+        check(self.lib.nlg_dns_count(self.h, C.byref(n)))
+        npts = 0 if self.hp is None else self.hp.npts
+        nf = self.mesh.dim + 1 + (1 if self.op.cfg.ifheat else 0)
+        t, p, d = np.zeros(n.value), np.zeros((n.value, npts, nf)), np.zeros(n.value)
+        check(self.lib.nlg_dns_series(self.h, 0, n.value, dptr(t), dptr(p) if p.size else None, dptr(d)))
+        return {"time": t, "probe": p, "dist": d}
+
+    def state(self, out: "nek_dvector | None" = None) -> nek_dvector:
+        out = out if out is not None else nek_dvector(self.mesh, self.X0.nscal, self.X0.lorder)
+        check(self.lib.nlg_dns_get_state(self.h, out.h))
+        return out
+
+    def info(self) -> dict:
+        a, t, dt = C.c_int64(), C.c_double(), C.c_double()
+        check(self.lib.nlg_dns_info(self.h, C.byref(a), C.byref(t), C.byref(dt)))
+        return {"istep": a.value, "time": t.value, "dt": dt.value}
+
+    def close(self):
+        if self.h:
+            self.lib.nlg_dns_destroy(self.h)
+            self.h = None
+        if self.op is not None and self._own_op:
+            self.op.close()
+        self.op = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def recurrence_period(time, dist, depth: float = 0.5):
+    """The first return of a run to its reference state: the first interior sample k with d_k < d_{k-1}, d_k <= d_{k+1} and
+    d_k <= depth * max_{j <= k} d_j; the period is the vertex of the parabola through the three samples of d^2 around it.
+    -> (T, d_k / max d), or None if there is no such sample."""
+    t, d = np.asarray(time, dtype=np.float64), np.asarray(dist, dtype=np.float64)
+    run_max = np.maximum.accumulate(d)
+    for k in range(1, len(d) - 1):
+        if d[k] < d[k - 1] and d[k] <= d[k + 1] and d[k] <= depth * run_max[k]:
+            y0, y1, y2 = d[k - 1] ** 2, d[k] ** 2, d[k + 1] ** 2
+            h0, h1 = t[k] - t[k - 1], t[k + 1] - t[k]
+            # vertex of the parabola through (t[k] - h0, y0), (t[k], y1), (t[k] + h1, y2)
+            s0, s1 = (y1 - y0) / h0, (y2 - y1) / h1
+            curv = (s1 - s0) / (0.5 * (h0 + h1))
+            T = t[k] if curv <= 0.0 else 0.5 * (t[k - 1] + t[k]) - s0 / curv
+            return float(T), float(d[k] / d.max())
+    return None
+
+
+def probe_period(time, signal):
+    """Mean spacing of the upward zero crossings of `signal` minus its mean, the crossings interpolated linearly; None with fewer
+    than two crossings."""
+    t, s = np.asarray(time, dtype=np.float64), np.asarray(signal, dtype=np.float64)
+    s = s - s.mean()
+    k = np.nonzero((s[:-1] < 0.0) & (s[1:] >= 0.0))[0]
+    if len(k) < 2:
+        return None
+    tc = t[k] + (t[k + 1] - t[k]) * (-s[k]) / (s[k + 1] - s[k])
+    return float((tc[-1] - tc[0]) / (len(tc) - 1))
+
+
+def dns_orbit_guess(dns: nek_dns, nsteps: int, depth: float = 0.5):
+    """A starting guess for newton_periodic_orbit from a run: the state as it stands becomes the reference snapshot, the run advances
+    nsteps, and the first recurrence of d(t) gives the period.  -> nek_ext_dvector(X, T) where X IS THE REFERENCE SNAPSHOT, the state
+    the run returned to after T, not the state at the end of the run; None if d(t) has no recurrence minimum in nsteps."""
+    ref = dns.state()
+    dns.set_reference(ref)
+    dns.advance(nsteps)
+    s = dns.series()
+    got = recurrence_period(s["time"] - s["time"][0], s["dist"], depth)
+    if got is None:
+        return None
+    return nek_ext_dvector(dns.mesh, ref.lorder, got[0], _vec=ref)

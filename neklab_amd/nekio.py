@@ -373,3 +373,40 @@ def partition_from_ma2(pmap, nranks):
         part[order[start: start + cnt]] = r
         start += cnt
     return part
+
+
+def read_his(path):
+    """A history-point file: the number of points on the first line, then one line of coordinates per point (Nek5000's .his input,
+    e.g. the reference's examples/cylinder/dns/Re180/1cyl.his).  What `write_his` appended after that is read back too.
+    -> dict(xyz [npts, dim], time [nsamples], probe [nsamples, npts, nf]); an input file has nsamples = 0."""
+    with open(path) as f:
+        rows = [ln.split() for ln in f if ln.strip()]
+    npts = int(rows[0][0])
+    if len(rows) < 1 + npts:
+        raise ValueError("read_his: %s announces %d points and holds %d lines" % (path, npts, len(rows) - 1))
+    xyz = np.array([[float(a) for a in r] for r in rows[1: 1 + npts]], dtype=np.float64).reshape(npts, -1)
+    body = rows[1 + npts:]
+    if not body:
+        return {"xyz": xyz, "time": np.zeros(0), "probe": np.zeros((0, npts, 0))}
+    if len(body) % npts:
+        raise ValueError("read_his: %s holds %d sample lines for %d points" % (path, len(body), npts))
+    a = np.array([[float(v) for v in r] for r in body], dtype=np.float64).reshape(len(body) // npts, npts, -1)
+    return {"xyz": xyz, "time": a[:, 0, 0].copy(), "probe": a[:, :, 1:].copy()}
+
+
+def write_his(path, xyz, time, probe):
+    """History-point series as text: the number of points and their coordinates (the input form `read_his` reads), then for every
+    sample and every point one line `time, fields...` in Fortran's 1pE15.7.  This is Nek5000's `hpts` layout restated from memory:
+    Nek5000 is not at hand here and the layout is UNVERIFIED against it.  `read_his` reads back what this writes."""
+    xyz = np.asarray(xyz, dtype=np.float64)
+    time, probe = np.asarray(time, dtype=np.float64), np.asarray(probe, dtype=np.float64)
+    npts = xyz.shape[0]
+    assert probe.shape[:2] == (len(time), npts), (probe.shape, len(time), npts)
+    fmt = lambda vals: "".join("%15.7E" % v for v in vals)
+    with open(path, "w") as f:
+        f.write("%d\n" % npts)
+        for p in xyz:
+            f.write(fmt(p) + "\n")
+        for k, t in enumerate(time):
+            for q in range(npts):
+                f.write(fmt([t] + list(probe[k, q])) + "\n")
