@@ -547,6 +547,20 @@ int nlg_op_pprec(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out, int overlap, i
 int nlg_op_opdiv(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_opgradt(nlg_mesh *mesh, const nlg_vec *in, nlg_vec *out);
 int nlg_op_conv(nlg_mesh *mesh, const nlg_vec *base, const nlg_vec *in, nlg_vec *out, int adjoint);
+/* The convective terms in the form the time stepper launches them, for tests against a reference: the s = 1..4 vectors go through one
+ * buffer with the lanes a constant stride apart (the stepper's slab layout) and the operator is called ONCE with (s, stride).
+ *   conv_lanes : out[v].v_i = conv(base, in[v], adjoint)_i, the term of nlg_op_conv; s = 1 launches the kernels of nlg_op_conv.
+ *   conv_scalar: the temperature (Boussinesq) terms; base, in[v] and out[v] carry one scalar (theta = scalar 0):
+ *       out[v].theta = J^T W [(U . grad) theta_v + (u_v . grad) Theta]     (adjoint = 0; weak, dealiased, element-local)
+ *                    = - J^T W [(U . grad) theta_v]                        (adjoint != 0: transport of the adjoint temperature)
+ *       out[v].v_i   = J^T W [theta_v dTheta/dx_i]                         (both values of adjoint: the temperature term of the adjoint
+ *                                                                           momentum equation, the transpose of (u . grad) Theta)
+ *     no buoyancy term and no bm1 b . u term.
+ * Only the fields named are written: the pressure, the restart history and (conv_lanes) the scalars of out[v] are left alone.  in and
+ * out may alias.  Refused with a message, out untouched: s outside 1..4, a vector on another mesh, (conv_scalar) a vector without a
+ * scalar. */
+int nlg_op_conv_lanes(nlg_mesh *mesh, const nlg_vec *base, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint);
+int nlg_op_conv_scalar(nlg_mesh *mesh, const nlg_vec *base, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint);
 /* ONE application of the operator of a PCG loop in the form that only the solver calls, for tests against a reference (nothing is
  * iterated, so nothing is amplified).  Host arrays, natural element layout, lane-major: a per-lane field argument is [nl][nf][points],
  * a per-lane scalar [nl].  On the device the lanes sit a padded stride apart, as in the solver's slab.  Every output buffer holds

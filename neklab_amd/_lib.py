@@ -188,6 +188,8 @@ SIGNATURES = {
     "nlg_op_opdiv": (C.c_int, [vp, vp, vp]),
     "nlg_op_opgradt": (C.c_int, [vp, vp, vp]),
     "nlg_op_conv": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+    "nlg_op_conv_lanes": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int]),
+    "nlg_op_conv_scalar": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int]),
     "nlg_op_helmholtz_pcg": (C.c_int, [vp, C.c_int, C.c_int, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, c_int_p]),
     "nlg_op_cdabdtp_pcg": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double,

@@ -3632,6 +3632,74 @@ int nlg_op_conv(nlg_mesh *m, const nlg_vec *base, const nlg_vec *in, nlg_vec *ou
     return rc;
 }
 
+// The convective terms as the time stepper launches them (adv_a, heat_step): s vectors as lanes of ONE buffer [s][nc][lvs] (components
+// lvs apart, lanes ld = nc * lvs apart), one sem_conv_apply / sem_conv_scalar_apply / sem_scalar_grad_apply call with (s, ld).  nc = dim
+// (velocity term) or dim + 1 (temperature term: the scalar behind the velocity).  The callers own the three buffers.
+static int op_conv_lanes_run(nlg_mesh *m, const nlg_vec *base, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint, bool scalar,
+                             double *fine, double *bin, double *bout) {
+    const int dim = m->dim, nc = dim + (scalar ? 1 : 0);
+    const int64_t ld = (int64_t)nc * m->lvs;
+    hipStream_t st = m->ctx->stream;
+    double *Ur[3] = {}, *GU[9] = {}, *GT[3] = {};
+    for (int c = 0; c < dim; ++c) Ur[c] = fine + (int64_t)c * m->lfn;
+    for (int q = 0; q < dim * dim; ++q) GU[q] = fine + (int64_t)(dim + q) * m->lfn;
+    for (int c = 0; c < dim; ++c) GT[c] = fine + (int64_t)(dim + dim * dim + c) * m->lfn;
+    double *U[3] = {base->vel(0), base->vel(1), dim == 3 ? base->vel(2) : nullptr};
+    NLG_TRY(sem_conv_setup(m, U, Ur, GU));
+    if (scalar) NLG_TRY(sem_conv_scalar_setup(m, base->theta(0), GT));
+    // vel(0) .. theta(0) of a vector are consecutive fields lvs apart: one copy per lane
+    for (int v = 0; v < s; ++v) NLG_HIP(hipMemcpyAsync(bin + v * ld, in[v]->vel(0), sizeof(double) * (size_t)ld, hipMemcpyDeviceToDevice, st));
+    NLG_HIP(hipMemsetAsync(bout, 0, sizeof(double) * (size_t)(s * ld), st));
+    double *u[3] = {}, *o[3] = {};
+    for (int c = 0; c < dim; ++c) u[c] = bin + (int64_t)c * m->lvs, o[c] = bout + (int64_t)c * m->lvs;
+    const int64_t lds = s > 1 ? ld : 0;   // the stride the stepper passes (Lanes::ld)
+    if (!scalar) {
+        NLG_TRY(sem_conv_apply(m, Ur, GU, u, o, adjoint, s, lds));
+    } else {
+        NLG_TRY(sem_conv_scalar_apply(m, Ur, GT, u, bin + (int64_t)dim * m->lvs, bout + (int64_t)dim * m->lvs, adjoint, s, lds));
+        NLG_TRY(sem_scalar_grad_apply(m, GT, bin + (int64_t)dim * m->lvs, o, 1.0, s, lds));   // onto the zeros of the memset
+    }
+    // the points of the nc fields only: the padding behind a field of out[v] and its pressure are not written
+    for (int v = 0; v < s; ++v)
+        for (int c = 0; c < nc; ++c)
+            NLG_HIP(hipMemcpyAsync(out[v]->vel(0) + (int64_t)c * m->lvs, bout + v * ld + (int64_t)c * m->lvs, sizeof(double) * (size_t)m->lvn,
+                                   hipMemcpyDeviceToDevice, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+static int op_conv_lanes(const char *name, nlg_mesh *m, const nlg_vec *base, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint,
+                         bool scalar) {
+    NLG_CHECK(m && base && in && out, "%s: NULL argument", name);
+    NLG_CHECK(s >= 1 && s <= kMaxLanes, "%s: s = %d out of range (1 to %d)", name, s, kMaxLanes);
+    NLG_CHECK(base->mesh == m, "%s: the base flow lives on another mesh", name);
+    NLG_CHECK(!scalar || base->nscal >= 1, "%s: the base flow carries no scalar", name);
+    for (int v = 0; v < s; ++v) {
+        NLG_CHECK(in[v] && out[v], "%s: vector %d is NULL", name, v);
+        NLG_CHECK(in[v]->mesh == m && out[v]->mesh == m, "%s: vector %d lives on another mesh", name, v);
+        NLG_CHECK(!scalar || (in[v]->nscal >= 1 && out[v]->nscal >= 1), "%s: vector %d carries no scalar", name, v);
+    }
+    const int dim = m->dim, nc = dim + (scalar ? 1 : 0);
+    nlg::DevBuf<> fine, bin, bout;
+    int rc = 1;
+    if (hipMalloc(&fine.p, sizeof(double) * (size_t)(dim * dim + 2 * dim) * m->lfn) == hipSuccess &&
+        hipMalloc(&bin.p, sizeof(double) * (size_t)s * nc * m->lvs) == hipSuccess &&
+        hipMalloc(&bout.p, sizeof(double) * (size_t)s * nc * m->lvs) == hipSuccess)
+        rc = op_conv_lanes_run(m, base, s, in, out, adjoint, scalar, fine.p, bin.p, bout.p);
+    else
+        nlg::set_error("%s: out of device memory", name);
+    if (rc) hipStreamSynchronize(m->ctx->stream);   // nothing in flight may still use the buffers
+    return rc;
+}
+
+int nlg_op_conv_lanes(nlg_mesh *m, const nlg_vec *base, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint) {
+    return op_conv_lanes("nlg_op_conv_lanes", m, base, s, in, out, adjoint, false);
+}
+
+int nlg_op_conv_scalar(nlg_mesh *m, const nlg_vec *base, int s, const nlg_vec *const *in, nlg_vec *const *out, int adjoint) {
+    return op_conv_lanes("nlg_op_conv_scalar", m, base, s, in, out, adjoint, true);
+}
+
 // the copies in, the launch and the copies out of nlg_op_filter; its caller owns (and frees) the two buffers whatever this returns
 static int op_filter_run(nlg_mesh *m, int nvec, nlg_vec *const *vecs, const std::vector<double> &filt, double *dF, double *buf) {
     // the kernel takes lanes as a stride: the fields of the vectors go through one buffer [nvec][ncomp][lvs]

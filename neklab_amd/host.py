@@ -146,6 +146,17 @@ class Mesh:
         out["npart"] = npart.value
         return out
 
+    # ---- the convective terms as the time stepper launches them: len(vec_in) lanes, one operator call (nlg_op_conv_lanes, nlg_op_conv_scalar)
+    def conv_lanes(self, base, vec_in, vec_out, adjoint=False):
+        s = len(vec_in)
+        assert len(vec_out) == s
+        check(self.lib.nlg_op_conv_lanes(self.h, base.h, s, (vp * s)(*[x.h for x in vec_in]), (vp * s)(*[x.h for x in vec_out]), int(bool(adjoint))))
+
+    def conv_scalar(self, base, vec_in, vec_out, adjoint=False):
+        s = len(vec_in)
+        assert len(vec_out) == s
+        check(self.lib.nlg_op_conv_scalar(self.h, base.h, s, (vp * s)(*[x.h for x in vec_in]), (vp * s)(*[x.h for x in vec_out]), int(bool(adjoint))))
+
     def close(self):
         if self.h:
             self.lib.nlg_mesh_destroy(self.h)
