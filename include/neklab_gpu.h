@@ -119,7 +119,8 @@ int nlg_mesh_create(nlg_ctx *ctx, const nlg_mesh_desc *desc, nlg_mesh **out);
 int nlg_mesh_destroy(nlg_mesh *mesh);
 int nlg_mesh_sizes(const nlg_mesh *mesh, int64_t *lvn, int64_t *lpn, int *dim, int *n);
 /* read back a derived array by name for verification: "bm1", "binvm1", "vmult", "jac", "bm2",
- * "g11".."g33" (Nek g1m1..g6m1 ordering by index pair), "rxm1"... (as "rst11".."rst33") */
+ * "g11".."g33" (Nek g1m1..g6m1 ordering by index pair), "rxm1"... (as "rst11".."rst33");
+ * 3-D: "slot_fg", "slot_xp" = the slot of each natural point of an element in the face-grouped / slab-permuted layout (lx1^3 values) */
 int nlg_mesh_get(const nlg_mesh *mesh, const char *name, double *out, int64_t count);
 /* *out = 1 if single-vector launches of the pressure operator (opgradt, opdiv) on this mesh take the matrix-pipe kernels: 3-D, lx1 = 8,
  * at least NLG_SMALL_E local elements, NLG_POP_MFMA not 0 */
@@ -588,6 +589,17 @@ int nlg_op_helmholtz_pcg(nlg_mesh *mesh, int nf, int nl, double h1, double h2, c
                          double *u_src, double *w_out, double *part, int part_cap, int *npart);
 int nlg_op_cdabdtp_pcg(nlg_mesh *mesh, int nl, const double *p, const double *z, const double *beta, const double *zmean, const double *done,
                        int fused, int ring, double sentinel, double *p_out, double *p_src, double *out, double *part, int part_cap, int *npart);
+/* The gather-scatter in the form the solvers call it, for tests against a reference: ONE call of the library's gather-scatter with
+ * (fields, nf, gates, layout, nl, lane stride, gate stride), under the conventions of the *_pcg entries above.  in and out are
+ * [nl][nf][points] in the natural element layout; done is [nl] (a lane with done != 0 is skipped) or NULL for no gate.
+ *   layout = 0 : natural;  1 : face-grouped (the intermediate fields of the pressure operator);  2 : slab-permuted (the velocity
+ *   solve).  The input is permuted into the layout on the way in (1: on the host, with the mesh's slot table; 2: by the kernel that
+ *   permutes the solver's right-hand side) and back on the way out.
+ * After the call the entry reads the whole slab and the gates back: a value outside the nf fields of a lane (the tail of a padded field,
+ * the gap between the lanes) that no longer equals `sentinel`, or a changed gate, is an error ("... were overwritten"), out untouched.
+ * Refused with a message, out untouched: nf outside 1..dim, nl outside 1..4, layout 1 or 2 on a mesh without those tables (2-D), a
+ * sentinel that is not finite (it is compared for equality). */
+int nlg_op_gs(nlg_mesh *mesh, int nf, int nl, int layout, const double *in, const double *done, double sentinel, double *out);
 /* The operator L itself in strong (pointwise) form, element-local: apply_L, apply_Lv, compute_LNS_conv, compute_LNS_laplacian and
  * compute_LNS_gradp of the reference (src/linops/neklab_linops.f90:24-28, :268-426) are this one call with other coefficients:
  *   u~_k  = mask_k in.v_k                                   (bcdirvc on read: `in` is not modified)

@@ -194,6 +194,7 @@ SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, c_int_p]),
     "nlg_op_cdabdtp_pcg": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double,
                                      c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, c_int_p]),
+    "nlg_op_gs": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.c_double, c_double_p]),
     "nlg_op_lns": (C.c_int, [vp, vp, vp, vp, C.c_double, C.c_int, c_double_p]),
     "nlg_lns_create": (C.c_int, [vp, vp, C.c_double, C.POINTER(vp)]),
     "nlg_lns_set_baseflow": (C.c_int, [vp, vp]),

@@ -4852,7 +4852,10 @@ int nlg_mesh_create(nlg_ctx *ctx, const nlg_mesh_desc *d, nlg_mesh **out) {
         if (m->ctx->distributed())   // halo_setup splits them by "holds a dof another rank shares"
             for (size_t gi = 0; gi + 1 < off.size(); ++gi) m->gs.h_groups.emplace_back(idx.begin() + off[gi], idx.begin() + off[gi + 1]);
         if (dim == 3 && !groups.empty()) {
-            // the same groups in face-grouped numbering, re-sorted by their first index
+            // the same groups in face-grouped numbering, re-sorted by their first index.  Contract (here and in the slab-permuted tables
+            // below): the MEMBERS of a group ascend in the layout's own index -- the summation order the comment above k_gs states, which
+            // makes a sum depend on the layout alone; tests/test_gpu_starmesh.py holds it bit for bit (nlg_mesh_get "slot_fg" / "slot_xp"
+            // give the layouts' indices).  The order of the GROUPS inside a class is free and is what the tuning below changes.
             std::vector<int> slot((size_t)m->np1);
             for (int p = 0; p < m->np1; ++p) slot[p] = fg_slot(n, p % n, (p / n) % n, p / (n * n));
             m->h_slot = slot;
@@ -5140,6 +5143,14 @@ int nlg_mesh_get(const nlg_mesh *m, const char *name, double *out, int64_t count
         NLG_TRY(sem_gs(mm, f, 1));
         NLG_HIP(hipMemcpyAsync(out, dg, sizeof(double) * (size_t)m->lvn, hipMemcpyDeviceToHost, m->ctx->stream));
         NLG_HIP(hipStreamSynchronize(m->ctx->stream));
+        return 0;
+    }
+    // "slot_fg" / "slot_xp": natural point of an element -> its slot in the face-grouped / slab-permuted layout (3-D; host tables)
+    if (strcmp(name, "slot_fg") == 0 || strcmp(name, "slot_xp") == 0) {
+        const std::vector<int> &slot = name[5] == 'f' ? m->h_slot : m->h_slot_xp;
+        NLG_CHECK(!slot.empty(), "nlg_mesh_get: this mesh has no table '%s'", name);
+        NLG_CHECK(count == (int64_t)slot.size(), "nlg_mesh_get: count %lld != length %lld of '%s'", (long long)count, (long long)slot.size(), name);
+        for (size_t p = 0; p < slot.size(); ++p) out[p] = (double)slot[p];
         return 0;
     }
     auto it = m->named.find(name);
@@ -5487,6 +5498,65 @@ int nlg_op_helmholtz_pcg(nlg_mesh *m, int nf, int nl, double h1, double h2, cons
     NLG_TRY(get(w_out, pw));
     NLG_TRY(slab_get(m, part, Pt.p, nl, 1, part_cap, ld, 0));
     NLG_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int nlg_op_gs(nlg_mesh *m, int nf, int nl, int layout, const double *in, const double *done, double sentinel, double *out) {
+    NLG_CHECK(m && in && out, "nlg_op_gs: bad arguments");
+    const int dim = m->dim;
+    NLG_CHECK(nf >= 1 && nf <= dim && nl >= 1 && nl <= kMaxLanes, "nlg_op_gs: nf = %d (1 to %d), nl = %d (1 to %d)", nf, dim, nl, kMaxLanes);
+    NLG_CHECK(layout >= LAYOUT_NAT && layout <= LAYOUT_XP, "nlg_op_gs: layout %d (0 natural, 1 face-grouped, 2 slab-permuted)", layout);
+    NLG_CHECK(layout != LAYOUT_FG || (dim == 3 && !m->h_slot.empty() && (m->gs.d_indices_fg || m->gs.ngroups == 0)),
+              "nlg_op_gs: this mesh has no face-grouped tables");
+    NLG_CHECK(layout != LAYOUT_XP || (dim == 3 && m->d_slot_xp && (m->gs.d_indices_xp || m->gs.ngroups == 0)),
+              "nlg_op_gs: this mesh has no slab-permuted tables");
+    NLG_CHECK(std::isfinite(sentinel), "nlg_op_gs: the sentinel must be finite");
+    hipStream_t st = m->ctx->stream;
+    const int64_t fs = m->lvs, n = m->lvn, np1 = m->np1;
+    const int64_t ld = round_up(nf * fs + kAlign, kAlign);   // a gap between the lanes, as the scalars of a lane leave one in the solver's slab
+    DevBuf<> F, T, S;
+    NLG_TRY(slab_new(m, F, nl * ld, sentinel));
+    if (layout == LAYOUT_XP) NLG_TRY(slab_new(m, T, nl * ld, sentinel));   // staging in the natural layout
+    std::vector<double> hs((size_t)(nl * ld), sentinel);
+    for (int v = 0; v < nl; ++v) hs[v * ld] = done ? done[v] : 0.0;
+    NLG_HIP(hipMalloc(&S.p, sizeof(double) * hs.size()));
+    NLG_HIP(hipMemcpyAsync(S.p, hs.data(), sizeof(double) * hs.size(), hipMemcpyHostToDevice, st));
+    double *pf[3], *pt[3];
+    for (int q = 0; q < 3; ++q) pf[q] = q < nf ? F.p + q * fs : nullptr, pt[q] = q < nf ? T.p + q * fs : nullptr;
+    std::vector<double> hp;   // the host array in the face-grouped layout
+    if (layout == LAYOUT_FG) {
+        hp.resize((size_t)nl * nf * n);
+        for (int64_t a = 0; a < (int64_t)nl * nf; ++a)
+            for (int64_t e = 0; e < m->E; ++e)
+                for (int64_t p = 0; p < np1; ++p) hp[a * n + e * np1 + m->h_slot[p]] = in[a * n + e * np1 + p];
+    }
+    NLG_TRY(slab_put(m, layout == LAYOUT_XP ? T.p : F.p, layout == LAYOUT_FG ? hp.data() : in, nl, nf, n, ld, fs));
+    if (layout == LAYOUT_XP) NLG_TRY(sem_to_xp(m, pt, pf, nf, nl, ld));
+    // ---- the call of the solvers
+    NLG_TRY(sem_gs(m, pf, nf, done ? S.p : nullptr, layout, nl, ld, ld));
+    // ---- output (out is written only once everything has run)
+    if (layout == LAYOUT_XP) NLG_TRY(sem_from_xp(m, pf, pt, nf, nl, ld));
+    std::vector<double> ho((size_t)nl * nf * n), hf((size_t)(nl * ld)), hg(hs.size());
+    NLG_TRY(slab_get(m, ho.data(), layout == LAYOUT_XP ? T.p : F.p, nl, nf, n, ld, fs));
+    // the whole slab of the call and the gates, as the gather-scatter left them: what lies outside the nf fields of a lane (the tail of a
+    // padded field, the gap between the lanes) must still hold the sentinel, the gates what they held
+    NLG_HIP(hipMemcpyAsync(hf.data(), F.p, sizeof(double) * hf.size(), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipMemcpyAsync(hg.data(), S.p, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, st));
+    NLG_HIP(hipStreamSynchronize(st));
+    int64_t stray = 0;
+    for (int64_t i = 0; i < nl * ld; ++i) {
+        const int64_t r = i % ld;
+        if (!(r < nf * fs && r % fs < n) && hf[i] != sentinel) ++stray;
+        if (hg[i] != hs[i]) ++stray;
+    }
+    NLG_CHECK(stray == 0, "nlg_op_gs: %lld values outside the fields of the call were overwritten", (long long)stray);
+    if (layout == LAYOUT_FG) {
+        for (int64_t a = 0; a < (int64_t)nl * nf; ++a)
+            for (int64_t e = 0; e < m->E; ++e)
+                for (int64_t p = 0; p < np1; ++p) out[a * n + e * np1 + p] = ho[a * n + e * np1 + m->h_slot[p]];
+    } else {
+        std::copy(ho.begin(), ho.end(), out);
+    }
     return 0;
 }
 

@@ -146,6 +146,18 @@ class Mesh:
         out["npart"] = npart.value
         return out
 
+    def gs(self, u, layout=0, done=None, sentinel=-7.25, out=None):
+        """The gather-scatter as the solvers call it (nlg_op_gs).  u: [nl][nf][lvn]; layout 0 natural, 1 face-grouped, 2 slab-permuted;
+        done: [nl] or None (no gate); out: the array to write (left untouched by a refused call)."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        nl, nf = u.shape[:2]
+        assert u.shape[2:] == (self.lvn,)
+        out = np.empty_like(u) if out is None else out
+        assert out.shape == u.shape and out.dtype == np.float64 and out.flags.c_contiguous
+        done = None if done is None else np.ascontiguousarray(np.broadcast_to(np.asarray(done, dtype=np.float64), (nl,)))
+        check(self.lib.nlg_op_gs(self.h, nf, nl, int(layout), dptr(u), None if done is None else dptr(done), float(sentinel), dptr(out)))
+        return out
+
     # ---- the convective terms as the time stepper launches them: len(vec_in) lanes, one operator call (nlg_op_conv_lanes, nlg_op_conv_scalar)
     def conv_lanes(self, base, vec_in, vec_out, adjoint=False):
         s = len(vec_in)

@@ -67,6 +67,73 @@ def run_cylinder(rank, world, segment, outdir, case):
     ctx.sync()
 
 
+def run_star(rank, world, segment, outdir, case):
+    """A mesh of irregular valence (tests/starmesh.py: a fan of 5 elements closed by a ring of 10, three layers), contiguous element
+    blocks per rank (halo_setup, the halo / rest split of the tables).  Two ranks: 23 + 22 elements, the cut runs through the fan
+    of the middle layer, so a 5-copy edge AND 10-copy vertices have members on both ranks.  Three ranks: 15 elements each, one whole
+    layer per rank: only the vertices and edges between layers (10, 6 and 8 copies) are split, no fan is cut.  On neither does a rank hold
+    more than 8 copies of one dof, so `star9` (k = 9, lx1 = 5, two layers, one per rank) adds that: the 18-copy centre vertex of the
+    middle plane has 9 copies on each rank (a shared group that takes a second round of eight in k_gs), and the 9-copy centre edge of a
+    layer lies inside one rank (the same among the groups summed while the exchange is under way)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from starmesh import star_mesh
+    from neklab_amd.mesh import partition_elements
+    nine = case.startswith("star9")
+    hm = star_mesh(9, 5, 2) if nine else star_mesh(5, 6, 3)
+    parts = partition_elements(hm.E, world)
+    if world > 1:
+        owner = np.empty(hm.E, dtype=np.int64)
+        for r, el in enumerate(parts):
+            owner[el] = r
+        g = hm.glo_num.ravel()
+        own = np.repeat(owner, hm.npts)
+        cnt = np.bincount(g)
+        labs = np.flatnonzero(cnt >= 5)
+        nranks = np.array([len(np.unique(own[g == lab])) for lab in labs])
+        local = np.array([np.sum((g == lab) & (own == rank)) for lab in labs])
+        big = cnt[labs]
+        if nine:
+            assert np.any((nranks > 1) & (local > 8)), "no shared dof has more than 8 copies on this rank"
+            assert np.any((nranks == 1) & (local > 8)), "no interior dof has more than 8 copies on this rank"
+        else:
+            assert np.any(nranks[big == 10] > 1), "no 10-copy vertex is shared between ranks"
+            if world == 2:
+                assert np.any(nranks[big == 5] > 1), "the centre fan of no layer is cut by the partition"
+    loc = hm.take(parts[rank])
+    ctx = host.Context(0)
+    if world > 1:
+        ctx.comm_init_shm(rank, world, segment)
+    gm = host.Mesh(ctx, loc)
+    bf = host.nek_dvector(gm)
+    U = [1.0 + 0.5 * np.sin(loc.x) * np.cos(loc.y), 0.3 * np.sin(2.0 * loc.z) * np.cos(loc.x), 0.2 * np.cos(loc.x + loc.y)]
+    for i in range(3):
+        bf.set_field(i, U[i] * loc.mask[i])
+    v, w = host.nek_dvector(gm), host.nek_dvector(gm)
+    v.rand(True, seed=11)
+    w.rand(False, seed=12)
+    scal = [v.dot(w), w.norm(), v.norm()]
+    A = host.exptA_linop(0.03, bf, re=40.0, dt=0.01, vtol=1e-13, ptol=1e-13, maxit_p=2000)
+    A.init()
+    out, outT = host.nek_dvector(gm), host.nek_dvector(gm)
+    A.matvec(v, out)
+    A.rmatvec(v, outT)
+    scal += [out.norm(), outT.norm(), out.dot(w)]
+    m = 4
+    B = host.KrylovBasis(gm, m + 1)
+    B[0].assign(v)
+    H = np.zeros((m + 1, m), order="F")
+    for k in range(m):
+        host.arnoldi_step(A, B, k, H)
+    fields = {"scal": np.array(scal), "H": H, "stats": np.array([A.stats()["p_iters"], A.stats()["v_iters"]], dtype=float)}
+    for i in range(3):
+        fields["out%d" % i] = out.get_field(i)
+        fields["outT%d" % i] = outT.get_field(i)
+        fields["v%d" % i] = v.get_field(i)
+    fields["outp"] = out.get_field(3)
+    np.savez(os.path.join(outdir, "%s_w%d_r%d.npz" % (case, world, rank)), **fields)
+    ctx.sync()
+
+
 def run_heat(rank, world, segment, outdir, case):
     """Boussinesq coupling (cfg.ifheat) and the nonlinear map on a slab partition: the scalar solve, the buoyancy and the
     scalar convection use the same halo / reductions as the fluid."""
@@ -154,6 +221,8 @@ def run(rank, world, segment, outdir, case):
         return run_heat(rank, world, segment, outdir, case)
     if case.startswith("cyl"):
         return run_cylinder(rank, world, segment, outdir, case)
+    if case.startswith("star"):
+        return run_star(rank, world, segment, outdir, case)
     base, _, mult = case.partition("@")          # "box3d@2" with world 1: the global mesh of the 2-rank run
     base = base.replace("+ovl", "")              # "+ovl": the same case with NLG_HALO_OVERLAP=1 in the environment (set by the test)
     base = base.replace("+sr", "")               # "+sr": NLG_PCG_SINGLE_RED=1, the one-reduction PCG of the velocity / scalar solves

@@ -70,11 +70,12 @@ def record(case, world, fields, hess, ritz):
 @pytest.mark.parametrize("case,world", [("box3d", 2), ("per3d", 2), ("box3d", 3), ("jac3d", 2), ("box2d", 2),
                                         ("agg3d", 2), ("cyl", 2), ("cyl", 3), ("heat", 2), ("proj", 2), ("proj", 3),
                                         ("blk3d", 2), ("blk3d", 3), ("box3d+ovl", 2), ("per3d+ovl", 2), ("cyl+ovl", 3), ("blk3d+ovl", 2),
-                                        ("box3d+sr", 2), ("heat+sr", 2), ("cyl+sr", 3)])
+                                        ("box3d+sr", 2), ("heat+sr", 2), ("cyl+sr", 3),
+                                        ("star3d", 2), ("star3d", 3), ("star3d+ovl", 2), ("star9", 2), ("star9+ovl", 2)])
 def test_partition_independent(tmp_path, case, world):
     parts = launch(world, tmp_path, case)
     # the single-rank run of the same global mesh (`world` times the elements in the last direction)
-    gcase = "%s@%d" % (case.replace("+ovl", "").replace("+sr", ""), world)       # (the cylinder case ignores the multiplier: the mesh is the global one)
+    gcase = "%s@%d" % (case.replace("+ovl", "").replace("+sr", ""), world)       # (the cylinder and star cases ignore the multiplier: the mesh is the global one)
     r = subprocess.run([sys.executable, WORKER, "0", "1", "", str(tmp_path), gcase], cwd=ROOT, capture_output=True,
                        text=True, timeout=420, env=case_env(gcase))
     assert r.returncode == 0 and "WORKER_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -51,6 +51,11 @@ def relerr(a, b):
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c["nel"])) + "_n%d" % c["n"])
 def test_mesh_geometry(gpu_ctx, case):
     hm, sem, gm = make(gpu_ctx, case)
+    check_geometry(sem, gm)
+
+
+def check_geometry(sem, gm):
+    """the arrays of the mesh set-up against the oracle (shared with test_gpu_starmesh.py)"""
     assert relerr(gm.get("bm1"), sem.bm1) < 1e-13
     assert relerr(gm.get("jac"), sem.jac) < 1e-13
     assert relerr(gm.get("vmult"), sem.vmult) < 1e-14
@@ -69,6 +74,11 @@ def test_mesh_geometry(gpu_ctx, case):
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c["nel"])) + "_n%d" % c["n"])
 def test_operators(gpu_ctx, case):
     hm, sem, gm = make(gpu_ctx, case)
+    check_operators(sem, gm)
+
+
+def check_operators(sem, gm):
+    """every operator of the hot path, one application against the oracle (shared with test_gpu_starmesh.py)"""
     rng = np.random.default_rng(1)
     ov, gv = rand_vec(sem, gm, rng)
     out = host.nek_dvector(gm)

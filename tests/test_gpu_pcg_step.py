@@ -59,6 +59,12 @@ def setup(ctx, kind, n):
             hm.mask[0] = box_mesh(nel, n, periodic=(True, True, False), deform=0.05).mask[0]
             hm.mask[2] = box_mesh(nel, n, periodic=(True, False, True), deform=0.05).mask[2]
             assert not same(hm.mask[0], hm.mask[1]) and not same(hm.mask[1], hm.mask[2]) and not same(hm.mask[0], hm.mask[2])
+        elif kind == "star":
+            # irregular valence (tests/starmesh.py): edges shared by 3 and 5 elements, vertices by 6 and 10, neighbours turned against
+            # one another; used by test_gpu_starmesh.py
+            from starmesh import star_mesh
+            hm = star_mesh(5, n, 2)
+            nel = hm.nel
         else:
             nel, per = (MESHES3 if kind in MESHES3 else MESHES2)[kind]
             hm = box_mesh(nel, n, periodic=per, deform=0.05)
