@@ -520,6 +520,54 @@ int nlg_dns_count(const nlg_dns *d, int64_t *nsamples);
 int nlg_dns_get_state(nlg_dns *d, nlg_vec *out);
 int nlg_dns_info(const nlg_dns *d, int64_t *istep, double *time, double *dt);
 int nlg_dns_destroy(nlg_dns *d);
+/* Wall forces, torque and heat flux on sets of element faces (Nek5000's `torque_calc` convention: symmetric 2 nu S . n, pressure and
+ * viscous parts apart; the drag, lift and Nusselt number of the reference's cylinder and temperature cases).
+ * A face is (global element id, face), face in the preprocessor's numbering 1 = s-, 2 = r+, 3 = s+, 4 = r-, 5 = t-, 6 = t+; it need not lie
+ * on the boundary.  An object is a set of faces; an element may carry several faces, in the same or in different objects.
+ * At face point q of a face normal to reference direction a on side sigma = +-1 the area-weighted outward normal is
+ *   N_q = sigma (J grad r_a)_q w_q,   w_q = the product of the GLL weights of the other dim - 1 directions.
+ * x_q is the face point, (grad u)_q the pointwise element-local gradient (D along every direction, metrics, division by J; not averaged
+ * across elements), p_q the element's pressure-mesh (Gauss) values carried to the face point by the tensor Lagrange interpolation
+ * GL -> GLL (it extrapolates along the normal), element-local: WITHOUT the direct-stiffness average of Nek5000's `mappr`, so that
+ * neither a gather-scatter nor a halo is needed.  No masks are applied.  Per object, summed over its faces and face points, with the
+ * object's centre c (0 by default):
+ *   Fp_i = sum p_q N_q,i               Fv_i = -nu sum_j (d_j u_i + d_i u_j)_q N_q,j
+ *   Tp   = sum (x_q - c) x (p_q N_q)   Tv   = the same with the viscous traction     (z component in 2-D, three components in 3-D)
+ *   Q    = sum (grad theta)_q . N_q    (0 for vectors without a scalar; times -conductivity it is the heat flux)
+ *   area = sum |N_q|                   (computed at creation)
+ * Sign: with the faces' outward normals pointing into the body, Fp + Fv is the force the fluid exerts on the body.  Coefficients are the
+ * caller's division, e.g. Cd = 2 (Fp_x + Fv_x) / (rho U^2 L).  Everything is linear in (u, p, theta): it applies to perturbations and
+ * modes as to flows; a complex mode passes its real and imaginary parts as two vectors.
+ * Output per (vector, object): NQ = 2 dim + 2 nt + 1 doubles Fp[dim], Fv[dim], Tp[nt], Tv[nt], Q; nt = 1 in 2-D, 3 in 3-D.
+ *   nlg_forces_geometry: pure host code, no GPU needed.  For the faces (elem_local[f], face[f]) of a mesh given by its GLL coordinates:
+ *     nds[nfaces][nfp][dim] = N_q, met[nfaces][nfp][dim * dim] = (d r_j / d x_i)_q at index j * dim + i, xc[nfaces][nfp][dim] = x_q - c,
+ *     area[nobj]; nfp = lx1^(dim-1) face points, the lower tangential direction fastest (nekio.face_nodes).  obj NULL: one object;
+ *     centre NULL: 0; any output may be NULL.  Returns 1 on a bad argument.
+ *   create: the face list is global and the same on every rank; a face belongs to the rank that holds its element.  Refused with a
+ *     message that names the argument: face outside 1..2 dim, an element id no rank holds, the same (element, face) twice, obj outside
+ *     0..nobj-1.  Several ranks: one all-reduce (holders and areas).
+ *   sample: s = 1..4 vectors in two launches -- k_wall_forces, one wave per (face, vector), and k_wall_forces_reduce, which sums the
+ *     faces of every (vector, object) in a fixed order (by global element id, then face) -- so the results repeat bit for bit and a vector
+ *     in a call of several equals its single call.  out[s][nobj][NQ], global sums (several ranks: one all-reduce).  Refused: s outside
+ *     1..4, vectors of another mesh or of differing nscal.
+ *   tractions: per face point of this rank's faces, in the order of the list: p[.][nfp] = p_q, trac[.][nfp][dim] = p_q N_q -
+ *     nu (grad u + grad u^T)_q N_q, nds[.][nfp][dim] = N_q (any may be NULL): the pressure and friction distribution along a wall.
+ *   destroy: refused while an nlg_dns samples the faces.
+ *   nlg_dns_set_forces (NULL detaches; the series starts again, as nlg_dns_set_probes): every sample also holds the nobj * NQ sums of the
+ *     state, with nu = 1 / Re of the run's operator: two more launches per step, no host synchronisation and no collective of their own.
+ *   nlg_dns_force_series: force[count][nobj][NQ] of the samples first .. first + count - 1. */
+int nlg_forces_geometry(int dim, int n, int64_t nel, const double *x, const double *y, const double *z, int64_t nfaces,
+                        const int64_t *elem_local, const int *face, const int *obj, int nobj, const double *centre, double *nds, double *met,
+                        double *xc, double *area);
+typedef struct nlg_forces nlg_forces;
+int nlg_forces_create(nlg_mesh *mesh, int nobj, int64_t nfaces, const int64_t *elem_gid, const int *face, const int *obj,
+                      const double *centre, nlg_forces **out);
+int nlg_forces_info(const nlg_forces *f, double *area, int64_t *nfaces_local);
+int nlg_forces_sample(nlg_forces *f, int s, const nlg_vec *const *vecs, double nu, double *out);
+int nlg_forces_tractions(nlg_forces *f, const nlg_vec *vec, double nu, double *p, double *trac, double *nds);
+int nlg_forces_destroy(nlg_forces *f);
+int nlg_dns_set_forces(nlg_dns *d, nlg_forces *f);
+int nlg_dns_force_series(nlg_dns *d, int64_t first, int64_t count, double *force);
 /* %tau read/written by the driver (src/neklab_analysis.f90:84; apply_exptA neklab_linops.f90:252) */
 int nlg_linop_set_tau(nlg_linop *op, double tau);
 int nlg_linop_get_info(const nlg_linop *op, double *tau, double *dt, int *nsteps, double *cfl);

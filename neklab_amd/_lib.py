@@ -179,6 +179,15 @@ SIGNATURES = {
     "nlg_dns_get_state": (C.c_int, [vp, vp]),
     "nlg_dns_info": (C.c_int, [vp, c_int64_p, c_double_p, c_double_p]),
     "nlg_dns_destroy": (C.c_int, [vp]),
+    "nlg_forces_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64, c_int64_p, c_int_p, c_int_p, C.c_int,
+                                      c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "nlg_forces_create": (C.c_int, [vp, C.c_int, C.c_int64, c_int64_p, c_int_p, c_int_p, c_double_p, C.POINTER(vp)]),
+    "nlg_forces_info": (C.c_int, [vp, c_double_p, c_int64_p]),
+    "nlg_forces_sample": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.c_double, c_double_p]),
+    "nlg_forces_tractions": (C.c_int, [vp, vp, C.c_double, c_double_p, c_double_p, c_double_p]),
+    "nlg_forces_destroy": (C.c_int, [vp]),
+    "nlg_dns_set_forces": (C.c_int, [vp, vp]),
+    "nlg_dns_force_series": (C.c_int, [vp, C.c_int64, C.c_int64, c_double_p]),
     "nlg_linop_get_info": (C.c_int, [vp, c_double_p, c_double_p, c_int_p, c_double_p]),
     "nlg_linop_get_stats": (C.c_int, [vp, c_int64_p, c_int64_p, c_int64_p, c_int64_p]),
     "nlg_op_helmholtz": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int]),

@@ -16,8 +16,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libneklab_gpu.so")
-SOURCES = ["ctx.hip", "shm_transport.hip", "vec.hip", "sem.hip", "halo.hip", "pprec.hip", "pprec_host.cpp", "lns.hip", "lns_strong.hip", "lns_sens.hip", "probe.hip", "probe_host.cpp", "krylov.hip", "dense_eig.cpp"]
-HEADERS = [os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "fg_slot.h"), os.path.join(CSRC, "pprec_host.h"), os.path.join(CSRC, "probe_host.h"), os.path.join(CSRC, "lns_elem.h"), os.path.join(ROOT, "include", "neklab_gpu.h")]
+SOURCES = ["ctx.hip", "shm_transport.hip", "vec.hip", "sem.hip", "halo.hip", "pprec.hip", "pprec_host.cpp", "lns.hip", "lns_strong.hip", "lns_sens.hip", "probe.hip", "probe_host.cpp", "forces.hip", "forces_host.cpp", "krylov.hip", "dense_eig.cpp"]
+HEADERS = [os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "fg_slot.h"), os.path.join(CSRC, "pprec_host.h"), os.path.join(CSRC, "probe_host.h"), os.path.join(CSRC, "forces_host.h"), os.path.join(CSRC, "lns_elem.h"), os.path.join(ROOT, "include", "neklab_gpu.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-ffp-contract=on",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 

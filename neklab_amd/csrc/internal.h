@@ -337,7 +337,33 @@ struct nlg_probes {
     double *d_out = nullptr;              // [kMaxLanes][npts][kMaxProbeFields]: the result of nlg_probes_sample before it goes to the host
 };
 
+// Wall forces (forces.hip): the listed faces this rank holds, sorted by global element id, then face -- the order every sum runs in --
+// with their precomputed geometry (forces_host.h) and, per object, the positions of its faces in that order.
+struct nlg_forces {
+    nlg_mesh *mesh = nullptr;
+    int nobj = 0, nq = 0, nfp = 0;        // objects, quantities per object (Fp, Fv, Tp, Tv, Q), points per face
+    int64_t nfaces = 0, nfl = 0;          // faces of the global list, faces on this rank's elements
+    int attached = 0;                     // nlg_dns objects that sample these faces (nlg_forces_destroy refuses while > 0)
+    std::vector<double> area;             // [nobj], global
+    std::vector<int64_t> order;           // [nfl] sorted position -> position among this rank's faces in creation order
+    int *d_elem = nullptr, *d_face = nullptr;                        // [nfl] local element, face
+    double *d_nds = nullptr, *d_met = nullptr, *d_xc = nullptr;      // [nfl][nfp][dim], [dim * dim], [dim]
+    int *d_ooff = nullptr, *d_oidx = nullptr;                        // [nobj + 1], [nfl]: the faces of every object, ascending
+    double *d_M = nullptr;                // [n][n2] Gauss points -> GLL points
+    double *d_part = nullptr;             // [kMaxLanes][nfl][nq] the faces' partial sums
+    double *d_out = nullptr;              // [kMaxLanes][nobj][nq] the result of nlg_forces_sample before it goes to the host
+    double *d_trac = nullptr;             // [nfl][nfp][1 + 2 dim] p, traction, N of nlg_forces_tractions (lazy)
+};
+
 namespace nlg {
+
+// ---- forces.hip ----
+// the fields of s lanes: velocity, pressure (Gauss mesh), temperature (null: none)
+struct ForceFields {
+    const double *u[kMaxLanes][3], *p[kMaxLanes], *th[kMaxLanes];
+};
+// out[v * ldo + o * nq + k] = this rank's share of quantity k of object o for the lanes v < s: two launches, nothing waits
+int forces_sample(nlg_forces *f, int s, const ForceFields &F, double nu, double *out, int64_t ldo);
 
 // ---- probe.hip ----
 constexpr int kMaxProbeFields = 5;   // velocity (dim), pressure, temperature

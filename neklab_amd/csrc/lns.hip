@@ -1217,19 +1217,21 @@ struct nlg_otd {
     double time = 0.0;
 };
 // A DNS run: lane 0 of the operator's slab advanced by the nonlinear step as ONE continuous run, sampled after every step into a ring
-// on the device -- slot k = [npts][nf] history-point values, then dist2 = |u - u_ref|^2 -- that is copied to the host series when it
-// fills and when the series is read.
+// on the device -- slot k = [npts][nf] history-point values, then dist2 = |u - u_ref|^2, then the [nobj][NQ] wall forces if any are
+// attached -- that is copied to the host series when it fills and when the series is read.
 struct nlg_dns {
     nlg_linop *op = nullptr;
     nlg_dns_opts o;
     nlg_probes *probes = nullptr;
     nlg_vec *ref = nullptr;
+    nlg_forces *forces = nullptr;
     int nf = 0;               // fields per point: velocity, pressure, temperature if carried
-    int64_t slot_len = 1;     // npts * nf + 1
+    int64_t np = 0, nforce = 0;   // npts * nf history-point values, nobj * NQ force values
+    int64_t slot_len = 1;     // np + 1 + nforce
     int fill = 0;             // slots of the ring in use
     bool started = false;     // sample 0 of the series is taken
     double *ring = nullptr, *part = nullptr;
-    std::vector<double> time, probe, dist2;   // the series on the host
+    std::vector<double> time, probe, dist2, force;   // the series on the host
 };
 // every entry point that would overwrite the lanes refuses while an OTD or a DNS run lives on the operator
 #define NLG_NO_OTD(op, who)                                                                                                                           \
@@ -3409,7 +3411,7 @@ static int dns_flush(nlg_dns *d) {
     if (d->fill == 0) return 0;
     nlg_mesh *m = d->op->mesh;
     hipStream_t st = m->ctx->stream;
-    const int64_t cnt = d->fill * d->slot_len, np = d->slot_len - 1;
+    const int64_t cnt = d->fill * d->slot_len, np = d->np;
     NLG_CHECK(cnt < ((int64_t)1 << 31), "nlg_dns: a ring of %lld values is too long for one all-reduce; use a smaller chunk", (long long)cnt);
     NLG_TRY(allreduce_sum(m->ctx, d->ring, (int)cnt));
     std::vector<double> h((size_t)cnt);
@@ -3420,12 +3422,13 @@ static int dns_flush(nlg_dns *d) {
         const double *s = h.data() + k * d->slot_len;
         d->probe.insert(d->probe.end(), s, s + np);
         d->dist2.push_back(s[np]);
+        d->force.insert(d->force.end(), s + np + 1, s + np + 1 + d->nforce);
     }
     d->fill = 0;
     return 0;
 }
 
-// one sample of the state as it stands: at most three launches, nothing waits for the device
+// one sample of the state as it stands: at most three launches, two more with wall forces; nothing waits for the device
 static int dns_sample(nlg_dns *d) {
     nlg_linop *op = d->op;
     nlg_mesh *m = op->mesh;
@@ -3446,7 +3449,15 @@ static int dns_sample(nlg_dns *d) {
         const double *u[4] = {}, *r[4] = {};
         for (int c = 0; c < dim; ++c) u[c] = op->ubuf[0][c], r[c] = d->ref->vel(c);
         if (op->cfg.ifheat) u[dim] = op->tbuf[0], r[dim] = d->ref->theta(0);
-        NLG_TRY(recur_dist2(m, dim + (op->cfg.ifheat ? 1 : 0), u, r, d->part, slot + d->slot_len - 1));
+        NLG_TRY(recur_dist2(m, dim + (op->cfg.ifheat ? 1 : 0), u, r, d->part, slot + d->np));
+    }
+    if (d->forces) {
+        ForceFields F;
+        memset(&F, 0, sizeof(F));
+        for (int c = 0; c < dim; ++c) F.u[0][c] = op->ubuf[0][c];
+        F.p[0] = op->p;
+        if (op->cfg.ifheat) F.th[0] = op->tbuf[0];
+        NLG_TRY(forces_sample(d->forces, 1, F, 1.0 / op->cfg.re, slot + d->np + 1, d->nforce));
     }
     d->time.push_back(op->istep * op->dt);
     d->fill += 1;
@@ -3459,12 +3470,14 @@ static int dns_restart_series(nlg_dns *d) {
     NLG_HIP(hipStreamSynchronize(st));
     (void)hipFree(d->ring);
     d->ring = nullptr;
-    d->slot_len = (d->probes ? d->probes->npts * d->nf : 0) + 1;
+    d->np = d->probes ? d->probes->npts * d->nf : 0;
+    d->nforce = d->forces ? (int64_t)d->forces->nobj * d->forces->nq : 0;
+    d->slot_len = d->np + 1 + d->nforce;
     NLG_HIP(hipMalloc(&d->ring, sizeof(double) * (size_t)(d->o.chunk * d->slot_len)));
     NLG_HIP(hipMemsetAsync(d->ring, 0, sizeof(double) * (size_t)(d->o.chunk * d->slot_len), st));
     d->fill = 0;
     d->started = false;
-    d->time.clear(), d->probe.clear(), d->dist2.clear();
+    d->time.clear(), d->probe.clear(), d->dist2.clear(), d->force.clear();
     return 0;
 }
 
@@ -3475,6 +3488,7 @@ int nlg_dns_destroy(nlg_dns *d) {
     const bool live = op && op->dns == d;
     if (live) op->dns = nullptr;
     if (d->probes) d->probes->attached -= 1;
+    if (d->forces) d->forces->attached -= 1;
     if (d->ref) nlg_vec_destroy(d->ref);
     (void)hipFree(d->ring);
     (void)hipFree(d->part);
@@ -3531,6 +3545,15 @@ int nlg_dns_set_probes(nlg_dns *d, nlg_probes *p) {
     return dns_restart_series(d);
 }
 
+int nlg_dns_set_forces(nlg_dns *d, nlg_forces *f) {
+    NLG_CHECK(d, "nlg_dns_set_forces: NULL");
+    NLG_CHECK(!f || f->mesh == d->op->mesh, "nlg_dns_set_forces: the faces were listed on a different mesh");
+    if (d->forces) d->forces->attached -= 1;
+    d->forces = f;
+    if (f) f->attached += 1;
+    return dns_restart_series(d);
+}
+
 int nlg_dns_set_reference(nlg_dns *d, const nlg_vec *ref) {
     NLG_CHECK(d, "nlg_dns_set_reference: NULL");
     nlg_linop *op = d->op;
@@ -3574,12 +3597,23 @@ int nlg_dns_series(nlg_dns *d, int64_t first, int64_t count, double *time, doubl
     NLG_TRY(dns_flush(d));
     NLG_CHECK(first >= 0 && count >= 0 && first + count <= (int64_t)d->time.size(), "nlg_dns_series: samples %lld .. %lld out of range (%lld taken)",
               (long long)first, (long long)(first + count), (long long)d->time.size());
-    const int64_t np = d->slot_len - 1;
+    const int64_t np = d->np;
     for (int64_t k = 0; k < count; ++k) {
         if (time) time[k] = d->time[first + k];
         if (dist) dist[k] = d->ref ? std::sqrt(std::max(d->dist2[first + k], 0.0)) : 0.0;
     }
     if (probe && np > 0) memcpy(probe, d->probe.data() + first * np, sizeof(double) * (size_t)(count * np));
+    return 0;
+}
+
+int nlg_dns_force_series(nlg_dns *d, int64_t first, int64_t count, double *force) {
+    NLG_CHECK(d && force, "nlg_dns_force_series: NULL argument");
+    NLG_CHECK(d->forces, "nlg_dns_force_series: no wall forces are attached (nlg_dns_set_forces)");
+    NLG_TRY(nlg_dns_advance(d, 0));
+    NLG_TRY(dns_flush(d));
+    NLG_CHECK(first >= 0 && count >= 0 && first + count <= (int64_t)d->time.size(), "nlg_dns_force_series: samples %lld .. %lld out of range (%lld taken)",
+              (long long)first, (long long)(first + count), (long long)d->time.size());
+    if (count > 0) memcpy(force, d->force.data() + first * d->nforce, sizeof(double) * (size_t)(count * d->nforce));
     return 0;
 }
 

@@ -496,6 +496,51 @@ module neklab_gpu_capi
          type(c_ptr), value :: dns
          integer(c_int) :: rc
       end function
+      ! wall forces, torque and heat flux (include/neklab_gpu.h, nlg_forces_*)
+      function c_forces_create(mesh, nobj, nfaces, elem_gid, face, obj, centre, f) bind(C, name="nlg_forces_create") result(rc)
+         import c_int, c_int64_t, c_ptr
+         type(c_ptr), value :: mesh
+         integer(c_int), value :: nobj
+         integer(c_int64_t), value :: nfaces
+         integer(c_int64_t), intent(in) :: elem_gid(*)      ! 0-based, as the C ABI has them
+         integer(c_int), intent(in) :: face(*), obj(*)
+         type(c_ptr), value :: centre                       ! address of centre(ldim, nobj), or c_null_ptr
+         type(c_ptr), intent(out) :: f
+         integer(c_int) :: rc
+      end function
+      function c_forces_info(f, area, nfaces_local) bind(C, name="nlg_forces_info") result(rc)
+         import c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: f
+         real(c_double), intent(out) :: area(*)
+         integer(c_int64_t), intent(out) :: nfaces_local
+         integer(c_int) :: rc
+      end function
+      function c_forces_sample(f, s, vecs, nu, out) bind(C, name="nlg_forces_sample") result(rc)
+         import c_int, c_double, c_ptr
+         type(c_ptr), value :: f
+         integer(c_int), value :: s
+         type(c_ptr), value :: vecs           ! address of an array of s vector handles
+         real(c_double), value :: nu
+         real(c_double), intent(out) :: out(*)
+         integer(c_int) :: rc
+      end function
+      function c_forces_destroy(f) bind(C, name="nlg_forces_destroy") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: f
+         integer(c_int) :: rc
+      end function
+      function c_dns_set_forces(dns, f) bind(C, name="nlg_dns_set_forces") result(rc)
+         import c_int, c_ptr
+         type(c_ptr), value :: dns, f         ! f c_null_ptr: detach
+         integer(c_int) :: rc
+      end function
+      function c_dns_force_series(dns, first, count, force) bind(C, name="nlg_dns_force_series") result(rc)
+         import c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: dns
+         integer(c_int64_t), value :: first, count
+         real(c_double), intent(out) :: force(*)
+         integer(c_int) :: rc
+      end function
       ! the operator L itself in strong form (include/neklab_gpu.h, nlg_lns_*)
       function c_lns_create(mesh, baseflow, re, lns) bind(C, name="nlg_lns_create") result(rc)
          import c_int, c_ptr, c_double

@@ -88,6 +88,22 @@ module neklab_systems
    integer, save, public :: upo_fixed_nsteps = 0, upo_gmres_kdim = 30
    public :: gmres_upo
 
+   !> Forces, torque and heat flux on sets of element faces (include/neklab_gpu.h, nlg_forces_*): drag and lift of the reference's
+   !! cylinder cases, the Nusselt number of its temperature cases.  init: elem(:) global element ids, 1-BASED as Nek5000's lglel, face(:)
+   !! in the preprocessor's numbering, obj(:) in 1..nobj, centres(ldim, nobj) optional.  sample: out(nq, nobj, size(vecs)) in the order
+   !! Fp(ldim), Fv(ldim), Tp(nt), Tv(nt), Q; coefficients are the caller's division, Cd = 2 (Fp_x + Fv_x) / (rho U^2 L).
+   type, public :: nek_wall_forces
+      integer :: nobj = 0, nq = 0
+      real(dp), allocatable :: area(:)
+      type(c_ptr), private :: h = c_null_ptr
+      integer(c_intptr_t), private :: owner = 0
+   contains
+      procedure, pass(self), public :: init => wf_init
+      procedure, pass(self), public :: sample => wf_sample
+      procedure, pass(self), public :: finalize => wf_close
+      final :: finalize_wf
+   end type
+
    !> A nonlinear run with history points and a recurrence monitor (include/neklab_gpu.h, nlg_dns_*): what the reference's case
    !! examples/cylinder/dns/Re180 does in its userchk with `call hpts()` and rnorm = |u(t) - u_ref|.  A plain type, not a LightKrylov
    !! object.  init(X0): the options of nek_case (dt > 0: that step; else the CFL rule at X0 with cfl_limit = 0.4), the step is then fixed.
@@ -95,13 +111,15 @@ module neklab_systems
       integer :: chunk = 256                                 ! ring length in steps
       type(c_ptr), private :: h = c_null_ptr, hop = c_null_ptr, hp = c_null_ptr
       integer(c_intptr_t), private :: owner = 0              ! the object that created the handles (a bitwise copy does not own them)
-      integer, private :: npts = 0, nf = 0
+      integer, private :: npts = 0, nf = 0, nobj = 0, nq = 0
       real(dp), allocatable, private :: xyz(:, :)
    contains
       procedure, pass(self), public :: init => dns_init
       procedure, pass(self), public :: advance => dns_advance
       procedure, pass(self), public :: set_history_points => dns_set_history_points
       procedure, pass(self), public :: set_reference => dns_set_reference
+      procedure, pass(self), public :: set_wall_forces => dns_set_wall_forces
+      procedure, pass(self), public :: force_series => dns_force_series
       procedure, pass(self), public :: series => dns_series
       procedure, pass(self), public :: nsamples => dns_nsamples
       procedure, pass(self), public :: state => dns_state
@@ -459,6 +477,74 @@ contains
       info = 0
    end subroutine
 
+   !---- nek_wall_forces ----------------------------------------------------------------------------------------------
+   subroutine wf_close(self)
+      class(nek_wall_forces), intent(inout) :: self
+      if (self%owner == loc(self) .and. c_associated(self%h)) then
+         call nlg_check(c_forces_destroy(self%h), 'nek_wall_forces finalize')      ! refused while a nek_dns samples the faces
+      end if
+      self%h = c_null_ptr; self%owner = 0; self%nobj = 0
+   end subroutine
+
+   subroutine finalize_wf(self)
+      type(nek_wall_forces), intent(inout) :: self
+      integer(c_int) :: rc
+      if (self%owner == loc(self) .and. c_associated(self%h)) rc = c_forces_destroy(self%h)
+      self%h = c_null_ptr; self%owner = 0
+   end subroutine
+
+   subroutine wf_init(self, elem, face, obj, nobj, centres)
+      class(nek_wall_forces), intent(inout) :: self
+      integer, intent(in) :: elem(:), face(:), obj(:), nobj
+      real(dp), target, intent(in), optional :: centres(:, :)
+      integer(c_int64_t), allocatable :: e0(:)
+      integer(c_int), allocatable :: f(:), o0(:)
+      integer(c_int64_t) :: nl
+      type(c_ptr) :: c
+      call wf_close(self)
+      if (size(face) /= size(elem) .or. size(obj) /= size(elem)) then
+         write (*, '(A)') 'ERROR in '//this_module//': nek_wall_forces init: elem, face and obj differ in length'
+         error stop 1
+      end if
+      e0 = int(elem, c_int64_t) - 1_c_int64_t
+      f = int(face, c_int)
+      o0 = int(obj, c_int) - 1_c_int
+      c = c_null_ptr
+      if (present(centres)) then
+         if (size(centres, 1) /= nek_ldim .or. size(centres, 2) /= nobj) then
+            write (*, '(A)') 'ERROR in '//this_module//': nek_wall_forces init: centres must be (ldim, nobj)'
+            error stop 1
+         end if
+         c = c_loc(centres)
+      end if
+      call nlg_check(c_forces_create(nlg_mesh, int(nobj, c_int), int(size(elem), c_int64_t), e0, f, o0, c, self%h), 'nek_wall_forces init')
+      self%owner = loc(self)
+      self%nobj = nobj
+      self%nq = 2*nek_ldim + 2*merge(3, 1, nek_ldim == 3) + 1
+      if (allocated(self%area)) deallocate (self%area)
+      allocate (self%area(nobj))
+      call nlg_check(c_forces_info(self%h, self%area, nl), 'nek_wall_forces init')
+   end subroutine
+
+   !> out(nq, nobj, size(vecs)) for 1 to 4 vectors in one call: global sums
+   subroutine wf_sample(self, vecs, nu, out)
+      class(nek_wall_forces), intent(in) :: self
+      type(nek_dvector), intent(in) :: vecs(:)
+      real(dp), intent(in) :: nu
+      real(dp), allocatable, intent(out) :: out(:, :, :)
+      type(c_ptr), target :: hs(max(size(vecs), 1))
+      integer :: v
+      if (.not. c_associated(self%h) .or. self%owner /= loc(self)) then
+         write (*, '(A)') 'ERROR in '//this_module//': nek_wall_forces%init() has not been called on this object'
+         error stop 1
+      end if
+      do v = 1, size(vecs)
+         hs(v) = nek_dvector_handle(vecs(v))
+      end do
+      allocate (out(self%nq, self%nobj, size(vecs)))
+      call nlg_check(c_forces_sample(self%h, int(size(vecs), c_int), c_loc(hs), nu, out), 'nek_wall_forces sample')
+   end subroutine
+
    !---- nek_dns ------------------------------------------------------------------------------------------------------
    function dns_handle(self) result(h)
       class(nek_dns), intent(in) :: self
@@ -478,7 +564,7 @@ contains
          if (c_associated(self%hp)) rc = c_probes_destroy(self%hp)
          if (c_associated(self%hop)) rc = c_linop_destroy(self%hop)
       end if
-      self%h = c_null_ptr; self%hop = c_null_ptr; self%hp = c_null_ptr; self%owner = 0; self%npts = 0
+      self%h = c_null_ptr; self%hop = c_null_ptr; self%hp = c_null_ptr; self%owner = 0; self%npts = 0; self%nobj = 0; self%nq = 0
    end subroutine
 
    subroutine finalize_dns(self)
@@ -539,6 +625,30 @@ contains
       else
          call nlg_check(c_dns_set_reference(dns_handle(self), c_null_ptr), 'nek_dns set_reference')
       end if
+   end subroutine
+
+   !> every sample also holds wf%sample(state, 1 / Re); without wf: detach.  The series starts again from the state as it stands.
+   !! wf must outlive its use: its finalize is refused while it is attached.
+   subroutine dns_set_wall_forces(self, wf)
+      class(nek_dns), intent(inout) :: self
+      type(nek_wall_forces), intent(in), optional :: wf
+      if (present(wf)) then
+         call nlg_check(c_dns_set_forces(dns_handle(self), wf%h), 'nek_dns set_wall_forces')
+         self%nobj = wf%nobj; self%nq = wf%nq
+      else
+         call nlg_check(c_dns_set_forces(dns_handle(self), c_null_ptr), 'nek_dns set_wall_forces')
+         self%nobj = 0; self%nq = 0
+      end if
+   end subroutine
+
+   !> force(nq, nobj, nsamples) of the attached wall forces: (re)allocated
+   subroutine dns_force_series(self, force)
+      class(nek_dns), intent(inout) :: self
+      real(dp), allocatable, intent(out) :: force(:, :, :)
+      integer :: n
+      n = dns_nsamples(self)
+      allocate (force(self%nq, self%nobj, n))
+      call nlg_check(c_dns_force_series(dns_handle(self), 0_c_int64_t, int(n, c_int64_t), force), 'nek_dns force_series')
    end subroutine
 
    function dns_nsamples(self) result(n)

@@ -2157,6 +2157,107 @@ class history_points:
             pass
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Wall forces, torque and heat flux on sets of element faces (nlg_forces_*): drag, lift and Strouhal number of the reference's cylinder
+# cases, the Nusselt number of its temperature cases.  Coefficients are the caller's division: Cd = 2 Fx / (rho U^2 L) with
+# Fx = Fp[0] + Fv[0], Cl the same with Fy; the heat flux is -conductivity * Q.
+def faces_from_bcs(bcs, tags=("W",), select=None):
+    """[(elem_gid 0-based, face)] of the boundary faces of nekio.read_re2_bcs (its third return value) that carry one of `tags`;
+    select(elem_gid, face) -> bool picks among them (e.g. the faces of one body)."""
+    out = [(int(e) - 1, int(f)) for e, f, t in bcs if str(t) in tags]
+    return [ef for ef in out if select is None or select(*ef)]
+
+
+def faces_from_mask(hostmesh):
+    """[(elem_gid, face)] of the faces of a host mesh on which every velocity mask is 0: the walls of a box mesh."""
+    from .nekio import face_nodes
+    n, dim, E = hostmesh.n, hostmesh.dim, hostmesh.E
+    m = np.max(np.stack([np.asarray(a).reshape(E, -1) for a in hostmesh.mask]), axis=0)
+    gid = np.arange(E) if hostmesh.elem_gid is None else hostmesh.elem_gid
+    return [(int(gid[e]), f) for e in range(E) for f in range(1, 2 * dim + 1) if not m[e, face_nodes(n, dim, f)].any()]
+
+
+def forces_geometry(hostmesh, faces, obj=None, nobj: int = 1, centres=None):
+    """nlg_forces_geometry on a host mesh (anything with dim, n, x, y, z): pure host code.  faces = [(LOCAL element, face)].
+    -> dict(nds [nf, nfp, dim], met [nf, nfp, dim, dim] (d r_j / d x_i at [j, i]), xc [nf, nfp, dim], area [nobj])"""
+    lib = _lib.load()
+    dim, n = hostmesh.dim, hostmesh.n
+    x, y = np.ascontiguousarray(hostmesh.x, dtype=np.float64), np.ascontiguousarray(hostmesh.y, dtype=np.float64)
+    z = np.ascontiguousarray(hostmesh.z, dtype=np.float64) if dim == 3 else None
+    el = np.ascontiguousarray([e for e, _ in faces], dtype=np.int64)
+    fc = np.ascontiguousarray([f for _, f in faces], dtype=np.int32)
+    ob = None if obj is None else np.ascontiguousarray(obj, dtype=np.int32)
+    c = None if centres is None else np.ascontiguousarray(np.asarray(centres, dtype=np.float64).reshape(nobj, dim))
+    nf, nfp = len(faces), n ** (dim - 1)
+    nds, met, xc, area = np.zeros((nf, nfp, dim)), np.zeros((nf, nfp, dim, dim)), np.zeros((nf, nfp, dim)), np.zeros(nobj)
+    rc = lib.nlg_forces_geometry(dim, n, x.shape[0], dptr(x), dptr(y), None if z is None else dptr(z), nf, el.ctypes.data_as(_lib.c_int64_p),
+                                 fc.ctypes.data_as(_lib.c_int_p), None if ob is None else ob.ctypes.data_as(_lib.c_int_p), int(nobj),
+                                 None if c is None else dptr(c), dptr(nds), dptr(met), dptr(xc), dptr(area))
+    if rc != 0:
+        raise NlgError("nlg_forces_geometry: bad argument")
+    return {"nds": nds, "met": met, "xc": xc, "area": area}
+
+
+class wall_forces:
+    """Forces, torque and heat flux on objects = list of lists of (elem_gid, face): see include/neklab_gpu.h (nlg_forces_*).  `area` is
+    the objects' area (global); `local` the positions in the flattened list of the faces this rank holds, the rows of tractions()."""
+
+    def __init__(self, mesh: Mesh, objects, centres=None):
+        self.mesh, self.lib = mesh, mesh.lib
+        self.nobj, self.dim = len(objects), mesh.dim
+        self.faces = [(int(e), int(f)) for faces in objects for e, f in faces]
+        obj = np.ascontiguousarray([o for o, faces in enumerate(objects) for _ in faces], dtype=np.int32)
+        el = np.ascontiguousarray([e for e, _ in self.faces], dtype=np.int64)
+        fc = np.ascontiguousarray([f for _, f in self.faces], dtype=np.int32)
+        c = None if centres is None else np.ascontiguousarray(np.asarray(centres, dtype=np.float64).reshape(self.nobj, self.dim))
+        self.nq = 2 * self.dim + 2 * (3 if self.dim == 3 else 1) + 1
+        h = vp()
+        self.h = None
+        check(self.lib.nlg_forces_create(mesh.h, self.nobj, len(self.faces), el.ctypes.data_as(_lib.c_int64_p), fc.ctypes.data_as(_lib.c_int_p),
+                                         obj.ctypes.data_as(_lib.c_int_p), None if c is None else dptr(c), C.byref(h)))
+        self.h = h
+        self.area = np.zeros(self.nobj)
+        nl = C.c_int64()
+        check(self.lib.nlg_forces_info(h, dptr(self.area), C.byref(nl)))
+        held = set(int(g) for g in (np.arange(mesh.host.E) if mesh.host.elem_gid is None else mesh.host.elem_gid))
+        self.local = [q for q, (e, _) in enumerate(self.faces) if e in held]
+        assert len(self.local) == nl.value
+
+    def sample(self, vecs, nu: float) -> np.ndarray:
+        """[len(vecs)][nobj][NQ] (a single vector: [nobj][NQ]) in the order Fp[dim], Fv[dim], Tp[nt], Tv[nt], Q; global sums."""
+        single = isinstance(vecs, nek_dvector)
+        vecs = [vecs] if single else list(vecs)
+        out = np.zeros((len(vecs), self.nobj, self.nq))
+        arr = (vp * max(len(vecs), 1))(*[v.h for v in vecs])
+        check(self.lib.nlg_forces_sample(self.h, len(vecs), arr, float(nu), dptr(out)))
+        return out[0] if single else out
+
+    def parts(self, out) -> dict:
+        """the named parts of sample()'s last axis"""
+        d, nt = self.dim, (3 if self.dim == 3 else 1)
+        out = np.asarray(out)
+        return {"Fp": out[..., :d], "Fv": out[..., d:2 * d], "Tp": out[..., 2 * d:2 * d + nt], "Tv": out[..., 2 * d + nt:2 * d + 2 * nt], "Q": out[..., -1]}
+
+    def tractions(self, vec: nek_dvector, nu: float) -> dict:
+        """Per face point of this rank's faces (rows = self.local): p [nl, nfp], trac [nl, nfp, dim] = p N - nu (grad u + grad u^T) N,
+        nds [nl, nfp, dim] = N.  Cp and Cf along a wall follow by division by |N| and the dynamic pressure."""
+        nl, nfp, d = len(self.local), self.mesh.host.n ** (self.dim - 1), self.dim
+        p, t, nds = np.zeros((nl, nfp)), np.zeros((nl, nfp, d)), np.zeros((nl, nfp, d))
+        check(self.lib.nlg_forces_tractions(self.h, vec.h, float(nu), dptr(p), dptr(t), dptr(nds)))
+        return {"p": p, "trac": t, "nds": nds}
+
+    def close(self):
+        if self.h:
+            check(self.lib.nlg_forces_destroy(self.h))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class nek_dns:
     """A nonlinear run from X0 with a fixed time step (`dt`, or the CFL rule at X0 with cfl_limit, 0.4 by default), sampled after every
     step: the fields at the history points and d(t) = |u(t) - u_ref|.  Keyword arguments are the options of exptA_linop.  While the run
@@ -2176,6 +2277,7 @@ class nek_dns:
             raise TypeError("nek_dns: an existing operator brings its own options")
         self.op = op   # `op=`: the run borrows an existing operator (its dt rule, tolerances, filter); X0 becomes its base flow
         self.hp = None
+        self.wf = None
         o = _lib.DnsOpts()
         check(self.lib.nlg_dns_opts_default(C.byref(o)))
         o.chunk = int(chunk)
@@ -2189,6 +2291,11 @@ class nek_dns:
         check(self.lib.nlg_dns_set_probes(self.h, None if hp is None else hp.h))
         self.hp = hp
 
+    def set_wall_forces(self, wf: "wall_forces | None"):
+        """Every sample also holds wf.sample(state, 1 / Re).  The series starts again from the state as it stands."""
+        check(self.lib.nlg_dns_set_forces(self.h, None if wf is None else wf.h))
+        self.wf = wf
+
     def set_reference(self, vec: "nek_dvector | None" = None):
         """u_ref of the recurrence norm: `vec`, or the state as it stands.  The series starts again from the state as it stands."""
         check(self.lib.nlg_dns_set_reference(self.h, None if vec is None else vec.h))
@@ -2197,7 +2304,8 @@ class nek_dns:
         check(self.lib.nlg_dns_advance(self.h, int(nsteps)))
 
     def series(self) -> dict:
-        """time[nsamples], probe[nsamples, npts, nf], dist[nsamples]; sample 0 is the state the series started from."""
+        """time[nsamples], probe[nsamples, npts, nf], dist[nsamples], with wall forces attached also force[nsamples, nobj, NQ]; sample 0 is
+        the state the series started from."""
         check(self.lib.nlg_dns_advance(self.h, 0))
         n = C.c_int64()
         check(self.lib.nlg_dns_count(self.h, C.byref(n)))
@@ -2205,7 +2313,12 @@ class nek_dns:
         nf = self.mesh.dim + 1 + (1 if self.op.cfg.ifheat else 0)
         t, p, d = np.zeros(n.value), np.zeros((n.value, npts, nf)), np.zeros(n.value)
         check(self.lib.nlg_dns_series(self.h, 0, n.value, dptr(t), dptr(p) if p.size else None, dptr(d)))
-        return {"time": t, "probe": p, "dist": d}
+        out = {"time": t, "probe": p, "dist": d}
+        if self.wf is not None:
+            f = np.zeros((n.value, self.wf.nobj, self.wf.nq))
+            check(self.lib.nlg_dns_force_series(self.h, 0, n.value, dptr(f)))
+            out["force"] = f
+        return out
 
     def state(self, out: "nek_dvector | None" = None) -> nek_dvector:
         out = out if out is not None else nek_dvector(self.mesh, self.X0.nscal, self.X0.lorder)
